@@ -12,6 +12,12 @@ models/yolo_nano.py:13) so that NMS does real work on random weights.  Multi-GPU
 shards, one process per GPU, no data-path collective ("scaling": "weak": 32 images per GPU).
 
 Rank 0 prints ONE JSON line; see DESIGN.md §Measurement for the roofline and cpu_baseline definitions.
+
+A plain run does only what the headline needs: set-up, --warmup untimed steps, ONE timed region of exactly --steps steps, the
+result line (roofline and cpu_baseline null).  --full adds everything else the benchmark measures: the headline as the median of
+three such regions, the device-only rate, one stream alone, the per-kernel HIP-event table and roofline, the bs=1 latency block,
+the other named workloads, the CPU baseline and the detail file.  --dump-outputs DIR writes what the last timed step delivered
+(detections.npy, offsets.npy) so that two builds can be compared output for output on identical seeded inputs.
 """
 import argparse
 import json
@@ -70,6 +76,12 @@ def parse():
                     help="steps that may be queued per stream (each on its own output buffers): 1 (default) = a stream is refilled after the host has "
                          "collected its previous step; 2 = the next step is already queued behind the running one (measured: 40.5 k against 41.0 k "
                          "images/s - the streams are not starved, the chip is the limit)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: three timed regions (median reported), device-only rate, single stream, per-kernel roofline, "
+                         "bs=1 latency, the extra workloads, CPU baseline, detail file (the --no-* switches below narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the host delivery of the last timed step (rank 0) as DIR/detections.npy (float32 [K, 6] = x1,y1,x2,y2,score,class) "
+                         "and DIR/offsets.npy (float64 [B+1]); inference mode only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the bs=1 p50/p99 latency block of the default run")
     ap.add_argument("--cpu-images", type=int, default=8)
@@ -99,7 +111,12 @@ def parse():
                     help="where the detail blocks of the default run go (per-kernel table, extras, latency, NMS split); default: bench_detail.json next to bench.py")
     ap.add_argument("--latency", type=int, default=0, metavar="N",
                     help="latency mode (BASELINE config 5): N synchronous single-batch calls after warm-up; reports p50/p99 ms")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.layers or args.dump_layers) and not args.full:
+        ap.error("--layers / --dump-layers come from the per-kernel pass: add --full")
+    if args.dump_outputs and (args.train or args.preprocess or args.latency > 0):
+        ap.error("--dump-outputs: inference mode only")
+    return args
 
 
 def cpu_baseline(args, sd, anchors):
@@ -464,9 +481,36 @@ class InferRig:
             if not self.deliver and any(int(v) < 0 for sl in self.slots[k] for v in sl["off_h"][:self.B]):
                 raise SystemExit("bench.py: an activation exceeded the split-f16 range (yn_range_status); re-run with yn_exact_f32")
 
+    def last_delivery(self):
+        """What the host received from the most recent step (call after drain): kept records [K, 6] and offsets [B+1], numpy copies."""
+        k = (self.step_no - 1) % self.ns
+        sl = self.slots[k][(self.visits[k] - 1) % self.depth]
+        off = sl["off_h"].numpy().copy()
+        return sl["rec_h"][:max(int(off[self.B]), 0)].numpy().copy(), off
+
     def close(self):
         for hk in self.handles:
             hk.close()
+
+
+DUMP_LIMIT = 64 << 20      # bytes of all dumped arrays together
+
+
+def dump_outputs(path, rec, off):
+    """--dump-outputs: the last timed step's host delivery as float32 / float64 .npy files.  Above DUMP_LIMIT the records are a fixed,
+    seeded sample of rows (in row order) and the row numbers are written beside them (detections_rows.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rec = np.ascontiguousarray(rec, dtype=np.float32)
+    arrays = {"offsets": off.astype(np.float64)}
+    room = (DUMP_LIMIT - arrays["offsets"].nbytes) // (rec.shape[1] * 4 + 8)
+    if rec.shape[0] > room:
+        rows = np.sort(np.random.RandomState(0).choice(rec.shape[0], room, replace=False))
+        arrays["detections_rows"] = rows.astype(np.float64)
+        rec = rec[rows]
+    arrays["detections"] = rec
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def build_rig(args, dev, rank, world, dist, *a, **kw):
@@ -771,14 +815,40 @@ def main():
         use_graph = r_g > 1.03 * r_e
         calib = {"eager_steps_per_s": round(r_e, 1), "graph_steps_per_s": round(r_g, 1)}
         rig.use_graph(use_graph)
-    # THREE timed regions of exactly --steps steps each (the first behind --warmup untimed steps, the others back to back behind two), the MEDIAN
-    # reported (round 5's single 15 ms region had no protection against one host hiccup; the extras have used the median of three since then);
-    # all three are in summary.timed_regions_images_per_s
+    # plain run: ONE timed region of exactly --steps steps behind --warmup untimed ones.  --full: THREE such regions (the others back to back
+    # behind two warm-up steps), the MEDIAN reported (round 5's single 15 ms region had no protection against one host hiccup; the extras have
+    # used the median of three since then); all three are in summary.timed_regions_images_per_s
     regions = []
-    for i in range(3):
+    for i in range(3 if args.full else 1):
         el = timed_infer(rig, args.steps, args.warmup if i == 0 else 2, dev, dist)
         regions.append((el, list(rig.rank_seconds), rig.delivered // max(1, args.steps)))
-    elapsed, rank_seconds, kept = sorted(regions, key=lambda r: r[0])[1]
+    elapsed, rank_seconds, kept = sorted(regions, key=lambda r: r[0])[len(regions) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *rig.last_delivery())
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * B * args.steps / elapsed
+    line = {
+        "metric": "images/sec YOLO-Nano-%s %dx%d bs=%d inference (network + decode + NMS + host delivery)" % (args.backbone, S, S, B),
+        "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (split-f16 MFMA x3, fp32 accumulate)", "data": "synthetic",
+        "config": {"workload": "YOLO-Nano-%s %dx%d bs=%d/GPU fp32 inference, COCO %d-class head + NMS (BASELINE configs[1]); inputs resident in HBM, "
+                               "kept detections delivered to pinned host memory inside the timed region" % (args.backbone, S, S, B, args.classes),
+                   "arithmetic": "fp32 storage / accumulation; GEMM-shaped convs on the f16 MFMA with fp32 operands split hi + lo*2^-11 (3 MFMAs per product, fp32-class)",
+                   "global_batch": world * B, "conf_thresh": args.conf, "nms_thresh": args.nms,
+                   "parallelism": "image-sharded x%d, no collective" % world, "rccl_ranks": world, "backend": backend if dist is not None else None,
+                   "per_rank_images_per_s": [round(B * args.steps / t, 1) for t in rank_seconds], "launch_mode": "hipgraph" if use_graph else "eager",
+                   "streams_per_gpu": ns, "ms_per_step_is": "inverse throughput, %d batches in flight per GPU; %s" % (
+                       ns * rig_depth, "median of three timed regions of %d steps each" % args.steps if args.full else "one timed region of %d steps" % args.steps),
+                   "detections_per_step_rank0": kept},
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if not args.full:
+        rig.close()
+        if rank == 0:
+            emit(line)
+        return finish()
 
     # the same step without the host delivery (detections stay in HBM; only the 32 counts cross PCIe): the round-1 definition
     rig.deliver = False
@@ -872,31 +942,13 @@ def main():
             except Exception as e:                                                                                              # reported, never hidden
                 extras["train_608_bs32_" + dt] = {"error": str(e)[:300]}
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * B * args.steps / elapsed
     if rank == 0:
-        per_rank = [round(B * args.steps / t, 1) for t in rank_seconds]
+        per_rank = line["config"]["per_rank_images_per_s"]
         frac_floor = round(pipeline["roofline_floor_ms"] / ms_per_step, 4) if pipeline else None
-        roof_line = None
         if roof:                                            # the contract's keys + what prices them; the rest of the block is in the detail file
-            roof_line = {k: roof[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "alg_bytes_per_launch", "avg_us",
-                                              "share_of_step", "launches_per_step")}
-        line = {
-            "metric": "images/sec YOLO-Nano-%s %dx%d bs=%d inference (network + decode + NMS + host delivery)" % (args.backbone, S, S, B),
-            "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (split-f16 MFMA x3, fp32 accumulate)", "data": "synthetic",
-            "config": {"workload": "YOLO-Nano-%s %dx%d bs=%d/GPU fp32 inference, COCO %d-class head + NMS (BASELINE configs[1]); inputs resident in HBM, "
-                                   "kept detections delivered to pinned host memory inside the timed region" % (args.backbone, S, S, B, args.classes),
-                       "arithmetic": "fp32 storage / accumulation; GEMM-shaped convs on the f16 MFMA with fp32 operands split hi + lo*2^-11 (3 MFMAs per product, fp32-class)",
-                       "global_batch": world * B, "conf_thresh": args.conf, "nms_thresh": args.nms,
-                       "parallelism": "image-sharded x%d, no collective" % world, "rccl_ranks": world, "backend": backend if dist is not None else None,
-                       "per_rank_images_per_s": per_rank, "launch_mode": "hipgraph" if use_graph else "eager",
-                       "streams_per_gpu": ns, "ms_per_step_is": "inverse throughput, %d batches in flight per GPU; median of three timed regions of %d steps each" % (ns * rig_depth, args.steps),
-                       "detections_per_step_rank0": kept},
-            "roofline": roof_line,
-            "cpu_baseline": None if args.no_cpu_baseline or world > 1 else cpu_baseline(args, sd, anchors),
-        }
+            line["roofline"] = {k: roof[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "alg_bytes_per_launch", "avg_us",
+                                                     "share_of_step", "launches_per_step")}
+        line["cpu_baseline"] = None if args.no_cpu_baseline or world > 1 else cpu_baseline(args, sd, anchors)
         # everything else: bench_detail.json + stderr (emit)
         detail = {
             "config_detail": {"arithmetic": "fp32 storage and fp32 accumulation everywhere; the GEMM-shaped convs multiply on the f16 MFMA with every fp32 operand split "

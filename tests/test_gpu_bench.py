@@ -30,7 +30,7 @@ def _run(extra):
 
 
 def test_two_rank_inference_bench():
-    d = _run(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-latency", "--no-extras", "--batch", "8"])
+    d = _run(["--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-latency", "--no-extras", "--batch", "8"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["global_batch"] == 16 and d["config"]["rccl_ranks"] == 2
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and d["cpu_baseline"] is None
 
@@ -41,7 +41,7 @@ def test_four_rank_default_run_walks_every_barrier():
     `extras` and `train_bench` is walked by more than two ranks, one autotune pass for the job, ONE JSON line, summary block at its end."""
     env = dict(os.environ, YN_BENCH_ONE_GPU="1", YN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "6", "--warmup", "2", "--batch", "4", "--size", "224",
+           "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--full", "--steps", "6", "--warmup", "2", "--batch", "4", "--size", "224",
            "--extras-small", "--latency-calls", "20", "--streams", "2"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -106,10 +106,10 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_driver_default_command_prints_one_small_parseable_line():
-    """EXACTLY what the driver runs at round end - `python3 bench.py --gpus 1 --steps 20 --warmup 5`, extras on, full sizes - must yield ONE
+    """The standard command with --full - `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`, extras on, full sizes - must yield ONE
     stdout line of fewer than 4096 bytes that json.loads accepts and that carries every contract key, roofline.frac and cpu_baseline.value
     (round 4's line was 22.9 KB: the driver's record kept a tail of it and parsed nothing).  The detail blocks are in the named file."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = [l for l in r.stdout.splitlines() if l.strip()]
@@ -144,11 +144,35 @@ def test_driver_default_command_prints_one_small_parseable_line():
     assert "bench_detail " in r.stderr                         # and the same object went to stderr
 
 
+def test_plain_run_times_exactly_steps_and_dumps_its_last_step(tmp_path):
+    """The plain form (no --full) times ONE region of exactly --steps steps and measures nothing else: no roofline, CPU baseline, summary or
+    detail file.  --dump-outputs writes what the host received from the last timed step; two runs with the same arguments deliver the
+    same arrays (seeded weights and inputs, every tile configuration of a family is bit-identical)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        dd = tmp_path / ("out%d" % i)
+        d = _run_single(["--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "4", "--size", "224", "--dump-outputs", str(dd)])
+        for k in CONTRACT:
+            assert k in d, k
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 2e-3 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "summary" not in d and "detail_file" not in d
+        assert "one timed region of 7 steps" in d["config"]["ms_per_step_is"]
+        assert sorted(os.listdir(dd)) == ["detections.npy", "offsets.npy"]
+        rec, off = np.load(dd / "detections.npy"), np.load(dd / "offsets.npy")
+        assert rec.dtype == np.float32 and rec.ndim == 2 and rec.shape[1] == 6 and off.dtype == np.float64 and off.shape == (5,)
+        assert off[0] == 0 and np.all(np.diff(off) >= 0) and off[-1] == rec.shape[0] > 0
+        assert np.all(np.isfinite(rec)) and np.all(rec[:, 4] >= 0.001) and np.all((rec[:, 5] >= 0) & (rec[:, 5] < 80))
+        dumps.append((rec, off))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
 def test_single_gpu_contract_line(tmp_path):
-    """The driver's contract for the default mode: one JSON line with the required keys, the roofline and cpu_baseline blocks and
+    """The contract of the --full mode: one JSON line with the required keys, the roofline and cpu_baseline blocks and
     the bs=1 latency block (small workload here to keep the test short)."""
     dp = str(tmp_path / "detail.json")
-    d = _run_single(["--steps", "8", "--warmup", "3", "--batch", "4", "--size", "224", "--cpu-images", "2", "--no-extras", "--latency-calls", "60", "--detail", dp])
+    d = _run_single(["--full", "--steps", "8", "--warmup", "3", "--batch", "4", "--size", "224", "--cpu-images", "2", "--no-extras", "--latency-calls", "60", "--detail", dp])
     assert d["detail_file"] == dp
     det = json.load(open(dp))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-LAYER HBM traffic from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --dump-layers layers.json`.
+"""Per-LAYER HBM traffic from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --full --dump-layers layers.json`.
 
 usage: python tools/pmc_layers.py <fetch_counter_collection.csv> <write_counter_collection.csv> <layers.json> <out.json>
 

@@ -6,7 +6,7 @@ O=$R/gpurun_out/prof_r05
 mkdir -p $O
 PARTS=${@:-stats pmc sq train}
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-latency --no-extras"
+B="--full --no-cpu-baseline --no-latency --no-extras"
 stats() {   # name, bench args...
     local name=$1; shift
     rm -rf /tmp/yn_prof_$name

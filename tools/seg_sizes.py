@@ -1,6 +1,6 @@
 import os, sys
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from yolo_nano_amd import arch, capi, weights
 """Largest class segments per image of the benchmark's synthetic workload, and how many the sweep takes:  S=608 BB=0.5x B=128 python3 tools/seg_sizes.py"""
 B, S, C = int(os.environ.get("B", "32")), int(os.environ.get("S", "416")), 80
