@@ -8,6 +8,10 @@
 //     Item (u, T) needs the outputs of (u-1, T-1), (u-1, T), (u-1, T+1) (the 3 x 3 window's halo) - all EARLIER tickets of their queues, so
 //     whoever holds them is resident and running: no wait on a workgroup that has not been dispatched, whatever else shares the chip
 //     (the four-stream run) and whatever the placement.
+//   * PRECONDITION W + 1 <= BM (map width against tile height; stage_pipe_form in yn_stage_form.h takes no other form).  Only then does the
+//     window of (u, T), flat pixels [m0 - W - 1, m0 + BM + W + 1), lie inside tiles T-1..T+1 - the three flags it waits for - and only then are
+//     the readers of tile T's rows of one ping-pong buffer exactly the items (u+1, T) waits for before it overwrites them.  Wider maps would
+//     read rows of T-2 / T+2 unwaited and let (u+1, T) overwrite rows (u, T+-2) still reads.
 //   * HAND-OFF between workgroups follows the placement-independent protocol (cdna_hip_programming.md 6, Guideline 16, form R1): the
 //     producer stores its rows WRITE-THROUGH (sc1), every storing wavefront drains its vector-memory counter, a barrier, ONE lane stores the
 //     tile's ready flag (sc1); the consumer polls the three flags relaxed (sc1 loads, one wavefront) and reads the rows with sc1 LDS-DMA
@@ -48,12 +52,12 @@ __device__ __forceinline__ void dma16_sc1(const void* gbase, unsigned goff, unsi
 template <int BF, int NW, bool PUB_EARLY>
 __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
 {
-    constexpr int WN = BF <= 64 ? 2 : 4, WM = NW / WN, BM = 32 * WM, NTHR = 64 * NW;
+    constexpr int WN = BF <= 64 ? 2 : 4, WM = NW / WN, BM = stage_pipe_bm(BF, NW), NTHR = 64 * NW;   // BM: yn_stage_form.h (the launcher's form rule)
     constexpr int KQ = (BF + 7) >> 3, PS = plane_stride(BF), S = (KQ + 1) >> 1, NPAD = (BF + 31) & ~31;
     constexpr int CG = BF / 4, RUN = 4;
     constexpr unsigned ROWB = BF * 4u;
     constexpr int X1C = BF / 4, X1S = BF;                                // 16-byte pieces / floats per pass-through row
-    static_assert(BF % 4 == 0 && BF <= 128 && WM >= 1 && WM * WN == NW && CG * (BM / RUN) <= NTHR, "channel quads, one 32-column tile per wavefront, one depthwise round");
+    static_assert(BF % 4 == 0 && BF <= 128 && WM >= 1 && WM * WN == NW && BM == 32 * WM && CG * (BM / RUN) <= NTHR, "channel quads, one 32-column tile per wavefront, one depthwise round");
     extern __shared__ __attribute__((aligned(16))) unsigned char sp_smem[];
     const int W = a.W, H = a.H, HW = H * W, tiles = a.tiles, nunits = a.nunits;
     const unsigned win_bytes = (unsigned)(BM + 2 * W + 2) * ROWB;
@@ -536,20 +540,22 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
     }
 }
 
-static size_t stage_pipe_lds(int bf, int W, int BM)
-{
-    const size_t win = (((size_t)(BM + 2 * W + 2) * bf * 4 + 15) & ~(size_t)15);
-    return win + (size_t)BM * bf * 4 + (size_t)2 * BM * plane_stride(bf) * 2 + (size_t)BM * 4 + (size_t)14 * bf * 4 + 64 + 192;      // (+ YN_EXP_STAGE_TIMING's phase sums)
-}
-
 size_t stage_sync_words(int tiles, int nunits) { return (size_t)STAGE_FLAGS + (size_t)tiles * nunits; }
 
-// true = launched (or, dry: would be).  false = no form for this shape or fewer than min_tiles tiles (the caller launches the units one by one).
+// true = launched (or, dry: would be).  false = no form for this shape (stage_pipe_form, yn_stage_form.h: none whose window stays inside the
+// three tiles an item waits for) or fewer than min_tiles tiles (the caller launches the units one by one).
 // The tile count of the form taken goes into the arguments here (a.tiles is ignored on entry).
 bool launch_stage_pipe(StageArgs a, int bf, int pub_early, int min_tiles, size_t sync_bytes, hipStream_t s, bool dry)
 {
     if (a.nunits < 2 || a.nunits > YN_STAGE_MAX || (a.M & 7)) return false;
     if ((double)a.M * bf * 8.0 >= 4.0e9) return false;                    // 32-bit byte offsets (DMA pieces, raw-buffer stores)
+    // two four-wavefront workgroups per CU where their windows fit (80 KB each), else one of eight (twice the rows per tile; 608 x 608 stage 3: W = 38);
+    // either only with W + 1 <= BM
+    const StagePipeForm f = stage_pipe_form(bf, a.W);
+    if (!f.nw) return false;
+    a.tiles = (a.M + f.bm - 1) / f.bm;
+    if (a.tiles < min_tiles || a.tiles >= (1 << 20) || stage_sync_words(a.tiles, a.nunits) * sizeof(unsigned) > sync_bytes) return false;
+    if (dry) return true;
     // workgroups: tickets in hand (~1.65 per workgroup) against the tiles of one unit decide how often an item finds its inputs unfinished
     static const int wg_env = getenv("YN_STAGE_G") ? atoi(getenv("YN_STAGE_G")) : 0;
     // 416 x 416 / bs 32, stage 3: 384 / 448 / 512 workgroups all run 96-98 us (fewer stalls against fewer slots); the narrow branches (<= 48
@@ -558,31 +564,22 @@ bool launch_stage_pipe(StageArgs a, int bf, int pub_early, int min_tiles, size_t
     // 320 / 384 / 448 / 512 workgroups 47.51 / 47.43 / 47.32 / 47.22 k - a workgroup that waits for a flag holds a CU slot another stream's kernel
     // could use, and the per-unit launches' idle tails are filled by the other streams anyway.  One stream: 384 ... 512 all +0.4 %.  384.
     const int wg4 = wg_env > 0 ? wg_env : (bf <= 48 ? 768 : 384);
-    // two four-wavefront workgroups per CU where their windows fit (80 KB each), else one of eight (twice the rows per tile; 608 x 608 stage 3: W = 38)
+    unsigned g = (unsigned)(f.nw == 4 ? wg4 : 256);
+    if (g > (unsigned)(a.tiles * a.nunits)) g = (unsigned)(a.tiles * a.nunits);
 #define YN_SP(BFv, NWv)                                                                                                  \
-    if (bf == BFv) {                                                                                                     \
-        constexpr int BM = 32 * (NWv / (BFv <= 64 ? 2 : 4));                                                             \
-        constexpr size_t LDS_MAX = (size_t)(NWv == 4 ? 80 : 160) * 1024;                                                 \
-        const size_t lds = stage_pipe_lds(bf, a.W, BM);                                                                  \
-        a.tiles = (a.M + BM - 1) / BM;                                                                                   \
-        if (lds <= LDS_MAX) {                                                                                            \
-            if (a.tiles < min_tiles || a.tiles >= (1 << 20) || stage_sync_words(a.tiles, a.nunits) * sizeof(unsigned) > sync_bytes) return false; \
-            if (dry) return true;                                                                                        \
-            unsigned g = (unsigned)(NWv == 4 ? wg4 : 256);                                                               \
-            if (g > (unsigned)(a.tiles * a.nunits)) g = (unsigned)(a.tiles * a.nunits);                                  \
-            if (pub_early) {                                                                                             \
-                static unsigned long long attr = 0;                                                                      \
-                if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stage_pipe_kernel<BFv, NWv, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX); \
-                set_last_kernel_name("stage_pipe_kernel<" #BFv "," #NWv ",true>");                                       \
-                hipLaunchKernelGGL((stage_pipe_kernel<BFv, NWv, true>), dim3(g), dim3(64 * NWv), lds, s, a);             \
-            } else {                                                                                                     \
-                static unsigned long long attr = 0;                                                                      \
-                if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stage_pipe_kernel<BFv, NWv, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX); \
-                set_last_kernel_name("stage_pipe_kernel<" #BFv "," #NWv ",false>");                                      \
-                hipLaunchKernelGGL((stage_pipe_kernel<BFv, NWv, false>), dim3(g), dim3(64 * NWv), lds, s, a);            \
-            }                                                                                                            \
-            return true;                                                                                                 \
+    if (bf == BFv && f.nw == NWv) {                                                                                      \
+        if (pub_early) {                                                                                                 \
+            static unsigned long long attr = 0;                                                                          \
+            if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stage_pipe_kernel<BFv, NWv, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_max); \
+            set_last_kernel_name("stage_pipe_kernel<" #BFv "," #NWv ",true>");                                           \
+            hipLaunchKernelGGL((stage_pipe_kernel<BFv, NWv, true>), dim3(g), dim3(64 * NWv), f.lds, s, a);               \
+        } else {                                                                                                         \
+            static unsigned long long attr = 0;                                                                          \
+            if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stage_pipe_kernel<BFv, NWv, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_max); \
+            set_last_kernel_name("stage_pipe_kernel<" #BFv "," #NWv ",false>");                                          \
+            hipLaunchKernelGGL((stage_pipe_kernel<BFv, NWv, false>), dim3(g), dim3(64 * NWv), f.lds, s, a);              \
         }                                                                                                                \
+        return true;                                                                                                     \
     }
     YN_SP(116, 4) YN_SP(116, 8)
     YN_SP(96, 4) YN_SP(96, 8)

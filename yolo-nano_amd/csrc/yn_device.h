@@ -2,6 +2,7 @@
 // activation, the opaque-mask load idiom, the GEMM epilogue of the f32 MFMA accumulator layout, the split-f16 GEMM tile, small vector helpers.
 #pragma once
 #include "yn_internal.h"
+#include "yn_stage_form.h"
 
 namespace ynk {
 
@@ -278,12 +279,7 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
     range_report(a.ovf, amax);
 }
 
-// Row stride (halves) of an operand plane [rows][C] in LDS that 16-byte fragment reads walk row by row (lane = row): a
-// ds_read_b128 is served in groups of 16 lanes, conflict-free when their 16-byte pieces tile the 64 banks, i.e. when the stride is an
-// ODD multiple of 16 bytes.  ceil(C/8)*8 + 8 is one only for an even octet count: C = 116 (15 octets) gave 256 bytes - all 16 lanes
-// on the same four banks (SQ_LDS_BANK_CONFLICT = 88 % of the stage-3 chain's LDS cycles, profiles/r04_sq_counters.txt) - and C = 232 a
-// two-way conflict.  The columns [C, stride) stay zero (K tail).
-__host__ __device__ constexpr int plane_stride(int C) { return ((((C + 7) >> 3) + 1) & ~1) * 8 + 8; }
+// plane_stride (the operand planes' LDS row stride): yn_stage_form.h
 
 // ---- LDS-DMA (global_load_lds_dwordx4) and the barriers that go with it (unit_pipe_kernel, head_tail_pipe_group_kernel) -----------------
 // One LDS-DMA piece: 64 lanes x 16 bytes, global (wave-uniform base + 32-bit lane offset) -> LDS (wave-uniform byte address + lane * 16).
