@@ -242,6 +242,37 @@ int  yn_infer(yn_handle* h, const float* x_dev, int B,
 int  yn_pack_detections(yn_handle* h, const float* out_boxes_dev, const float* out_scores_dev, const int32_t* out_cls_dev,
                         const int32_t* count_dev, int B, int N, float* rec_dev, int32_t* offsets_dev);
 
+/* ---- VOC mAP: VOCAPIEvaluator.evaluate + do_python_eval (evaluator/vocapi_evaluator.py:56-198, voc_eval :233-338, voc_ap :199-230)
+ * on the device, bit for bit with the reference's numpy arithmetic (DESIGN.md §VOC mAP).  The evaluator is an object of its own, so it
+ * outlives any handle; every call launches on the stream of the handle it is given.  Per class, detections are ordered by score
+ * descending and, among equal 3-decimal scores, in file order (image in add order, then position in the image's record list): the
+ * reference's np.argsort is unstable there, the one point where it is not deterministic. */
+typedef struct yn_eval yn_eval;
+/* num_classes 1..2000, ovthresh = voc_eval's ovthresh (a strict >) */
+int  yn_eval_create(yn_handle* h, int num_classes, double ovthresh, yn_eval** out);
+void yn_eval_destroy(yn_eval* e);
+/* drops every image, record and ground-truth box added so far */
+int  yn_eval_reset(yn_handle* h, yn_eval* e);
+/* B images: rec_dev / offsets_dev as yn_pack_detections wrote them (device; normalised boxes of the letterboxed square), geom_host
+ * int32 [B][7] = w0, h0, rw, rh, left, top, side (the letterbox geometry, ValTransforms.geometry), gt_host int32 [G][6] = x1, y1, x2,
+ * y2, class, difficult (the VOC XML integers, parse_rec :100-117) with gt_offsets_host [B+1].  Reads offsets_dev[B] to size the
+ * store (one 4-byte read-back, synchronises the stream); a negative total (the split-f16 range mark) returns YN_STATUS_RANGE and
+ * adds nothing.  Records are mapped to image pixels and through the reference's text-file route (score to 3 decimals, box + 1 to
+ * 1 decimal) on the device.  At most 4096 ground-truth boxes per (image, class), 2^22 records per image, 2^21 images. */
+int  yn_eval_add(yn_handle* h, yn_eval* e, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom_host,
+                 const int32_t* gt_host, const int32_t* gt_offsets_host);
+/* per-class AP into ap_host [C] (-1 for a class without detections, as :334-336; use_07_metric: 11-point, else area), non-difficult
+ * ground truth npos_host [C] and detections ndet_host [C] (either may be NULL).  mAP = np.mean(ap) is the caller's.  Fails, naming
+ * it, if an added record had a score outside 0.000..1.000 after rounding, a class outside 0..C-1 or a non-finite coordinate. */
+int  yn_eval_finish(yn_handle* h, yn_eval* e, int use_07_metric, double* ap_host, int64_t* npos_host, int64_t* ndet_host);
+/* after yn_eval_finish: the first min(ndet, cap) points of class cls's rec / prec arrays (:328-333); either pointer may be NULL */
+int  yn_eval_curve(yn_handle* h, yn_eval* e, int cls, double* rec_host, double* prec_host, int64_t cap);
+/* testing aid: the first min(n, cap) ingested records as host int32 [n][7] = image, class, score bin k (score = k / 1000), x1, y1,
+ * x2, y2 in tenths (coordinate + 1 = tenths / 10), in ingest order */
+int  yn_eval_records(yn_handle* h, yn_eval* e, int32_t* host, int64_t cap);
+/* records and images added so far (host counters, no device work) */
+int  yn_eval_size(yn_eval* e, int64_t* records, int64_t* images);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

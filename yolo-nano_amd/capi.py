@@ -108,6 +108,14 @@ SIGNATURES = {
     "yn_op_h16_bn": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "yn_op_h16_gemm_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "yn_op_h16_bn_unit": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "yn_eval_create": (_i32, [_vp, _i32, ctypes.c_double, ctypes.POINTER(_vp)]),
+    "yn_eval_destroy": (None, [_vp]),
+    "yn_eval_reset": (_i32, [_vp, _vp]),
+    "yn_eval_add": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "yn_eval_finish": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "yn_eval_curve": (_i32, [_vp, _vp, _i32, _vp, _vp, ctypes.c_int64]),
+    "yn_eval_records": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
+    "yn_eval_size": (_i32, [_vp, _i64p, _i64p]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

@@ -70,6 +70,8 @@ struct GraphEntry {
 
 }  // namespace
 
+struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
+
 struct yn_handle {
     yn_config cfg;
     hipStream_t stream = nullptr;
@@ -2184,6 +2186,78 @@ int yn_profile_get(yn_handle* h, int i, char* name, int name_cap, char* kernel, 
     if (ms) *ms = t;
     if (alg_flops) *alg_flops = r.flops;
     if (alg_bytes) *alg_bytes = r.bytes;
+    return 0;
+}
+
+// ---- VOC mAP (kernels_eval.hip) ---------------------------------------------------------------------------------------------
+int yn_eval_create(yn_handle* h, int num_classes, double ovthresh, yn_eval** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_eval_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::EvalState* st = nullptr;
+    if (ynk::eval_create(h->cfg.device, num_classes, ovthresh, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_eval{st};
+    return 0;
+}
+
+void yn_eval_destroy(yn_eval* e)
+{
+    if (!e) return;
+    ynk::eval_destroy(e->st);
+    delete e;
+}
+
+#define YN_EVAL_CALL(call)                                                   \
+    do {                                                                     \
+        std::string err;                                                     \
+        const int rc_ = (call);                                              \
+        if (rc_ == 1) return fail(h, "%s", err.c_str());                     \
+        if (rc_ == YN_STATUS_RANGE) { h->err = err; return YN_STATUS_RANGE; } \
+        return 0;                                                            \
+    } while (0)
+
+int yn_eval_reset(yn_handle* h, yn_eval* e)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_eval_reset: null evaluator");
+    YN_EVAL_CALL(ynk::eval_reset(e->st, h->stream, err));
+}
+
+int yn_eval_add(yn_handle* h, yn_eval* e, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom_host,
+                const int32_t* gt_host, const int32_t* gt_offsets_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_eval_add: null evaluator");
+    YN_EVAL_CALL(ynk::eval_add(e->st, h->stream, B, rec_dev, offsets_dev, geom_host, gt_host, gt_offsets_host, err));
+}
+
+int yn_eval_finish(yn_handle* h, yn_eval* e, int use_07_metric, double* ap_host, int64_t* npos_host, int64_t* ndet_host)
+{
+    YN_ENTER(h);
+    if (!e || !ap_host) return fail(h, "yn_eval_finish: null argument");
+    YN_EVAL_CALL(ynk::eval_finish(e->st, h->stream, use_07_metric, ap_host, npos_host, ndet_host, err));
+}
+
+int yn_eval_curve(yn_handle* h, yn_eval* e, int cls, double* rec_host, double* prec_host, int64_t cap)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_eval_curve: null evaluator");
+    YN_EVAL_CALL(ynk::eval_curve(e->st, h->stream, cls, rec_host, prec_host, cap, err));
+}
+
+int yn_eval_records(yn_handle* h, yn_eval* e, int32_t* host, int64_t cap)
+{
+    YN_ENTER(h);
+    if (!e || !host) return fail(h, "yn_eval_records: null argument");
+    YN_EVAL_CALL(ynk::eval_records(e->st, h->stream, host, cap, err));
+}
+
+int yn_eval_size(yn_eval* e, int64_t* records, int64_t* images)
+{
+    if (!e) return 1;
+    ynk::eval_size(e->st, records, images);
     return 0;
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace ynk {
 
 // Every launch of the library goes through this form of hipLaunchKernelGGL: with YN_LOG_LDS=1 in the environment each distinct (kernel, dynamic
@@ -227,6 +229,18 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
                          float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
                          hipStream_t s, const NmsHook* hook = nullptr);
 void launch_pack(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, float* rec, int32_t* offsets, hipStream_t s);
+
+// ---- VOC mAP (kernels_eval.hip): the state behind yn_eval; 0 = ok, 1 = error (text in err), 2 = range mark (eval_add only) --------
+struct EvalState;
+int  eval_create(int device, int C, double ovthresh, EvalState** out, std::string& err);
+void eval_destroy(EvalState* e);
+int  eval_reset(EvalState* e, hipStream_t s, std::string& err);
+int  eval_add(EvalState* e, hipStream_t s, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom,
+              const int32_t* gt, const int32_t* gt_off, std::string& err);
+int  eval_finish(EvalState* e, hipStream_t s, int use07, double* ap_host, int64_t* npos_host, int64_t* ndet_host, std::string& err);
+int  eval_curve(EvalState* e, hipStream_t s, int cls, double* rec_host, double* prec_host, int64_t cap, std::string& err);
+int  eval_records(EvalState* e, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
+void eval_size(const EvalState* e, int64_t* records, int64_t* images);
 void launch_nms_single(const float* dets, const float* scores, int n, float thresh, int diou,
                        int32_t* ids_scratch, float* sbox_scratch, void* matrix_scratch, int32_t* keep, int32_t* count, hipStream_t s);
 
