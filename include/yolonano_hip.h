@@ -95,31 +95,31 @@ int  yn_range_status(yn_handle* h, int* weights_exceed_f16, int* activation_over
  * candidates (:308-330, 362-367) run as ONE kernel, so the raw head tensors are neither written nor re-read (default on; needs
  * the split-f16 family and A(5+C) <= 256, otherwise yn_infer runs head GEMM + decode kernel as before).  Outputs are bit-identical
  * either way: a speed switch for A/B runs.  enable = 1: when the stride-8 head has >= 8192 pixels (below that three GEMMs + one decode
- * launch are faster), 2: always.  Env: YN_FUSE_DECODE=0/1/2. */
+ * launch are faster), 2: always. */
 int  yn_fuse_decode(yn_handle* h, int enable);
 /* Layer k of the three detection heads (models/yolo_nano.py:299-301: same operator, three pyramid levels) and the three FPN
  * laterals (:286-288) run as ONE grouped launch each instead of three (default on; split-f16 family only).  Bit-identical outputs:
- * a speed switch for A/B runs.  Env: YN_GROUP=0/1. */
+ * a speed switch for A/B runs. */
 int  yn_group_launch(yn_handle* h, int enable);
 /* A stride-2 ShuffleV2 unit (backbone/shufflenetv2.py:30-51, 73-74: branch 2 = pointwise -> depthwise stride 2 -> pointwise, branch 1 =
  * depthwise stride 2 -> pointwise, then concat + channel shuffle) as ONE kernel where its tile fits (input channels <= 32, branch
  * width <= 64: stage 2, whose intermediate is the largest tensor of the network); the wider units (stages 3 / 4, branch width <= 256) as
  * their first pointwise conv + ONE kernel for everything behind it.  Default on, split-f16 family only, bit-identical to the five
- * launches.  Env: YN_DOWN_FUSE=0/1 (YN_DOWN2=0: only the wide units back to five launches). */
+ * launches. */
 int  yn_down_fuse(yn_handle* h, int enable);
 /* Layers .2 + .3 + .4 of the three detection heads and the candidate decode as ONE grouped kernel — depthwise 3x3 + pointwise conv +
  * last conv + decode on an 8 x 4 pixel tile; layer .3's activation never reaches memory (models/yolo_nano.py:60-82, 299-330, 362-367).
  * Default on; needs yn_fuse_decode and yn_group_launch in effect and a head of 129..256 columns (COCO); otherwise, or with 0, two
- * grouped kernels (depthwise + pointwise, last conv + decode).  Bit-identical either way.  Env: YN_TAIL_FUSE=0/1. */
+ * grouped kernels (depthwise + pointwise, last conv + decode).  Bit-identical either way. */
 int  yn_tail_fuse(yn_handle* h, int enable);
 /* Per-class NMS (models/yolo_nano.py:159-188, 263-272): resolve the 64 best-scored boxes of every class first and drop every later box
  * one of their KEPT boxes suppresses before the dense pairwise phase (exact: a removed box suppresses nothing).  mode 0 = off, 1 (default) =
- * for batches of >= 4 images, 2 = always.  Same kept sets either way.  Env: YN_NMS_PREFILTER=0/1/2. */
+ * for batches of >= 4 images, 2 = always.  Same kept sets either way. */
 int  yn_nms_prefilter(yn_handle* h, int mode);
 /* Large class segments (> 1 024 boxes behind the prefilter) whose boxes are spread out get their suppression words from a sweep over bins of
  * the boxes' left edges - only pairs whose x-extents intersect are evaluated, with the same exact predicate (models/yolo_nano.py:159-188: `ovr <=
  * thresh` keeps) - instead of the dense 64 x 64 tiles; the kernel decides per segment from a pair-count estimate.  1 (default) / 0: every segment
- * dense.  Kept sets are identical either way.  Env: YN_NMS_SWEEP=0/1. */
+ * dense.  Kept sets are identical either way. */
 int  yn_nms_sweep(yn_handle* h, int enable);
 /* Testing aid: how many (image, class) segments of the LAST yn_infer / yn_postprocess call (B images, C classes) the sweep handled
  * (synchronises the handle's stream); -1 on a failed copy. */

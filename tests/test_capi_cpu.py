@@ -82,3 +82,27 @@ def test_shim_state_dict_matches_reference_keys():
     assert tuple(g.shape) == (1, 2100, 1, 2) and tuple(s.shape) == (1, 2100, 3, 2) and tuple(a.shape) == (1, 2100, 3, 2)
     with pytest.raises(Exception):
         YOLONano(torch.device("cuda"), input_size=320, num_classes=20, anchor_size=arch.MULTI_ANCHOR_SIZE, backbone="3.0x")
+
+
+# The only environment variables the library reads at run time: test hooks and an output-neutral launch log.  Anything
+# else that could change a run's kernels or results belongs behind a C-ABI setter, where a caller states it.
+RUNTIME_ENV = {
+    "YN_DOWN_PIPE", "YN_DWPW_PIPE",                                  # one-tile-per-workgroup reference forms (tools/ab_hash.py)
+    "YN_TRAIN_POISON", "YN_TRAIN_FUSE_STATS", "YN_TRAIN_FUSE_SUMS",  # training-step test hooks
+    "YN_TRAIN_STEM_FUSE", "YN_LOSS_SCALE",
+    "YN_LOG_LDS",                                                    # launch shapes to stderr (tools/concurrency.py)
+}
+
+
+def test_native_code_reads_only_the_listed_environment_variables():
+    csrc = os.path.join(ROOT, "yolo-nano_amd", "csrc")
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".inc")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        for m in re.finditer(r"getenv\s*\(", text):
+            lit = re.match(r'\s*"([A-Za-z0-9_]+)"\s*\)', text[m.end():])
+            assert lit, "%s: getenv without a string literal: %r" % (f, text[m.start():m.end() + 40])
+            names.add(lit.group(1))
+    assert names == RUNTIME_ENV

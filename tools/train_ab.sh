@@ -1,5 +1,5 @@
 #!/bin/bash
-# Kernel stats of the training step (DTYPE=f16|f32, default f16) on the GPU box, per step.   bash tools/train_ab.sh [size] [steps] [env assignments to compare, e.g. YN_RED_G=512]
+# Kernel stats of the training step (DTYPE=f16|f32, default f16) on the GPU box, per step.   bash tools/train_ab.sh [size] [steps] [env assignments to compare, e.g. YN_TRAIN_FUSE_STATS=0]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/train_ab
 mkdir -p $O

@@ -38,7 +38,7 @@ static Lanes lanes_for(int C)
 static int reduce_blocks(int M, int rowsPer)
 {
     long b = ((long)M + (long)rowsPer * 4 - 1) / ((long)rowsPer * 4);      // >= 4 rows per row-lane
-    static const int gmax = getenv("YN_RED_G") ? atoi(getenv("YN_RED_G")) : 512;
+    constexpr int gmax = 512;
     if (b > gmax) b = gmax;
     if (b < 1) b = 1;
     return (int)b;
@@ -487,9 +487,8 @@ static void launch_wgrad_t(const WgradArgs& a, hipStream_t s)
 {
     const int gn = (a.N + NT * 32 - 1) / (NT * 32), gk = (a.K + KT * 32 - 1) / (KT * 32);
     // M slices: enough blocks for one wave per SIMD (three for the 2x2 tile, whose accumulators leave room for three
-    // resident waves); more slices only add per-slice copies of dW to write and re-read.  YN_WG_SLICES overrides (tuning).
-    static const int senv = getenv("YN_WG_SLICES") ? atoi(getenv("YN_WG_SLICES")) : 0;
-    const int smax = senv > 0 ? senv : (NT * KT <= 4 ? 768 : 256);
+    // resident waves); more slices only add per-slice copies of dW to write and re-read.
+    constexpr int smax = NT * KT <= 4 ? 768 : 256;
     int slices = smax / (gn * gk);
     const int max_slices = (a.M + 255) / 256;
     if (slices > max_slices) slices = max_slices;
@@ -622,9 +621,9 @@ void launch_dw_wgrad(const float* dy, const float* x, int x_ld, int x_off, int B
     const Lanes L = lanes_for(C);
     // per-block partial rows instead of atomics into 8 slots (round 3, as the fp16 step's hdw_wgrad_kernel): the same-address chains had capped
     // the grid at 128 blocks
-    static const int rpl = getenv("YN_DWW_RUNS") ? atoi(getenv("YN_DWW_RUNS")) : 2;
+    constexpr int rpl = 2;
     int G = (runs + L.rowsPer * rpl - 1) / (L.rowsPer * rpl);
-    static const int gmax = getenv("YN_DWW_G") ? atoi(getenv("YN_DWW_G")) : 1024;
+    constexpr int gmax = 1024;
     if (G > gmax) G = gmax;
     if ((size_t)G * C * 9 > part_cap) G = (int)(part_cap / ((size_t)C * 9));
     if (G < 8) G = 8;
@@ -769,7 +768,7 @@ void launch_stem_wgrad(const float* dy, const float* x, int B, int H, int W, int
 {
     const int nrows = B * ((H - 1) / 2 + 1);
     int G = (nrows + 3) / 4;
-    static const int gmax = getenv("YN_STEM_G") ? atoi(getenv("YN_STEM_G")) : 2048;
+    constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
     const long n = (long)Cout * 27;
     if ((long)G * n > (long)partial_cap) G = (int)((long)partial_cap / n);

@@ -326,302 +326,21 @@ __global__ __launch_bounds__(256, 2) void unit_chain_kernel(ChainArgs a)
 }
 
 // -------------------------------------------------------------------------------------------------
-// The same chain on the split-f16 family (gemm_split_kernel's numerics: x = hi + lo*2^-11, three f16 MFMAs per product, K in chunks
-// of 32 in the same order => bit-identical to the three-kernel path on gemm_split_kernel).  With the GEMM phases 4-5x shorter the
-// unit is the depthwise (memory) phase plus two short matrix phases, so ONE launch per unit beats three again.  LDS: the depthwise
-// output / x2' as two planes of halves P[2][BM][PS] (A operands), the fp32 tile T32 [BM][bf+2] for y (the interleave pass needs y
-// in full precision), one buffer of pre-split weight chunks.
+// The same chain on the split-f16 family (gemm_split_kernel's numerics: x = hi + lo*2^-11, three f16 MFMAs per product, K in order
+// => bit-identical to the three-kernel path on gemm_split_kernel).  With the GEMM phases 4-5x shorter the unit is the depthwise
+// (memory) phase plus two short matrix phases, so ONE launch per unit beats three again.  LDS: the depthwise output / x2' as two
+// planes of halves P[2][BM][PS] (A operands); the weights go through registers.
 // -------------------------------------------------------------------------------------------------
 typedef _Float16 uch16;
 typedef _Float16 uch16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 uch16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 uch16x2 __attribute__((ext_vector_type(2)));
 
-template <int WM, int WN, int NT, int V>
-__global__ __launch_bounds__(256, 2) void unit_chain_split_kernel(ChainArgs a)
-{
-    typedef typename VecT<V>::type vec;
-    constexpr int BM = 32 * WM, BN = 32 * NT * WN, KC = 32, G = V / 2;
-    constexpr int B_PER = (2 * 4 * BN + 255) / 256;
-    constexpr int MAXB = (BM * (BN / (2 * G)) + 255) / 256;
-    static_assert(WM * WN == 4, "4 waves");
-    extern __shared__ __attribute__((aligned(16))) float ucs_smem[];
-    const int bf = a.bf, CS = bf + 2, W = a.W, H = a.H, HW = H * W;
-    const int KQ = (bf + 7) >> 3, PS = plane_stride(bf), nchunks = (bf + KC - 1) / KC;
-    float* T32 = ucs_smem;                                              // [BM][CS]
-    uch16* Ph = reinterpret_cast<uch16*>(ucs_smem + ((BM * CS + 3) & ~3));  // [BM][PS]
-    uch16* Pl = Ph + BM * PS;
-    uch16* Bh = Pl + BM * PS;                                           // [4][BN][8], then the lo plane
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
-    const int wm = wave % WM, wn = wave / WM;
-    const int m0 = (int)xcd_block(blockIdx.x, gridDim.x) * BM;
-    if (m0 >= a.M) return;
-
-#ifdef YN_EXP_TIMING
-    long long TS[8]; int tsn = 0;
-#define YN_TS() TS[tsn++] = __builtin_readcyclecounter()
-#else
-#define YN_TS()
-#endif
-    YN_TS();
-    uch16x8 b_reg[B_PER];
-    auto prefetch_b = [&](const void* Wh, const void* Wl, int c) {
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) {
-            const int g = t + 256 * i;
-            const int pl = g / (4 * BN), r = g - pl * (4 * BN);
-            const int o = r / BN, n = r - o * BN;
-            const int kq = c * (KC / 8) + o;
-            const bool ok = g < 2 * 4 * BN && kq < KQ && n < a.Npad;
-            uch16x8 v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? Wl : Wh) + ((size_t)(ok ? kq : 0) * a.Npad + (ok ? n : 0)) * 8);
-            if (!ok) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-            }
-            b_reg[i] = v;
-        }
-    };
-    auto stage_b = [&]() {
-#pragma unroll
-        for (int i = 0; i < B_PER; ++i) {
-            const int g = t + 256 * i;
-            if (g < 2 * 4 * BN) *reinterpret_cast<uch16x8*>(Bh + (size_t)g * 8) = b_reg[i];
-        }
-    };
-    float amax = 0.0f;                                                   // range guard (yn_device.h): largest |value| this thread has split
-    auto split_store = [&](int r, int c, float v0, float v1) {           // two adjacent channels of row r -> both planes
-        uch16x2 hi, lo;
-        amax = range_track(range_track(amax, v0), v1);
-        hi[0] = (uch16)v0; hi[1] = (uch16)v1;
-        lo[0] = (uch16)((v0 - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((v1 - (float)hi[1]) * 2048.0f);
-        *reinterpret_cast<uch16x2*>(Ph + r * PS + c) = hi;
-        *reinterpret_cast<uch16x2*>(Pl + r * PS + c) = lo;
-    };
-
-    float bias2[NT], bias1n[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int n = wn * NT * 32 + nt * 32 + l31;
-        bias2[nt] = n < bf ? a.b2[n] : 0.0f;
-        bias1n[nt] = (a.Wp1n && n < bf) ? a.b1n[n] : 0.0f;
-    }
-    const int hipr = bf / (2 * G), jhi = bf >> 1;
-    float2 xg[MAXB], xl[MAXB];
-    auto x1_prefetch = [&]() {
-#pragma unroll
-    for (int i = 0; i < MAXB; ++i) {
-        const int it = t + 256 * i;
-        const int r = it / hipr, j0 = (it - r * hipr) * G;
-        const int m = m0 + r < a.M ? m0 + r : a.M - 1;
-        xg[i] = make_float2(0.0f, 0.0f); xl[i] = xg[i];
-        if (it < BM * hipr) {
-            const float* px = a.x1 + (size_t)m * a.x1_ld + a.x1_off + j0;
-            if constexpr (G == 2) {
-                xg[i] = *reinterpret_cast<const float2*>(px);
-                xl[i] = *reinterpret_cast<const float2*>(px + jhi);
-            } else {
-                xg[i].x = px[0];
-                xl[i].x = px[jhi];
-            }
-        }
-    }
-    };
-
-    // ---- 1. depthwise 3x3 of the block's pixels -> split planes (the same fma chain as dwconv3x3_kernel) ------------------------
-    {
-        const int cgn = bf / V, ppl = 256 / cgn;
-        const int cg = t % cgn, pl = t / cgn, c = cg * V;
-        const bool worker = pl < ppl;
-        constexpr int R = 4;
-        auto issue = [&](int run, vec (&win)[3][R + 2]) {
-            const int q0 = m0 + run * R - 1;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int i = 0; i < R + 2; ++i) {
-                    int q = q0 + (dy - 1) * W + i;
-                    q = q < 0 ? 0 : (q >= a.M ? a.M - 1 : q);
-                    win[dy][i] = *reinterpret_cast<const vec*>(a.t1 + (size_t)q * a.t1_ld + a.t1_off + c);
-                }
-        };
-        vec w[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) w[k] = *reinterpret_cast<const vec*>(a.wdw + k * bf + c);
-        const vec bias = *reinterpret_cast<const vec*>(a.bdw + c);
-        auto finish = [&](int run, vec (&win)[3][R + 2]) {
-            const int mrun = m0 + run * R;
-            const int rem0 = (mrun < a.M ? mrun : m0) % HW;
-            int y = rem0 / W, x = rem0 - y * W;
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const int r = run * R + i;
-                const bool live = mrun + i < a.M;
-                const bool yk[3] = {live && y >= 1, live, live && y + 1 < H};
-                const bool xk[3] = {x >= 1, true, x + 1 < W};
-                vec acc = bias;
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const bool ok = yk[ky] && xk[kx];
-                        vec v = win[ky][i + kx];
-                        if constexpr (V == 4) v = make_float4(ok ? v.x : 0.0f, ok ? v.y : 0.0f, ok ? v.z : 0.0f, ok ? v.w : 0.0f);
-                        else v = make_float2(ok ? v.x : 0.0f, ok ? v.y : 0.0f);
-                        vfma(acc, v, w[ky * 3 + kx]);
-                    }
-                acc = vact(acc, a.dw_act);
-                if constexpr (V == 4) { split_store(r, c, acc.x, acc.y); split_store(r, c + 2, acc.z, acc.w); }
-                else split_store(r, c, acc.x, acc.y);
-                if (++x == W) { x = 0; if (++y == H) y = 0; }
-            }
-        };
-        vec win[3][R + 2];
-        if (worker) issue(pl, win);
-        prefetch_b(a.Ws2h, a.Ws2l, 0);
-        x1_prefetch();
-        stage_b();
-#ifdef YN_EXP_TIMING
-        long long td[6]; int tdn = 0; td[tdn++] = __builtin_readcyclecounter();
-#endif
-        if (nchunks > 1) prefetch_b(a.Ws2h, a.Ws2l, 1);
-        if (worker) {
-            for (int run = pl; run < BM / R; run += ppl) {
-                finish(run, win);
-#ifdef YN_EXP_TIMING
-                if (tdn < 5) td[tdn++] = __builtin_readcyclecounter();
-#endif
-                if (run + ppl < BM / R) issue(run + ppl, win);
-            }
-        }
-#ifdef YN_EXP_TIMING
-        if (t == 0 && (blockIdx.x % 97) == 5) printf("chaindw bf %d blk %d start->stage_b %lld run0 %lld run1 %lld\n", bf, (int)blockIdx.x, td[0] - TS[0], td[1] - td[0], tdn > 2 ? td[2] - td[1] : 0LL);
-#endif
-        // K tail: the columns [bf, PS) of both planes are zero (they meet zero weight rows, but must not be NaN bit patterns)
-        const int padn = PS - bf;
-        for (int i = t; i < BM * padn; i += 256) { const int r = i / padn, c2 = bf + i - r * padn; Ph[r * PS + c2] = (uch16)0.0f; Pl[r * PS + c2] = (uch16)0.0f; }
-    }
-    __syncthreads();
-    YN_TS();
-
-    f32x16 acc0[NT], acc1[NT];
-    // entry state: chunk 0 staged (visible), chunk 1 requested into b_reg
-    auto gemm = [&](const void* Wh, const void* Wl) {
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { acc0[i][k] = 0.0f; acc1[i][k] = 0.0f; }
-        for (int c = 0; c < nchunks; ++c) {
-            const uch16* Ahb = Ph + (wm * 32 + l31) * PS + c * KC + h * 8;
-            const uch16* Alb = Pl + (wm * 32 + l31) * PS + c * KC + h * 8;
-            const uch16* Bhb = Bh + (size_t)(h * BN + wn * NT * 32 + l31) * 8;
-            const uch16* Blb = Bhb + 4 * BN * 8;
-#pragma unroll
-            for (int ks = 0; ks < KC / 16; ++ks) {
-                if (c * (KC / 8) + ks * 2 >= KQ) break;                 // wave-uniform: this 16-deep step lies beyond the (zero-padded) K
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const uch16x8 bh = *reinterpret_cast<const uch16x8*>(Bhb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                    const uch16x8 bl = *reinterpret_cast<const uch16x8*>(Blb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                    acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[nt], 0, 0, 0);
-                }
-            }
-            if (c + 1 < nchunks) {
-                __syncthreads();                                        // every wave is done with this chunk's weights
-                stage_b();
-                __syncthreads();
-                if (c + 2 < nchunks) prefetch_b(Wh, Wl, c + 2);
-            }
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[nt][r] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]);
-    };
-    gemm(a.Ws2h, a.Ws2l);
-    YN_TS();
-    if (a.Wp1n) prefetch_b(a.Ws1h, a.Ws1l, 0);
-    __syncthreads();                                                    // all waves are done reading the planes and the weights
-
-    // ---- 3. y = act(acc + b2) -> T32 ----------------------------------------------------------------------------------------
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int n = wn * NT * 32 + nt * 32 + l31;
-        if (n < bf) {
-            const float bias = bias2[nt];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) T32[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * CS + n] = apply_act(acc0[nt][r] + bias, a.act2);
-        }
-    }
-    if (a.Wp1n) {
-        stage_b();
-        if (nchunks > 1) prefetch_b(a.Ws1h, a.Ws1l, 1);
-    }
-    __syncthreads();
-
-    // interleave pass (as unit_chain_kernel): first half-row -> global; second half-row -> global (last unit) or x2' -> planes
-    float2 yl[MAXB];
-#pragma unroll
-    for (int i = 0; i < MAXB; ++i) {
-        const int it = t + 256 * i;
-        const int r = it / hipr, j0 = (it - r * hipr) * G, m = m0 + r;
-        yl[i] = make_float2(0.0f, 0.0f);
-        if (it < BM * hipr) {
-            float2 y = make_float2(0.0f, 0.0f);
-            if constexpr (G == 2) { y = *reinterpret_cast<const float2*>(T32 + r * CS + j0); yl[i] = *reinterpret_cast<const float2*>(T32 + r * CS + jhi + j0); }
-            else { y.x = T32[r * CS + j0]; yl[i].x = T32[r * CS + jhi + j0]; }
-            if (m < a.M) {
-                float* o = a.out + (size_t)m * a.out_ld + 2 * j0;
-                if constexpr (G == 2) {
-                    *reinterpret_cast<float4*>(o) = make_float4(xg[i].x, y.x, xg[i].y, y.y);
-                    if (!a.Wp1n) *reinterpret_cast<float4*>(o + 2 * jhi) = make_float4(xl[i].x, yl[i].x, xl[i].y, yl[i].y);
-                } else {
-                    *reinterpret_cast<float2*>(o) = make_float2(xg[i].x, y.x);
-                    if (!a.Wp1n) *reinterpret_cast<float2*>(o + 2 * jhi) = make_float2(xl[i].x, yl[i].x);
-                }
-            }
-        }
-    }
-    YN_TS();
-    if (!a.Wp1n) { range_report(a.ovf, amax); return; }
-    // x2' = interleave(x1[bf/2:], y[bf/2:]) -> the planes (free since the first GEMM; their pad columns are still zero)
-#pragma unroll
-    for (int i = 0; i < MAXB; ++i) {
-        const int it = t + 256 * i;
-        const int r = it / hipr, c0 = 2 * (it - r * hipr) * G;
-        if (it < BM * hipr) {
-            split_store(r, c0, xl[i].x, yl[i].x);
-            if constexpr (G == 2) split_store(r, c0 + 2, xl[i].y, yl[i].y);
-        }
-    }
-    __syncthreads();
-
-    // ---- 4. the next unit's pw1 on x2' -> global ------------------------------------------------------------------------------
-    YN_TS();
-    gemm(a.Ws1h, a.Ws1l);
-    YN_TS();
-    GemmArgs e{};
-    e.out = a.t1n; e.out_ld = bf; e.out_off = 0; e.M = a.M; e.N = bf; e.Npad = a.Npad; e.bias = a.b1n; e.act = a.act1n; e.pass = nullptr;
-    gemm_epilogue<NT>(e, acc0, m0 + wm * 32, wn * NT * 32, (bf & 3) == 0, lane, bias1n);
-    range_report(a.ovf, amax);
-#ifdef YN_EXP_TIMING
-    YN_TS();
-    if (t == 0 && (blockIdx.x % 97) == 5)
-        printf("chains bf %d blk %d dw %lld gemm1 %lld y+interleave %lld x2split %lld gemm2 %lld epi %lld total %lld\n", bf, (int)blockIdx.x, TS[1] - TS[0], TS[2] - TS[1],
-               TS[3] - TS[2], TS[4] - TS[3], TS[5] - TS[4], TS[6] - TS[5], TS[6] - TS[0]);
-#endif
-#undef YN_TS
-}
-
 // -------------------------------------------------------------------------------------------------
-// unit_chain_split_kernel, second form (round 3).  What changed against the kernel above, and why (tools/phase_timing.sh chain2: of a
-// block's ~50 k cycles only the first ~14 k move data from HBM; the rest is a chain of latency-bound phases with the memory idle):
-//   * the fp32 tile T32 and its two passes are gone.  The accumulator layout already gives every lane ONE column n and 16 rows:
-//     the lane loads x1[row][n] itself (16 * NT scalar loads at kernel start, 128-byte rows per half-wavefront), and after the
+// unit_chain2_kernel (round 3).  What changed against the round-2 form, and why (tools/phase_timing.sh chain2: of a block's ~50 k
+// cycles only the first ~14 k move data from HBM; the rest is a chain of latency-bound phases with the memory idle):
+//   * the fp32 tile T32 [BM][bf+2] for y and its two passes are gone.  The accumulator layout already gives every lane ONE column n
+//     and 16 rows: the lane loads x1[row][n] itself (16 * NT scalar loads at kernel start, 128-byte rows per half-wavefront), and after the
 //     first GEMM turns each accumulator value straight into its final place - out[row][2n .. 2n+1] = (x1, y) as one 8-byte
 //     store (columns n < bf/2 - or all of them in the last unit of a stage), or x2'[2(n - bf/2) ..] = split(x1, y) into the
 //     operand planes (columns n >= bf/2).  One barrier and ~9 k cycles of LDS round trips less per block; LDS 78 -> 64 KB at bf = 116.
@@ -631,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void unit_chain_split_kernel(ChainArgs a)
 //     throughput, 39.2 k -> 36.8 k images/s)
 //   * K goes through LDS in chunks of KC = 64 instead of 32: half the barrier pairs inside the two GEMMs (two chunks at bf = 116;
 //     a chunk round costs ~2 k cycles whatever it multiplies).  Same k order (16-deep steps in sequence, zero-padded tail skipped):
-//     bit-identical to the first form and to gemm_split_kernel.
+//     bit-identical to the round-2 form and to gemm_split_kernel.
 // -------------------------------------------------------------------------------------------------
 #ifndef YN_UC2_OCC_NARROW
 #define YN_UC2_OCC_NARROW 3                                 // workgroups per CU the 58-channel (stage 2) instantiation is compiled for
@@ -905,12 +624,6 @@ static size_t unit_chain2_lds(int bf, int BM)
     return (size_t)2 * BM * PS * 2;                          // the two operand planes; the weights go through registers
 }
 
-static size_t unit_chain_split_lds(int bf, int BM, int BN)
-{
-    const int PS = plane_stride(bf);
-    return (size_t)((BM * (bf + 2) + 3) & ~3) * sizeof(float) + ((size_t)2 * BM * PS + (size_t)2 * 4 * BN * 8) * 2;
-}
-
 static size_t unit_chain_lds(int bf, int BM, int BN) { return ((size_t)((BM * (bf + 2) + 3) & ~3) + (size_t)2 * 16 * BN * 2) * sizeof(float); }
 
 // false when no instantiated tile covers the shape (Npad must be one block column; bf % 4 == 0 or the 2-channel variant)
@@ -934,19 +647,6 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
         hipLaunchKernelGGL((unit_chain_kernel<WMv, WNv, NTv, Vv>), dim3(xcd_grid((a.M + BM - 1) / BM)), dim3(256), lds, s, a); \
         return true;                                                                                                   \
     }
-#define YN_UCS(WMv, WNv, NTv, Vv)                                                                                      \
-    {                                                                                                                  \
-        constexpr int BM = 32 * WMv, BN = 32 * NTv * WNv;                                                              \
-        const size_t lds = unit_chain_split_lds(a.bf, BM, BN);                                                         \
-        if (lds > 160 * 1024) return false;                                                                            \
-        if (dry) return true;                                                                                          \
-        static unsigned long long attr = 0;                                                                            \
-        if (attr_pending(attr)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unit_chain_split_kernel<WMv, WNv, NTv, Vv>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }              \
-        set_last_kernel_name("unit_chain_split_kernel<" #WMv "," #WNv "," #NTv "," #Vv ">");                            \
-        hipLaunchKernelGGL((unit_chain_split_kernel<WMv, WNv, NTv, Vv>), dim3(xcd_grid((a.M + BM - 1) / BM)), dim3(256), lds, s, a); \
-        return true;                                                                                                   \
-    }
 #define YN_UC2(WMv, WNv, NTv, Vv, KCv)                                                                                 \
     {                                                                                                                  \
         constexpr int BM = 32 * WMv, BN = 32 * NTv * WNv;                                                              \
@@ -960,15 +660,14 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
         hipLaunchKernelGGL((unit_chain2_kernel<WMv, WNv, NTv, Vv, KCv>), dim3(xcd_grid((a.M + BM - 1) / BM)), dim3(64 * WMv * WNv), lds, s, a); \
         return true;                                                                                                   \
     }
-    static const int chain_v = getenv("YN_CHAIN_V") ? atoi(getenv("YN_CHAIN_V")) : 2;      // 1: the round-2 kernel (A/B runs); 2: unit_chain2_kernel
-    if (a.Ws2h && chain_v >= 2) {
+    if (a.Ws2h) {
         // round 5: the persistent, software-pipelined form where it applies (kernels_pipe.hip); coverage is still decided by the tiles below
         if (!dry && launch_unit_pipe(a, s)) return true;
         if (a.Npad == 64 && !v4) YN_UC2(2, 2, 1, 2, 4)
         if (a.Npad == 64 && v4) YN_UC2(2, 2, 1, 4, 4)
         // small maps (one image): 32-row tiles - twice the workgroups, and a workgroup's serial chain (one depthwise round instead of two,
         // half the epilogue rows) is what a launch of a few dozen workgroups costs
-        static const int small_m = getenv("YN_CHAIN_SMALL_M") ? atoi(getenv("YN_CHAIN_SMALL_M")) : 4096;
+        constexpr int small_m = 4096;
         if (a.Npad == 128 && v4 && a.M <= small_m) YN_UC2(1, 4, 1, 4, 4)
         if (a.Npad == 128 && v4) YN_UC2(2, 2, 2, 4, 3)
         if (a.Npad == 256 && v4) YN_UC2(1, 4, 2, 4, 3)          // 32-row tiles, four wavefronts x 64 columns (NT = 4 would need 128 accumulator + 64 pass-through registers)
@@ -977,16 +676,6 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
         return false;
     }
 #undef YN_UC2
-    if (a.Ws2h) {                                            // split-f16 family
-        if (a.Npad == 64 && !v4) YN_UCS(2, 2, 1, 2)
-        if (a.Npad == 64 && v4) YN_UCS(2, 2, 1, 4)
-        if (a.Npad == 128 && v4) YN_UCS(2, 2, 2, 4)
-        if (a.Npad == 256 && v4) YN_UCS(2, 2, 4, 4)
-        if (a.Npad == 32 && v4) YN_UCS(4, 1, 1, 4)
-        if (a.Npad == 96 && v4) YN_UCS(4, 1, 3, 4)
-        return false;
-    }
-#undef YN_UCS
     const int tiles64 = (a.M + 63) / 64;
     if (a.Npad == 64 && !v4) YN_UC(2, 2, 1, 2)
     if (a.Npad == 64 && v4) YN_UC(2, 2, 1, 4)
@@ -1002,7 +691,7 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
 //     branch 2:  y1 = relu(pw1(x)) at H x W  ->  y2 = dw3x3_s2(y1) at H/2 x W/2  ->  y3 = relu(pw2(y2))
 //     branch 1:  z1 = dw3x3_s2(x)  ->  z2 = relu(pw(z1))                                  out = shuffle(cat(z2, y3))
 // y1 is the largest tensor of the network (stage 2: 104 x 104 x 58 per image, 80 MB per 32-image step written and read back once) and the
-// launches around it cost their full duration even with four streams (tools/ablate.sh: the big-tensor regions do not overlap with
+// launches around it cost their full duration even with four streams (profiles/r06_ablation_4stream.txt: the big-tensor regions do not overlap with
 // anything).  One workgroup = an 8 x 4 tile of OUTPUT pixels of one image: pw1 on the 17 x 9 input pixels the tile's depthwise
 // windows cover (20 % recomputed on tile borders; K = cin <= 32 is one chunk), y1 in an fp32 LDS tile (zero outside the image: the
 // depthwise conv pads its INPUT), depthwise -> split planes, pw2 (K = bf <= 64: two chunks) on wavefronts 0..NP-1 while wavefronts
@@ -1011,7 +700,6 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
 // Every sum runs in the order of gemm_split_kernel / dwconv3x3_kernel: bit-identical to the five launches
 // (test_down_unit_is_bit_identical).  LDS 76 KB: two workgroups per CU.  94 us of launches -> 75 us; 33.3 -> 35.2 k images/s together
 // with the branch-free activation this kernel led to (three branches per accumulator value in the first version's epilogue).
-// pass != null: branch 1's output is read from memory instead (the two-kernel form of branch 1; A/B runs, YN_DOWN_B1=0).
 // -------------------------------------------------------------------------------------------------
 template <int NP>                                           // Npad / 32 of both GEMMs (bf <= 32 * NP)
 __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
@@ -1033,7 +721,6 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     uch16* A3h = B2 + 2 * 8 * BN * 8;
     uch16* A3l = A3h + NO * AST1;
     uch16* B3 = A3l + NO * AST1;
-    const bool fuse1 = a.pass == nullptr;                   // branch 1 (depthwise stride 2 on x, then pointwise) computed here too
     float* T32 = du_smem + (R1_HALVES + 1) / 2;             // [RT1*32][CS] (rows >= NPIX are written as zeros, never read)
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
@@ -1078,34 +765,32 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     constexpr int B3_PER = (2 * 4 * BN + 255) / 256;
     uch16x8 b3_reg[B3_PER];
     float bias3v = 0.0f;
-    if (fuse1) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) w1d[k] = *reinterpret_cast<const float2*>(a.wdw1 + k * a.cin + c1);
-        b1d = *reinterpret_cast<const float2*>(a.bdw1 + c1);
+    for (int k = 0; k < 9; ++k) w1d[k] = *reinterpret_cast<const float2*>(a.wdw1 + k * a.cin + c1);
+    b1d = *reinterpret_cast<const float2*>(a.bdw1 + c1);
 #pragma unroll
-        for (int i = 0; i < NI1; ++i) {
-            const int op = p1 + i * p1_n;
-            const int dy = op / TW, dx = op - dy * TW;
+    for (int i = 0; i < NI1; ++i) {
+        const int op = p1 + i * p1_n;
+        const int dy = op / TW, dx = op - dy * TW;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int iy = 2 * (oy0 + dy) - 1 + k / 3, ix = 2 * (ox0 + dx) - 1 + k % 3;
-                const bool ok = op < NO && p1 < p1_n && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                x1w[i][k] = vmask(*reinterpret_cast<const float2*>(a.x + ((size_t)(b * a.H + (ok ? iy : 0)) * a.W + (ok ? ix : 0)) * a.cin + c1), opaque_mask(ok));
-            }
+        for (int k = 0; k < 9; ++k) {
+            const int iy = 2 * (oy0 + dy) - 1 + k / 3, ix = 2 * (ox0 + dx) - 1 + k % 3;
+            const bool ok = op < NO && p1 < p1_n && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+            x1w[i][k] = vmask(*reinterpret_cast<const float2*>(a.x + ((size_t)(b * a.H + (ok ? iy : 0)) * a.W + (ok ? ix : 0)) * a.cin + c1), opaque_mask(ok));
         }
-#pragma unroll
-        for (int i = 0; i < B3_PER; ++i) {
-            const int g = t + 256 * i;
-            const int pl = g / (4 * BN), r = g - pl * (4 * BN);
-            const int o = r / BN, n = r - o * BN;
-            uch16x8 v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-            if (g < 2 * 4 * BN && o < KQ1 && n < a.Npad3) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.W3l : a.W3h) + ((size_t)o * a.Npad3 + n) * 8);
-            b3_reg[i] = v;
-        }
-        if (wave >= NP && wave < 2 * NP && (wave - NP) * 32 + l31 < bf) bias3v = a.b3[(wave - NP) * 32 + l31];
     }
+#pragma unroll
+    for (int i = 0; i < B3_PER; ++i) {
+        const int g = t + 256 * i;
+        const int pl = g / (4 * BN), r = g - pl * (4 * BN);
+        const int o = r / BN, n = r - o * BN;
+        uch16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
+        if (g < 2 * 4 * BN && o < KQ1 && n < a.Npad3) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.W3l : a.W3h) + ((size_t)o * a.Npad3 + n) * 8);
+        b3_reg[i] = v;
+    }
+    if (wave >= NP && wave < 2 * NP && (wave - NP) * 32 + l31 < bf) bias3v = a.b3[(wave - NP) * 32 + l31];
     if (t < RT1 * 32) {                                     // one window pixel per thread: all of its (<= 32) input channels
         const int p = t;
         const int wy = p / WW, wx = p - wy * WW;
@@ -1204,33 +889,31 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
         const int g = t + 256 * i;
         if (g < 2 * 8 * BN) *reinterpret_cast<uch16x8*>(B2 + (size_t)g * 8) = b2_reg[i];
     }
-    if (fuse1) {
 #pragma unroll
-        for (int i = 0; i < B3_PER; ++i) {
-            const int g = t + 256 * i;
-            if (g < 2 * 4 * BN) *reinterpret_cast<uch16x8*>(B3 + (size_t)g * 8) = b3_reg[i];
-        }
-        if (p1 < p1_n) {
+    for (int i = 0; i < B3_PER; ++i) {
+        const int g = t + 256 * i;
+        if (g < 2 * 4 * BN) *reinterpret_cast<uch16x8*>(B3 + (size_t)g * 8) = b3_reg[i];
+    }
+    if (p1 < p1_n) {
 #pragma unroll
-            for (int i = 0; i < NI1; ++i) {
-                const int op = p1 + i * p1_n;
-                if (op < NO) {
-                    float2 acc = b1d;
+        for (int i = 0; i < NI1; ++i) {
+            const int op = p1 + i * p1_n;
+            if (op < NO) {
+                float2 acc = b1d;
 #pragma unroll
-                    for (int k = 0; k < 9; ++k) vfma(acc, x1w[i][k], w1d[k]);
-                    acc = vact(acc, a.dw1_act);
-                    amax = range_track(range_track(amax, acc.x), acc.y);
-                    uch16x2 hi, lo;
-                    hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
-                    lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
-                    *reinterpret_cast<uch16x2*>(A3h + op * AST1 + c1) = hi;
-                    *reinterpret_cast<uch16x2*>(A3l + op * AST1 + c1) = lo;
-                }
+                for (int k = 0; k < 9; ++k) vfma(acc, x1w[i][k], w1d[k]);
+                acc = vact(acc, a.dw1_act);
+                amax = range_track(range_track(amax, acc.x), acc.y);
+                uch16x2 hi, lo;
+                hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
+                lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
+                *reinterpret_cast<uch16x2*>(A3h + op * AST1 + c1) = hi;
+                *reinterpret_cast<uch16x2*>(A3l + op * AST1 + c1) = lo;
             }
         }
-        const int pad1 = AST1 - a.cin;                      // K tail of branch 1's planes: zero
-        for (int i = t; i < NO * pad1; i += 256) { const int r = i / pad1, c2 = a.cin + i - r * pad1; A3h[r * AST1 + c2] = (uch16)0.0f; A3l[r * AST1 + c2] = (uch16)0.0f; }
     }
+    const int pad1 = AST1 - a.cin;                          // K tail of branch 1's planes: zero
+    for (int i = t; i < NO * pad1; i += 256) { const int r = i / pad1, c2 = a.cin + i - r * pad1; A3h[r * AST1 + c2] = (uch16)0.0f; A3l[r * AST1 + c2] = (uch16)0.0f; }
     if (dworker) {
         for (int op = dpl; op < NO; op += ppl) {
             const int dy = op / TW, dx = op - dy * TW;
@@ -1262,7 +945,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     f32x16 acc0, acc1;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-    if (fuse1 && wave >= NP && wave < 2 * NP) {
+    if (wave >= NP && wave < 2 * NP) {
         const int nt = wave - NP;
         const uch16* Ahb = A3h + l31 * AST1 + h * 8;
         const uch16* Alb = A3l + l31 * AST1 + h * 8;
@@ -1299,14 +982,13 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1, 0, 0, 0);
         }
     }
-    if (fuse1) __syncthreads();                             // branch 1's tile is complete
+    __syncthreads();                                        // branch 1's tile is complete
     // ---- 5. concat + shuffle store: out[2n] = branch 1, out[2n+1] = branch 2 -------------------------------------------------------
     if (wave < NP) {
         const int n = wave * 32 + l31;
         if (n < bf) {
             const float bias = bias2v;
-            // the 16 pass-through values of this lane are requested together, before any store (a load issued next to the store that
-            // needs it is followed by a full wait: 16 memory latencies in a row)
+            // the 16 branch-1 values of this lane are read together, before any store
             float pv[16];
             size_t mrow[16];
             unsigned okm = 0;
@@ -1317,7 +999,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
                 const bool ok = oy < Ho && ox < Wo;
                 okm |= (ok ? 1u : 0u) << r;
                 mrow[r] = ((size_t)b * Ho + (ok ? oy : 0)) * Wo + (ok ? ox : 0);
-                pv[r] = fuse1 ? PT[op * (BN + 1) + n] : __uint_as_float(__float_as_uint(a.pass[mrow[r] * bf + n]) & opaque_mask(ok));
+                pv[r] = PT[op * (BN + 1) + n];
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1674,7 +1356,7 @@ bool down_unit_covers(const DownArgs& a)
 {
     return a.W1h && a.W1l && a.W2h && a.W2l && a.cin <= 32 && !(a.cin & 1) && a.bf <= 64 && !(a.bf & 1) && a.Npad1 == a.Npad2 && a.Npad1 <= 64 &&
            !(a.H & 1) && !(a.W & 1) && a.B > 0 && a.cin >= 16 && (size_t)a.B * a.H * a.W * (size_t)(a.cin > a.bf / 2 ? a.cin : a.bf / 2) < ((size_t)1 << 30) &&      // 32-bit byte offsets
-           (a.pass || (a.wdw1 && a.bdw1 && a.W3h && a.W3l && a.b3 && a.Npad3 == a.Npad1));
+           a.wdw1 && a.bdw1 && a.W3h && a.W3l && a.b3 && a.Npad3 == a.Npad1;
 }
 
 void launch_down_unit(const DownArgs& a, hipStream_t s)
@@ -1692,14 +1374,13 @@ void launch_down_unit(const DownArgs& a, hipStream_t s)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    // the pipelined form (a workgroup walks tiles): branch 1 computed here, channel quads (YN_DOWN_PIPE=0: one tile per workgroup, A/B runs)
+    // the pipelined form (a workgroup walks tiles), channel quads (YN_DOWN_PIPE=0: one tile per workgroup, the test reference)
     static const int pipe = getenv("YN_DOWN_PIPE") ? atoi(getenv("YN_DOWN_PIPE")) : 1;
-    static const int pipe_g = getenv("YN_DOWN_PIPE_G") ? atoi(getenv("YN_DOWN_PIPE_G")) : 1024;     // walking workgroups: ~3 tiles each at bs = 32 (512 / 768 / 1024 / 1456 / one per tile measured within 1 % of each other)
-    if (pipe && !a.pass && !(a.cin & 3)) {
+    constexpr unsigned pipe_g = 1024;   // walking workgroups (a multiple of 8): ~3 tiles each at bs = 32 (512 / 768 / 1024 / 1456 / one per tile measured within 1 % of each other)
+    if (pipe && !(a.cin & 3)) {
         const size_t plds = down_unit_pipe_lds(a.bf, a.cin);
         unsigned g = xcd_grid(tiles);
-        const unsigned cap = (unsigned)((pipe_g > 8 ? pipe_g : 8) & ~7);
-        if (g > cap) g = cap;
+        if (g > pipe_g) g = pipe_g;
         const bool relu = a.act1 == 1 && a.act2 == 1 && a.act3 == 1 && a.dw_act == 0 && a.dw1_act == 0;
 #define YN_DUP(np, rl) { set_last_kernel_name("down_unit_pipe_kernel<" #np "," #rl ">"); hipLaunchKernelGGL((down_unit_pipe_kernel<np, rl>), dim3(g), dim3(256), plds, s, a, (int)tiles); }
         if (NP == 1) { if (relu) YN_DUP(1, true) else YN_DUP(1, false) }
@@ -2286,21 +1967,15 @@ bool dwpw_group_ok(const DwPwArgs* a, int n)
 
 void launch_dwpw_group(const DwPwArgs* a, int n, hipStream_t s)
 {
-    static const int th_env = getenv("YN_DWPW_TH") ? atoi(getenv("YN_DWPW_TH")) : 0;
-    unsigned tiles4 = 0;
-    for (int p = 0; p < n; ++p) tiles4 += (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8);
-    (void)tiles4;
-    const int TH = th_env == 8 ? 8 : 4;                     // 64-pixel tiles (half the weight traffic) measured the same end to end, 43 vs 39 us alone: YN_DWPW_TH=8 keeps them for A/B runs
     Group<DwPwArgs> g{};
     unsigned tot = 0;
-    // the tile-walking form (8 x 4 tiles only; YN_DWPW_PIPE=0: one tile per workgroup; YN_DWPW_PIPE_T: tiles per walking workgroup)
+    // the tile-walking form (YN_DWPW_PIPE=0: one tile per workgroup, the test reference)
     static const int pipe = getenv("YN_DWPW_PIPE") ? atoi(getenv("YN_DWPW_PIPE")) : 1;
-    static const int pipe_t = getenv("YN_DWPW_PIPE_T") ? atoi(getenv("YN_DWPW_PIPE_T")) : 3;
-    if (pipe && TH == 4) {
+    if (pipe) {
         bool fits = true;
         for (int p = 0; p < n; ++p) fits = fits && (size_t)a[p].B * a[p].H * a[p].W * 96 < ((size_t)1 << 30);      // 32-bit byte offsets
         if (fits) {
-            const unsigned per = (unsigned)(pipe_t > 0 ? pipe_t : 1);
+            constexpr unsigned per = 3;                     // tiles per walking workgroup
             for (int p = 0; p < YN_GROUP_MAX; ++p) {
                 g.first[p] = tot;
                 if (p < n) { g.a[p] = a[p]; const unsigned tiles = (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8); tot += xcd_grid((tiles + per - 1) / per); }
@@ -2311,6 +1986,8 @@ void launch_dwpw_group(const DwPwArgs* a, int n, hipStream_t s)
             return;
         }
     }
+    // one 8 x 4 tile per workgroup (8 x 8 tiles, half the weight traffic, measured the same end to end: 43 vs 39 us alone)
+    constexpr int TH = 4;
     for (int p = 0; p < YN_GROUP_MAX; ++p) {
         g.first[p] = tot;
         if (p < n) { g.a[p] = a[p]; tot += xcd_grid((unsigned)a[p].B * ((a[p].H + TH - 1) / TH) * ((a[p].W + 7) / 8)); }
@@ -2318,12 +1995,9 @@ void launch_dwpw_group(const DwPwArgs* a, int n, hipStream_t s)
     g.first[YN_GROUP_MAX] = tot;
     const size_t lds = ((size_t)2 * 8 * TH * 104 + (size_t)2 * 12 * 96 * 8) * 2;
     static unsigned long long attr = 0;
-    if (attr_pending(attr)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwpw_group_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwpw_group_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-    if (TH == 8) { set_last_kernel_name("dwpw_group_kernel<8>"); hipLaunchKernelGGL(dwpw_group_kernel<8>, dim3(tot), dim3(256), lds, s, g); }
-    else         { set_last_kernel_name("dwpw_group_kernel<4>"); hipLaunchKernelGGL(dwpw_group_kernel<4>, dim3(tot), dim3(256), lds, s, g); }
+    if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwpw_group_kernel<TH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_last_kernel_name("dwpw_group_kernel<4>");
+    hipLaunchKernelGGL(dwpw_group_kernel<TH>, dim3(tot), dim3(256), lds, s, g);
 }
 
 bool launch_unit_chain(const ChainArgs& a, hipStream_t s) { return unit_chain_dispatch(a, s, false); }

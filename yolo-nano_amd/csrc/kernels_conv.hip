@@ -717,7 +717,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_tap_kernel(GemmArgs a)
 // MFMAs (products exact in the fp32 accumulators) into TWO accumulator sets, combined once in the epilogue.  Per-product error
 // <= ~3 * 2^-22 relative — the size of the fp32 path's own accumulation rounding; measured against the float64 oracle the two paths
 // are indistinguishable (tests/test_gpu_parity.py::test_split_f16_conv_is_fp32_class).  Operands must fit the f16 range (|x| < 65504:
-// normalised activations and folded weights are O(1)); YN_EXACT_F32=1 keeps the f32-MFMA kernel.
+// normalised activations and folded weights are O(1)); yn_exact_f32 keeps the f32-MFMA kernel.
 // Structure as conv3x3_halo_tap_kernel: the pixel range of a flat 128-pixel tile + halo is staged ONCE in LDS (already split, two
 // planes of halves, FPN/PAN resample-add fused), the nine taps read their A fragments from it, the pre-split packed weights stream
 // per tap through one LDS buffer with register prefetch.
@@ -1264,11 +1264,10 @@ void launch_conv3x3(const GemmArgs& a, hipStream_t s)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_tap_kernel<1, 96, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         }
         const int tiles = (a.M + 127) / 128;
-        static const int two_per_cu = getenv("YN_C3_SPLIT") ? atoi(getenv("YN_C3_SPLIT")) : 1;
         if (tiles * (a.Npad / 96) >= 256) {
             g_last_kernel = "conv3x3_halo_tap_kernel<3,96,1>";
             hipLaunchKernelGGL((conv3x3_halo_tap_kernel<3, 96, 1>), dim3(xcd_grid(tiles), a.Npad / 96), dim3(256), conv3x3_halo_tap_lds(a.W, 96, 3), s, a);
-        } else if (two_per_cu && conv3x3_halo_tap_lds(a.W, 96, 1) > 80 * 1024 && conv3x3_halo_tap_lds(a.W, 96, 1, 2) <= 80 * 1024) {
+        } else if (conv3x3_halo_tap_lds(a.W, 96, 1) > 80 * 1024 && conv3x3_halo_tap_lds(a.W, 96, 1, 2) <= 80 * 1024) {
             // half-tap weight chunks: 6 KB less LDS, which is what lets TWO blocks share a CU on the 26x26 maps (83.6 -> 77.5 KB)
             g_last_kernel = "conv3x3_halo_tap_kernel<1,96,2>";
             hipLaunchKernelGGL((conv3x3_halo_tap_kernel<1, 96, 2>), dim3(xcd_grid(tiles), a.Npad / 32), dim3(256), conv3x3_halo_tap_lds(a.W, 96, 1, 2), s, a);

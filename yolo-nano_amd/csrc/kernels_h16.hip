@@ -599,14 +599,13 @@ __global__ __launch_bounds__(256) void hwgrad2_kernel(HWgradArgs a)
 
 void launch_hwgrad(const HWgradArgs& a, hipStream_t s)
 {
-    // wider wave tiles where the layer has the columns for them (YN_WG_WIDE=0: the 64 x 64 blocks everywhere)
-    static const int wide = getenv("YN_WG_WIDE") ? atoi(getenv("YN_WG_WIDE")) : 1;
-    const int TN = (wide && a.Np > 64) ? 2 : 1, TK = (wide && a.Kp > 64) ? 2 : 1;
+    // wider wave tiles where the layer has the columns for them
+    const int TN = a.Np > 64 ? 2 : 1, TK = a.Kp > 64 ? 2 : 1;
     const int gn = (a.Np + 64 * TN - 1) / (64 * TN), gk = (a.Kp + 64 * TK - 1) / (64 * TK) * a.taps;
-    static const int wg_blocks = getenv("YN_WG_BLOCKS") ? atoi(getenv("YN_WG_BLOCKS")) : 2048;
+    constexpr int wg_blocks = 2048;
     int slices = wg_blocks / (gn * gk);
     if (slices > 512) slices = 512;
-    static const int slice_rows = getenv("YN_WG_SLICE_ROWS") ? atoi(getenv("YN_WG_SLICE_ROWS")) : 512;
+    constexpr int slice_rows = 512;
     const int max_slices = (a.M + slice_rows - 1) / slice_rows;
     if (slices > max_slices) slices = max_slices;
     const long nk = (long)a.Np * a.Kp * a.taps;
@@ -815,12 +814,11 @@ void launch_hdw(const HDwArgs& a, hipStream_t s)
     const int Ho = (a.H - 1) / a.stride + 1, Wo = (a.W - 1) / a.stride + 1;
     const long total = (long)a.B * Ho * Wo * (a.Cp >> 3);
     const dim3 grid(xcd_grid((unsigned)((total + 255) / 256)));
-    static const int runs_on = getenv("YN_HDW_RUNS") ? atoi(getenv("YN_HDW_RUNS")) : 1;        // 0: one output per thread (A/B runs; no statistics then)
-    if (a.stride == 1 && (runs_on || a.st.acc) && a.Cp <= 256) {
+    if (a.stride == 1 && a.Cp <= 256) {
         const int OC = a.Cp >> 3, PB = 256 / OC;
         const long runs = (long)a.B * a.H * ((a.W + 3) / 4);
         const long nb1 = (runs + PB - 1) / PB;                              // workgroups at one block of runs each
-        static const int gtarget = getenv("YN_HDW_G") ? atoi(getenv("YN_HDW_G")) : 256;      // with statistics: one workgroup per CU - 2 C double atomics each (7.56 / 7.62 / 7.66 / 7.72 / 7.77 ms per step at 256 / 512 / 1 024 / 2 048 / 4 096)
+        constexpr long gtarget = 256;      // with statistics: one workgroup per CU - 2 C double atomics each (7.56 / 7.62 / 7.66 / 7.72 / 7.77 ms per step at 256 / 512 / 1 024 / 2 048 / 4 096)
         const long cap = a.st.acc ? gtarget : 4096;
         const int NR = (int)((nb1 + cap - 1) / cap);
         const dim3 g2(xcd_grid((unsigned)((nb1 + NR - 1) / NR)));
@@ -1121,7 +1119,7 @@ void launch_hcol_reduce(const HRedArgs& a0, int mode, hipStream_t s)
     a.lanes = hlanes_for(a.Cp);
     // one block per CU measured best (11.9 ms per 608 / bs-32 step against 12.0 at 512 and 12.4 at 1024 blocks): the per-block tail
     // (cross-wave combine + 2*C fp64 atomics) outweighs the extra loads in flight
-    static const int gmax = getenv("YN_RED_G") ? atoi(getenv("YN_RED_G")) : 256;
+    constexpr int gmax = 256;
     const dim3 grid(hreduce_blocks(a.M, 256 / a.lanes, gmax));
     if (mode == 0) hipLaunchKernelGGL(hcol_reduce_kernel<0>, grid, dim3(256), 0, s, a);
     else if (mode == 2) hipLaunchKernelGGL(hcol_reduce_kernel<2>, grid, dim3(256), 0, s, a);
@@ -1242,7 +1240,7 @@ static int hstream_blocks(long M, int rowsPer)
     // two workgroups per CU: every workgroup of these launches first adds up the HACC_SLOTS double copies of its layer's sums (30 KB for 116
     // channels at 16 copies), so the prologue traffic grows with the grid - with 32 copies 7.79 ms per 608 / bs-32 step at 1 536 workgroups, 7.68 at
     // 768 and at 512; with 16 copies 7.42 / 7.37 / 7.29 / 7.25 / 7.25 / 7.26 ms at 1 536 / 1 024 / 768 / 512 / 384 / 256
-    static const int cap = getenv("YN_STREAM_CAP") ? atoi(getenv("YN_STREAM_CAP")) : 256 * 2;
+    constexpr int cap = 256 * 2;
     if (b > cap) b = cap;
     if (b < 1) b = 1;
     return (int)b;
@@ -1500,9 +1498,9 @@ void launch_hdw_wgrad(const h16* dy, int dy_ld, const h16* x, int x_ld, int x_of
     const int OL = hlanes_for(Cp);
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long npix = (long)B * Ho * ((Wo + 3) / 4);                    // runs of 4 output pixels
-    static const int runs = getenv("YN_DWW_RUNS") ? atoi(getenv("YN_DWW_RUNS")) : 4;
+    constexpr int runs = 4;
     long G = (npix + (256 / OL) * runs - 1) / ((256 / OL) * runs);
-    static const int gmax = getenv("YN_DWW_G") ? atoi(getenv("YN_DWW_G")) : 2048;
+    constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
     if ((size_t)G * C * 9 > part_cap) G = (long)(part_cap / ((size_t)C * 9));
     if (G < 1) G = 1;
@@ -1570,15 +1568,13 @@ void launch_hstem(const float* x, int B, int H, int W, const float* w, const flo
 
 // dw[oc][r] = sum over output pixels p of patch[p][r] * dy[p][oc]  (r = (ci, ky, kx) < 27).  A block walks its range of pixels in chunks
 // of 64: the chunk's dy rows (h16 -> fp32) and its 64 x 27 input patch go to LDS once (the next chunk's values are requested into
-// registers before the current one is used), then thread = (pixel lane pg < 3, patch element r, channel octet og < 3) accumulates 8
-// channels over the pixels pg, pg + 3, ... from LDS: one x value and 8 dy values per 8 FMAs.  (First version: the same thread roles
-// reading straight from global — 81 threads x 2 loads per pixel, 27-fold redundant: 725 us at 608 x 608, bs 32, at the very end of
-// the backward pass where nothing overlaps it.)
-// MFMA = true (round 4): the accumulation loop - 66 LDS reads and 176 FMAs per thread and 64-pixel chunk, ~70 us of the kernel's 170 at the very end
-// of the step - as dW[24 -> 32][27 -> 32] = dy^T x patch on the f16 MFMA: wavefront w takes the 16 pixels of k-step w of the chunk, gathers its
+// registers before the current one is used).  (First version: thread = (pixel lane, patch element, channel octet) reading straight
+// from global — 81 threads x 2 loads per pixel, 27-fold redundant: 725 us at 608 x 608, bs 32, at the very end of the backward pass
+// where nothing overlaps it.)
+// Round 4: the accumulation - an FMA loop before, 66 LDS reads and 176 FMAs per thread and 64-pixel chunk, ~70 us of the kernel's 170 at the
+// very end of the step - as dW[24 -> 32][27 -> 32] = dy^T x patch on the f16 MFMA: wavefront w takes the 16 pixels of k-step w of the chunk, gathers its
 // dy fragment (exact: dy IS fp16) and its patch fragment from the same LDS tiles, splits the fp32 patch values into hi + lo * 2^-11 (two MFMAs,
 // 2^-22 relative against the fp32 product) and keeps one 32 x 32 accumulator pair; the four wavefronts' tiles are added through LDS at the end.
-template <bool MFMA>
 __global__ __launch_bounds__(256) void hstem_wgrad_kernel(const h16* __restrict__ dy, const float* __restrict__ x, int B, int H, int W,
                                                            float* __restrict__ dw /* slots, reference layout [24][3][3][3] */, size_t slot_stride)
 {
@@ -1634,11 +1630,6 @@ __global__ __launch_bounds__(256) void hstem_wgrad_kernel(const h16* __restrict_
             *reinterpret_cast<float4*>(gs + t * 8 + 4) = make_float4((float)gr[4], (float)gr[5], (float)gr[6], (float)gr[7]);
         }
     };
-    const int pg = t / 81, u = t - pg * 81, r = u / 3, og = u - r * 3;
-    const bool live = pg < 3;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
     const int lane = t & 63, wave = t >> 6, l31 = lane & 31, hh = lane >> 5;
     f32x16 m0, m1;
 #pragma unroll
@@ -1649,59 +1640,36 @@ __global__ __launch_bounds__(256) void hstem_wgrad_kernel(const h16* __restrict_
         stage();
         __syncthreads();
         if (base + P < end) fetch(base + P);
-        if (MFMA) {
-            // k-step `wave` of the chunk: pixels p0 .. p0 + 7 of this half-wave; lane = (dy channel | patch element) l31
-            const int p0 = wave * 16 + hh * 8;
-            h16x8 av, bh, bl;
+        // k-step `wave` of the chunk: pixels p0 .. p0 + 7 of this half-wave; lane = (dy channel | patch element) l31
+        const int p0 = wave * 16 + hh * 8;
+        h16x8 av, bh, bl;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float gv = l31 < 24 ? gs[(p0 + j) * 24 + l31] : 0.0f;
-                const float xv = l31 < 27 ? xs[(p0 + j) * 27 + l31] : 0.0f;
-                av[j] = (h16)gv;
-                const h16 hi = (h16)xv;
-                bh[j] = hi; bl[j] = (h16)((xv - (float)hi) * 2048.0f);
-            }
-            m0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bh, m0, 0, 0, 0);
-            m1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bl, m1, 0, 0, 0);
-        } else if (live) {
-#pragma unroll 2
-            for (int p = pg; p < P; p += 3) {
-                const float xv = xs[p * 27 + r];
-                const float4 g0 = *reinterpret_cast<const float4*>(gs + p * 24 + og * 8), g1 = *reinterpret_cast<const float4*>(gs + p * 24 + og * 8 + 4);
-                acc[0] = __builtin_fmaf(xv, g0.x, acc[0]); acc[1] = __builtin_fmaf(xv, g0.y, acc[1]);
-                acc[2] = __builtin_fmaf(xv, g0.z, acc[2]); acc[3] = __builtin_fmaf(xv, g0.w, acc[3]);
-                acc[4] = __builtin_fmaf(xv, g1.x, acc[4]); acc[5] = __builtin_fmaf(xv, g1.y, acc[5]);
-                acc[6] = __builtin_fmaf(xv, g1.z, acc[6]); acc[7] = __builtin_fmaf(xv, g1.w, acc[7]);
+        for (int j = 0; j < 8; ++j) {
+            const float gv = l31 < 24 ? gs[(p0 + j) * 24 + l31] : 0.0f;
+            const float xv = l31 < 27 ? xs[(p0 + j) * 27 + l31] : 0.0f;
+            av[j] = (h16)gv;
+            const h16 hi = (h16)xv;
+            bh[j] = hi; bl[j] = (h16)((xv - (float)hi) * 2048.0f);
+        }
+        m0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bh, m0, 0, 0, 0);
+        m1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bl, m1, 0, 0, 0);
+    }
+    // m[k]: dy channel n = (k & 3) + 8 (k >> 2) + 4 hh, patch element l31; the four wavefronts' tiles through `red` ([256][8] floats) in two halves
+    float* rf = &red[0][0];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) rf[(wave * 64 + lane) * 8 + k] = __builtin_fmaf(m1[half * 8 + k], 1.0f / 2048.0f, m0[half * 8 + k]);
+        __syncthreads();
+        if (wave == 0 && l31 < 27 && begin < end) {
+            float* out = dw + (size_t)(blockIdx.x & (GRAD_SLOTS - 1)) * slot_stride;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int kk = half * 8 + k, n = (kk & 3) + 8 * (kk >> 2) + 4 * hh;
+                if (n < 24) atomicAdd(out + (size_t)n * 27 + l31, (rf[lane * 8 + k] + rf[(64 + lane) * 8 + k]) + (rf[(128 + lane) * 8 + k] + rf[(192 + lane) * 8 + k]));
             }
         }
-    }
-    if (MFMA) {
-        // m[k]: dy channel n = (k & 3) + 8 (k >> 2) + 4 hh, patch element l31; the four wavefronts' tiles through `red` ([256][8] floats) in two halves
-        float* rf = &red[0][0];
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 8; ++k) rf[(wave * 64 + lane) * 8 + k] = __builtin_fmaf(m1[half * 8 + k], 1.0f / 2048.0f, m0[half * 8 + k]);
-            __syncthreads();
-            if (wave == 0 && l31 < 27 && begin < end) {
-                float* out = dw + (size_t)(blockIdx.x & (GRAD_SLOTS - 1)) * slot_stride;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int kk = half * 8 + k, n = (kk & 3) + 8 * (kk >> 2) + 4 * hh;
-                    if (n < 24) atomicAdd(out + (size_t)n * 27 + l31, (rf[lane * 8 + k] + rf[(64 + lane) * 8 + k]) + (rf[(128 + lane) * 8 + k] + rf[(192 + lane) * 8 + k]));
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[t][j] = acc[j];
-    __syncthreads();
-    if (t < 81 && begin < end) {
-        float* out = dw + (size_t)(blockIdx.x & (GRAD_SLOTS - 1)) * slot_stride;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) atomicAdd(out + (size_t)(og * 8 + j) * 27 + r, red[t][j] + red[t + 81][j] + red[t + 162][j]);
     }
 }
 
@@ -1709,12 +1677,10 @@ void launch_hstem_wgrad(const h16* dy, const float* x, int B, int H, int W, floa
 {
     const long npix = (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
     long G = (npix + 255) / 256;
-    static const int gmax = getenv("YN_STEM_G") ? atoi(getenv("YN_STEM_G")) : 2048;
+    constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
     if (G < 1) G = 1;
-    static const int mfma = getenv("YN_STEM_WG_MFMA") ? atoi(getenv("YN_STEM_WG_MFMA")) : 1;        // 0: the FMA loop (A/B runs)
-    if (mfma) hipLaunchKernelGGL(hstem_wgrad_kernel<true>, dim3((unsigned)G), dim3(256), 0, s, dy, x, B, H, W, dw_slots, slot_stride);
-    else hipLaunchKernelGGL(hstem_wgrad_kernel<false>, dim3((unsigned)G), dim3(256), 0, s, dy, x, B, H, W, dw_slots, slot_stride);
+    hipLaunchKernelGGL(hstem_wgrad_kernel, dim3((unsigned)G), dim3(256), 0, s, dy, x, B, H, W, dw_slots, slot_stride);
 }
 
 // ---- 3x3 stride-2 max pool with recorded arg-max (first maximum in scan order, as ATen) and its gather-form backward; C = 24
@@ -1923,7 +1889,7 @@ void launch_hstem_apply_pool(const HBnApplyArgs& a, int B, int H, int W, h16* ou
 {
     const long npix = (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
     long G = (npix + 84) / 85;
-    static const int gmax = getenv("YN_STEMPOOL_G") ? atoi(getenv("YN_STEMPOOL_G")) : 2048;
+    constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
     hipLaunchKernelGGL(hstem_apply_pool_kernel, dim3((unsigned)(G < 1 ? 1 : G)), dim3(256), 0, s, a, B, H, W, out, idx);
 }
@@ -2054,7 +2020,7 @@ __global__ __launch_bounds__(256) void hstem_bwd_kernel(HRedArgs a, const h16* _
 void launch_hstem_bwd(const HRedArgs& a, const h16* g1, const uint8_t* idx, int B, int H, int W, h16* dy, float* dgamma, float* dbeta, hipStream_t s)
 {
     const long npix = (long)B * H * W;
-    static const int g0 = getenv("YN_STEMBWD_G0") ? atoi(getenv("YN_STEMBWD_G0")) : 2048, g1n = getenv("YN_STEMBWD_G1") ? atoi(getenv("YN_STEMBWD_G1")) : 2048;
+    constexpr long g0 = 2048, g1n = 2048;
     long G = (npix + 84) / 85;
     const long G0 = G > g0 ? g0 : G, G1 = G > g1n ? g1n : G;
     hipLaunchKernelGGL(hstem_bwd_kernel<0>, dim3((unsigned)G0), dim3(256), 0, s, a, g1, idx, B, H, W, dy, dgamma, dbeta);

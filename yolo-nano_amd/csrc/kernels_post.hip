@@ -258,7 +258,7 @@ template <int NT> struct HeadDecodeLds {
 
 template <int NT, int KMAX>
 __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridInfo& g, int scale, float conf_thresh,
-                                                  float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls, int dbg,
+                                                  float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls,
                                                   c3h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int BM = 32, BN = 128 * NT, LD = BN + 4;
@@ -267,9 +267,6 @@ __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridI
     const int m0 = (int)(((bid & 7u) * (nblocks >> 3)) + (bid >> 3)) * BM;      // XCD x streams a contiguous run of rows
     if (m0 >= a.M) return;
     f32x16 acc[NT];
-    if (dbg & 1) {
-        for (int nt = 0; nt < NT; ++nt) for (int r = 0; r < 16; ++r) acc[nt][r] = 0.01f * (float)(r + lane);
-    } else
     gemm_split_tile<1, 4, NT>(a, smem, m0, 0, acc);
     __syncthreads();                                        // every wave is past its last operand read: the raw tile reuses the space
     float* raw = reinterpret_cast<float*>(smem);
@@ -291,7 +288,6 @@ __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridI
     }
     const unsigned magicA = (65536u + (unsigned)g.A - 1u) / (unsigned)g.A;     // c / A == (c * magicA) >> 16 for c < BM * A <= 256
     __syncthreads();
-    if (dbg & 2) return;
     // Decode in three passes so that no per-candidate scalar work is replicated over 16 lanes:
     //   A  16 lanes per candidate, 16 candidates per pass: the class softmax statistics (cand_class) -> LDS
     //   B  one thread per candidate: objectness sigmoid, score, threshold -> scores / cls
@@ -334,10 +330,10 @@ __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridI
 
 template <int NT, int KMAX>
 __global__ __launch_bounds__(256) void head_decode_kernel(GemmArgs a, GridInfo g, int scale, float conf_thresh,
-                                                           float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls, int dbg)
+                                                           float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls)
 {
     __shared__ __attribute__((aligned(16))) c3h16 smem[HeadDecodeLds<NT>::HALVES];
-    head_decode_block<NT, KMAX>(a, g, scale, conf_thresh, boxes, scores, cls, dbg, smem, blockIdx.x, gridDim.x);
+    head_decode_block<NT, KMAX>(a, g, scale, conf_thresh, boxes, scores, cls, smem, blockIdx.x, gridDim.x);
 }
 
 // the three scales' last conv + decode as one launch (problem p = scale p)
@@ -348,7 +344,7 @@ __global__ __launch_bounds__(256) void head_decode_group_kernel(Group<GemmArgs> 
     __shared__ __attribute__((aligned(16))) c3h16 smem[HeadDecodeLds<NT>::HALVES];
     unsigned local, nb;
     const int p = group_problem(q.first, blockIdx.x, local, nb);
-    head_decode_block<NT, KMAX>(q.a[p], g, p, conf_thresh, boxes, scores, cls, 0, smem, local, nb);
+    head_decode_block<NT, KMAX>(q.a[p], g, p, conf_thresh, boxes, scores, cls, smem, local, nb);
 }
 
 template <bool FULL>
@@ -388,8 +384,7 @@ void launch_head_decode(const GemmArgs& a, const GridInfo& g, int scale, float c
 {
     const unsigned blocks = (unsigned)(((a.M + 31) / 32 + 7) & ~7);
     const dim3 grid(blocks), blk(256);
-    static const int dbg = getenv("YN_HD_DBG") ? atoi(getenv("YN_HD_DBG")) : 0;
-#define YN_HD(nt, kmax) hipLaunchKernelGGL((head_decode_kernel<nt, kmax>), grid, blk, 0, s, a, g, scale, conf_thresh, boxes, scores, cls, dbg)
+#define YN_HD(nt, kmax) hipLaunchKernelGGL((head_decode_kernel<nt, kmax>), grid, blk, 0, s, a, g, scale, conf_thresh, boxes, scores, cls)
     if (a.Npad > 128) YN_HD(2, 5);
     else if (g.C <= 16) YN_HD(1, 1);
     else if (g.C <= 32) YN_HD(1, 2);
@@ -2473,18 +2468,15 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     set_sort_attr();
     const int large_cap = wk.large_cap;
     auto mark = [&](const char* k) { if (hook && hook->fn) hook->fn(hook->ctx, k); };
-    // YN_DBG_NMS_SKIP (timing ablation only, outputs are wrong): bit0 sort, bit1 matrix, bit2 resolve
-    static const int skip = getenv("YN_DBG_NMS_SKIP") ? atoi(getenv("YN_DBG_NMS_SKIP")) : 0;
     float4* sbox = reinterpret_cast<float4*>(wk.sbox);
     u64* M = reinterpret_cast<u64*>(wk.matrix);
-    static const int fuse_bs = getenv("YN_NMS_FUSE_BUCKET") ? atoi(getenv("YN_NMS_FUSE_BUCKET")) : 1;       // A/B: 0 = bucket_kernel + sort_kernel also for few segments
     // "few segments" (one to three images at 80 classes): everything of an image's NMS on big workgroups that are all resident at once.  Not for
     // maps with more than 16 K candidates per image (608 x 608: one class of the benchmark's images holds ~10 000 boxes): there the 16 384-key
     // bitonic network of the one-workgroup sort is 60 us of a 0.57 ms call, and the chunked sort + merge (three launches) is shorter
-    static const int few_n = getenv("YN_NMS_FEW_N") ? atoi(getenv("YN_NMS_FEW_N")) : 16384;
+    constexpr int few_n = 16384;
     const bool few = (long)B * C <= 256 && N <= few_n;
     const int32_t* seg_order = wk.seg_order;                // bucket_kernel's size ranking; the fused kernel does not produce one (few segments: nothing to order)
-    if (few && fuse_bs && wk.ctr && !(skip & 1)) {
+    if (few && wk.ctr) {
         seg_order = nullptr;
         static unsigned long long attr_bs = 0;
         if (attr_pending(attr_bs)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, YN_SORT_LARGE * 8);
@@ -2492,41 +2484,36 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
         hipLaunchKernelGGL(bucket_sort_kernel, dim3(C, B), dim3(1024), YN_SORT_LARGE * 8, s, boxes, scores, cls, N, C, wk.seg_count, wk.seg_off, wk.tile_off, wk.bucket,
                            wk.keep, sbox, M, wk.matrix_stride, wk.ctr);
     } else {
-    mark("bucket_kernel");
-    hipLaunchKernelGGL(bucket_kernel, dim3(B), dim3(1024), 2 * C * sizeof(int32_t), s, cls, N, C, wk.seg_count, wk.seg_off, wk.tile_off, wk.bucket, wk.keep,
-                       wk.large_list, large_cap, YN_SORT_SMALL, wk.seg_order);
-    static const int chunked_env = getenv("YN_NMS_SORT_CHUNKS") ? atoi(getenv("YN_NMS_SORT_CHUNKS")) : 1;   // A/B: 0 = one 1024-thread workgroup per large segment
-    const bool chunks = !few && chunked_env && wk.large_list && (size_t)N <= wk.matrix_stride;
-    mark(chunks ? "sort_chunk_kernel" : "sort_kernel");
-    if (!(skip & 1)) {
-    if (few) {
-        // few segments (bs <= 3 at 80 classes): every one gets a 1024-thread / 128 KB-LDS workgroup, all resident at once - one launch
-        // whose duration is the largest segment's sort instead of the small launch followed by the large one (64 -> 35 us at bs = 1)
-        hipLaunchKernelGGL(sort_kernel, dim3(B, C), dim3(1024), YN_SORT_LARGE * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                           N, C, 0, YN_SORT_LARGE, (u64*)nullptr, (size_t)0, (const int32_t*)nullptr, 0, (const int32_t*)wk.seg_order);
-    } else {
-    if (chunks) {
-        // small segments whole + the large segments' 1024-box chunks in one launch of 256-thread workgroups, then the merge (keys in the not yet used matrix area)
-        const int slots = N > YN_SORT_SMALL ? nms_chunk_slots(N, large_cap) : 0;
-        hipLaunchKernelGGL(sort_chunk_kernel, dim3(B, C + slots), dim3(256), YN_SORT_SMALL * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                           N, C, (const int32_t*)wk.seg_order, (const int32_t*)wk.large_list, large_cap, M, wk.matrix_stride);
-        if (N > YN_SORT_SMALL) {
-            mark("sort_merge_kernel");
-            hipLaunchKernelGGL(sort_merge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, boxes, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                               N, C, (const int32_t*)wk.large_list, large_cap, (const u64*)M, wk.matrix_stride);
+        mark("bucket_kernel");
+        hipLaunchKernelGGL(bucket_kernel, dim3(B), dim3(1024), 2 * C * sizeof(int32_t), s, cls, N, C, wk.seg_count, wk.seg_off, wk.tile_off, wk.bucket, wk.keep,
+                           wk.large_list, large_cap, YN_SORT_SMALL, wk.seg_order);
+        const bool chunks = !few && wk.large_list && (size_t)N <= wk.matrix_stride;
+        mark(chunks ? "sort_chunk_kernel" : "sort_kernel");
+        if (few) {
+            // few segments (bs <= 3 at 80 classes): every one gets a 1024-thread / 128 KB-LDS workgroup, all resident at once - one launch
+            // whose duration is the largest segment's sort instead of the small launch followed by the large one (64 -> 35 us at bs = 1)
+            hipLaunchKernelGGL(sort_kernel, dim3(B, C), dim3(1024), YN_SORT_LARGE * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                               N, C, 0, YN_SORT_LARGE, (u64*)nullptr, (size_t)0, (const int32_t*)nullptr, 0, (const int32_t*)wk.seg_order);
+        } else if (chunks) {
+            // small segments whole + the large segments' 1024-box chunks in one launch of 256-thread workgroups, then the merge (keys in the not yet used matrix area)
+            const int slots = N > YN_SORT_SMALL ? nms_chunk_slots(N, large_cap) : 0;
+            hipLaunchKernelGGL(sort_chunk_kernel, dim3(B, C + slots), dim3(256), YN_SORT_SMALL * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                               N, C, (const int32_t*)wk.seg_order, (const int32_t*)wk.large_list, large_cap, M, wk.matrix_stride);
+            if (N > YN_SORT_SMALL) {
+                mark("sort_merge_kernel");
+                hipLaunchKernelGGL(sort_merge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, boxes, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                                   N, C, (const int32_t*)wk.large_list, large_cap, (const u64*)M, wk.matrix_stride);
+            }
+        } else {
+            hipLaunchKernelGGL(sort_kernel, dim3(B, C), dim3(256), YN_SORT_SMALL * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                               N, C, 0, YN_SORT_SMALL, (u64*)nullptr, (size_t)0, (const int32_t*)nullptr, 0, (const int32_t*)wk.seg_order);
+            if (N > YN_SORT_SMALL)                              // only the (few) listed large segments get a 128 KB-LDS workgroup
+                hipLaunchKernelGGL(sort_kernel, dim3(large_cap, B), dim3(1024), YN_SORT_LARGE * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                                   N, C, YN_SORT_SMALL, YN_SORT_LARGE, (u64*)nullptr, (size_t)0, (const int32_t*)wk.large_list, large_cap, (const int32_t*)nullptr);
         }
-    } else {
-    hipLaunchKernelGGL(sort_kernel, dim3(B, C), dim3(256), YN_SORT_SMALL * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                       N, C, 0, YN_SORT_SMALL, (u64*)nullptr, (size_t)0, (const int32_t*)nullptr, 0, (const int32_t*)wk.seg_order);
-    if (N > YN_SORT_SMALL)                                  // only the (few) listed large segments get a 128 KB-LDS workgroup
-        hipLaunchKernelGGL(sort_kernel, dim3(large_cap, B), dim3(1024), YN_SORT_LARGE * 8, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                           N, C, YN_SORT_SMALL, YN_SORT_LARGE, (u64*)nullptr, (size_t)0, (const int32_t*)wk.large_list, large_cap, (const int32_t*)nullptr);
-    }
-    }
-    if (N > YN_SORT_LARGE && !chunks)                       // at most one such segment per image: keys in the (not yet used) matrix area
-        hipLaunchKernelGGL(sort_kernel, dim3(large_cap, B), dim3(1024), 0, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
-                           N, C, YN_SORT_LARGE, 1 << 30, M, wk.matrix_stride, (const int32_t*)wk.large_list, large_cap, (const int32_t*)nullptr);
-    }
+        if (N > YN_SORT_LARGE && !chunks)                   // at most one such segment per image: keys in the (not yet used) matrix area
+            hipLaunchKernelGGL(sort_kernel, dim3(large_cap, B), dim3(1024), 0, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
+                               N, C, YN_SORT_LARGE, 1 << 30, M, wk.matrix_stride, (const int32_t*)wk.large_list, large_cap, (const int32_t*)nullptr);
     }
     const int32_t* m_count = wk.seg_count;
     const int32_t* m_toff = wk.tile_off;
@@ -2543,7 +2530,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
         // The sweep's workgroups carry the segment in LDS (20 bytes per box): 60 KB - two per CU - for maps of up to 16 K candidates (a class above 3 072 boxes stays
         // dense there), 120 KB beyond (608 x 608: ~5 000-box classes); the first four listed segments of an image only (the list is by size: a fifth class above
         // 1 024 boxes is rare, and every listed slot is a workgroup with that LDS to schedule whether it has work or not)
-        sweep = wk.sweep && !few && wk.seg_sparse && wk.work_off && wk.large_list && large_cap > 0 && N > YN_SORT_SMALL && nms_thresh >= 1e-6f && !(skip & 2);
+        sweep = wk.sweep && !few && wk.seg_sparse && wk.work_off && wk.large_list && large_cap > 0 && N > YN_SORT_SMALL && nms_thresh >= 1e-6f;
         sweep_maxn = N <= 16384 ? YN_SWEEP_MAXN / 2 : YN_SWEEP_MAXN;
         sweep_slots = large_cap < 4 ? large_cap : 4;
         const int pre_ranks = (seg_order && wk.pre_sync && (size_t)B * YN_PRE_RANKS <= YN_PRE_TICKETS) ? (C < YN_PRE_RANKS ? C : YN_PRE_RANKS) : 0;      // large segments: band sliced over YN_PRE_Z workgroups
@@ -2558,9 +2545,8 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     if (G < 32) G = 32;
     if (G > 2048) G = 2048;
     mark(diou ? "matrix_kernel<true>" : "matrix_kernel<false>");
-    if (skip & 2) {}
-    else if (diou) hipLaunchKernelGGL(matrix_kernel<true>, dim3(G, B), dim3(256), 0, s, m_box, m_count, wk.seg_off, m_toff, N, C, nms_thresh, M, wk.matrix_stride,
-                                      (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, 0);
+    if (diou) hipLaunchKernelGGL(matrix_kernel<true>, dim3(G, B), dim3(256), 0, s, m_box, m_count, wk.seg_off, m_toff, N, C, nms_thresh, M, wk.matrix_stride,
+                                 (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, 0);
     else      hipLaunchKernelGGL(matrix_kernel<false>, dim3(G, B), dim3(256), 0, s, m_box, m_count, wk.seg_off, m_toff, N, C, nms_thresh, M, wk.matrix_stride,
                                  (const int32_t*)(sweep ? wk.work_off : nullptr), (const int32_t*)(sweep ? wk.seg_sparse : nullptr), (const int32_t*)wk.large_list, large_cap);
     if (sweep) {
@@ -2577,12 +2563,12 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     }
     mark("resolve_kernel");
     const bool split = N > YN_SORT_SMALL && wk.large_list && large_cap > 0;
-    if (!(skip & 4) && (long)B * C <= 256) {
+    if ((long)B * C <= 256) {
         // few segments (bs <= 3 at 80 classes): all of them on the 512-thread kernel in ONE launch — the short walks ride along with the long
         // ones instead of preceding them (one image: -20 us)
         hipLaunchKernelGGL(resolve_large_kernel, dim3(C, B), dim3(512), 0, s, m_count, wk.seg_off, m_toff, m_ids, N, C, M, wk.matrix_stride,
                            wk.keep, (const int32_t*)nullptr, 0, 0);
-    } else if (!(skip & 4)) {
+    } else {
         hipLaunchKernelGGL(resolve_kernel, dim3(B, C), dim3(256), 0, s, m_count, wk.seg_off, m_toff, m_ids, N, C, M, wk.matrix_stride, wk.keep,
                            split ? YN_SORT_SMALL : 1 << 30, seg_order);
         if (split) hipLaunchKernelGGL(resolve_large_kernel, dim3(B, large_cap), dim3(512), 0, s, m_count, wk.seg_off, m_toff, m_ids, N, C, M, wk.matrix_stride,

@@ -132,14 +132,12 @@ struct yn_handle {
     size_t train_arena_bytes = 0;
     // graphs / profiling
     bool use_graph = false;
-    long net_passes = 0;                   // run_network calls so far (dbg_skip)
-    bool dwpw_fuse = true;                 // YN_DWPW_FUSE=0: the heads' depthwise + pointwise pairs as two grouped launches instead of one kernel
-    bool tail_fuse = true;                 // YN_TAIL_FUSE=0: layers .2+.3 and .4+decode of the heads as two grouped kernels instead of one (head_tail_group_kernel)
-    bool down_fuse = true;                 // yn_down_fuse / YN_DOWN_FUSE=0: the main branch of a stride-2 unit as one kernel (down_unit_kernel)
-    bool group_launch = true;              // yn_group_launch / YN_GROUP=0: the three heads' layers (and the laterals) as grouped launches
-    bool fuse_decode = true;               // yn_fuse_decode / YN_FUSE_DECODE=0: yn_infer's last head conv + candidate decode as one kernel
+    bool tail_fuse = true;                 // yn_tail_fuse: off = layers .2+.3 and .4+decode of the heads as two grouped kernels instead of one (head_tail_group_kernel)
+    bool down_fuse = true;                 // yn_down_fuse: the main branch of a stride-2 unit as one kernel (down_unit_kernel)
+    bool group_launch = true;              // yn_group_launch: the three heads' layers (and the laterals) as grouped launches
+    bool fuse_decode = true;               // yn_fuse_decode: yn_infer's last head conv + candidate decode as one kernel
     int fuse_decode_mode = 1;              // 1 = when the stride-8 head has >= 8192 pixels, 2 = always
-    bool exact_f32 = false;                // yn_exact_f32 / YN_EXACT_F32=1: GEMM-shaped convs on the f32 MFMA only (no split-f16 operands)
+    bool exact_f32 = false;                // yn_exact_f32: GEMM-shaped convs on the f32 MFMA only (no split-f16 operands)
     bool range_fallback = false;           // yn_fold_bn found a folded GEMM weight outside the split's range (|w| >= 65504): same effect as exact_f32
     unsigned* range_host = nullptr;        // one word of pinned host memory: set by compact_kernel beside the negative counts (the range flag, out of band);
     unsigned* range_host_dev = nullptr;    // its device view.  While set, yn_infer / yn_pack_detections return YN_STATUS_RANGE; yn_range_status clears it
@@ -147,11 +145,11 @@ struct yn_handle {
                                            // (range_report, yn_device.h; read and cleared by yn_range_status), [2] the same as [0] for a yn_op_* call
     bool autotune = true;
     int force_pw_cfg = -1;                         // yn_set_pw_config (testing aid)
-    int unit_chain = 1;                            // stride-1 ShuffleV2 units as one kernel each: 0 off, 1 where the map is large enough, 2 always (yn_unit_chain / YN_UNIT_CHAIN)
-    bool pw_pipe = true;                           // pw_pipe_kernel among the pointwise candidates (yn_pw_pipe / YN_PW_PIPE=0)
-    int chain_pipe = 1;                            // unit_pipe_kernel (the persistent per-unit walk): 0 never, 1 by the size rule, 2 always (yn_chain_pipe / YN_CHAIN_PIPE)
-    int stage_fuse = 1;                            // all but the last stride-1 unit of a stage as ONE persistent launch (stage_pipe_kernel): 0 off, 1 from 256 tiles, 2 always (yn_stage_fuse / YN_STAGE_FUSE)
-    int stage_pub_early = 0;                       // its tiles raise their ready flag right behind their stores (1) or under the next tile's depthwise phase (0, default: 608 x 608 stage 3 144 vs 150 us, 0.5x bs 128 101 vs 105, 416 bs 32 equal) (YN_STAGE_PUB)
+    int unit_chain = 1;                            // stride-1 ShuffleV2 units as one kernel each: 0 off, 1 where the map is large enough, 2 always (yn_unit_chain)
+    bool pw_pipe = true;                           // pw_pipe_kernel among the pointwise candidates (yn_pw_pipe)
+    int chain_pipe = 1;                            // unit_pipe_kernel (the persistent per-unit walk): 0 never, 1 by the size rule, 2 always (yn_chain_pipe)
+    int stage_fuse = 1;                            // all but the last stride-1 unit of a stage as ONE persistent launch (stage_pipe_kernel): 0 off, 1 from 256 tiles, 2 always (yn_stage_fuse)
+    int stage_pub_early = 0;                       // its tiles raise their ready flag right behind their stores (1) or under the next tile's depthwise phase (0, default: 608 x 608 stage 3 144 vs 150 us, 0.5x bs 128 101 vs 105, 416 bs 32 equal) (yn_stage_fuse publish_early)
     unsigned* stage_sync = nullptr;                // its queue heads / ready flags / exit count: behind the activation arena, zero between launches
     size_t stage_sync_bytes = 0;
     hipEvent_t tune_e0 = nullptr, tune_e1 = nullptr;
@@ -468,8 +466,6 @@ const Layer& L(yn_handle* h, const std::string& name) { return h->layers[h->by_n
 // handle's stream (all configurations are bit-identical, so this only affects speed).  Never runs during capture.
 int tune_pw(yn_handle* h, GemmArgs a)
 {
-    static const int forced = getenv("YN_PW_FORCE_CFG") ? atoi(getenv("YN_PW_FORCE_CFG")) : -1;     // debugging / A-B runs
-    if (forced >= 0) return forced;
     if (h->force_pw_cfg >= 0) return h->force_pw_cfg;
     if (!h->autotune) return -1;
     // the candidates: the split-f16 family for a layer that carries split packs, else the f32-MFMA family (each bit-identical inside)
@@ -525,27 +521,6 @@ int tune_pw(yn_handle* h, GemmArgs a)
     return best;
 }
 
-// Timing ablation (tools/ablate.sh): YN_DBG_SKIP_LAYERS=<substr,substr,...> drops the launches of every layer whose name contains one of
-// the substrings, from the (YN_DBG_SKIP_AFTER, default 8)-th network pass of the handle on - the activation arena then still holds the
-// layer's output of the earlier passes on the same input, so everything downstream (NMS included) does its normal work.
-static bool dbg_skip(yn_handle* h, const std::string& name)
-{
-    static const char* pat = getenv("YN_DBG_SKIP_LAYERS");
-    if (!pat) return false;
-    static const int after = getenv("YN_DBG_SKIP_AFTER") ? atoi(getenv("YN_DBG_SKIP_AFTER")) : 8;
-    if (h->net_passes <= after) return false;
-    std::string p(pat);
-    size_t i = 0;
-    while (i <= p.size()) {
-        const size_t j = p.find(',', i);
-        const std::string tok = p.substr(i, j == std::string::npos ? std::string::npos : j - i);
-        if (!tok.empty() && name.find(tok) != std::string::npos) return true;
-        if (j == std::string::npos) break;
-        i = j + 1;
-    }
-    return false;
-}
-
 GemmArgs pw_args(yn_handle* h, const Layer& l, const float* in, int in_ld, int in_off, long M,
                  float* out, int out_ld, int out_off, const float* pass, int pass_ld, int pass_off, int n_store = 0)
 {
@@ -568,7 +543,6 @@ void run_pw(yn_handle* h, const Layer& l, const float* in, int in_ld, int in_off
 {
     GemmArgs a = pw_args(h, l, in, in_ld, in_off, M, out, out_ld, out_off, pass, pass_ld, pass_off, n_store);
     a.cfg = tune_pw(h, a);
-    if (dbg_skip(h, l.name)) return;
     Bracket br(h, l.name, 2.0 * M * l.cin * l.cout,
                4.0 * (M * (double)(l.cin + l.cout + (pass ? 2 * l.cout : 0)) + (double)l.cin * l.cout));
     launch_pw(a, h->cur);
@@ -582,7 +556,6 @@ void run_dw(yn_handle* h, const Layer& l, const float* in, int in_ld, int in_off
     a.out = out; a.out_ld = out_ld; a.out_off = out_off;
     a.B = B; a.H = H; a.W = W; a.C = l.cout; a.stride = l.stride; a.act = l.act;
     const double Mi = (double)B * H * W, Mo = (double)B * ((H - 1) / l.stride + 1) * ((W - 1) / l.stride + 1);
-    if (dbg_skip(h, l.name)) return;
     Bracket br(h, l.name, 2.0 * Mo * 9 * l.cout, 4.0 * (Mi + Mo) * l.cout);
     launch_dw(a, h->cur);
 }
@@ -619,9 +592,7 @@ int run_unit_chain(yn_handle* h, int stage, int R, float* oA, int B, int H, int 
     // from M = 4 096 pixels only while the chain kernel staged its weights through LDS (eight chunk rounds per GEMM: 32 + 30 + 19 us against 3 x 29 on
     // one image).  With the weights register-direct (round 4) the chain costs one image what its three launches did (0.5245 vs 0.5227 ms at 416,
     // 0.653-0.660 either way at 608; bs 2 / 4 / 8 / 16: 0.554 / 0.622 / 0.714 / 0.847 vs 0.548 / 0.617 / 0.718 / 0.850 ms) and is six launches
-    // less: it chains at every size now (YN_CHAIN_MIN4=<M> restores a threshold).
-    static const long min4 = getenv("YN_CHAIN_MIN4") ? atol(getenv("YN_CHAIN_MIN4")) : 0;       // A/B: smallest M that chains the bf > 128 stage
-    if (h->unit_chain != 2 && bf > 128 && M < min4) return 0;
+    // less: it chains at every size now.
     char nm[96];
     auto name = [&](int bi) { snprintf(nm, sizeof nm, "backbone.stage%d.%d", stage, bi); return std::string(nm); };
     {
@@ -697,10 +668,8 @@ int run_unit_chain(yn_handle* h, int stage, int R, float* oA, int B, int H, int 
         if (ok && launch_stage_pipe(sa, bf, h->stage_pub_early, min_tiles, h->stage_sync_bytes, h->cur, true)) {
             snprintf(nm, sizeof nm, "backbone.stage%d.1-%d.dw+pw2+pw1n", stage, R - 2);
             const std::string sname = nm;
-            if (!dbg_skip(h, sname) && !dbg_skip(h, name(1) + ".chain")) {
-                Bracket br(h, sname, fl, by);
-                (void)launch_stage_pipe(sa, bf, h->stage_pub_early, min_tiles, h->stage_sync_bytes, h->cur);
-            }
+            Bracket br(h, sname, fl, by);
+            (void)launch_stage_pipe(sa, bf, h->stage_pub_early, min_tiles, h->stage_sync_bytes, h->cur);
             staged = R - 2;
         }
     }
@@ -710,7 +679,6 @@ int run_unit_chain(yn_handle* h, int stage, int R, float* oA, int B, int H, int 
         const ChainArgs& a = ua[bi - 1];
         Bracket br(h, P + (last ? ".dw+pw2" : ".dw+pw2+pw1n"), 2.0 * M * bf * (9.0 + bf + (last ? 0.0 : (double)bf)),
                    4.0 * (4.0 * M * bf + (last ? 1.0 : 2.0) * bf * bf + 10.0 * bf));
-        if (dbg_skip(h, P + ".chain")) { br.cancel(); continue; }
         if (!launch_unit_chain(a, h->cur)) {                 // cannot happen after the coverage check above
             br.cancel();
             fail(h, "unit chain: no tile for stage %d unit %d after the coverage check", stage, bi);
@@ -739,7 +707,6 @@ void run_c3(yn_handle* h, const Layer& l, const float* in, const float* in2, int
     a.cfg = -1;
     if (!exact(h)) { a.Wsh = l.ws_hi; a.Wsl = l.ws_lo; }         // split-f16 MFMA path (fp32-class); exact_f32 / range fallback: the f32-MFMA kernel
     a.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
-    if (dbg_skip(h, l.name)) return;
     const double M = (double)a.M;
     const double in2px = resample == 1 ? M / 4 : (resample == 2 ? M * 4 : 0);
     Bracket br(h, l.name, 2.0 * M * 9 * l.cin * l.cout, 4.0 * ((M + in2px) * l.cin + M * l.cout + 9.0 * l.cin * l.cout));
@@ -785,7 +752,6 @@ bool run_pw_group(yn_handle* h, const Layer* const l[], GemmArgs a[], int n, con
             }
         }
     } else if (h->force_pw_cfg >= 0) a[0].cfg = h->force_pw_cfg;
-    if (dbg_skip(h, name)) return true;
     double fl = 0, by = 0;
     for (int p = 0; p < n; ++p) {
         fl += 2.0 * a[p].M * l[p]->cin * l[p]->cout;
@@ -805,7 +771,6 @@ void run_dw_group(yn_handle* h, const Layer* const l[], DwArgs a[], int n, const
         fl += 2.0 * M * 9 * l[p]->cout;
         by += 4.0 * 2 * M * l[p]->cout;
     }
-    if (dbg_skip(h, name)) return;
     Bracket br(h, name, fl, by);
     launch_dw_group(a, n, h->cur);
 }
@@ -867,7 +832,6 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
     const int S = h->grid.S;
     h->arena_used = 0;
     h->cur = h->stream;
-    ++h->net_passes;
 #define TAKE(var, floats)                                                                   \
     float* var = arena_take(h, (size_t)(floats));                                           \
     if (!var) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes)
@@ -879,7 +843,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
         const Layer& l = L(h, "stem");
         const double Mo = (double)B * H1 * H1;
         Bracket br(h, "stem+maxpool", 2.0 * Mo * 27 * 24, 4.0 * ((double)B * 3 * S * S + (double)B * H2 * H2 * 24));
-        if (!dbg_skip(h, "stem")) launch_stem_pool(x, B, S, S, l.w_packed, l.b_packed, l.cout, l.act, a1, h->cur);
+        launch_stem_pool(x, B, S, S, l.w_packed, l.b_packed, l.cout, l.act, a1, h->cur);
     }
     const float* cur = a1;
     int curC = 24, curH = H2;
@@ -915,8 +879,6 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             d.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
             const bool use_down = h->down_fuse && !exact(h) && lp1.cin == curC && lp1.cout == bf && lp2.cin == bf && lp2.cout == bf && ldw.stride == 2 &&
                                   l1d.stride == 2 && l1d.cout == curC && l1p.cin == curC && l1p.cout == bf && down_unit_covers(d);
-            static const int down_b1 = getenv("YN_DOWN_B1") ? atoi(getenv("YN_DOWN_B1")) : 1;      // 0: branch 1 as its own two kernels (A/B runs)
-            static const int down2_env = getenv("YN_DOWN2") ? atoi(getenv("YN_DOWN2")) : 1;        // 0: the wide units (stages 3 / 4) as five launches (A/B runs)
             Down2Args d2{};
             d2.x = cur; d2.cin = curC; d2.y1 = t1;
             d2.wdw = ldw.w_packed; d2.bdw = ldw.b_packed; d2.dw_act = ldw.act;
@@ -925,15 +887,14 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             d2.W3h = l1p.ws_hi; d2.W3l = l1p.ws_lo; d2.b3 = l1p.b_packed; d2.act3 = l1p.act;
             d2.out = oA; d2.B = B; d2.H = curH; d2.W = curH; d2.bf = bf; d2.Npad = lp2.Npad;
             d2.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
-            const bool use_down2 = !use_down && h->down_fuse && down2_env && !exact(h) && lp1.ws_hi && lp1.cin == curC && lp1.cout == bf && lp2.cin == bf && lp2.cout == bf &&
+            const bool use_down2 = !use_down && h->down_fuse && !exact(h) && lp1.ws_hi && lp1.cin == curC && lp1.cout == bf && lp2.cin == bf && lp2.cout == bf &&
                                    ldw.stride == 2 && ldw.cout == bf && l1d.stride == 2 && l1d.cout == curC && l1p.cin == curC && l1p.cout == bf && l1p.Npad == lp2.Npad &&
                                    down2_covers(d2);
             // when the stride-1 units behind it run as a chain, the kernel also computes unit 1's pw1 (on channels [bf, 2bf) of its own output)
             // ... in the launch-latency regime only (at most 64 tiles of 32 pixels: one to a few images - one 608 x 608 image saves two 10-15 us
             // launches).  Beyond that the extra k-steps stream their weights at the CU's L1 rate (each 32-row workgroup pulls the whole
             // matrix): 42 us against 30 + 13 at stage 3 (676 tiles), 58 against 34 + 17 at stage 4 (169 tiles) of a 32-image batch.
-            static const int down2_next = getenv("YN_DOWN2_NEXT") ? atoi(getenv("YN_DOWN2_NEXT")) : 1;     // 0: never, 2: always (A/B runs, tests)
-            const bool next_pays = down2_next == 2 || (down2_next == 1 && Mo <= 32 * 64);
+            const bool next_pays = Mo <= 32 * 64;
             if (use_down2 && next_pays && STAGE_REP[si] > 1 && run_unit_chain(h, si + 2, STAGE_REP[si], oA, B, Ho, Ho, C, oB, t2, t1, nullptr, true) == 1) {
                 snprintf(nm, sizeof nm, "backbone.stage%d.1.b2.pw1", si + 2);
                 const Layer& l1n = L(h, nm);
@@ -942,28 +903,18 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
                     down_chained = true;
                 }
             }
-            if (use_down && !down_b1) {
-                run_dw(h, l1d, cur, curC, 0, B, curH, curH, tdw1, curC, 0);
-                run_pw(h, l1p, tdw1, curC, 0, Mo, tb1, bf, 0, nullptr, 0, 0);
-                d.pass = tb1;
-                Bracket br(h, P0 + ".b2", 2.0 * (Mi * curC * bf + Mo * bf * (9.0 + bf)), 4.0 * (Mi * (double)curC + 3.0 * Mo * bf + (double)curC * bf + (double)bf * bf));
+            if (use_down) {
+                Bracket br(h, P0 + ".unit", 2.0 * (Mi * curC * bf + Mo * bf * (9.0 + bf) + Mo * curC * (9.0 + bf)),
+                           4.0 * (Mi * (double)curC + 2.0 * Mo * bf + 2.0 * (double)curC * bf + (double)bf * bf));
                 launch_down_unit(d, h->cur);
-            } else if (use_down) {
-                if (!dbg_skip(h, P0 + ".unit")) {
-                    Bracket br(h, P0 + ".unit", 2.0 * (Mi * curC * bf + Mo * bf * (9.0 + bf) + Mo * curC * (9.0 + bf)),
-                               4.0 * (Mi * (double)curC + 2.0 * Mo * bf + 2.0 * (double)curC * bf + (double)bf * bf));
-                    launch_down_unit(d, h->cur);
-                }
             } else if (use_down2) {
                 // stages 3 / 4 (cin = bf = 116 / 232): pw1 as a GEMM launch, everything behind it - both depthwise convs, both pointwise convs,
                 // concat + shuffle - as one kernel (down2_kernel): two launches instead of five
                 run_pw(h, lp1, cur, curC, 0, Mi, t1, bf, 0, nullptr, 0, 0);
-                if (!dbg_skip(h, P0 + ".tail")) {
-                    const double nx = down_chained ? 1.0 : 0.0;
-                    Bracket br(h, P0 + (down_chained ? ".dw+pw2|b1+pw1n" : ".dw+pw2|b1"), 2.0 * (Mo * bf * (9.0 + bf) + Mo * curC * (9.0 + bf) + nx * Mo * bf * bf),
-                               4.0 * (Mi * (double)(curC + bf) + (2.0 + nx) * Mo * bf + (double)curC * bf + (1.0 + nx) * bf * bf));
-                    launch_down2(d2, h->cur);
-                }
+                const double nx = down_chained ? 1.0 : 0.0;
+                Bracket br(h, P0 + (down_chained ? ".dw+pw2|b1+pw1n" : ".dw+pw2|b1"), 2.0 * (Mo * bf * (9.0 + bf) + Mo * curC * (9.0 + bf) + nx * Mo * bf * bf),
+                           4.0 * (Mi * (double)(curC + bf) + (2.0 + nx) * Mo * bf + (double)curC * bf + (1.0 + nx) * bf * bf));
+                launch_down2(d2, h->cur);
             } else {
         fork_to(h, 0);                                      // branch1 and branch2 only meet in the fused cat+shuffle
         {
@@ -1041,7 +992,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
     // traffic it removes, i.e. when the stride-8 head is large (bs >= 4 at 416x416); yn_fuse_decode(2) forces it (tests)
     // ... unless the wider fusion applies (head_tail_group_kernel: layers .2-.4 + decode as ONE launch instead of three: bs = 1 0.602 -> 0.593 ms)
     bool tail_possible = false;
-    if (fuse_all && h->tail_fuse && h->dwpw_fuse && h->group_launch && h->grid.C > 32) {
+    if (fuse_all && h->tail_fuse && h->group_launch && h->grid.C > 32) {
         const GemmArgs gf = head_final_args(h, L(h, "head_det_1.4"), nullptr, (long)B * W3 * W3);
         tail_possible = gf.Npad > 128 && gf.Npad <= 256;
     }
@@ -1123,15 +1074,14 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
                 fl += 2.0 * M * NECK * (9.0 + NECK);
                 by += 4.0 * (2.0 * M * NECK + (double)NECK * NECK);
             }
-            if (!h->dwpw_fuse || !dwpw_group_ok(q, 3)) return false;
-            if (dbg_skip(h, name)) return true;
+            if (!dwpw_group_ok(q, 3)) return false;
             Bracket br(h, name, fl, by);
             launch_dwpw_group(q, 3, h->cur);
             return true;
         };
         // layers .2 + .3 + .4 + the decode as ONE grouped kernel (head_tail_group_kernel): layer .3's output never reaches memory
         auto tail_layer = [&](float* const src[3]) {
-            if (!fuse_all || !h->tail_fuse || !h->dwpw_fuse) return false;
+            if (!fuse_all || !h->tail_fuse) return false;
             HeadTailArgs q[3];
             double fl = 0, by = 0;
             for (int hd = 0; hd < 3; ++hd) {
@@ -1150,7 +1100,6 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
                 by += 4.0 * (M * NECK + (double)NECK * NECK + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A);
             }
             if (!head_tail_ok(q, 3, h->grid)) return false;
-            if (dbg_skip(h, "head_det_*.2+3+4")) return true;
             set_last_kernel_name("head_tail_group_kernel");
             Bracket br(h, "head_det_*.2+3+4+decode", fl, by);
             launch_head_tail_group(q, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
@@ -1171,7 +1120,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
                 }
                 set_last_kernel_name("head_decode_group_kernel");
                 Bracket br(h, "head_det_*.4+decode", fl, by);
-                if (!dbg_skip(h, "head_det_*.4")) launch_head_decode_group(g3, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
+                launch_head_decode_group(g3, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
             } else {
                 float* outs[3] = {heads[0], heads[1], heads[2]};
                 ok = pw_layer(4, hC, outs, head_ld, head_ld, "head_det_*.4");
@@ -1258,20 +1207,8 @@ int yn_create(const yn_config* cfg, yn_handle** out)
     if (h->cfg.max_batch < 1) h->cfg.max_batch = 1;
     h->stream = (hipStream_t)cfg->stream;
     h->cur = h->stream;
-    if (const char* e7 = getenv("YN_EXACT_F32")) h->exact_f32 = atoi(e7) != 0;
-    h->nms.prefilter = getenv("YN_NMS_PREFILTER") ? atoi(getenv("YN_NMS_PREFILTER")) : 1;
-    h->nms.sweep = getenv("YN_NMS_SWEEP") ? (atoi(getenv("YN_NMS_SWEEP")) != 0) : 1;
-    if (const char* e9 = getenv("YN_GROUP")) h->group_launch = atoi(e9) != 0;
-    if (const char* e10 = getenv("YN_DOWN_FUSE")) h->down_fuse = atoi(e10) != 0;
-    if (const char* e11 = getenv("YN_DWPW_FUSE")) h->dwpw_fuse = atoi(e11) != 0;
-    if (const char* e12 = getenv("YN_TAIL_FUSE")) h->tail_fuse = atoi(e12) != 0;
-    if (const char* e8 = getenv("YN_FUSE_DECODE")) { h->fuse_decode = atoi(e8) != 0; h->fuse_decode_mode = atoi(e8); }
-    if (const char* e6 = getenv("YN_MULTI_STREAM")) h->multi_stream = atoi(e6) != 0;  // A/B switch: fork independent chains onto side streams
-    if (const char* e = getenv("YN_CHAIN_PIPE")) h->chain_pipe = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
-    if (const char* e = getenv("YN_STAGE_FUSE")) h->stage_fuse = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
-    if (const char* e = getenv("YN_STAGE_PUB")) h->stage_pub_early = atoi(e) != 0;
-    if (const char* e = getenv("YN_PW_PIPE")) h->pw_pipe = atoi(e) != 0;
-    if (const char* e4 = getenv("YN_UNIT_CHAIN")) h->unit_chain = atoi(e4) < 0 ? 0 : (atoi(e4) > 2 ? 2 : atoi(e4));    // A/B switch for the one-kernel-per-unit chain
+    h->nms.prefilter = 1;
+    h->nms.sweep = 1;
     build_layers(h);
     if (set_grid_info(h, cfg->input_size)) { g_create_error = h->err; delete h; return 1; }
     // (hipMemsetAsync on the handle's stream, never hipMemset: ONE operation on the legacy null stream and every later launch of the

@@ -812,8 +812,7 @@ int yn_train_skipped_steps(yn_handle* h, int64_t* count)
 }
 
 // The fp16 step runs the head towers of levels 3 / 4 on fork streams when that measured faster on THIS device (steps 3-6 of a handle time
-// the step both ways): the decision, so that a run can be reproduced (force > 0: pin it to `force - 1`; YN_TRAIN_HEAD_FORK does the same
-// for a whole process).  *decision: -1 undecided yet, 0 one stream, 1 forked.
+// the step both ways): the decision, so that a run can be reproduced (force > 0: pin it to `force - 1`).  *decision: -1 undecided yet, 0 one stream, 1 forked.
 int yn_train_head_fork(yn_handle* h, int force, int* decision)
 {
     YN_ENTER(h);

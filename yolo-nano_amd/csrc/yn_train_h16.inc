@@ -43,8 +43,6 @@ struct HTrainer {
     char* base; size_t used = 0, cap;
     size_t gused = 0;
     std::vector<HRec> recs;
-    int batch = BATCH;
-    bool fuse_dw = true;                                                         // ... of the depthwise run kernel too (YN_TRAIN_FUSE_DW = 0: hcol_reduce launches behind the depthwise convs)
     bool fuse_stats = true, fuse_sums = true;                                   // HColStat epilogues (YN_TRAIN_FUSE_STATS / YN_TRAIN_FUSE_SUMS = 0: separate reduction launches)
     h16* even_dst = nullptr; int even_ld = 0; bool even_done = false;         // back(): also extract the unit gradient's even channels (set by the caller per call)
     // The weight gradients run on a second stream.  A layer's BatchNorm backward writes dy IN PLACE over the pre-BN conv output y (nothing
@@ -154,7 +152,7 @@ struct HTrainer {
             HDwArgs a{};
             a.in = x.p; a.in_ld = x.ld; a.in_off = x.off; a.w = pk.dwf; a.bias = pk.bias; a.out = r.y; a.out_ld = r.Np; a.out_off = 0;
             a.B = B_; a.H = H; a.W = W; a.Cp = x.Cp; a.stride = l.stride; a.accumulate = 0;
-            if (r.acc && fuse_stats && fuse_dw && l.stride == 1 && x.Cp <= 256) { a.st.acc = r.acc; a.st.C = r.oC; a.st.half = r.ohalf; a.st.gap = r.ogap; r.stats_done = true; }   // statistics in the run kernel's epilogue
+            if (r.acc && fuse_stats && l.stride == 1 && x.Cp <= 256) { a.st.acc = r.acc; a.st.C = r.oC; a.st.half = r.ohalf; a.st.gap = r.ogap; r.stats_done = true; }   // statistics in the run kernel's epilogue
             launch_hdw(a, st);
         } else {
             launch_hstem(x_nchw, B_, H, W, pk.dwf, nullptr, r.y, st);
@@ -212,7 +210,7 @@ struct HTrainer {
         launch_hstem_bwd(q, pool_grad, idx, B_, H1, H1, r.y, G(l.bn + ".weight"), G(l.bn + ".bias"), st);
         if (!side) { params_on_side(r, r.y); return; }
         pending.push_back(Pending{&r, r.y});
-        if ((int)pending.size() >= batch) flush_params();
+        if ((int)pending.size() >= BATCH) flush_params();
     }
 
     // ---- backward pieces ----
@@ -238,7 +236,7 @@ struct HTrainer {
         }
         if (!side) { params_on_side(r, d); return d; }
         pending.push_back(Pending{&r, d});
-        if ((int)pending.size() >= batch) flush_params();
+        if ((int)pending.size() >= BATCH) flush_params();
         return d;
     }
     // everything queued so far is complete on the main stream after this point: hand it to the side stream
@@ -256,12 +254,6 @@ struct HTrainer {
     void params_on_side(const HRec& r, const h16* d)
     {
         const Layer& l = *r.l;
-#ifdef YN_EXP_TIMING
-        // (timing experiment, experiment builds only - the gradients are WRONG: the step WITHOUT its weight gradients shows what the side
-        //  stream costs the main one - 6.27 against 7.48 ms)
-        static const int exp_now = getenv("YN_EXP_NOWGRAD") ? atoi(getenv("YN_EXP_NOWGRAD")) : 0;
-        if (exp_now) return;
-#endif
         hipStream_t s2 = side ? side : st;
         if (l.has_bias && l.bn.empty()) {                        // a bias in front of a train-mode BatchNorm has an exactly zero gradient
             HRedArgs q{};
@@ -294,7 +286,7 @@ struct HTrainer {
             HDwArgs a{};
             a.in = d; a.in_ld = r.Np; a.in_off = 0; a.w = pk.dwb; a.bias = nullptr; a.out = dx.p; a.out_ld = dx.ld; a.out_off = dx.off;
             a.B = r.B; a.H = r.H; a.W = r.W; a.Cp = r.Np; a.stride = 1; a.accumulate = accumulate ? 1 : 0;
-            if (below >= 0 && fuse_sums && fuse_dw && !accumulate && dx.off == 0 && r.Np <= 256) {       // this launch writes the COMPLETE dz of layer `below`: its BatchNorm-backward sums on the way
+            if (below >= 0 && fuse_sums && !accumulate && dx.off == 0 && r.Np <= 256) {       // this launch writes the COMPLETE dz of layer `below`: its BatchNorm-backward sums on the way
                 HRec& b = recs[below];
                 const Layer& bl = *b.l;
                 if (b.acc && b.Mo == r.Mi && b.Np == dx.Cp && dx.ld == dx.Cp) {
@@ -343,14 +335,11 @@ int train_body_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
     if (h->multi_stream && !h->profiling && h->train_side && h->train_events.size() >= (size_t)HTrainer::NEV + 1) {
         T.side = h->train_side;
         for (int i = 0; i < HTrainer::NEV; ++i) T.ev[i] = h->train_events[i];
-        static const int bt = getenv("YN_TRAIN_EVBATCH") ? atoi(getenv("YN_TRAIN_EVBATCH")) : HTrainer::BATCH;
-        T.batch = bt > 0 ? bt : 1;
     }
     {
         // (read at every step, not once per process: the tests compare the two forms of a step inside one process)
         const int fs = getenv("YN_TRAIN_FUSE_STATS") ? atoi(getenv("YN_TRAIN_FUSE_STATS")) : 1, fb = getenv("YN_TRAIN_FUSE_SUMS") ? atoi(getenv("YN_TRAIN_FUSE_SUMS")) : 1;
         T.fuse_stats = fs != 0; T.fuse_sums = fb != 0;
-        T.fuse_dw = !(getenv("YN_TRAIN_FUSE_DW") && atoi(getenv("YN_TRAIN_FUSE_DW")) == 0);
     }
     {
         size_t nstat = 0;
@@ -370,7 +359,7 @@ int train_body_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
     const int H1 = S / 2, H2 = S / 4;
     const long M1 = (long)B * H1 * H1, M2 = (long)B * H2 * H2;
     // the stem's BatchNorm + activation + max pool as one kernel, its backward without the full-resolution gradient (kernels_h16.hip,
-    // hstem_apply_pool_kernel / hstem_bwd_kernel; YN_TRAIN_STEM_FUSE=0: the separate launches, A/B runs and tests)
+    // hstem_apply_pool_kernel / hstem_bwd_kernel; YN_TRAIN_STEM_FUSE=0: the separate launches, for the tests)
     const bool stem_fuse = !(getenv("YN_TRAIN_STEM_FUSE") && atoi(getenv("YN_TRAIN_STEM_FUSE")) == 0);
     HTen a0{}, a1 = T.mk(M2, 24);
     if (!stem_fuse) a0 = T.mk(M1, 24);
@@ -604,8 +593,7 @@ int train_step_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
         if (!h->train_side) {
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            static const int lowprio = getenv("YN_TRAIN_SIDE_PRIO") ? atoi(getenv("YN_TRAIN_SIDE_PRIO")) : 1;
-            if (hipStreamCreateWithPriority(&h->train_side, hipStreamNonBlocking, lowprio ? least : 0) != hipSuccess) h->train_side = nullptr;
+            if (hipStreamCreateWithPriority(&h->train_side, hipStreamNonBlocking, least) != hipSuccess) h->train_side = nullptr;
         }
         for (int i = 0; i < 2; ++i)
             if (!h->train_fork[i] && hipStreamCreateWithFlags(&h->train_fork[i], hipStreamNonBlocking) != hipSuccess) h->train_fork[i] = nullptr;
@@ -619,7 +607,7 @@ int train_step_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
     if (!h->train_losses) HIPCHK(h, hipMalloc((void**)&h->train_losses, 4 * sizeof(float)));
 
     // ---- the body: direct, or replayed from / captured into a hipGraph ----
-    // Opt-in (yn_train_graph / YN_TRAIN_GRAPH=1): measured at 608 / bs 32 the replayed step takes 8.93 ms against 8.50 ms for direct launches -
+    // Opt-in (yn_train_graph): measured at 608 / bs 32 the replayed step takes 8.93 ms against 8.50 ms for direct launches -
     // the runtime serialises more of the two-stream graph than the streams themselves do, and the direct path's remaining queue gaps are
     // only ~0.35 ms.  The graph is keyed by everything the launches bake in (x and target pointers, B, S, the executor's switches; the
     // losses go through a buffer of the handle); the first two steps of a key run directly (they allocate: weight packs, the pack table),
@@ -628,10 +616,8 @@ int train_step_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
     // process that already holds many streams (the default bench.py run, after the inference rigs: the runtime multiplexes streams onto a few
     // hardware queues and the forks then serialise behind each other).  So the handle decides by measurement: steps 3-6 of its life run
     // alternately with and without the forks between two timing events, the faster form (minimum of its two samples) stays.
-    static const int fork_env = getenv("YN_TRAIN_HEAD_FORK") ? atoi(getenv("YN_TRAIN_HEAD_FORK")) : -1;
     int trial = -1;
-    if (fork_env >= 0) h->head_fork_now = fork_env != 0;
-    else if (h->head_fork >= 0) h->head_fork_now = h->head_fork;
+    if (h->head_fork >= 0) h->head_fork_now = h->head_fork;
     else if (!h->hpack_table || h->fwd_only[0] || !h->train_fork[0] || !h->train_fork[1] || !h->train_side) h->head_fork_now = 0;       // not yet (steps 1-2 allocate)
     else if (h->fork_trials < 4) {
         trial = h->fork_trials++;
@@ -647,15 +633,14 @@ int train_step_h16(yn_handle* h, const float* x_dev, const float* target_dev, in
         h->head_fork = with_forks < 0.98f * without ? 1 : 0;
         h->head_fork_now = h->head_fork;
     }
-    static const int graph_env = getenv("YN_TRAIN_GRAPH") ? atoi(getenv("YN_TRAIN_GRAPH")) : -1;
-    const bool graphable = (graph_env >= 0 ? graph_env != 0 : h->train_graph) && st != nullptr && !h->profiling && !h->fwd_only[0] && !getenv("YN_TRAIN_POISON") && h->train_graph_misses < 64;
+    const bool graphable = h->train_graph && st != nullptr && !h->profiling && !h->fwd_only[0] && !getenv("YN_TRAIN_POISON") && h->train_graph_misses < 64;
     int rc = 0;
     bool ran = false;
     if (graphable) {
-        // the per-step A/B switches select different launches (and a different arena carve): part of the key, or a flipped switch replays the stale form
-        auto sw = [](const char* n) { const char* v = getenv(n); return (uintptr_t)(v ? atoi(v) + 1 : 0); };
+        // the per-step test switches select different launches (and a different arena carve): part of the key, or a flipped switch replays the stale form
+        auto sw = [](const char* v) { return (uintptr_t)(v ? atoi(v) + 1 : 0); };
         const std::vector<uintptr_t> key{(uintptr_t)x_dev, (uintptr_t)target_dev, (uintptr_t)B, (uintptr_t)S, (uintptr_t)h->multi_stream, (uintptr_t)h->head_fork_now,
-                                         sw("YN_TRAIN_FUSE_STATS") | sw("YN_TRAIN_FUSE_SUMS") << 8 | sw("YN_TRAIN_FUSE_DW") << 16 | sw("YN_TRAIN_STEM_FUSE") << 24};
+                                         sw(getenv("YN_TRAIN_FUSE_STATS")) | sw(getenv("YN_TRAIN_FUSE_SUMS")) << 8 | sw(getenv("YN_TRAIN_STEM_FUSE")) << 16};
         TrainGraph* tg = nullptr;
         for (TrainGraph& g : h->train_graphs) if (g.key == key) { tg = &g; break; }
         if (!tg) {
