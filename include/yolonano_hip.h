@@ -220,6 +220,31 @@ int  yn_preprocess(yn_handle* h, const uint8_t* img_dev, int h0, int w0, int rw,
 int  yn_preprocess_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, int side,
                          const float* mean_host, const float* std_host, float* x_dev);
 
+/* TrainTransforms / ColorTransforms pixel work (data/transforms.py:402-442; call site data/voc.py:231), n images in one launch per
+ * 32: imgs_host[i] = device pointer of frame i, uint8 [h0][w0][3] BGR as cv2.imread gives it -> x_dev float32 [n][3][side][side]
+ * RGB (the network's input batch).  Every random draw and all box arithmetic stay on the host (yolo_nano_amd.TrainTransforms.sample
+ * restates them); per image the device gets
+ *   geom_host[12*i + ...]  int32  0 h0, 1 w0       frame shape (ToAbsoluteCoords :122-130)
+ *                                 2 x, 3 y, 4 w, 5 h   crop (RandomSampleCrop :285-287: rect[0], rect[1], rect[2] - rect[0],
+ *                                                  rect[3] - rect[1]); the uncropped image is 0, 0, w0, h0
+ *                                 6 mirror          RandomMirror :312 fired (image[:, ::-1] of the crop)
+ *                                 7 rw, 8 rh        Resize :79-111 resized extent of the w x h crop (`int(r * size)`)
+ *                                 9 left, 10 top    its place inside the side x side square (`dw // 2`, `dh // 2`)
+ *                                 11 flags          YN_AUG_* bits: which photometric draws fired, and the branch (:365-368)
+ *   photo_host[7*i + ...]  float  0 brightness delta (:222), 1 contrast alpha (:209), 2 saturation factor (:147), 3 hue delta
+ *                                 (:160), each float32(u) of the float64 draw (unused unless its flag is set);
+ *                                 4..6 letterbox pad, BGR: float32(float64(mean[c]) * 255) (Resize.mean :76)
+ * The chain runs per pixel in the reference's order: brightness, then [contrast,] BGR->HSV, saturation, hue, HSV->BGR [, contrast],
+ * nothing clipped; the resize is cv2's float INTER_LINEAR (area fast path for an exact 2:1 reduction, copy when w x h = rw x rh);
+ * Normalize uses mean_host / std_host: 3 host floats each, BGR order.  n == 0 is not an error. */
+#define YN_AUG_BRIGHTNESS     1   /* RandomBrightness fired */
+#define YN_AUG_CONTRAST       2   /* RandomContrast fired */
+#define YN_AUG_CONTRAST_FIRST 4   /* PhotometricDistort drew pd[:-1] (contrast before HSV); clear: pd[1:] (contrast after BGR) */
+#define YN_AUG_SATURATION     8   /* RandomSaturation fired */
+#define YN_AUG_HUE            16  /* RandomHue fired */
+int  yn_train_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, const float* photo_host,
+                              int side, const float* mean_host, const float* std_host, float* x_dev);
+
 /* YOLONano.postprocess :245-279, batched: all_local [B,N,4], all_conf [B,N,C] ->
  * per image b: count[b] = K_b and, in ascending candidate order, out_boxes[b,0:K_b,4],
  * out_scores[b,0:K_b], out_cls[b,0:K_b], out_index[b,0:K_b] (candidate index; may be NULL).

@@ -1752,6 +1752,33 @@ int yn_preprocess_batch(yn_handle* h, int n, const uint8_t* const* imgs, const i
     return 0;
 }
 
+static_assert(YN_AUG_BRIGHTNESS == ynk::AUG_BRIGHT && YN_AUG_CONTRAST == ynk::AUG_CONTRAST && YN_AUG_CONTRAST_FIRST == ynk::AUG_CONTRAST_FIRST &&
+              YN_AUG_SATURATION == ynk::AUG_SAT && YN_AUG_HUE == ynk::AUG_HUE, "yn_train_transform_batch flag bits");
+
+int yn_train_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs, const int32_t* geom, const float* photo, int side,
+                             const float* mean, const float* stdv, float* x)
+{
+    YN_ENTER(h);
+    if (n == 0) return 0;                                   // an empty batch is not an error
+    if (n < 0 || side <= 0) return fail(h, "yn_train_transform_batch: bad arguments (n %d, side %d)", n, side);
+    if (!imgs || !geom || !photo || !x || !mean || !stdv) return fail(h, "yn_train_transform_batch: null pointer");
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f)) return fail(h, "yn_train_transform_batch: std must be positive");
+    for (int i = 0; i < n; ++i) {
+        const int32_t* g = geom + (size_t)i * ynk::AUG_GEOM;
+        if (!imgs[i]) return fail(h, "yn_train_transform_batch: null frame pointer for image %d", i);
+        if (g[0] <= 0 || g[1] <= 0 || g[2] < 0 || g[3] < 0 || g[4] <= 0 || g[5] <= 0 || g[4] > g[1] - g[2] || g[5] > g[0] - g[3])
+            return fail(h, "yn_train_transform_batch: crop (%d,%d) %dx%d outside the %dx%d frame of image %d", g[2], g[3], g[4], g[5], g[1], g[0], i);
+        if (g[7] <= 0 || g[8] <= 0 || g[9] < 0 || g[10] < 0 || g[7] > side - g[9] || g[8] > side - g[10])
+            return fail(h, "yn_train_transform_batch: resized extent %dx%d at (%d,%d) outside %d for image %d", g[7], g[8], g[9], g[10], side, i);
+        if ((g[6] != 0 && g[6] != 1) || (g[11] & ~ynk::AUG_FLAGS_ALL))
+            return fail(h, "yn_train_transform_batch: bad mirror / flags (%d, %d) for image %d", g[6], g[11], i);
+    }
+    launch_train_aug_batch(n, imgs, geom, photo, side, mean, stdv, x, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 int yn_nms_merge(yn_handle* h, const float* boxes, const float* scores, const int32_t* cls, int n, int num_classes, float nms_thresh, int diou,
                  float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count)
 {

@@ -305,6 +305,11 @@ void launch_preprocess(const unsigned char* img, int h0, int w0, int rw, int rh,
                        const float* mean, const float* stdv, float* out, hipStream_t s);
 void launch_preprocess_batch(int n, const unsigned char* const* imgs, const int* geom, int side, const float* mean, const float* stdv,
                              float* out, hipStream_t s);
+// ---- TrainTransforms pixel pass (kernels_aug.hip): the rows of yn_train_transform_batch (include/yolonano_hip.h) ------------------
+constexpr int AUG_GEOM = 12, AUG_PHOTO = 7;    // int32 h0, w0, crop x, y, w, h, mirror, rw, rh, left, top, flags | f32 4 factors + pad[3]
+enum { AUG_BRIGHT = 1, AUG_CONTRAST = 2, AUG_CONTRAST_FIRST = 4, AUG_SAT = 8, AUG_HUE = 16, AUG_FLAGS_ALL = 31, AUG_MIRROR = 32 };
+void launch_train_aug_batch(int n, const unsigned char* const* imgs, const int* geom, const float* photo, int side, const float* mean,
+                            const float* stdv, float* out, hipStream_t s);
 void launch_ema(float* v, const float* m, long n, float d, float one_minus_d, hipStream_t s);
 // flag: int[2] on the device or null — [0] set when g holds a NaN/Inf (the update is then skipped), [1] counts skipped steps
 void launch_sgd(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd, float grad_scale, int first, int* flag, hipStream_t s);
