@@ -2228,4 +2228,10 @@ int yn_eval_size(yn_eval* e, int64_t* records, int64_t* images)
 }  // extern "C"
 #pragma GCC visibility pop
 
+// the training step, in dependency order: shared pieces, the two executors, the wiring they both run, the entry points
+#include "yn_train_shared.inc"
 #include "yn_train.inc"
+#include "yn_train_h16.inc"
+#include "yn_train_h16_ops.inc"
+#include "yn_train_tape.inc"
+#include "yn_train_api.inc"
