@@ -245,6 +245,31 @@ int  yn_preprocess_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, c
 int  yn_train_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, const float* photo_host,
                               int side, const float* mean_host, const float* std_host, float* x_dev);
 
+/* Mosaic samples (data/voc.py:140-211 load_mosaic, then ColorTransforms data/transforms.py:424-442; call site data/voc.py:216-220),
+ * n mosaics in one launch per 14 (the descriptors travel in the kernel arguments): imgs_host[4*i + k] = device pointer of frame k of
+ * mosaic i, uint8 [h0][w0][3] BGR -> x_dev float32 [n][3][side][side] RGB.  The 2*mosaic_size square canvas is never built: every
+ * canvas pixel is computed where the Resize of the canvas reads it.  Every draw and all box arithmetic stay on the host
+ * (yolo_nano_amd.Mosaic.sample restates them); per mosaic the device gets
+ *   geom_host[50*i + 12*k + ...]  int32, frame k = 0..3 in load_mosaic's order (top left, top right, bottom left, bottom right)
+ *                                 0 h0, 1 w0        frame shape (:165)
+ *                                 2 rw, 3 rh        cv2.resize extent `(int(w0 * r), int(h0 * r))`, r = mosaic_size / max(h0, w0)
+ *                                                   (:168-171); w0, h0 when r == 1 (the frame is then pasted unresized)
+ *                                 4 x1a, 5 y1a, 6 x2a, 7 y2a     canvas rectangle `mosaic_img[y1a:y2a, x1a:x2a]` (:175-187)
+ *                                 8 x1b, 9 y1b, 10 x2b, 11 y2b   source rectangle `img_i[y1b:y2b, x1b:x2b]` of the resized frame, same size
+ *   geom_host[50*i + 48]          mirror: RandomMirror :312 fired on the canvas (`image[:, ::-1]`)
+ *   geom_host[50*i + 49]          flags: YN_AUG_* bits, as for yn_train_transform_batch
+ *   photo_host[7*i + ...]  float  0..3 the four photometric factors as for yn_train_transform_batch; 4..6 canvas fill, BGR:
+ *                                 float32(float64(mean[c]) * 255) (:155-156: the canvas is float64, ConvertFromInts makes it float32)
+ * The frame resize is cv2's 8-bit INTER_LINEAR (as yn_preprocess: copy when the extent is the frame's, the area fast path for an
+ * exact 2:1 reduction); the photometric chain then runs on every canvas pixel, the fill included (unlike Resize's letterbox pad,
+ * the fill is part of the image PhotometricDistort sees); the canvas goes to side x side with cv2's float INTER_LINEAR (area fast
+ * path when 2*mosaic_size == 2*side, copy when 2*mosaic_size == side).  A frame pasted later overwrites an earlier one.
+ * Refused before anything is launched, with yn_last_error naming the mosaic and frame: null pointers, non-positive extents, a
+ * canvas rectangle outside [0, 2*mosaic_size], a source rectangle outside the resized frame, rectangle sizes that differ, bad
+ * mirror / flags, non-positive std.  n == 0 is not an error. */
+int  yn_mosaic_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, const float* photo_host,
+                               int mosaic_size, int side, const float* mean_host, const float* std_host, float* x_dev);
+
 /* YOLONano.postprocess :245-279, batched: all_local [B,N,4], all_conf [B,N,C] ->
  * per image b: count[b] = K_b and, in ascending candidate order, out_boxes[b,0:K_b,4],
  * out_scores[b,0:K_b], out_cls[b,0:K_b], out_index[b,0:K_b] (candidate index; may be NULL).

@@ -11,7 +11,7 @@ def __getattr__(name):
     if name in ("YOLONano", "fuse_conv_bn", "Conv", "ShuffleNetV2", "ShuffleV2Block", "shufflenetv2", "SGD", "multi_gt_creator", "ModelEMA", "TestTimeAugmentation", "ValTransforms", "rescale_boxes"):
         from . import model
         return getattr(model, name)
-    if name in ("TrainTransforms", "ColorTransforms", "AugParams"):
+    if name in ("TrainTransforms", "ColorTransforms", "AugParams", "Mosaic", "MosaicParams"):
         from . import augment                                 # numpy only: safe to import in DataLoader workers
         return getattr(augment, name)
     if name in ("VOCEval", "evaluate", "parse_rec", "gt_array", "voc_geometry"):

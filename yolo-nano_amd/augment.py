@@ -16,7 +16,13 @@ Quirks of the reference kept on purpose (DESIGN.md "TrainTransforms on the devic
 `random.uniform(width - w)`, an IoU test that never rejects (max_iou is always inf), no crop ever accepted for the empty-image target
 `zeros([1, 5])` (its box centre is (0, 0)), the crop's width in RandomMirror, no clipping anywhere, the HSV round trip even when no
 HSV draw fired, and a letterbox pad of float32(float64(mean) * 255).
+
+`Mosaic` (data/voc.py:140-233: load_mosaic, then the dataset's ColorTransforms) splits the same way: `sample_ids` / `sample` on the host
+(Python's `random` for the ids and the centre, np.random inside the colour pass), `batch` on the device, where the four uint8 frames
+become one network input without the float64 2S x 2S canvas ever being built (DESIGN.md "Mosaic on the device").  `sample_item` and
+`collate` restate pull_item's branch and fill one batch tensor from a mixed list of single-image and mosaic records.
 """
+import random as pyrandom
 from collections import namedtuple
 
 import numpy as np
@@ -31,6 +37,12 @@ SAMPLE_OPTIONS = (None, (0.1, None), (0.3, None), (0.7, None), (0.9, None), (Non
 AugParams = namedtuple("AugParams", "geom photo")
 AugParams.__doc__ = """One image's device parameters: geom int32 [12] = h0, w0, crop x, y, w, h, mirror, rw, rh, left, top, flags;
 photo float32 [7] = brightness, contrast, saturation, hue (float32 of the float64 draws), letterbox pad B, G, R."""
+
+
+MosaicParams = namedtuple("MosaicParams", "geom photo")
+MosaicParams.__doc__ = """One mosaic's device parameters: geom int32 [50] = per frame k (12 values at 12*k) h0, w0, rw, rh, canvas
+rectangle x1a, y1a, x2a, y2a, source rectangle x1b, y1b, x2b, y2b; then mirror, flags; photo float32 [7] as AugParams (the pad is
+the canvas fill)."""
 
 
 def letterbox(h0, w0, size):
@@ -185,3 +197,147 @@ class ColorTransforms(TrainTransforms):
     """data/transforms.py:424-442: TrainTransforms without RandomSampleCrop (the colour pass of mosaic batches)."""
 
     crop = False
+
+
+def place(i, h, w, xc, yc, s):
+    """load_mosaic's four placement cases (data/voc.py:174-185) for resized frame i of h x w around the centre (xc, yc) of the
+    2s x 2s canvas: (x1a, y1a, x2a, y2a) on the canvas, (x1b, y1b, x2b, y2b) in the frame."""
+    if i == 0:                                                          # top left
+        x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+        x1b, y1b, x2b, y2b = w - (x2a - x1a), h - (y2a - y1a), w, h
+    elif i == 1:                                                        # top right
+        x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, s * 2), yc
+        x1b, y1b, x2b, y2b = 0, h - (y2a - y1a), min(w, x2a - x1a), h
+    elif i == 2:                                                        # bottom left
+        x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(s * 2, yc + h)
+        x1b, y1b, x2b, y2b = w - (x2a - x1a), 0, w, min(y2a - y1a, h)
+    else:                                                               # bottom right
+        x1a, y1a, x2a, y2a = xc, yc, min(xc + w, s * 2), min(s * 2, yc + h)
+        x1b, y1b, x2b, y2b = 0, 0, min(w, x2a - x1a), min(y2a - y1a, h)
+    return (x1a, y1a, x2a, y2a), (x1b, y1b, x2b, y2b)
+
+
+def use_mosaic(mosaic):
+    """pull_item's branch (data/voc.py:216): `self.mosaic and np.random.randint(2)` - the draw happens only when mosaic is on."""
+    return bool(mosaic and np.random.randint(2))
+
+
+class Mosaic(object):
+    """load_mosaic (data/voc.py:140-211, data/coco.py:126-197) followed by the dataset's `color_augment` (ColorTransforms), with the
+    pixel work on the device: four uint8 BGR frames -> one float32 [3,size,size] network input, the 2S x 2S canvas never built.
+
+    `sample_ids` and `sample` are the host half (Python's `random` for load_mosaic's own draws, `np.random` inside
+    `color_augment.sample`, as in the reference; numpy only); `batch` is the device half.  Quirks kept: the canvas is float64 and its
+    fill float64(mean) * 255 goes through the photometric chain as part of the image; `int()` truncates the centre and the resized
+    extents; a frame whose long side equals `img_size` is pasted unresized (`r != 1`)."""
+
+    def __init__(self, img_size, color_augment):
+        self.img_size = int(img_size)
+        self.color_augment = color_augment
+
+    def sample_ids(self, index, n_ids):
+        """[index, j2, j3, j4]: `random.sample(self.ids[:index] + self.ids[index+1:], 3)` (:141-145) by position.  Sampling
+        range(n_ids - 1) consumes the same draws and picks the same positions as sampling the list itself."""
+        picks = pyrandom.sample(range(n_ids - 1), 3)
+        return [index] + [j if j < index else j + 1 for j in picks]
+
+    def compose(self, shapes, targets, center=None):
+        """load_mosaic without the pixels: the four (h0, w0) shapes and four target lists (rows x1, y1, x2, y2 as fractions, class;
+        a list may be empty) -> (frames int32 [4,12] = the per-frame part of MosaicParams.geom, (yc, xc), mosaic_tg float64 [n,5]).
+        `center=(yc, xc)` replaces the two `random.uniform` draws."""
+        s = self.img_size
+        if center is None:
+            yc, xc = [int(pyrandom.uniform(-x, 2 * s + x)) for x in [(-s) // 2, (-s) // 2]]     # :158, yc first
+        else:
+            yc, xc = int(center[0]), int(center[1])
+        frames = np.zeros((4, 12), np.int32)
+        mosaic_tg = []
+        for i in range(4):
+            target_i = np.array(targets[i])
+            h0, w0 = int(shapes[i][0]), int(shapes[i][1])
+            r = s / max(h0, w0)                                          # :168
+            h, w = h0, w0
+            if r != 1:
+                w, h = int(w0 * r), int(h0 * r)                          # cv2.resize(img_i, (int(w0 * r), int(h0 * r)))
+                if w <= 0 or h <= 0:
+                    raise ValueError("mosaic frame %d: %dx%d resizes to %dx%d at img_size %d" % (i, w0, h0, w, h, s))
+            a, b = place(i, h, w, xc, yc, s)
+            frames[i] = (h0, w0, w, h) + a + b
+            padw = a[0] - b[0]
+            padh = a[1] - b[1]
+            target_i_ = target_i.copy()
+            if len(target_i) > 0:                                        # :193-200
+                target_i_[:, 0] = (w * (target_i[:, 0]) + padw)
+                target_i_[:, 1] = (h * (target_i[:, 1]) + padh)
+                target_i_[:, 2] = (w * (target_i[:, 2]) + padw)
+                target_i_[:, 3] = (h * (target_i[:, 3]) + padh)
+                mosaic_tg.append(target_i_)
+        if len(mosaic_tg) == 0:                                          # :202-209
+            mosaic_tg = np.zeros([1, 5])
+        else:
+            mosaic_tg = np.concatenate(mosaic_tg, axis=0)
+            np.clip(mosaic_tg[:, :4], 0, 2 * s, out=mosaic_tg[:, :4])
+            mosaic_tg[:, :4] /= (s * 2)
+        return frames, (yc, xc), mosaic_tg
+
+    def sample(self, shapes, targets, center=None):
+        """The host half of one mosaic sample -> (MosaicParams, boxes, labels, scale, offset), as pull_item's mosaic branch
+        (:218-220) returns them."""
+        s = self.img_size
+        frames, _, target = self.compose(shapes, targets, center)
+        rec, boxes, labels, scale, offset = self.color_augment.sample((2 * s, 2 * s), target[:, :4], target[:, 4])
+        geom = np.concatenate([frames.reshape(-1), [rec.geom[6], rec.geom[11]]]).astype(np.int32)
+        return MosaicParams(geom, rec.photo), boxes, labels, scale, offset
+
+    def batch(self, frame_quads, records, out=None):
+        """The device half: per mosaic its four uint8 HxWx3 BGR frames (numpy arrays or CUDA uint8 tensors) and its record -> x
+        float32 [n,3,size,size] on the device."""
+        import torch
+        ca = self.color_augment
+        hd = ca._h()
+        assert len(frame_quads) == len(records) and all(len(q) == 4 for q in frame_quads)
+        frames = [im if isinstance(im, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(im, dtype=np.uint8))
+                  for q in frame_quads for im in q]
+        frames = [f.to(hd.device, non_blocking=True).contiguous() for f in frames]
+        geom = np.stack([r.geom for r in records]) if records else np.zeros((0, 50), np.int32)
+        photo = np.stack([r.photo for r in records]) if records else np.zeros((0, 7), np.float32)
+        return hd.mosaic_transform_batch(frames, geom, photo, self.img_size, ca.size, ca._mean32, ca._std32, out=out)
+
+
+def sample_item(index, n_ids, load, transform, mosaic=None):
+    """pull_item (data/voc.py:214-233) up to the pixels, for a worker: `load(j) -> (uint8 frame, target list)` is the dataset's
+    load_img_targets, `transform` its TrainTransforms, `mosaic` its Mosaic or None.  -> (frames, record, target): `frames` is the one
+    frame or the list of four, `record` an AugParams or MosaicParams for `collate`, `target` the [n,5] rows of :233."""
+    if use_mosaic(mosaic is not None):
+        ids = mosaic.sample_ids(index, n_ids)
+        loaded = [load(j) for j in ids]
+        frames = [f for f, _ in loaded]
+        rec, boxes, labels, _, _ = mosaic.sample([f.shape for f in frames], [t for _, t in loaded])
+    else:
+        frames, target = load(index)
+        target = np.zeros([1, 5]) if len(target) == 0 else np.array(target)
+        rec, boxes, labels, _, _ = transform.sample(frames.shape, target[:, :4], target[:, 4])
+    return frames, rec, np.hstack((boxes, np.expand_dims(labels, axis=1)))
+
+
+def collate(transform, mosaic, items, out=None):
+    """The mixed batch: items = [(frames, record), ...] from `sample_item` -> ONE float32 [B,3,size,size] tensor on the device, in the
+    items' order, with one yn_train_transform_batch call for all single images and one yn_mosaic_transform_batch call for all
+    mosaics.  A kind whose samples fill a run of neighbouring slots is written in place; otherwise it is computed into a buffer of
+    its own and copied to its slots on the device."""
+    import torch
+    size = transform.size
+    hd = transform._h()
+    if out is None:
+        out = torch.empty((len(items), 3, size, size), dtype=torch.float32, device=hd.device)
+    assert tuple(out.shape) == (len(items), 3, size, size)
+    kinds = [[k for k, (_, r) in enumerate(items) if isinstance(r, MosaicParams) == m] for m in (False, True)]
+    for slots, run in zip(kinds, (transform.batch, None if mosaic is None else mosaic.batch)):
+        if not slots:
+            continue
+        frames, recs = [items[k][0] for k in slots], [items[k][1] for k in slots]
+        if slots[-1] - slots[0] + 1 == len(slots):
+            run(frames, recs, out=out[slots[0]:slots[-1] + 1])
+        else:
+            out.index_copy_(0, torch.as_tensor(slots, device=out.device), run(frames, recs))
+    return out

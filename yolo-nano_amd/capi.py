@@ -93,6 +93,7 @@ SIGNATURES = {
     "yn_preprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "yn_preprocess_batch": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yn_train_transform_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "yn_mosaic_transform_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "yn_nms_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "yn_ema_update": (_i32, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "yn_sgd_step": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _f32, _f32, _f32, _f32, _i32]),
@@ -572,6 +573,31 @@ class Handle:
         self._ck(self.lib.yn_train_transform_batch(self.h, n, ctypes.cast(ptrs, ctypes.c_void_p), geom.ctypes.data_as(ctypes.c_void_p),
                                                    photo.ctypes.data_as(ctypes.c_void_p), int(side), ctypes.cast(m, ctypes.c_void_p),
                                                    ctypes.cast(sd, ctypes.c_void_p), out.data_ptr()), "yn_train_transform_batch")
+        return out
+
+    def mosaic_transform_batch(self, imgs_u8, geom, photo, mosaic_size, side, mean, std, out=None):
+        """The pixel work of n mosaic samples (yn_mosaic_transform_batch): imgs_u8 = list of 4n uint8 [h0,w0,3] CUDA tensors (four
+        frames per mosaic, in load_mosaic's order), geom = int32 [n,50], photo = float32 [n,7] (the rows the header documents) ->
+        float32 [n,3,side,side]."""
+        n = len(imgs_u8) // 4
+        assert len(imgs_u8) == 4 * n
+        geom = np.ascontiguousarray(geom, dtype=np.int32).reshape(n, 50)
+        photo = np.ascontiguousarray(photo, dtype=np.float32).reshape(n, 7)
+        if out is None:
+            out = torch.empty((n, 3, side, side), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * 3 * side * side
+        ptrs = (ctypes.c_void_p * max(4 * n, 1))()
+        for i, im in enumerate(imgs_u8):
+            assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous() and im.is_cuda
+            assert (int(im.shape[0]), int(im.shape[1])) == (int(geom[i // 4, 12 * (i % 4)]), int(geom[i // 4, 12 * (i % 4) + 1])), \
+                "frame %d of mosaic %d does not match its record" % (i % 4, i // 4)
+            ptrs[i] = im.data_ptr()
+        m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self._ck(self.lib.yn_mosaic_transform_batch(self.h, n, ctypes.cast(ptrs, ctypes.c_void_p), geom.ctypes.data_as(ctypes.c_void_p),
+                                                    photo.ctypes.data_as(ctypes.c_void_p), int(mosaic_size), int(side),
+                                                    ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p), out.data_ptr()),
+                 "yn_mosaic_transform_batch")
         return out
 
     def nms_merge(self, boxes, scores, cls, num_classes, nms_thresh, diou=False):

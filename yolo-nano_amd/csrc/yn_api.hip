@@ -1779,6 +1779,41 @@ int yn_train_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs, co
     return 0;
 }
 
+int yn_mosaic_transform_batch(yn_handle* h, int n, const uint8_t* const* imgs, const int32_t* geom, const float* photo, int mosaic_size,
+                              int side, const float* mean, const float* stdv, float* x)
+{
+    YN_ENTER(h);
+    if (n == 0) return 0;                                   // an empty batch is not an error
+    if (n < 0 || side <= 0 || mosaic_size <= 0 || mosaic_size > (1 << 14))
+        return fail(h, "yn_mosaic_transform_batch: bad arguments (n %d, mosaic_size %d, side %d)", n, mosaic_size, side);
+    if (!imgs || !geom || !photo || !x || !mean || !stdv) return fail(h, "yn_mosaic_transform_batch: null pointer");
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f)) return fail(h, "yn_mosaic_transform_batch: std must be positive");
+    const int m2 = 2 * mosaic_size;
+    for (int i = 0; i < n; ++i) {
+        const int32_t* g = geom + (size_t)i * ynk::MOS_GEOM;
+        for (int k = 0; k < 4; ++k) {
+            const int32_t* q = g + 12 * k;
+            if (!imgs[(size_t)i * 4 + k]) return fail(h, "yn_mosaic_transform_batch: null frame pointer for mosaic %d frame %d", i, k);
+            if (q[0] <= 0 || q[1] <= 0 || q[2] <= 0 || q[3] <= 0)
+                return fail(h, "yn_mosaic_transform_batch: non-positive extent (%dx%d -> %dx%d) for mosaic %d frame %d", q[1], q[0], q[2], q[3], i, k);
+            if (q[4] < 0 || q[5] < 0 || q[6] < q[4] || q[7] < q[5] || q[6] > m2 || q[7] > m2)
+                return fail(h, "yn_mosaic_transform_batch: canvas rectangle (%d,%d)-(%d,%d) outside [0, %d] for mosaic %d frame %d", q[4], q[5], q[6], q[7], m2, i, k);
+            if (q[8] < 0 || q[9] < 0 || q[10] < q[8] || q[11] < q[9] || q[10] > q[2] || q[11] > q[3])
+                return fail(h, "yn_mosaic_transform_batch: source rectangle (%d,%d)-(%d,%d) outside the %dx%d resized frame for mosaic %d frame %d",
+                            q[8], q[9], q[10], q[11], q[2], q[3], i, k);
+            if (q[6] - q[4] != q[10] - q[8] || q[7] - q[5] != q[11] - q[9])
+                return fail(h, "yn_mosaic_transform_batch: rectangle sizes differ (%dx%d canvas, %dx%d source) for mosaic %d frame %d",
+                            q[6] - q[4], q[7] - q[5], q[10] - q[8], q[11] - q[9], i, k);
+        }
+        if ((g[48] != 0 && g[48] != 1) || (g[49] & ~ynk::AUG_FLAGS_ALL))
+            return fail(h, "yn_mosaic_transform_batch: bad mirror / flags (%d, %d) for mosaic %d", g[48], g[49], i);
+    }
+    launch_mosaic_aug_batch(n, imgs, geom, photo, mosaic_size, side, mean, stdv, x, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 int yn_nms_merge(yn_handle* h, const float* boxes, const float* scores, const int32_t* cls, int n, int num_classes, float nms_thresh, int diou,
                  float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count)
 {

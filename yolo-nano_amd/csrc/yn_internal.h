@@ -310,6 +310,10 @@ constexpr int AUG_GEOM = 12, AUG_PHOTO = 7;    // int32 h0, w0, crop x, y, w, h,
 enum { AUG_BRIGHT = 1, AUG_CONTRAST = 2, AUG_CONTRAST_FIRST = 4, AUG_SAT = 8, AUG_HUE = 16, AUG_FLAGS_ALL = 31, AUG_MIRROR = 32 };
 void launch_train_aug_batch(int n, const unsigned char* const* imgs, const int* geom, const float* photo, int side, const float* mean,
                             const float* stdv, float* out, hipStream_t s);
+// mosaic pass: the rows of yn_mosaic_transform_batch — int32 4 x {h0, w0, rw, rh, x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b}, mirror, flags
+constexpr int MOS_GEOM = 50;
+void launch_mosaic_aug_batch(int n, const unsigned char* const* imgs, const int* geom, const float* photo, int mosaic_size, int side,
+                             const float* mean, const float* stdv, float* out, hipStream_t s);
 void launch_ema(float* v, const float* m, long n, float d, float one_minus_d, hipStream_t s);
 // flag: int[2] on the device or null — [0] set when g holds a NaN/Inf (the update is then skipped), [1] counts skipped steps
 void launch_sgd(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd, float grad_scale, int first, int* flag, hipStream_t s);
