@@ -323,6 +323,42 @@ int  yn_eval_records(yn_handle* h, yn_eval* e, int32_t* host, int64_t cap);
 /* records and images added so far (host counters, no device work) */
 int  yn_eval_size(yn_eval* e, int64_t* records, int64_t* images);
 
+/* ---- COCO box AP: what evaluator/cocoapi_evaluator.py:85-130 obtains from pycocotools' COCOeval(iouType 'bbox') - computeIoU,
+ * evaluateImg and accumulate on the device (COCO box AP); summarize, 12 means over the two arrays, is the caller's
+ * (yolo_nano_amd.coco does it in numpy).  An object of its own like yn_eval; every call launches on the stream of the handle given.
+ * All orders are COCOeval's stable ones: by score descending; inside an image equal scores in results-list order; between images
+ * equal scores in ascending image id.  Parity with pycocotools itself is unpinned where the library cannot be installed; the
+ * host restatement tests/coco_oracle.py is what the device is tested against, bit for bit. */
+typedef struct yn_coco yn_coco;
+/* num_classes 1..2000 (all are evaluated), max_det = the last entry of maxDets (100), 1..1023: what is kept per (image, category) */
+int  yn_coco_create(yn_handle* h, int num_classes, int max_det, yn_coco** out);
+void yn_coco_destroy(yn_coco* e);
+/* drops every image, detection and ground-truth box added so far */
+int  yn_coco_reset(yn_handle* h, yn_coco* e);
+/* B images: rec_dev / offsets_dev as yn_pack_detections wrote them (device), geom_host int32 [B][7] as for yn_eval_add,
+ * image_ids_host int64 [B], gt_host float64 [G][5] = x, y, w, h, area (area as the annotation file gives it), gt_meta_host int32
+ * [G][2] = category index, iscrowd, gt_offsets_host [B+1].  Boxes are mapped to image pixels in the evaluator's float32 steps;
+ * per (image, category) the max_det best by score are kept (float32 x1, y1, x2, y2, score), so the store is bounded by
+ * max_det * num_classes per image.  Two 4-byte read-backs; a negative offsets[B] (the split-f16 range mark) returns
+ * YN_STATUS_RANGE and adds nothing.  Limits, each refused by name: 4096 ground-truth boxes per (image, category), 2^21 images,
+ * 2^31 - 1 detections kept and ground-truth boxes in all; non-finite ground truth or a category outside 0..C-1 fails here. */
+int  yn_coco_add(yn_handle* h, yn_coco* e, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom_host,
+                 const int64_t* image_ids_host, const double* gt_host, const int32_t* gt_meta_host, const int32_t* gt_offsets_host);
+/* The parameters are the caller's doubles (numpy's linspace values), never recomputed: iou_thrs [num_iou <= 10], rec_thrs
+ * [num_rec <= 256, ascending], area_rng [num_area <= 4][2], max_dets [num_max_dets <= 8, ascending, last == max_det].
+ * precision_host [num_iou][num_rec][C][num_area][num_max_dets] and recall_host [num_iou][C][num_area][num_max_dets] in
+ * COCOeval's layout, -1 where a category has no non-ignored ground truth.  Fails, naming it, if an image id was added twice or a
+ * detection had a non-finite coordinate or score or a category outside 0..C-1. */
+int  yn_coco_finish(yn_handle* h, yn_coco* e, const double* iou_thrs_host, int num_iou, const double* rec_thrs_host, int num_rec,
+                    const double* area_rng_host, int num_area, const int32_t* max_dets_host, int num_max_dets, double* precision_host,
+                    double* recall_host);
+/* testing aid, after yn_coco_finish: the store det_host [n][5] = x1, y1, x2, y2, score; seg_host [images * C + 1] = where the
+ * detections of (image in add order, category) start, in rank order; flags_host [num_area][n] with bit t = matched at IoU
+ * threshold t and bit 16 + t = ignored at it.  Any pointer may be NULL. */
+int  yn_coco_matches(yn_handle* h, yn_coco* e, float* det_host, int64_t* seg_host, uint32_t* flags_host, int num_area);
+/* detections kept and images added so far (host counters, no device work) */
+int  yn_coco_size(yn_coco* e, int64_t* detections, int64_t* images);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

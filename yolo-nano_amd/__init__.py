@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("VOCEval", "evaluate", "parse_rec", "gt_array", "voc_geometry"):
         from . import voc                                     # evaluate.py would be shadowed by its own evaluate()
         return getattr(voc, name)
+    if name in ("COCOEval", "coco_gt_arrays", "evaluate_coco"):
+        from . import coco
+        return getattr(coco, name)
     if name in ("Handle", "YnError", "YnRangeError", "load_library"):
         from . import capi
         return getattr(capi, name)

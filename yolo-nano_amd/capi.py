@@ -118,6 +118,13 @@ SIGNATURES = {
     "yn_eval_curve": (_i32, [_vp, _vp, _i32, _vp, _vp, ctypes.c_int64]),
     "yn_eval_records": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
     "yn_eval_size": (_i32, [_vp, _i64p, _i64p]),
+    "yn_coco_create": (_i32, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
+    "yn_coco_destroy": (None, [_vp]),
+    "yn_coco_reset": (_i32, [_vp, _vp]),
+    "yn_coco_add": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_coco_finish": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "yn_coco_matches": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32]),
+    "yn_coco_size": (_i32, [_vp, _i64p, _i64p]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

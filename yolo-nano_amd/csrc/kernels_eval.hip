@@ -23,12 +23,15 @@
 #include <vector>
 
 #include "yn_internal.h"
+#include "yn_eval_shared.h"
 
 namespace ynk {
 
 namespace {
 
-constexpr int EV_LOCAL = 2048;                 // keys per workgroup in the LDS stages of the bitonic sort
+using namespace evs;                           // unletterbox, bitonic_sort, lower_bound, block_scan_incl, EVCHK, grow
+
+constexpr int EV_LOCAL = SORT_LOCAL;           // keys per workgroup in the LDS stages of the bitonic sort
 constexpr int EV_MAX_GT = 4096;                // GT per (image, class): 64 chunks of 64, one claimed bit per chunk in each lane's mask
 constexpr uint64_t KEY_IDX_BITS = 43;          // key A: class 11 | 1000-k 10 | ingest index 43
 constexpr uint64_t KEY_LOCAL_BITS = 22;        // key B: class 11 | image 21 | 1000-k 10 | index in image 22
@@ -53,27 +56,13 @@ __global__ void eval_ingest_kernel(const float* __restrict__ rec, const int32_t*
         if (offsets[i + 1] - offsets[i] >= (1 << KEY_LOCAL_BITS)) atomicOr(err, EV_ERR_IMAGE);
     }
     if (i >= total) return;
-    int lo = 0, hi = B;                         // image b: offsets[b] <= i < offsets[b+1]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid] <= i) lo = mid; else hi = mid;
-    }
-    const int b = lo;
-    const int32_t* g = geom + 7 * b;            // w0, h0, rw, rh, left, top, side
-    const double side = (double)g[6];
-    const double off[2] = {(double)g[4] / side, (double)g[5] / side};   // ValTransforms.geometry: left/h, top/w
-    const double sc[2] = {(double)g[2] / side, (double)g[3] / side};    //                         w/h, h/w (1. on the long side)
-    const double size[2] = {(double)g[0], (double)g[1]};
+    const int b = image_of(offsets, B, i);
     const float* r = rec + 6 * i;
     const int64_t o = n0 + i;
     int32_t* out = soa;
-    for (int c = 0; c < 4; ++c) {               // bboxes -= offset; bboxes /= scale; bboxes *= size  (float32 array, float64 operands)
-        float v = r[c];
-        v = (float)((double)v - off[c & 1]);
-        v = (float)((double)v / sc[c & 1]);
-        v = (float)((double)v * size[c & 1]);
-        out[(3 + c) * cap + o] = tenths(v + 1.0f, err);   // dets[k, c] + 1: a float32 addition (NEP 50)
-    }
+    float px[4];
+    unletterbox(r, geom + 7 * b, px);           // bboxes -= offset; bboxes /= scale; bboxes *= size  (float32 array, float64 operands)
+    for (int c = 0; c < 4; ++c) out[(3 + c) * cap + o] = tenths(px[c] + 1.0f, err);   // dets[k, c] + 1: a float32 addition (NEP 50)
     const double ks = rint((double)r[4] * 1000.0);         // '{:.3f}'.format(score)
     int k = 0;
     if (ks >= 0.0 && ks <= 1000.0) k = (int)ks; else atomicOr(err, EV_ERR_SCORE);
@@ -94,64 +83,6 @@ __global__ void eval_keys_kernel(const int32_t* __restrict__ soa, int64_t cap, c
     const uint64_t img = (uint32_t)soa[i], cls = (uint32_t)soa[cap + i], inv = 1000u - (uint32_t)soa[2 * cap + i];
     keyA[i] = (cls << 53) | (inv << KEY_IDX_BITS) | (uint64_t)i;
     keyB[i] = (cls << 53) | (img << 32) | (inv << KEY_LOCAL_BITS) | (uint64_t)(i - img_first[img]);
-}
-
-// ---- bitonic sort of unique keys (ascending) -----------------------------------------------------------------------------------
-__device__ __forceinline__ void cswap(uint64_t& a, uint64_t& b, bool up)
-{
-    if ((a > b) == up) { const uint64_t t = a; a = b; b = t; }
-}
-
-// kfull != 0: sort each 2048-key tile completely (every stage k <= 2048); otherwise finish stage k (its steps j <= 1024) in LDS
-__global__ __launch_bounds__(1024) void eval_bitonic_local_kernel(uint64_t* __restrict__ a, int64_t k, int kfull)
-{
-    __shared__ uint64_t s[EV_LOCAL];
-    const int64_t base = (int64_t)blockIdx.x * EV_LOCAL;
-    const int t = threadIdx.x;
-    s[t] = a[base + t];
-    s[t + 1024] = a[base + t + 1024];
-    __syncthreads();
-    const int64_t k0 = kfull ? 2 : k, k1 = kfull ? EV_LOCAL : k;
-    for (int64_t kk = k0; kk <= k1; kk <<= 1) {
-        for (int j = (int)(kk / 2 < 1024 ? kk / 2 : 1024); j > 0; j >>= 1) {
-            const int i = 2 * t - (t & (j - 1));
-            cswap(s[i], s[i + j], ((base + i) & kk) == 0);
-            __syncthreads();
-        }
-    }
-    a[base + t] = s[t];
-    a[base + t + 1024] = s[t + 1024];
-}
-
-__global__ void eval_bitonic_global_kernel(uint64_t* __restrict__ a, int64_t j, int64_t k, int64_t half)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= half) return;
-    const int64_t i = 2 * t - (t & (j - 1));
-    uint64_t x = a[i], y = a[i + j];
-    const bool up = (i & k) == 0;
-    if ((x > y) == up) { a[i] = y; a[i + j] = x; }
-}
-
-void bitonic_sort(uint64_t* a, int64_t npow, hipStream_t s)
-{
-    const int tiles = (int)(npow / EV_LOCAL);
-    hipLaunchKernelGGL(eval_bitonic_local_kernel, dim3(tiles), dim3(1024), 0, s, a, (int64_t)0, 1);
-    for (int64_t k = 2 * EV_LOCAL; k <= npow; k <<= 1) {
-        for (int64_t j = k / 2; j >= EV_LOCAL; j >>= 1)
-            hipLaunchKernelGGL(eval_bitonic_global_kernel, dim3((unsigned)((npow / 2 + 255) / 256)), dim3(256), 0, s, a, j, k, npow / 2);
-        hipLaunchKernelGGL(eval_bitonic_local_kernel, dim3(tiles), dim3(1024), 0, s, a, k, 0);
-    }
-}
-
-__device__ __forceinline__ int64_t lower_bound(const uint64_t* a, int64_t n, uint64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // ---- greedy match (:293-327) ----------------------------------------------------------------------------------------------------
@@ -244,23 +175,6 @@ __global__ __launch_bounds__(256) void eval_match_kernel(const uint64_t* __restr
 
 // ---- PR curve + AP (:328-333, voc_ap :199-230) ----------------------------------------------------------------------------------
 constexpr int CT = 256;                                          // threads of eval_curve_kernel
-
-template <typename T, typename Op>
-__device__ __forceinline__ T block_scan_incl(T v, Op op, T* lds)  // inclusive scan over the 256 threads in thread order
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o);
-        if (lane >= o) v = op(u, v);
-    }
-    if (lane == 63) lds[wv] = v;
-    __syncthreads();
-    T pre = lds[0];
-    for (int w = 1; w < wv; ++w) pre = op(pre, lds[w]);
-    if (wv > 0) v = op(pre, v);
-    __syncthreads();
-    return v;
-}
 
 // numpy's pairwise_sum of float64 (n <= 128: eight accumulators; longer: split at n/2 rounded down to a multiple of 8), as an
 // explicit post-order walk.
@@ -430,29 +344,6 @@ struct EvalState {
     bool finished = false;
     std::vector<int64_t> starts;               // [C+1] class segments of the last finish
 };
-
-namespace {
-
-#define EVCHK(expr)                                                                                         \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) { err = std::string(#expr " failed: ") + hipGetErrorString(e_); return 1; }   \
-    } while (0)
-
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need, std::string& err)
-{
-    if (need <= cap) return 0;
-    size_t nc = cap ? cap : 1;
-    while (nc < need) nc *= 2;
-    if (p) EVCHK(hipFree(p));
-    p = nullptr;
-    EVCHK(hipMalloc((void**)&p, nc * sizeof(T)));
-    cap = nc;
-    return 0;
-}
-
-}  // namespace
 
 int eval_create(int device, int C, double ovthresh, EvalState** out, std::string& err)
 {

@@ -70,6 +70,7 @@ struct GraphEntry {
 
 }  // namespace
 
+struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
 
 struct yn_handle {
@@ -2257,6 +2258,65 @@ int yn_eval_size(yn_eval* e, int64_t* records, int64_t* images)
 {
     if (!e) return 1;
     ynk::eval_size(e->st, records, images);
+    return 0;
+}
+
+// ---- COCO box AP (kernels_coco.hip) -----------------------------------------------------------------------------------------
+int yn_coco_create(yn_handle* h, int num_classes, int max_det, yn_coco** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_coco_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::CocoState* st = nullptr;
+    if (ynk::coco_create(h->cfg.device, num_classes, max_det, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_coco{st};
+    return 0;
+}
+
+void yn_coco_destroy(yn_coco* e)
+{
+    if (!e) return;
+    ynk::coco_destroy(e->st);
+    delete e;
+}
+
+int yn_coco_reset(yn_handle* h, yn_coco* e)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_coco_reset: null evaluator");
+    YN_EVAL_CALL(ynk::coco_reset(e->st, h->stream, err));
+}
+
+int yn_coco_add(yn_handle* h, yn_coco* e, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom_host,
+                const int64_t* image_ids_host, const double* gt_host, const int32_t* gt_meta_host, const int32_t* gt_offsets_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_coco_add: null evaluator");
+    YN_EVAL_CALL(ynk::coco_add(e->st, h->stream, B, rec_dev, offsets_dev, geom_host, image_ids_host, gt_host, gt_meta_host, gt_offsets_host, err));
+}
+
+int yn_coco_finish(yn_handle* h, yn_coco* e, const double* iou_thrs_host, int num_iou, const double* rec_thrs_host, int num_rec,
+                   const double* area_rng_host, int num_area, const int32_t* max_dets_host, int num_max_dets, double* precision_host,
+                   double* recall_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_coco_finish: null evaluator");
+    YN_EVAL_CALL(ynk::coco_finish(e->st, h->stream, iou_thrs_host, num_iou, rec_thrs_host, num_rec, area_rng_host, num_area, max_dets_host,
+                                  num_max_dets, precision_host, recall_host, err));
+}
+
+int yn_coco_matches(yn_handle* h, yn_coco* e, float* det_host, int64_t* seg_host, uint32_t* flags_host, int num_area)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_coco_matches: null evaluator");
+    YN_EVAL_CALL(ynk::coco_matches(e->st, h->stream, det_host, seg_host, flags_host, num_area, err));
+}
+
+int yn_coco_size(yn_coco* e, int64_t* detections, int64_t* images)
+{
+    if (!e) return 1;
+    ynk::coco_size(e->st, detections, images);
     return 0;
 }
 

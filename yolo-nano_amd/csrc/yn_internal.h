@@ -241,6 +241,18 @@ int  eval_finish(EvalState* e, hipStream_t s, int use07, double* ap_host, int64_
 int  eval_curve(EvalState* e, hipStream_t s, int cls, double* rec_host, double* prec_host, int64_t cap, std::string& err);
 int  eval_records(EvalState* e, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
 void eval_size(const EvalState* e, int64_t* records, int64_t* images);
+
+// ---- COCO box AP (kernels_coco.hip): the state behind yn_coco; 0 = ok, 1 = error (text in err), 2 = range mark (coco_add only) ------
+struct CocoState;
+int  coco_create(int device, int C, int max_det, CocoState** out, std::string& err);
+void coco_destroy(CocoState* e);
+int  coco_reset(CocoState* e, hipStream_t s, std::string& err);
+int  coco_add(CocoState* e, hipStream_t s, int B, const float* rec_dev, const int32_t* offsets_dev, const int32_t* geom,
+              const int64_t* image_ids, const double* gt, const int32_t* gt_meta, const int32_t* gt_off, std::string& err);
+int  coco_finish(CocoState* e, hipStream_t s, const double* iou_thrs, int T, const double* rec_thrs, int R, const double* area_rng, int A,
+                 const int32_t* max_dets, int M, double* precision_host, double* recall_host, std::string& err);
+int  coco_matches(CocoState* e, hipStream_t s, float* det_host, int64_t* seg_host, uint32_t* flags_host, int areas, std::string& err);
+void coco_size(const CocoState* e, int64_t* detections, int64_t* images);
 void launch_nms_single(const float* dets, const float* scores, int n, float thresh, int diou,
                        int32_t* ids_scratch, float* sbox_scratch, void* matrix_scratch, int32_t* keep, int32_t* count, hipStream_t s);
 
