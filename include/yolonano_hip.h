@@ -501,6 +501,36 @@ int  yn_op_h16_bn(yn_handle* h, const float* y, const float* dz, int64_t M, int 
 int  yn_op_h16_bn_unit(yn_handle* h, const float* y, const float* pass, const float* dunit, int64_t M, int C, const float* gamma, const float* beta,
                        int act, float* unit, float* dy, float* deven, float* dgamma, float* dbeta);
 
+/* Single layers of the fp32 training step (the default precision) over fp32 device tensors, for op-level tests against a float64
+ * reference.  Each entry runs the step's own per-layer launch code: the same weight packs, tile / kernel choices, weight-gradient
+ * scratch, gradient slots (+ their combine) and BatchNorm double accumulators as yn_train_step.
+ * One conv: kind 0 pointwise, 1 depthwise 3x3 (stride 1|2), 2 dense 3x3, 3 stem (3 -> 24, stride 2).  x is NHWC [B*H*W][x_ld] and the
+ * conv reads its channels [x_off, x_off + Cin) (a channel slice of a wider tensor, as the second half of a ShuffleV2 unit tensor);
+ * the stem takes NCHW [B,3,H,W] with x_ld = x_off = 0.  w / dw in the reference layouts.  y = conv(x) + bias, [B*Ho*Wo][y_ld]; y_ld =
+ * Cout, or for a pointwise conv Cout rounded up to a multiple of 4 (the row padding of a BN-less head conv: the extra columns of y are
+ * written as zeros, those of dy must be zeros).  For dy [B*Ho*Wo][y_ld] any of dx (the geometry of x: only the conv's channels are
+ * touched; accumulate != 0 adds to what is there), dw and dbias [Cout] is computed (null = skip; the stem has no dx).
+ * partial_cap: floats of weight-gradient scratch, 0 = as much as the step has (a small value forces the launchers to clip their slice count). */
+int  yn_op_f32_conv(yn_handle* h, int kind, const float* x, int B, int H, int W, int Cin, int x_ld, int x_off, const float* w, const float* bias,
+                    int Cout, int stride, int y_ld, int64_t partial_cap, const float* dy, int accumulate, float* y, float* dx, float* dw,
+                    float* dbias);
+/* Train-mode BatchNorm (+ activation) over y [M][C], C even, as nn.BatchNorm2d(momentum = 0.1, eps = 1e-5).train() (utils/modules.py:12-21): z,
+ * the batch mean and 1 / sqrt(biased variance + eps) [C], running_mean / running_var [C] updated in place (unbiased variance; both null =
+ * skip).  unit == 0: z [M][C]; with dz, a view of rows dz_ld whose channels start at dz_off, also dy [M][C], dgamma, dbeta [C].
+ * unit != 0, the last layer of a ShuffleV2 unit (backbone/shufflenetv2.py:69-78 with :14-28): z is the unit output [M][2C] with
+ * z[m][2c] = pass[m][c] (pass [M][C]) and z[m][2c+1] = act(BN(y))[m][c]; dz is the unit output's gradient [M][2C] (dz_ld / dz_off
+ * unused), read at its odd channels; deven [M][C] = dz[:, 0::2], the pass-through half. */
+int  yn_op_f32_bn(yn_handle* h, const float* y, int64_t M, int C, const float* gamma, const float* beta, int act, int unit, const float* pass,
+                  float* running_mean, float* running_var, float* z, float* mean, float* invstd, const float* dz, int dz_ld, int dz_off,
+                  float* dy, float* deven, float* dgamma, float* dbeta);
+/* 3x3 stride-2 max pool (pad 1) that records its arg-max: y, idx [B,Ho,Wo,C] (idx = iy*W + ix of the first maximum in window scan
+ * order, as F.max_pool2d(return_indices=True)); with dy also dx [B,H,W,C] (C even). */
+int  yn_op_f32_maxpool(yn_handle* h, const float* x, int B, int H, int W, int C, float* y, int32_t* idx, const float* dy, float* dx);
+/* The FPN / PAN adds (models/yolo_nano.py:291-296) and their backwards, every tensor NHWC with C channels:
+ * mode 0  out[B,H,W] = a[B,H,W] + up2(b[B,H/2,W/2])          mode 1  out[B,H,W] = a[B,H,W] + b[B,2H,2W] at the even pixels
+ * mode 2  out[B,H/2,W/2] += the four children of a[B,H,W]     mode 3  out[B,2H,2W] at the even pixels += a[B,H,W]          (b unused) */
+int  yn_op_f32_resample(yn_handle* h, int mode, const float* a, const float* b, float* out, int B, int H, int W, int C);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every kernel launch of yn_forward_raw / yn_infer is bracketed by a pair of HIP
  * events recorded on the handle's stream (graph replay is bypassed while enabled).  After the

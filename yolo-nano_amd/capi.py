@@ -110,6 +110,10 @@ SIGNATURES = {
     "yn_op_h16_bn": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "yn_op_h16_gemm_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "yn_op_h16_bn_unit": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "yn_op_f32_conv": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, ctypes.c_int64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "yn_op_f32_bn": (_i32, [_vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "yn_op_f32_maxpool": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "yn_op_f32_resample": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "yn_eval_create": (_i32, [_vp, _i32, ctypes.c_double, ctypes.POINTER(_vp)]),
     "yn_eval_destroy": (None, [_vp]),
     "yn_eval_reset": (_i32, [_vp, _vp]),
@@ -838,6 +842,73 @@ class Handle:
         self._ck(self.lib.yn_op_h16_bn_unit(self.h, yc.data_ptr(), pc.data_ptr(), _ptr(dc), M, C, gamma.data_ptr(), beta.data_ptr(), int(act),
                                             unit.data_ptr(), _ptr(dy), _ptr(dev), _ptr(dg), _ptr(db)), "yn_op_h16_bn_unit")
         return unit, dy, dev, dg, db
+
+    def op_f32_conv(self, kind, x, w, bias=None, stride=1, dy=None, x_off=0, cin=None, y_ld=None, dx=None, accumulate=False, partial_cap=0,
+                    want=("dx", "dw", "dbias")):
+        """One conv of the fp32 training step and, with dy, the gradients named in `want`: kind 0 pw / 1 dw / 2 dense3x3 over x [B,H,W,x_ld] fp32
+        NHWC, reading channels [x_off, x_off + cin); kind 3 the stem over x NCHW.  -> (y [B,Ho,Wo,y_ld], dx like x, dw like w, dbias); `dx` given:
+        the tensor the input gradient is written (accumulate: added) into."""
+        stem = int(kind) == 3
+        x = self._in(x)
+        if stem:
+            (B, Cin, H, W), x_ld = x.shape, 0
+        else:
+            B, H, W, x_ld = x.shape
+            Cin = int(cin) if cin is not None else x_ld - int(x_off)
+        Cout = w.shape[0]
+        y_ld = Cout if y_ld is None else int(y_ld)
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        y = torch.empty((B, Ho, Wo, y_ld), dtype=torch.float32, device=x.device)
+        keep = [self._in(t) if t is not None else None for t in (w, bias, dy)]
+        if dy is not None and "dx" in want and not stem:
+            dx = torch.zeros_like(x) if dx is None else dx
+        else:
+            dx = None
+        dw = torch.empty_like(keep[0]) if dy is not None and "dw" in want else None
+        db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if dy is not None and "dbias" in want else None
+        self._ck(self.lib.yn_op_f32_conv(self.h, int(kind), x.data_ptr(), B, H, W, Cin, x_ld, int(x_off), keep[0].data_ptr(), _ptr(keep[1]), Cout, int(stride),
+                                         y_ld, int(partial_cap), _ptr(keep[2]), int(bool(accumulate)), y.data_ptr(), _ptr(dx), _ptr(dw), _ptr(db)), "yn_op_f32_conv")
+        return y, dx, dw, db
+
+    def op_f32_bn(self, y, gamma, beta, act=0, passthrough=None, running=None, dz=None, dz_off=0):
+        """Train-mode BatchNorm + activation of the fp32 step over y [M,C]; passthrough [M,C]: the ShuffleV2 unit form (z and dz are [M,2C]).  running =
+        (running_mean, running_var), updated in place.  dz [M,dz_ld] is read at channels [dz_off, dz_off + C).
+        -> dict z, mean, invstd and, with dz, dy, dgamma, dbeta (unit form: deven)."""
+        M, C = y.shape
+        unit = passthrough is not None
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y.device)
+        out = {"z": mk(M, 2 * C if unit else C), "mean": mk(C), "invstd": mk(C)}
+        if dz is not None:
+            out.update(dy=mk(M, C), dgamma=mk(C), dbeta=mk(C))
+            if unit:
+                out["deven"] = mk(M, C)
+        keep = [self._in(t) if t is not None else None for t in (y, gamma, beta, passthrough, dz)]
+        rm, rv = running if running is not None else (None, None)
+        self._ck(self.lib.yn_op_f32_bn(self.h, keep[0].data_ptr(), M, C, keep[1].data_ptr(), keep[2].data_ptr(), int(act), int(unit), _ptr(keep[3]), _ptr(rm), _ptr(rv),
+                                       out["z"].data_ptr(), out["mean"].data_ptr(), out["invstd"].data_ptr(), _ptr(keep[4]),
+                                       keep[4].shape[1] if dz is not None else 0, int(dz_off), _ptr(out.get("dy")), _ptr(out.get("deven")),
+                                       _ptr(out.get("dgamma")), _ptr(out.get("dbeta"))), "yn_op_f32_bn")
+        return out
+
+    def op_f32_maxpool(self, x, dy=None):
+        """The step's index-recording 3x3 stride-2 max pool over x [B,H,W,C]: -> (y, idx int32, dx or None)."""
+        B, H, W, C = x.shape
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+        idx = torch.empty((B, Ho, Wo, C), dtype=torch.int32, device=x.device)
+        dx = torch.empty_like(x) if dy is not None else None
+        keep = [self._in(x), self._in(dy) if dy is not None else None]
+        self._ck(self.lib.yn_op_f32_maxpool(self.h, keep[0].data_ptr(), B, H, W, C, y.data_ptr(), idx.data_ptr(), _ptr(keep[1]), _ptr(dx)), "yn_op_f32_maxpool")
+        return y, idx, dx
+
+    def op_f32_resample(self, mode, a, b=None, out=None):
+        """launch_resample's four modes (include/yolonano_hip.h); modes 2 / 3 add into `out`.  H, W are those of `a`."""
+        B, H, W, C = a.shape
+        if out is None:
+            out = torch.empty_like(a)
+        keep = [self._in(a), self._in(b) if b is not None else None]
+        self._ck(self.lib.yn_op_f32_resample(self.h, int(mode), keep[0].data_ptr(), _ptr(keep[1]), out.data_ptr(), B, H, W, C), "yn_op_f32_resample")
+        return out
 
     def to_nhwc(self, x):
         B, C, H, W = x.shape

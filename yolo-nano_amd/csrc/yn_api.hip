@@ -2328,5 +2328,6 @@ int yn_coco_size(yn_coco* e, int64_t* detections, int64_t* images)
 #include "yn_train.inc"
 #include "yn_train_h16.inc"
 #include "yn_train_h16_ops.inc"
+#include "yn_train_ops.inc"
 #include "yn_train_tape.inc"
 #include "yn_train_api.inc"

@@ -183,33 +183,12 @@ int yn_train_bind(yn_handle* h, float* params, float* grads, float* momentum, in
     h->tP = params; h->tG = grads; h->tM = momentum; h->tN = n; h->train_steps = 0;
     if (h->hpack_table) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->hpack_table); h->hpack_table = nullptr; h->hpack_table_n = 0; }
     h->hpack_jobs.clear();                                 // the fp16 step's pack table points into the (new) flat parameter buffer
-    if (!h->zeros) {
-        HIPCHK(h, hipMalloc((void**)&h->zeros, 4096 * sizeof(float)));
-        HIPCHK(h, hipMemsetAsync(h->zeros, 0, 4096 * sizeof(float), h->stream));
-    }
+    if (zeros_ready(h)) return 1;
     // per-layer packs (forward: raw weights; backward: transposed / flipped)
     if (h->tpacks.empty()) {
         h->tpacks.resize(h->layers.size());
-        for (size_t i = 0; i < h->layers.size(); ++i) {
-            Layer& l = h->layers[i];
-            TrainPack& pk = h->tpacks[i];
-            const PackDims d = pack_dims(l);
-            const size_t fwd = (size_t)d.Kp * d.Npad, nbias = (size_t)((d.Npad + 31) & ~31);
-            size_t bwd = l.kind == K_DW ? fwd : 0;
-            if (l.kind == K_PW || l.kind == K_DENSE3) {
-                pk.Kb = (l.cout * d.kk + 1) & ~1; pk.Npad_b = (l.cin + 31) & ~31; bwd = (size_t)pk.Kb * pk.Npad_b;
-                if (l.kind == K_DENSE3) pk.Kb = l.cout;              // conv3x3 launcher takes Cin', not 9*Cin'
-            }
-            l.Kp = d.Kp; l.Npad = d.Npad;                              // the same values yn_fold_bn derives
-            HIPCHK(h, hipMalloc((void**)&pk.wp, fwd * sizeof(float)));
-            HIPCHK(h, hipMalloc((void**)&pk.bias, nbias * sizeof(float)));
-            HIPCHK(h, hipMemsetAsync(pk.wp, 0, fwd * sizeof(float), h->stream));
-            HIPCHK(h, hipMemsetAsync(pk.bias, 0, nbias * sizeof(float), h->stream));
-            if (bwd) {
-                HIPCHK(h, hipMalloc((void**)&pk.wp_bwd, bwd * sizeof(float)));
-                HIPCHK(h, hipMemsetAsync(pk.wp_bwd, 0, bwd * sizeof(float), h->stream));
-            }
-        }
+        for (size_t i = 0; i < h->layers.size(); ++i)
+            if (alloc_packs(h, h->layers[i], h->tpacks[i])) return 1;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;

@@ -3,10 +3,10 @@
 
 namespace {
 
-// zero-filled scratch of the op-level entry points (yn_op_h16_*), freed on scope exit
+// scratch of the op-level entry points (yn_op_h16_*, yn_op_f32_*), filled with the byte `fill` (zero; 0xff makes every float a NaN), freed on scope exit
 struct DevBuf {
     void* p = nullptr;
-    explicit DevBuf(size_t bytes, hipStream_t st) { if (hipMalloc(&p, bytes ? bytes : 16) == hipSuccess) (void)hipMemsetAsync(p, 0, bytes ? bytes : 16, st); else p = nullptr; }
+    explicit DevBuf(size_t bytes, hipStream_t st, int fill = 0) { if (hipMalloc(&p, bytes ? bytes : 16) == hipSuccess) (void)hipMemsetAsync(p, fill, bytes ? bytes : 16, st); else p = nullptr; }
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <class T> T* as() { return (T*)p; }
 };

@@ -33,6 +33,7 @@ struct StepArena {
 
 // The fixed fp32 scratch of a step: BatchNorm sum accumulators (one memset per step), the per-slice weight-gradient copies of one layer at
 // a time, GRAD_SLOTS copies of the flat gradient buffer (atomics targets; slot s is h->tN floats further).
+constexpr size_t WPART_FLOATS = (size_t)16 << 20;       // floats of weight-gradient scratch
 struct StepScratch {
     double* stats = nullptr; size_t stats_used = 0, stats_cap = 0;
     float* wpart = nullptr; size_t wpart_cap = 0;
@@ -47,7 +48,7 @@ int carve_scratch(yn_handle* h, StepArena& ar, int acc_slots, hipStream_t st, St
     sc.stats = (double*)ar.up(nstat * sizeof(double));
     sc.stats_cap = nstat;
     HIPCHK(h, hipMemsetAsync(sc.stats, 0, nstat * sizeof(double), st));
-    sc.wpart_cap = (size_t)16 << 20;
+    sc.wpart_cap = WPART_FLOATS;
     sc.wpart = (float*)ar.up(sc.wpart_cap * sizeof(float));
     sc.gslots = (float*)ar.up((size_t)GRAD_SLOTS * h->tN * sizeof(float));
     HIPCHK(h, hipMemsetAsync(sc.gslots, 0, (size_t)GRAD_SLOTS * h->tN * sizeof(float), st));
