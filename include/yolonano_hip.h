@@ -359,6 +359,39 @@ int  yn_coco_matches(yn_handle* h, yn_coco* e, float* det_host, int64_t* seg_hos
 /* detections kept and images added so far (host counters, no device work) */
 int  yn_coco_size(yn_coco* e, int64_t* detections, int64_t* images);
 
+/* ---- anchor-box k-means: kmeans_anchor.py's init_centroids / do_kmeans / anchor_box_kmeans on the device, in float64 with exact sums
+ * (Anchor k-means).  Boxes are (w, h) pairs centred at the origin; the distance is 1 - IoU in the reference's operation
+ * order; every sum (group sums, loss, the k-means++ prefix sums) is the correctly rounded exact sum, so a result does not depend on
+ * box order, grid or timing.  Domain: 1 <= w, h < 65536, finite.  An object of its own like yn_coco; every call launches on the
+ * stream of the handle given.  N is bounded by the limb layout of the pass: 256 workgroups of at most 2^16 boxes each, whose 47-bit
+ * limbs fit a 64-bit accumulator, which is 2^24 boxes. */
+typedef struct yn_kmeans yn_kmeans;
+/* capacity 1..2^24 boxes, max_k 1..32 centroids */
+int  yn_kmeans_create(yn_handle* h, int64_t capacity, int max_k, yn_kmeans** out);
+void yn_kmeans_destroy(yn_kmeans* e);
+/* wh_dev float64 [n][2] on the device, copied into the object; fails, giving their number, if any box lies outside the domain
+ * (one read-back).  Drops the centroids. */
+int  yn_kmeans_set_boxes(yn_handle* h, yn_kmeans* e, const double* wh_dev, int64_t n);
+/* k-means++ as init_centroids: centroid 0 is box first_index; for centroid r = 1..k-1 the pick is the first index whose exact prefix
+ * sum of min_distance exceeds sum_distance * u_host[r-1] (the caller's uniform draws in [0, 1), in the reference's order), or no box
+ * (picked -1, centroid (0, 0)) if no index qualifies.  centroids_host float64 [k][2], picked_host int32 [k]; either may be NULL.
+ * One read-back per round. */
+int  yn_kmeans_seed(yn_handle* h, yn_kmeans* e, int k, int64_t first_index, const double* u_host, double* centroids_host,
+                    int32_t* picked_host);
+/* wh_host float64 [k][2], each side finite and in [0, 65536) */
+int  yn_kmeans_set_centroids(yn_handle* h, yn_kmeans* e, const double* wh_host, int k);
+/* anchor_box_kmeans's loop from the current centroids: passes until |old_loss - loss| < loss_convergence or iterations > iters,
+ * decided on the device; the host enqueues passes in batches and reads the `done` word once per batch.  centroids_host [k][2],
+ * counts_host int64 [k], loss_host, iterations_host of the last pass; any may be NULL. */
+int  yn_kmeans_run(yn_handle* h, yn_kmeans* e, double loss_convergence, int iters, double* centroids_host, int64_t* counts_host,
+                   double* loss_host, int32_t* iterations_host);
+/* one do_kmeans: the current centroids are replaced by their groups' means; outputs as yn_kmeans_run's */
+int  yn_kmeans_pass(yn_handle* h, yn_kmeans* e, double* centroids_host, int64_t* counts_host, double* loss_host);
+/* group_dev int32 [n] on the device: the group of every box for the current centroids (ties to the lower index).  Asynchronous. */
+int  yn_kmeans_assign(yn_handle* h, yn_kmeans* e, int32_t* group_dev);
+/* passes run and host reads made by the last yn_kmeans_run (host counters, no device work) */
+int  yn_kmeans_stats(yn_kmeans* e, int64_t* passes, int64_t* host_reads);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

@@ -20,6 +20,9 @@ def __getattr__(name):
     if name in ("COCOEval", "coco_gt_arrays", "evaluate_coco"):
         from . import coco
         return getattr(coco, name)
+    if name in ("anchor_box_kmeans", "AnchorKMeans", "dataset_boxes", "as_anchor_table"):
+        from . import anchors                                 # numpy only until a device object is made
+        return getattr(anchors, name)
     if name in ("Handle", "YnError", "YnRangeError", "load_library"):
         from . import capi
         return getattr(capi, name)

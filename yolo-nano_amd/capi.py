@@ -129,6 +129,15 @@ SIGNATURES = {
     "yn_coco_finish": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
     "yn_coco_matches": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32]),
     "yn_coco_size": (_i32, [_vp, _i64p, _i64p]),
+    "yn_kmeans_create": (_i32, [_vp, ctypes.c_int64, _i32, ctypes.POINTER(_vp)]),
+    "yn_kmeans_destroy": (None, [_vp]),
+    "yn_kmeans_set_boxes": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
+    "yn_kmeans_seed": (_i32, [_vp, _vp, _i32, ctypes.c_int64, _vp, _vp, _vp]),
+    "yn_kmeans_set_centroids": (_i32, [_vp, _vp, _vp, _i32]),
+    "yn_kmeans_run": (_i32, [_vp, _vp, ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "yn_kmeans_pass": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "yn_kmeans_assign": (_i32, [_vp, _vp, _vp]),
+    "yn_kmeans_stats": (_i32, [_vp, _i64p, _i64p]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

@@ -71,6 +71,7 @@ struct GraphEntry {
 }  // namespace
 
 struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
+struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
 
 struct yn_handle {
@@ -2317,6 +2318,76 @@ int yn_coco_size(yn_coco* e, int64_t* detections, int64_t* images)
 {
     if (!e) return 1;
     ynk::coco_size(e->st, detections, images);
+    return 0;
+}
+
+// ---- anchor-box k-means (kernels_kmeans.hip) -------------------------------------------------------------------------------------
+int yn_kmeans_create(yn_handle* h, int64_t capacity, int max_k, yn_kmeans** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_kmeans_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::KmeansState* st = nullptr;
+    if (ynk::kmeans_create(h->cfg.device, capacity, max_k, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_kmeans{st};
+    return 0;
+}
+
+void yn_kmeans_destroy(yn_kmeans* e)
+{
+    if (!e) return;
+    ynk::kmeans_destroy(e->st);
+    delete e;
+}
+
+int yn_kmeans_set_boxes(yn_handle* h, yn_kmeans* e, const double* wh_dev, int64_t n)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_set_boxes: null object");
+    YN_EVAL_CALL(ynk::kmeans_set_boxes(e->st, h->stream, wh_dev, n, err));
+}
+
+int yn_kmeans_seed(yn_handle* h, yn_kmeans* e, int k, int64_t first_index, const double* u_host, double* centroids_host, int32_t* picked_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_seed: null object");
+    YN_EVAL_CALL(ynk::kmeans_seed(e->st, h->stream, k, first_index, u_host, centroids_host, picked_host, err));
+}
+
+int yn_kmeans_set_centroids(yn_handle* h, yn_kmeans* e, const double* wh_host, int k)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_set_centroids: null object");
+    YN_EVAL_CALL(ynk::kmeans_set_centroids(e->st, h->stream, wh_host, k, err));
+}
+
+int yn_kmeans_run(yn_handle* h, yn_kmeans* e, double loss_convergence, int iters, double* centroids_host, int64_t* counts_host,
+                  double* loss_host, int32_t* iterations_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_run: null object");
+    YN_EVAL_CALL(ynk::kmeans_run(e->st, h->stream, loss_convergence, iters, centroids_host, counts_host, loss_host, iterations_host, err));
+}
+
+int yn_kmeans_pass(yn_handle* h, yn_kmeans* e, double* centroids_host, int64_t* counts_host, double* loss_host)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_pass: null object");
+    YN_EVAL_CALL(ynk::kmeans_pass(e->st, h->stream, centroids_host, counts_host, loss_host, err));
+}
+
+int yn_kmeans_assign(yn_handle* h, yn_kmeans* e, int32_t* group_dev)
+{
+    YN_ENTER(h);
+    if (!e) return fail(h, "yn_kmeans_assign: null object");
+    YN_EVAL_CALL(ynk::kmeans_assign(e->st, h->stream, group_dev, err));
+}
+
+int yn_kmeans_stats(yn_kmeans* e, int64_t* passes, int64_t* host_reads)
+{
+    if (!e) return 1;
+    ynk::kmeans_stats(e->st, passes, host_reads);
     return 0;
 }
 

@@ -253,6 +253,19 @@ int  coco_finish(CocoState* e, hipStream_t s, const double* iou_thrs, int T, con
                  const int32_t* max_dets, int M, double* precision_host, double* recall_host, std::string& err);
 int  coco_matches(CocoState* e, hipStream_t s, float* det_host, int64_t* seg_host, uint32_t* flags_host, int areas, std::string& err);
 void coco_size(const CocoState* e, int64_t* detections, int64_t* images);
+// ---- anchor-box k-means (kernels_kmeans.hip): the state behind yn_kmeans; 0 = ok, 1 = error (text in err) ----------------------------
+struct KmeansState;
+int  kmeans_create(int device, int64_t capacity, int max_k, KmeansState** out, std::string& err);
+void kmeans_destroy(KmeansState* e);
+int  kmeans_set_boxes(KmeansState* e, hipStream_t s, const double* wh_dev, int64_t n, std::string& err);
+int  kmeans_seed(KmeansState* e, hipStream_t s, int k, int64_t first_index, const double* u_host, double* centroids_host,
+                 int32_t* picked_host, std::string& err);
+int  kmeans_set_centroids(KmeansState* e, hipStream_t s, const double* wh_host, int k, std::string& err);
+int  kmeans_run(KmeansState* e, hipStream_t s, double loss_convergence, int iters, double* centroids_host, int64_t* counts_host,
+                double* loss_host, int32_t* iterations_host, std::string& err);
+int  kmeans_pass(KmeansState* e, hipStream_t s, double* centroids_host, int64_t* counts_host, double* loss_host, std::string& err);
+int  kmeans_assign(KmeansState* e, hipStream_t s, int32_t* group_dev, std::string& err);
+void kmeans_stats(const KmeansState* e, int64_t* passes, int64_t* host_reads);
 void launch_nms_single(const float* dets, const float* scores, int n, float thresh, int diou,
                        int32_t* ids_scratch, float* sbox_scratch, void* matrix_scratch, int32_t* keep, int32_t* count, hipStream_t s);
 
