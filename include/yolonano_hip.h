@@ -392,6 +392,49 @@ int  yn_kmeans_assign(yn_handle* h, yn_kmeans* e, int32_t* group_dev);
 /* passes run and host reads made by the last yn_kmeans_run (host counters, no device work) */
 int  yn_kmeans_stats(yn_kmeans* e, int64_t* passes, int64_t* host_reads);
 
+/* ---- test-time augmentation for whole batches: utils/misc.py:90-148 (TestTimeAugmentation) for B images at once, nothing but one
+ * small read-back crossing to the host (Test-time augmentation).  An object of its own like yn_coco; every call launches on
+ * the stream of the handle given.
+ *
+ * The bilinear resize (F.interpolate, mode 'bilinear', align_corners False, no antialias; :108-111) is DEFINED here, since torch's own
+ * kernel is not reproducible bit for bit across thread counts.  Per axis, scale = (float)S0 / (float)s;
+ * src = max(fmaf(scale, d + 0.5f, -0.5f), 0) with one rounding; i0 = (int)src, i1 = i0 + (i0 < S0 - 1); l1 = src - i0, l0 = 1 - l1;
+ * v = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d), every multiply and add rounded on its own.  s == S0 copies the bits.
+ * tests/tta_oracle.py restates it in numpy; the distance to torch is bounded in tests/test_tta_cpu.py. */
+/* x_dev float32 [B][3][S0][S0] -> out_dev [B][3][s][s], or with flip_pairs [2B][3][s][s]: image 2b the resize of image b, image
+ * 2b + 1 its horizontal mirror (out[..., j] = resized[..., s - 1 - j], torch.flip(x, [-1])).  Any sides 1..16384 (the network's
+ * multiple-of-32 rule is yn_set_grid's, not this call's); B == 0 does nothing.  Asynchronous.  Also the F.interpolate of multi-scale
+ * training (train.py:202-208). */
+int  yn_resize_batch(yn_handle* h, const float* x_dev, int B, int S0, int s, int flip_pairs, float* out_dev);
+typedef struct yn_tta yn_tta;
+/* scales: ascending positive multiples of 32 (num_scales 1..64; np.arange(320, 641, 32) is the reference's default); flip: also the
+ * mirrored forward of every scale; max_batch: images per call; list_capacity: rows of an image's merge list, 1..131072 - the sum
+ * over all forwards of what yn_infer keeps for that image.  Every work buffer is allocated here, for max_batch images and the
+ * largest scale.  The handle gives the device, the anchors per cell and the class count. */
+int  yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip, int max_batch, int list_capacity, yn_tta** out);
+void yn_tta_destroy(yn_tta* t);
+/* x_dev float32 [B][3][S0][S0].  Per scale s, ascending: one resize (+ mirror) launch, yn_set_grid(s), ONE yn_infer over the 2B (B
+ * without flip) images on the handle's own path and thresholds, one append of every image's kept rows to its merge list - plain rows
+ * copied, mirrored rows with x1' = 1.0f - x2, x2' = 1.0f - x1 (:126).  List order is the reference's concatenation order: scale by
+ * scale, plain before mirrored, ascending candidate order inside a forward.  Then ONE read-back (list sizes, overflow flag, range
+ * mark), per-class NMS of the B lists (nms_thresh; the reference uses 0.4; never DIoU) and yn_pack_detections into the object's
+ * record buffer.  The grid that was set before the call is restored, also on failure.
+ * Needs a handle created with max_batch >= 2B (B without flip), refused by name otherwise.  A forward that left the split-f16 range
+ * returns YN_STATUS_RANGE and delivers nothing (acknowledge with yn_range_status, yn_exact_f32(h, 1), run again).  A list that would
+ * pass list_capacity fails, naming the first such image and the rows it needed; nothing is written past a list.  B == 0 is an empty
+ * result, not an error. */
+int  yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, float nms_thresh);
+/* the last successful yn_tta_infer's result, owned by the object and valid until its next call: rec_dev [total][6] + offsets_dev
+ * [B+1], exactly yn_pack_detections' layout (what yn_eval_add / yn_coco_add take).  Any pointer may be NULL; asking for `total` costs
+ * one 4-byte read-back (once per result).  Returns 1 when there is no result. */
+int  yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev, int32_t* total);
+/* testing aid: the merge lists of the last yn_tta_infer (also one that failed on list_capacity) before the NMS, to the host:
+ * boxes_host [B][list_capacity][4], scores_host / cls_host [B][list_capacity] (rows >= count: class -1), count_host [B] (the rows the
+ * list needed, which may exceed list_capacity) and forward_start_host [forwards][B], forwards = (flip ? 2 : 1) * num_scales in list
+ * order: where forward f's rows start in image b's list.  Any pointer may be NULL.  Synchronises the stream. */
+int  yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host,
+                     int32_t* forward_start_host);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

@@ -8,7 +8,7 @@ from . import arch, weights  # noqa: F401
 
 
 def __getattr__(name):
-    if name in ("YOLONano", "fuse_conv_bn", "Conv", "ShuffleNetV2", "ShuffleV2Block", "shufflenetv2", "SGD", "multi_gt_creator", "ModelEMA", "TestTimeAugmentation", "ValTransforms", "rescale_boxes"):
+    if name in ("YOLONano", "fuse_conv_bn", "Conv", "ShuffleNetV2", "ShuffleV2Block", "shufflenetv2", "SGD", "multi_gt_creator", "ModelEMA", "TestTimeAugmentation", "ValTransforms", "rescale_boxes", "resize_batch"):
         from . import model
         return getattr(model, name)
     if name in ("TrainTransforms", "ColorTransforms", "AugParams", "Mosaic", "MosaicParams"):

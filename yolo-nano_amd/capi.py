@@ -138,6 +138,12 @@ SIGNATURES = {
     "yn_kmeans_pass": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "yn_kmeans_assign": (_i32, [_vp, _vp, _vp]),
     "yn_kmeans_stats": (_i32, [_vp, _i64p, _i64p]),
+    "yn_resize_batch": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "yn_tta_create": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
+    "yn_tta_destroy": (None, [_vp]),
+    "yn_tta_infer": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32]),
+    "yn_tta_result": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
+    "yn_tta_forwards": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),
@@ -225,6 +231,7 @@ class Handle:
         self.h = h
         self._stream_ptr = cfg.stream
         self.C, self.S = int(num_classes), int(input_size)
+        self.max_batch = max(int(max_batch), 1)
         self.backbone = backbone
         self.head_ch = arch.head_channels(self.C, self.A)
 
@@ -620,6 +627,19 @@ class Handle:
                  "yn_mosaic_transform_batch")
         return out
 
+    def resize_batch(self, x, size, flip_pairs=False, out=None):
+        """x float32 [B,3,S0,S0] on the device -> [B,3,size,size], with flip_pairs [2B,3,size,size] (image 2b the resize, 2b + 1 its
+        horizontal mirror): the library's bilinear resize (yn_resize_batch; align_corners False, no antialias)."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3], tuple(x.shape)
+        x = self._in(x)
+        B, S0, s = int(x.shape[0]), int(x.shape[2]), int(size)
+        nb = 2 * B if flip_pairs else B
+        if out is None:
+            out = torch.empty((nb, 3, s, s), dtype=torch.float32, device=x.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == nb * 3 * s * s
+        self._ck(self.lib.yn_resize_batch(self.h, x.data_ptr(), B, S0, s, int(bool(flip_pairs)), out.data_ptr()), "yn_resize_batch")
+        return out
+
     def nms_merge(self, boxes, scores, cls, num_classes, nms_thresh, diou=False):
         """Per-class NMS over a detection list (TTA merge, utils/misc.py:132-146) -> (boxes [K,4], scores [K], cls [K], index [K])."""
         n = int(boxes.shape[0])
@@ -930,3 +950,77 @@ class Handle:
         y = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
         self._ck(self.lib.yn_op_nhwc_to_nchw(self.h, _ptr(self._in(x)), B, C, H, W, y.data_ptr()), "yn_op_nhwc_to_nchw")
         return y
+
+
+class _DeviceView:
+    """A region of device memory the library owns, in the form torch.as_tensor adopts without a copy."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+class Tta:
+    """One yn_tta: test-time augmentation for whole batches.  Thin, 1:1 with the C ABI; `handle` gives the device, the anchors per cell
+    and the class count, and is the default handle of infer()."""
+
+    def __init__(self, handle, scales, flip=True, max_batch=1, list_capacity=8192):
+        self.lib = handle.lib
+        self.handle = handle
+        self.scales = [int(s) for s in scales]
+        self.flip, self.max_batch, self.list_capacity = bool(flip), int(max_batch), int(list_capacity)
+        self.forwards = len(self.scales) * (2 if self.flip else 1)
+        arr = (ctypes.c_int32 * max(len(self.scales), 1))(*self.scales)
+        t = _vp()
+        handle._ck(self.lib.yn_tta_create(handle.h, ctypes.cast(arr, _vp), len(self.scales), int(self.flip), self.max_batch, self.list_capacity,
+                                          ctypes.byref(t)), "yn_tta_create")
+        self.t = t
+        self.B = None
+
+    def close(self):
+        if getattr(self, "t", None):
+            self.lib.yn_tta_destroy(self.t)
+            self.t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def infer(self, x, nms_thresh=0.4, handle=None):
+        """x float32 [B,3,S0,S0] on the device: every scale (x flip) forward, the per-image merge and the pack (yn_tta_infer).  Raises
+        YnRangeError on the split-f16 range mark, YnError naming the image when a merge list would pass list_capacity."""
+        h = self.handle if handle is None else handle
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3], tuple(x.shape)
+        x = h._in(x)
+        self.B = None
+        h._ck(self.lib.yn_tta_infer(h.h, self.t, x.data_ptr(), int(x.shape[0]), int(x.shape[2]), float(nms_thresh)), "yn_tta_infer")
+        self.B = int(x.shape[0])
+
+    def result(self, total=False):
+        """(rec [max_batch * list_capacity, 6] float32, offsets [B+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
+        object's buffers, valid until its next infer() (yn_tta_result).  total=True: also offsets[B] as an int (one read-back)."""
+        if self.B is None:
+            raise YnError("yn_tta_result: no result (infer() first)")
+        rec, off, n = _vp(), _vp(), _i32(0)
+        if self.lib.yn_tta_result(self.t, ctypes.byref(rec), ctypes.byref(off), ctypes.byref(n) if total else None):
+            raise YnError("yn_tta_result: no result")
+        dev = self.handle.device
+        r = torch.as_tensor(_DeviceView(rec.value, (self.max_batch * self.list_capacity, 6), "<f4", self), device=dev)
+        o = torch.as_tensor(_DeviceView(off.value, (self.B + 1,), "<i4", self), device=dev)
+        return (r, o, int(n.value)) if total else (r, o)
+
+    def forwards_to_host(self, B, handle=None):
+        """Testing aid (yn_tta_forwards): the merge lists before the NMS -> (boxes [B,cap,4], scores [B,cap], cls [B,cap] int32,
+        count [B] int32, forward_start [forwards,B] int32) numpy arrays."""
+        h = self.handle if handle is None else handle
+        cap = self.list_capacity
+        boxes = np.zeros((B, cap, 4), np.float32)
+        scores = np.zeros((B, cap), np.float32)
+        cls = np.zeros((B, cap), np.int32)
+        count = np.zeros((B,), np.int32)
+        start = np.zeros((self.forwards, B), np.int32)
+        h._ck(self.lib.yn_tta_forwards(h.h, self.t, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
+              "yn_tta_forwards")
+        return boxes, scores, cls, count, start

@@ -73,6 +73,23 @@ struct GraphEntry {
 struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
+// test-time augmentation for whole batches (kernels_tta.hip): every buffer is allocated once, for max_batch images and the largest scale
+struct yn_tta {
+    int device = 0, flip = 1, max_batch = 0, cap = 0, A = 0, C = 0, Nmax = 0, smax = 0;
+    std::vector<int> scales;
+    float* xr = nullptr;                                             // the resized (+ mirrored) batch [nb][3][smax][smax], nb = flip ? 2 max_batch : max_batch
+    float* fb = nullptr; float* fs = nullptr; int32_t* fc = nullptr; int32_t* fcount = nullptr;      // yn_infer's outputs for one scale: [nb][Nmax]
+    float* lb = nullptr; float* ls = nullptr; int32_t* lc = nullptr;                                 // the merge lists [max_batch][cap]
+    int32_t* state = nullptr;                                        // [TTA_STATE + max_batch]: flags + cursors (tta_append_kernel)
+    int32_t* fstart = nullptr;                                       // [forwards][max_batch]
+    float* mb = nullptr; float* ms = nullptr; int32_t* mc = nullptr; int32_t* mcount = nullptr;      // the merge's kept rows [max_batch][cap]
+    float* rec = nullptr; int32_t* offsets = nullptr;                // yn_pack_detections layout: [max_batch * cap][6], [max_batch + 1]
+    std::vector<int32_t> state_host;                                 // the one read-back of yn_tta_infer
+    int last_B = -1;                                                 // images of the last successful yn_tta_infer, -1: none
+    int lists_B = -1;                                                // images whose merge lists are valid (yn_tta_forwards), -1: none
+    int total = -1;                                                  // offsets[last_B], read on the first yn_tta_result that asks for it
+    hipStream_t last_stream = nullptr;
+};
 
 struct yn_handle {
     yn_config cfg;
@@ -2388,6 +2405,183 @@ int yn_kmeans_stats(yn_kmeans* e, int64_t* passes, int64_t* host_reads)
 {
     if (!e) return 1;
     ynk::kmeans_stats(e->st, passes, host_reads);
+    return 0;
+}
+
+// ---- test-time augmentation for whole batches (kernels_tta.hip; utils/misc.py:90-148) ----------------------------------------------
+int yn_resize_batch(yn_handle* h, const float* x_dev, int B, int S0, int s, int flip_pairs, float* out_dev)
+{
+    YN_ENTER(h);
+    if (B < 0 || S0 < 1 || s < 1 || S0 > 16384 || s > 16384) return fail(h, "yn_resize_batch: bad extent (B %d, %d -> %d; sides 1..16384)", B, S0, s);
+    if (B == 0) return 0;
+    if (!x_dev || !out_dev) return fail(h, "yn_resize_batch: null argument");
+    if (B > 21845) return fail(h, "yn_resize_batch: %d images exceed the launch grid (21845: one plane per grid row)", B);
+    launch_tta_resize(x_dev, B, S0, s, flip_pairs != 0, out_dev, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+void yn_tta_destroy(yn_tta* t)
+{
+    if (!t) return;
+    int prev = -1;
+    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != t->device && hipSetDevice(t->device) == hipSuccess;
+    if (t->last_stream || t->lists_B >= 0) (void)hipDeviceSynchronize();
+    void* ptrs[] = {t->xr, t->fb, t->fs, t->fc, t->fcount, t->lb, t->ls, t->lc, t->state, t->fstart, t->mb, t->ms, t->mc, t->mcount, t->rec, t->offsets};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (moved) (void)hipSetDevice(prev);
+    delete t;
+}
+
+int yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip, int max_batch, int list_capacity, yn_tta** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_tta_create: null argument");
+    *out = nullptr;
+    if (!scales || num_scales < 1 || num_scales > 64) return fail(h, "yn_tta_create: 1..64 scales (got %d)", num_scales);
+    for (int i = 0; i < num_scales; ++i) {
+        if (scales[i] <= 0 || scales[i] % 32 || scales[i] > 4096) return fail(h, "yn_tta_create: scale %d is not a positive multiple of 32 up to 4096", scales[i]);
+        if (i && scales[i] <= scales[i - 1]) return fail(h, "yn_tta_create: scales must ascend (%d after %d)", scales[i], scales[i - 1]);
+    }
+    if (max_batch < 1 || max_batch > 4096) return fail(h, "yn_tta_create: max_batch %d outside 1..4096", max_batch);
+    if (list_capacity < 1 || list_capacity > nms_max_segment())
+        return fail(h, "yn_tta_create: list_capacity %d outside 1..%d (the largest list the merge's NMS takes)", list_capacity, nms_max_segment());
+    yn_tta* t = new yn_tta();
+    t->device = h->cfg.device; t->flip = flip != 0; t->max_batch = max_batch; t->cap = list_capacity;
+    t->A = h->cfg.num_anchors; t->C = h->cfg.num_classes;
+    t->scales.assign(scales, scales + num_scales);
+    t->smax = scales[num_scales - 1];
+    t->Nmax = t->A * ((t->smax / 8) * (t->smax / 8) + (t->smax / 16) * (t->smax / 16) + (t->smax / 32) * (t->smax / 32));
+    const size_t nb = (size_t)(t->flip ? 2 : 1) * max_batch, fN = nb * t->Nmax, lN = (size_t)max_batch * t->cap;
+    const size_t forwards = (size_t)(t->flip ? 2 : 1) * num_scales;
+    t->state_host.resize(TTA_STATE + max_batch);
+    struct { void** p; size_t bytes; } req[] = {
+        {(void**)&t->xr, nb * 3 * t->smax * t->smax * sizeof(float)},
+        {(void**)&t->fb, fN * 4 * sizeof(float)}, {(void**)&t->fs, fN * sizeof(float)}, {(void**)&t->fc, fN * sizeof(int32_t)}, {(void**)&t->fcount, nb * sizeof(int32_t)},
+        {(void**)&t->lb, lN * 4 * sizeof(float)}, {(void**)&t->ls, lN * sizeof(float)}, {(void**)&t->lc, lN * sizeof(int32_t)},
+        {(void**)&t->state, (TTA_STATE + max_batch) * sizeof(int32_t)}, {(void**)&t->fstart, forwards * max_batch * sizeof(int32_t)},
+        {(void**)&t->mb, lN * 4 * sizeof(float)}, {(void**)&t->ms, lN * sizeof(float)}, {(void**)&t->mc, lN * sizeof(int32_t)}, {(void**)&t->mcount, max_batch * sizeof(int32_t)},
+        {(void**)&t->rec, lN * 6 * sizeof(float)}, {(void**)&t->offsets, (max_batch + 1) * sizeof(int32_t)}};
+    for (auto& r : req) {
+        if (hipMalloc(r.p, r.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            yn_tta_destroy(t);
+            return fail(h, "yn_tta_create: out of device memory (%zu bytes for %d images, %d scales up to %d, %d rows per list)", r.bytes, max_batch, num_scales,
+                        t->smax, t->cap);
+        }
+    }
+    // the lists' unused rows are never candidates (class -1, set per call), but the NMS kernels may load them: finite values once
+    if (hipMemsetAsync(t->lb, 0, lN * 4 * sizeof(float), h->stream) != hipSuccess || hipMemsetAsync(t->ls, 0, lN * sizeof(float), h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+        yn_tta_destroy(t);
+        return fail(h, "yn_tta_create: clearing the merge lists failed");
+    }
+    *out = t;
+    return 0;
+}
+
+int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, float nms_thresh)
+{
+    YN_ENTER(h);
+    if (!t) return fail(h, "yn_tta_infer: null object");
+    t->last_B = -1; t->lists_B = -1; t->total = -1;
+    if (t->device != h->cfg.device || t->A != h->cfg.num_anchors || t->C != h->cfg.num_classes)
+        return fail(h, "yn_tta_infer: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", t->device, t->A, t->C,
+                    h->cfg.device, h->cfg.num_anchors, h->cfg.num_classes);
+    if (B < 0 || B > t->max_batch) return fail(h, "yn_tta_infer: %d images, the object's max_batch is %d", B, t->max_batch);
+    const int nb = t->flip ? 2 * B : B;
+    if (nb > h->cfg.max_batch)
+        return fail(h, "yn_tta_infer: %d images%s need a handle with max_batch >= %d, this one has max_batch %d", B, t->flip ? " with their mirrors" : "", nb,
+                    h->cfg.max_batch);
+    t->last_stream = h->stream;
+    if (B == 0) {
+        HIPCHK(h, hipMemsetAsync(t->offsets, 0, sizeof(int32_t), h->stream));
+        t->last_B = 0; t->lists_B = 0; t->total = 0;
+        return 0;
+    }
+    if (!x_dev || S0 < 1 || S0 > 16384) return fail(h, "yn_tta_infer: bad input (side %d)", S0);
+    if (check_ready(h, B)) return 1;
+    if (int rp = range_pending(h, "yn_tta_infer")) return rp;
+    const int S_prev = h->grid.S;
+    struct Restore { yn_handle* h; int S; ~Restore() { if (h->grid.S != S) (void)yn_set_grid(h, S); } } restore{h, S_prev};      // the grid that was set before the call
+    const size_t lN = (size_t)B * t->cap;
+    HIPCHK(h, hipMemsetAsync(t->state, 0, (TTA_STATE + B) * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(t->lc, 0xFF, lN * sizeof(int32_t), h->stream));      // class -1: not a candidate (bucket_kernel)
+    for (size_t si = 0; si < t->scales.size(); ++si) {
+        const int s = t->scales[si];
+        launch_tta_resize(x_dev, B, S0, s, t->flip, t->xr, h->stream);
+        HIPCHK(h, hipGetLastError());
+        if (yn_set_grid(h, s)) return 1;
+        const int N = h->grid.N;
+        if (N > t->Nmax) return fail(h, "yn_tta_infer: %d predictions at %d exceed the object's %d", N, s, t->Nmax);
+        if (int rc = yn_infer(h, t->xr, nb, t->fb, t->fs, t->fc, nullptr, t->fcount)) return rc;
+        launch_tta_append(t->fb, t->fs, t->fc, t->fcount, B, N, t->flip, t->cap, t->max_batch, (int)si * (t->flip ? 2 : 1), t->lb, t->ls, t->lc, t->state,
+                          t->fstart, h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
+    // the one read-back: flags + list sizes
+    int32_t* st = t->state_host.data();
+    HIPCHK(h, hipMemcpyAsync(st, t->state, (TTA_STATE + B) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    t->lists_B = B;
+    if (st[2] || range_pending(h, "yn_tta_infer")) {
+        fail(h, "yn_tta_infer: a forward split an activation >= 65504 (split-f16 range): nothing is delivered - call yn_range_status to acknowledge, "
+                "then yn_exact_f32(h, 1) and run again");
+        return YN_STATUS_RANGE;
+    }
+    if (st[0]) {
+        int worst = 0;
+        for (int b = 0; b < B; ++b) if (st[TTA_STATE + b] > t->cap) { worst = b; break; }
+        return fail(h, "yn_tta_infer: the merge list of image %d needs %d rows, list_capacity is %d (the largest list of the batch needs %d)", worst,
+                    st[TTA_STATE + worst], t->cap, st[1]);
+    }
+    if (ensure_post(h, B, t->cap, t->C)) return 1;
+    NmsWork wk = h->nms;
+    wk.ovf = nullptr; wk.ovf_host = nullptr;
+    launch_nms_pipeline(t->lb, t->ls, t->lc, B, t->cap, t->C, nms_thresh, 0, wk, t->mb, t->ms, t->mc, nullptr, t->mcount, h->stream);
+    launch_pack(t->mb, t->ms, t->mc, t->mcount, B, t->cap, t->rec, t->offsets, h->stream);
+    HIPCHK(h, hipGetLastError());
+    t->last_B = B;
+    return 0;
+}
+
+int yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
+{
+    if (!t || t->last_B < 0) return 1;
+    if (rec_dev) *rec_dev = t->rec;
+    if (offsets_dev) *offsets_dev = t->offsets;
+    if (total) {
+        if (t->total < 0) {
+            int prev = -1;
+            const bool moved = hipGetDevice(&prev) == hipSuccess && prev != t->device && hipSetDevice(t->device) == hipSuccess;
+            int32_t v = 0;
+            const bool ok = hipMemcpyAsync(&v, t->offsets + t->last_B, sizeof(int32_t), hipMemcpyDeviceToHost, t->last_stream) == hipSuccess &&
+                            hipStreamSynchronize(t->last_stream) == hipSuccess;
+            if (moved) (void)hipSetDevice(prev);
+            if (!ok) return 1;
+            t->total = v;
+        }
+        *total = t->total;
+    }
+    return 0;
+}
+
+int yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host, int32_t* forward_start_host)
+{
+    YN_ENTER(h);
+    if (!t) return fail(h, "yn_tta_forwards: null object");
+    if (t->lists_B < 0) return fail(h, "yn_tta_forwards: no yn_tta_infer has filled the lists");
+    const int B = t->lists_B;
+    if (B == 0) return 0;
+    const size_t lN = (size_t)B * t->cap, forwards = t->scales.size() * (t->flip ? 2 : 1);
+    if (boxes_host) HIPCHK(h, hipMemcpyAsync(boxes_host, t->lb, lN * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) HIPCHK(h, hipMemcpyAsync(scores_host, t->ls, lN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (cls_host) HIPCHK(h, hipMemcpyAsync(cls_host, t->lc, lN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (count_host) HIPCHK(h, hipMemcpyAsync(count_host, t->state + TTA_STATE, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (forward_start_host)
+        for (size_t f = 0; f < forwards; ++f)
+            HIPCHK(h, hipMemcpyAsync(forward_start_host + f * B, t->fstart + f * t->max_batch, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 

@@ -269,6 +269,14 @@ void kmeans_stats(const KmeansState* e, int64_t* passes, int64_t* host_reads);
 void launch_nms_single(const float* dets, const float* scores, int n, float thresh, int diou,
                        int32_t* ids_scratch, float* sbox_scratch, void* matrix_scratch, int32_t* keep, int32_t* count, hipStream_t s);
 
+// ---- test-time augmentation (kernels_tta.hip): the kernels behind yn_tta / yn_resize_batch ------------------------------------------
+constexpr int TTA_STATE = 4;                    // int32 words in front of the per-image cursors: overflow flag, needed size, range mark, pad
+// x [B][3][S0][S0] -> out [flip ? 2B : B][3][s][s] (image 2b the resize, 2b + 1 its horizontal mirror)
+void launch_tta_resize(const float* x, int B, int S0, int s, int flip, float* out, hipStream_t st);
+// the kept rows of one yn_infer over (flip ? 2B : B) images, appended to the B merge lists [B][cap] at state[TTA_STATE + b]
+void launch_tta_append(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, int flip, int cap,
+                       int bstride, int fwd, float* lboxes, float* lscores, int32_t* lcls, int32_t* state, int32_t* fstart, hipStream_t st);
+
 // ---- training loss (kernels_train.hip) --------------------------------------------------------------
 int  loss_num_blocks(const GridInfo& g, int B);
 void launch_loss(const float* conf, const float* cls, const float* t, const float* const head[3], float* const ghead[3],

@@ -650,6 +650,84 @@ class TestTimeAugmentation(object):
                                      torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.nms_thresh)
         return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
 
+    # ---- whole batches on the device (yn_tta_*, kernels_tta.hip).  Everything below stands BESIDE __call__, which stays the reference's
+    # loop statement for statement: per scale one resize + mirror launch and ONE yn_infer over the 2B images, one append per scale, one
+    # read-back, one batched merge.  The resize is the library's (yn_resize_batch), pinned bit for bit to tests/tta_oracle.py and within
+    # a derived bound of F.interpolate - so batch() and __call__ agree up to that bound's effect on near-threshold candidates, not bit
+    # for bit.
+    list_capacity = 8192                                       # rows of one image's merge list (all forwards together); an instance may set its own
+
+    def device_handle(self, model, B):
+        """The model's handle, able to take the 2B images of one scale (a handle made for fewer is replaced, so call this before
+        anything else is built on the handle), with this object's yn_tta for at least B images."""
+        from . import capi
+        nb = 2 * int(B)
+        h = model._handle
+        if h is not None and h.max_batch < nb:
+            if model._bound is h:
+                raise YnError("TestTimeAugmentation: the model's handle holds its training buffers and was made for %d images; %d images "
+                              "with their mirrors need %d" % (h.max_batch, B, nb))
+            h.close()
+            model._handle = None
+        h = model.handle(nb)
+        obj = getattr(self, "_tta", None)
+        cap = int(self.list_capacity)
+        if obj is None or obj.handle is not h or obj.max_batch < B or obj.list_capacity != cap:
+            if obj is not None:
+                obj.close()
+            self._tta = None
+            obj = self._tta = capi.Tta(h, [int(s) for s in self.scales], True, max_batch=max(int(B), 1), list_capacity=cap)
+        return h
+
+    def records(self, x, model):
+        """x [B,3,S,S] on the model's device -> (rec [>= total, 6] float32, offsets [B+1] int32) ON THE DEVICE, in yn_pack_detections'
+        layout (what VOCEval.add / COCOEval.add take): views of the yn_tta object's buffers, valid until the next records() / batch().
+        On the split-f16 range mark the model's own fallback runs: acknowledge, yn_exact_f32(1), once more."""
+        h = self.device_handle(model, x.shape[0])
+        obj = self._tta
+        xf = x.float()
+        try:
+            obj.infer(xf, self.nms_thresh, handle=h)
+        except YnRangeError:
+            if model._exact_f32:
+                raise
+            import warnings
+            warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
+                          "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
+            h.range_status()
+            model._exact_f32 = True
+            h.exact_f32(True)
+            obj.infer(xf, self.nms_thresh, handle=h)
+        return obj.result()
+
+    def batch(self, x, model):
+        """One (bboxes [K,4] f32, scores [K] f32, cls_inds [K] i64) numpy triple per image of x [B,3,S,S]: two device-to-host copies."""
+        rec, offsets = self.records(x, model)
+        off = offsets.cpu().numpy()
+        host = rec[: int(off[-1])].cpu().numpy()
+        res = []
+        for b in range(len(off) - 1):
+            r = host[off[b]:off[b + 1]]
+            res.append((r[:, :4].copy(), r[:, 4].copy(), r[:, 5].astype(np.int64)))
+        return res
+
+
+_resize_handles = {}
+
+
+def resize_batch(x, size, flip_pairs=False):
+    """F.interpolate(x, size=(size, size), mode='bilinear', align_corners=False) for x [B,3,S0,S0] on the GPU, in the library's pinned
+    arithmetic (yn_resize_batch; train.py:202-208, utils/misc.py:108-111).  flip_pairs: [2B,3,size,size], every image followed by
+    its horizontal mirror."""
+    if not x.is_cuda:
+        raise YnError("resize_batch: x is on %s; the HIP path needs it on the GPU (there is no CPU fallback)" % (x.device,))
+    key = str(x.device)
+    h = _resize_handles.get(key)
+    if h is None:                                              # a bare handle: only its stream / error plumbing is used
+        h = _resize_handles[key] = Handle(32, 1, arch.MULTI_ANCHOR_SIZE, "1.0x", device=x.device)
+    h.follow_current_stream()
+    return h.resize_batch(x.float(), size, flip_pairs)
+
 
 _target_handles = {}
 

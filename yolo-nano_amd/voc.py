@@ -165,22 +165,29 @@ class VOCEval:
         return out
 
 
-def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5):
+def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None):
     """VOCAPIEvaluator.evaluate + do_python_eval for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3
     BGR arrays, `annotations` one int array [G][6] per image (gt_array).  Per batch: ValTransforms.batch -> yn_infer ->
-    yn_pack_detections -> yn_eval_add; nothing comes back to the host but each batch's 4-byte record count.  -> (aps, mAP)."""
+    yn_pack_detections -> yn_eval_add; nothing comes back to the host but each batch's 4-byte record count.  -> (aps, mAP).
+    test_aug: a yolo_nano_amd.TestTimeAugmentation - every batch goes through its records() (yn_tta_infer: all scales x flip, merged
+    per image on the device) instead of the single forward: the mAP eval.py's -tta flag promises (eval.py:132 builds the object,
+    the evaluator never calls it)."""
     from .model import ValTransforms
     size = int(model.input_size)
     ev = None
     for s in range(0, len(images), batch):
         chunk = images[s:s + batch]
-        h = model.handle(len(chunk))
+        h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
         if ev is None:
             ev = VOCEval(model.num_classes, ovthresh, handle=h)
         tf = ValTransforms(size, handle=h)
         x = tf.batch(chunk)[0]
         geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
         gts = annotations[s:s + batch]
+        if test_aug is not None:
+            rec, off = test_aug.records(x, model)               # (its own range fallback)
+            ev.add(rec, off, geoms, gts, handle=h)
+            continue
 
         def finish(out, geoms=geoms, gts=gts, h=h):
             rec, off = h.pack_detections(out)
