@@ -435,6 +435,42 @@ int  yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev
 int  yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host,
                      int32_t* forward_start_host);
 
+/* ---- detections painted onto frames in list order: test.py:50-92 / demo.py:48-71 (visualize, plot_bbox_labels) for B frames at once,
+ * straight from the rec_dev / offsets_dev pair of yn_pack_detections or yn_tta_result: no read-back, no per-detection host work
+ * (DESIGN.md 23 is the specification).  A frame is uint8 [h0][w0][3] BGR on the device, rows contiguous, sides 1..16384.  Records
+ * are painted in record order, a later one over an earlier one.  Per record: the box goes to pixels (YN_DRAW_LETTERBOX: the
+ * evaluators' bboxes -= offset; /= scale; *= size with geom_host rows w0, h0, rw, rh, left, top, side as yn_eval_add takes them;
+ * YN_DRAW_PIXELS: the box is pixels already, only w0, h0 are read), every coordinate through int() (toward zero).  Drawn iff score >
+ * vis_thresh (strict, float32); a record that passes this but has a class that is no integer in 0..C-1, a coordinate that is not
+ * finite with |v| < 2^30, or '%.2f' digits k = rint(score * 100) outside 0..100 is skipped and counted.  Then, clipped to the frame,
+ * inclusive coordinates, a = t / 2, c = (t - 1) / 2: the outline [x1-a, x2+a] x [y1-a, y2+a] minus the hole [x1+c+1, x2-c-1] x
+ * [y1+c+1, y2-c-1] (an empty hole: filled) in colors[class]; with labels the title bar [x1, x1 + L*gw + 1] x [y1 - gh - 1, y1] in
+ * the same colour, L = strlen(label) + 6, and the text label + ": " + "D.DD", glyph j's cell pixel (r, col) at (x1 + 1 + j*gw + col,
+ * y1 - gh + r), black with coverage a8: out = (dst * (255 - a8) + 127) / 255.  The raster rules and the font are this library's own:
+ * parity with cv2's rasteriser and Hershey font is not claimed. */
+#define YN_DRAW_LETTERBOX 0
+#define YN_DRAW_PIXELS    1
+typedef struct yn_draw yn_draw;
+/* num_classes 1..2000; colors_host [C][3] BGR; labels_host C strings of at most 32 bytes in 32..126, or NULL: outlines only;
+ * atlas_host the A8 glyph atlas [95][gh][gw] for ASCII 32..126 with 4 <= gw, gh <= 32, NULL iff labels_host is; thickness 1..8 (the
+ * reference: 2).  Everything is copied to the device here. */
+int  yn_draw_create(yn_handle* h, int num_classes, const uint8_t* colors_host, const char* const* labels_host, const uint8_t* atlas_host, int gw, int gh,
+                    int thickness, yn_draw** out);
+void yn_draw_destroy(yn_draw* d);
+/* In place, on the handle's stream, asynchronous: frames_host [B] device pointers, geom_host [B][7], rec_dev [rec_capacity][6] (no
+ * record at or past rec_capacity is read, whatever the offsets hold), offsets_dev [B+1].  offsets_dev[B] < 0 (the split-f16 range
+ * mark) draws nothing and sets the status' range_mark.  Refused before any launch, naming the frame: null pointers, a side outside
+ * 1..16384, a bad letterbox geometry, a space that is neither mode, two frames that are the same buffer or overlap; also a handle on another device than the
+ * one the object was created on.  B == 0 is not an
+ * error.  Work buffers grow with rec_capacity and B (a growth frees the old buffer, which waits for the device). */
+int  yn_draw_batch(yn_handle* h, yn_draw* d, int B, uint8_t* const* frames_host, const int32_t* geom_host, int space, const float* rec_dev,
+                   const int32_t* offsets_dev, int64_t rec_capacity, float vis_thresh);
+/* of the last yn_draw_batch: records drawn, records skipped (see above), range mark.  Any pointer may be NULL.  Synchronises. */
+int  yn_draw_status(yn_handle* h, yn_draw* d, int64_t* drawn, int64_t* skipped, int* range_mark);
+/* testing aid, like yn_eval_records: the drawn primitives of the last yn_draw_batch in drawing order, host int32 [n][7] = frame,
+ * class, x1, y1, x2, y2 (the unclipped integers), k; n = drawn, cap = rows of room.  Synchronises. */
+int  yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("anchor_box_kmeans", "AnchorKMeans", "dataset_boxes", "as_anchor_table"):
         from . import anchors                                 # numpy only until a device object is made
         return getattr(anchors, name)
+    if name in ("Visualizer", "class_colors", "default_font"):
+        from . import draw                                    # numpy only until a Visualizer is made
+        return getattr(draw, name)
     if name in ("Handle", "YnError", "YnRangeError", "load_library"):
         from . import capi
         return getattr(capi, name)

@@ -144,6 +144,11 @@ SIGNATURES = {
     "yn_tta_infer": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32]),
     "yn_tta_result": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
     "yn_tta_forwards": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_draw_create": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
+    "yn_draw_destroy": (None, [_vp]),
+    "yn_draw_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, ctypes.c_int64, _f32]),
+    "yn_draw_status": (_i32, [_vp, _vp, _i64p, _i64p, ctypes.POINTER(_i32)]),
+    "yn_draw_prims": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

@@ -72,6 +72,7 @@ struct GraphEntry {
 
 struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
+struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
 // test-time augmentation for whole batches (kernels_tta.hip): every buffer is allocated once, for max_batch images and the largest scale
 struct yn_tta {
@@ -2406,6 +2407,53 @@ int yn_kmeans_stats(yn_kmeans* e, int64_t* passes, int64_t* host_reads)
     if (!e) return 1;
     ynk::kmeans_stats(e->st, passes, host_reads);
     return 0;
+}
+
+// ---- detections painted onto frames (kernels_draw.hip; test.py:50-92) ---------------------------------------------------------------
+static_assert(YN_DRAW_LETTERBOX == 0 && YN_DRAW_PIXELS == 1, "yn_draw_batch spaces");
+
+int yn_draw_create(yn_handle* h, int num_classes, const uint8_t* colors_host, const char* const* labels_host, const uint8_t* atlas_host, int gw, int gh,
+                   int thickness, yn_draw** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_draw_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::DrawState* st = nullptr;
+    if (ynk::draw_create(h->cfg.device, num_classes, colors_host, labels_host, atlas_host, gw, gh, thickness, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_draw{st};
+    return 0;
+}
+
+void yn_draw_destroy(yn_draw* d)
+{
+    if (!d) return;
+    ynk::draw_destroy(d->st);
+    delete d;
+}
+
+int yn_draw_batch(yn_handle* h, yn_draw* d, int B, uint8_t* const* frames_host, const int32_t* geom_host, int space, const float* rec_dev,
+                  const int32_t* offsets_dev, int64_t rec_capacity, float vis_thresh)
+{
+    YN_ENTER(h);
+    if (!d) return fail(h, "yn_draw_batch: null object");
+    if (ynk::draw_device(d->st) != h->cfg.device)
+        return fail(h, "yn_draw_batch: the object was made for device %d, the handle is on device %d", ynk::draw_device(d->st), h->cfg.device);
+    YN_EVAL_CALL(ynk::draw_batch(d->st, h->stream, B, frames_host, geom_host, space, rec_dev, offsets_dev, rec_capacity, vis_thresh, err));
+}
+
+int yn_draw_status(yn_handle* h, yn_draw* d, int64_t* drawn, int64_t* skipped, int* range_mark)
+{
+    YN_ENTER(h);
+    if (!d) return fail(h, "yn_draw_status: null object");
+    YN_EVAL_CALL(ynk::draw_status(d->st, h->stream, drawn, skipped, range_mark, err));
+}
+
+int yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap)
+{
+    YN_ENTER(h);
+    if (!d || (!host && cap > 0)) return fail(h, "yn_draw_prims: null argument");
+    YN_EVAL_CALL(ynk::draw_prims(d->st, h->stream, host, cap, err));
 }
 
 // ---- test-time augmentation for whole batches (kernels_tta.hip; utils/misc.py:90-148) ----------------------------------------------

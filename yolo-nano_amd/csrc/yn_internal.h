@@ -277,6 +277,17 @@ void launch_tta_resize(const float* x, int B, int S0, int s, int flip, float* ou
 void launch_tta_append(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, int flip, int cap,
                        int bstride, int fwd, float* lboxes, float* lscores, int32_t* lcls, int32_t* state, int32_t* fstart, hipStream_t st);
 
+// ---- detections painted onto frames (kernels_draw.hip): the state behind yn_draw; 0 = ok, 1 = error (text in err) ---------------------
+struct DrawState;
+int  draw_create(int device, int C, const uint8_t* colors, const char* const* labels, const uint8_t* atlas, int gw, int gh, int thickness,
+                 DrawState** out, std::string& err);
+void draw_destroy(DrawState* d);
+int  draw_device(const DrawState* d);
+int  draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, const int32_t* geom, int space, const float* rec_dev,
+                const int32_t* offsets_dev, int64_t rec_capacity, float vis_thresh, std::string& err);
+int  draw_status(DrawState* d, hipStream_t s, int64_t* drawn, int64_t* skipped, int* range_mark, std::string& err);
+int  draw_prims(DrawState* d, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
+
 // ---- training loss (kernels_train.hip) --------------------------------------------------------------
 int  loss_num_blocks(const GridInfo& g, int B);
 void launch_loss(const float* conf, const float* cls, const float* t, const float* const head[3], float* const ghead[3],
