@@ -57,6 +57,9 @@ int  yn_abi_version(void);
 int  yn_create(const yn_config* cfg, yn_handle** out);          /* YOLONano.__init__            :13  */
 void yn_destroy(yn_handle* h);
 const char* yn_last_error(yn_handle* h);
+/* device memory the library holds in this process, over every handle and object: blocks and bytes (either pointer may be NULL).  A card's free
+ * memory is shared with other processes and cannot show that a destroy gave everything back; this count can. */
+int  yn_live_device_memory(int64_t* blocks, int64_t* bytes);
 int  yn_set_grid(yn_handle* h, int input_size);                 /* YOLONano.set_grid            :115 */
 int  yn_set_stream(yn_handle* h, void* stream);                /* drains the previous stream first  */
 int  yn_set_thresholds(yn_handle* h, float conf_thresh, float nms_thresh, int diou_nms);

@@ -106,3 +106,15 @@ def test_native_code_reads_only_the_listed_environment_variables():
             assert lit, "%s: getenv without a string literal: %r" % (f, text[m.start():m.end() + 40])
             names.add(lit.group(1))
     assert names == RUNTIME_ENV
+
+
+def test_device_memory_is_allocated_and_freed_in_one_header():
+    """Every device or pinned block of the library belongs to a DevBuf / PinnedBuf (csrc/yn_devbuf.h): no other file calls the allocator."""
+    csrc = os.path.join(ROOT, "yolo-nano_amd", "csrc")
+    calls = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".inc")):
+            found = set(re.findall(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\s*\(", open(os.path.join(csrc, f)).read()))
+            if found:
+                calls[f] = found
+    assert calls == {"yn_devbuf.h": {"hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree"}}

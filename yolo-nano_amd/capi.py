@@ -35,6 +35,7 @@ SIGNATURES = {
     "yn_create": (_i32, [ctypes.POINTER(YnConfig), ctypes.POINTER(_vp)]),
     "yn_destroy": (None, [_vp]),
     "yn_last_error": (ctypes.c_char_p, [_vp]),
+    "yn_live_device_memory": (_i32, [_i64p, _i64p]),
     "yn_set_grid": (_i32, [_vp, _i32]),
     "yn_set_stream": (_i32, [_vp, _vp]),
     "yn_set_thresholds": (_i32, [_vp, _f32, _f32, _i32]),

@@ -355,52 +355,31 @@ struct CocoState {
     int device = 0, C = 0, keep = 100;
     int64_t n = 0;                             // detections in the store
     int n_img = 0;
-    float* det = nullptr; size_t det_cap = 0;  // [det_cap / 5][5]
-    int64_t* seg = nullptr; size_t seg_cap = 0;   // [n_img * C + 1]
+    DevBuf<float> det;                         // [cap / 5][5]
+    DevBuf<int64_t> seg;                       // [n_img * C + 1]
     // per-add scratch
-    float* tmp = nullptr; size_t tmp_cap = 0;
-    int32_t *pc = nullptr, *grp = nullptr; size_t pc_cap = 0, grp_cap = 0;
-    int32_t *cnt = nullptr, *fill = nullptr, *start = nullptr, *kstart = nullptr;
-    size_t cnt_cap = 0, fill_cap = 0, start_cap = 0, kstart_cap = 0;
-    int32_t* geom_dev = nullptr; size_t geom_cap = 0;
-    int32_t* kept_dev = nullptr;
-    int32_t* pinned = nullptr; size_t pinned_cap = 0;
-    int* err_dev = nullptr;
+    DevBuf<float> tmp;
+    DevBuf<int32_t> pc, grp, cnt, fill, start, kstart, geom_dev, kept_dev;
+    PinnedBuf<int32_t> pinned;
+    DevBuf<int> err_dev;
     // ground truth (host until finish), grouped by (image, category), file order inside
     std::vector<int64_t> ids;
     std::vector<double> gt;                    // [G][5] x, y, w, h, area
     std::vector<uint8_t> gt_crowd;
     std::vector<int32_t> gt_seg{0};            // [n_img * C + 1]
     // finish
-    double* gt_dev = nullptr; size_t gtd_cap = 0;
-    uint8_t* crowd_dev = nullptr; size_t crowd_cap = 0;
-    int32_t* gt_seg_dev = nullptr; size_t gseg_cap = 0;
-    int32_t* rank_dev = nullptr; size_t rank_cap = 0;
-    uint32_t* flags = nullptr; size_t flags_cap = 0;
-    Key128* keys = nullptr; size_t keys_cap = 0;
-    unsigned long long* npig = nullptr; size_t npig_cap = 0;
-    double *rec_thrs = nullptr, *prec_dev = nullptr, *recall_dev = nullptr;
-    size_t thr_cap = 0, prec_cap = 0, recall_cap = 0;
+    DevBuf<double> gt_dev;
+    DevBuf<uint8_t> crowd_dev;
+    DevBuf<int32_t> gt_seg_dev, rank_dev;
+    DevBuf<uint32_t> flags;
+    DevBuf<Key128> keys;
+    DevBuf<unsigned long long> npig;
+    DevBuf<double> rec_thrs, prec_dev, recall_dev;
     bool finished = false;
     int fin_A = 0;
 };
 
 namespace {
-
-template <typename T>
-int grow_keep(T*& p, size_t& cap, size_t need, size_t used, hipStream_t s, std::string& err)   // keeps the first `used` elements
-{
-    if (need <= cap) return 0;
-    size_t nc = cap ? cap : 4096;
-    while (nc < need) nc *= 2;
-    T* q = nullptr;
-    EVCHK(hipMalloc((void**)&q, nc * sizeof(T)));
-    if (used) EVCHK(hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
-    EVCHK(hipStreamSynchronize(s));
-    if (p) EVCHK(hipFree(p));
-    p = q; cap = nc;
-    return 0;
-}
 
 const char* coco_err_text(int bits)
 {
@@ -417,12 +396,11 @@ int coco_create(int device, int C, int max_det, CocoState** out, std::string& er
     if (max_det < 1 || max_det > CO_MAX_KEEP) { err = "yn_coco_create: max_det must be 1..1023"; return 1; }
     auto* e = new CocoState;
     e->device = device; e->C = C; e->keep = max_det;
-    hipError_t r = hipMalloc((void**)&e->err_dev, 16);
-    if (r == hipSuccess) r = hipMemset(e->err_dev, 0, 16);
-    if (r == hipSuccess) r = hipMalloc((void**)&e->kept_dev, 16);
-    if (r == hipSuccess) r = hipHostMalloc((void**)&e->pinned, 64 * sizeof(int32_t), hipHostMallocDefault);
-    if (r != hipSuccess) { err = std::string("yn_coco_create: ") + hipGetErrorString(r); coco_destroy(e); return 1; }
-    e->pinned_cap = 64;
+    int r = e->err_dev.reserve(4);
+    if (!r) r = e->kept_dev.reserve(4);
+    if (!r) r = e->pinned.reserve(64);
+    if (!r) r = hipMemset(e->err_dev, 0, 16);
+    if (r) { err = std::string("yn_coco_create: ") + hipGetErrorString((hipError_t)r); coco_destroy(e); return 1; }
     *out = e;
     return 0;
 }
@@ -433,13 +411,8 @@ void coco_destroy(CocoState* e)
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     (void)hipSetDevice(e->device);
-    void* dev[] = {e->det, e->seg, e->tmp, e->pc, e->grp, e->cnt, e->fill, e->start, e->kstart, e->geom_dev, e->kept_dev, e->err_dev,
-                   e->gt_dev, e->crowd_dev, e->gt_seg_dev, e->rank_dev, e->flags, e->keys, e->npig, e->rec_thrs, e->prec_dev, e->recall_dev};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (prev >= 0) (void)hipSetDevice(prev);
     delete e;
+    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int coco_reset(CocoState* e, hipStream_t s, std::string& err)
@@ -480,12 +453,9 @@ int coco_add(CocoState* e, hipStream_t s, int B, const float* rec_dev, const int
             if (++cnt[cat] > CO_MAX_GT) { err = "yn_coco_add: more than 4096 ground-truth boxes of one category in one image"; return 1; }
         }
     }
-    if (e->pinned_cap < 1 + 7 * (size_t)B) {
+    if (e->pinned.cap() < 1 + 7 * (size_t)B) {
         EVCHK(hipStreamSynchronize(s));
-        EVCHK(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        EVCHK(hipHostMalloc((void**)&e->pinned, (1 + 7 * (size_t)B) * sizeof(int32_t), hipHostMallocDefault));
-        e->pinned_cap = 1 + 7 * (size_t)B;
+        EVCHK(e->pinned.reserve(1 + 7 * (size_t)B));
     }
     EVCHK(hipMemcpyAsync(e->pinned, offsets_dev + B, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     EVCHK(hipStreamSynchronize(s));            // also retires the previous batch's use of the staging and scratch buffers
@@ -494,11 +464,14 @@ int coco_add(CocoState* e, hipStream_t s, int B, const float* rec_dev, const int
     if (e->n + total >= ((int64_t)1 << 31)) { err = "yn_coco_add: more than 2^31 - 1 detections"; return 1; }
     const int P = B * C;
     const size_t tn = total > 0 ? (size_t)total : 1;
-    if (grow(e->tmp, e->tmp_cap, 5 * tn, err) || grow(e->pc, e->pc_cap, tn, err) || grow(e->grp, e->grp_cap, tn, err) ||
-        grow(e->cnt, e->cnt_cap, (size_t)P, err) || grow(e->fill, e->fill_cap, (size_t)P, err) ||
-        grow(e->start, e->start_cap, (size_t)P + 1, err) || grow(e->kstart, e->kstart_cap, (size_t)P + 1, err) ||
-        grow(e->geom_dev, e->geom_cap, 7 * (size_t)B, err))
-        return 1;
+    EVCHK(e->tmp.reserve(5 * tn, 1));              // every scratch buffer doubles from one element
+    EVCHK(e->pc.reserve(tn, 1));
+    EVCHK(e->grp.reserve(tn, 1));
+    EVCHK(e->cnt.reserve((size_t)P, 1));
+    EVCHK(e->fill.reserve((size_t)P, 1));
+    EVCHK(e->start.reserve((size_t)P + 1, 1));
+    EVCHK(e->kstart.reserve((size_t)P + 1, 1));
+    EVCHK(e->geom_dev.reserve(7 * (size_t)B, 1));
     memcpy(e->pinned + 1, geom, 7 * (size_t)B * sizeof(int32_t));
     EVCHK(hipMemcpyAsync(e->geom_dev, e->pinned + 1, 7 * (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     EVCHK(hipMemsetAsync(e->cnt, 0, (size_t)P * sizeof(int32_t), s));
@@ -512,8 +485,8 @@ int coco_add(CocoState* e, hipStream_t s, int B, const float* rec_dev, const int
     EVCHK(hipStreamSynchronize(s));
     const int32_t kept = e->pinned[0];
     if (kept < 0 || kept > total) { err = "yn_coco_add: internal count mismatch"; return 1; }
-    if (grow_keep(e->det, e->det_cap, 5 * (size_t)(e->n + kept) + 5, 5 * (size_t)e->n, s, err)) return 1;
-    if (grow_keep(e->seg, e->seg_cap, (size_t)(e->n_img + B) * C + 1, e->n_img ? (size_t)e->n_img * C + 1 : 0, s, err)) return 1;
+    EVCHK(e->det.reserve_keep(5 * (size_t)(e->n + kept) + 5, 5 * (size_t)e->n, s, 4096));
+    EVCHK(e->seg.reserve_keep((size_t)(e->n_img + B) * C + 1, e->n_img ? (size_t)e->n_img * C + 1 : 0, s, 4096));
     if (total > 0)
         hipLaunchKernelGGL(coco_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const int32_t*)e->pc, (int)total,
                            (const int32_t*)e->start, e->fill, e->grp);
@@ -575,12 +548,16 @@ int coco_finish(CocoState* e, hipStream_t s, const double* iou_thrs, int T, cons
     while (npow < n) npow *= 2;
     const size_t np_out = (size_t)T * R * C * A * M, nr_out = (size_t)T * C * A * M;
     EVCHK(hipStreamSynchronize(s));
-    if (grow(e->gt_dev, e->gtd_cap, e->gt.size() + 5, err) || grow(e->crowd_dev, e->crowd_cap, e->gt_crowd.size() + 1, err) ||
-        grow(e->gt_seg_dev, e->gseg_cap, e->gt_seg.size(), err) || grow(e->rank_dev, e->rank_cap, (size_t)n_img + 1, err) ||
-        grow(e->flags, e->flags_cap, (size_t)A * (size_t)n + 1, err) || grow(e->keys, e->keys_cap, (size_t)npow, err) ||
-        grow(e->npig, e->npig_cap, (size_t)C * A, err) || grow(e->rec_thrs, e->thr_cap, (size_t)R, err) ||
-        grow(e->prec_dev, e->prec_cap, np_out, err) || grow(e->recall_dev, e->recall_cap, nr_out, err))
-        return 1;
+    EVCHK(e->gt_dev.reserve(e->gt.size() + 5, 1));
+    EVCHK(e->crowd_dev.reserve(e->gt_crowd.size() + 1, 1));
+    EVCHK(e->gt_seg_dev.reserve(e->gt_seg.size(), 1));
+    EVCHK(e->rank_dev.reserve((size_t)n_img + 1, 1));
+    EVCHK(e->flags.reserve((size_t)A * (size_t)n + 1, 1));
+    EVCHK(e->keys.reserve((size_t)npow, 1));
+    EVCHK(e->npig.reserve((size_t)C * A, 1));
+    EVCHK(e->rec_thrs.reserve((size_t)R, 1));
+    EVCHK(e->prec_dev.reserve(np_out, 1));
+    EVCHK(e->recall_dev.reserve(nr_out, 1));
     if (!e->gt.empty()) {
         EVCHK(hipMemcpyAsync(e->gt_dev, e->gt.data(), e->gt.size() * sizeof(double), hipMemcpyHostToDevice, s));
         EVCHK(hipMemcpyAsync(e->crowd_dev, e->gt_crowd.data(), e->gt_crowd.size(), hipMemcpyHostToDevice, s));
@@ -596,7 +573,7 @@ int coco_finish(CocoState* e, hipStream_t s, const double* iou_thrs, int T, cons
     }
     hipLaunchKernelGGL(coco_keys_kernel, dim3((unsigned)((npow + 255) / 256)), dim3(256), 0, s, (const float*)e->det, (const int64_t*)e->seg,
                        P, C, (const int32_t*)e->rank_dev, n, npow, e->keys);
-    if (n > 0) bitonic_sort(e->keys, npow, s);
+    if (n > 0) bitonic_sort(e->keys.get(), npow, s);
     hipLaunchKernelGGL(coco_curve_kernel, dim3(C, A, M), dim3(256), 0, s, (const Key128*)e->keys, n, (const uint32_t*)e->flags,
                        (const unsigned long long*)e->npig, (const double*)e->rec_thrs, prm, T, R, C, A, M, e->prec_dev, e->recall_dev);
     EVCHK(hipGetLastError());

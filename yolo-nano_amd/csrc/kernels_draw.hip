@@ -260,13 +260,13 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_tile_kernel(DrawFrames fr, 
 struct DrawState {
     int device = 0, C = 0, thickness = 2, gw = 0, gh = 0;
     bool labelled = false;
-    uint32_t* colors = nullptr;
-    unsigned char* labels = nullptr;
-    int32_t* lens = nullptr;
-    unsigned char* atlas = nullptr;
-    int32_t* prims = nullptr; size_t prims_cap = 0;             // [records][DRAW_PRIM]: frame b's list starts at its first record's slot
-    int32_t* book = nullptr; size_t book_cap = 0;               // [2][book_cap]: start, count per frame
-    unsigned long long* stat = nullptr;                         // drawn, skipped, range mark of the last batch
+    DevBuf<uint32_t> colors;
+    DevBuf<unsigned char> labels, atlas;
+    DevBuf<int32_t> lens;
+    DevBuf<int32_t> prims;                                      // [records][DRAW_PRIM]: frame b's list starts at its first record's slot
+    DevBuf<int32_t> book;                                       // [2][frames()]: start, count per frame
+    size_t frames() const { return book.cap() / 2; }
+    DevBuf<unsigned long long> stat;                            // drawn, skipped, range mark of the last batch
     int last_B = -1;
 };
 
@@ -278,17 +278,13 @@ void draw_destroy(DrawState* d)
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     (void)hipSetDevice(d->device);
-    void* dev[] = {d->colors, d->labels, d->lens, d->atlas, d->prims, d->book, d->stat};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    if (prev >= 0) (void)hipSetDevice(prev);
     delete d;
+    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int draw_create(int device, int C, const uint8_t* colors, const char* const* labels, const uint8_t* atlas, int gw, int gh, int thickness,
                 DrawState** out, std::string& err)
 {
-    using evs::grow;
     if (!colors) { err = "yn_draw_create: null colours"; return 1; }
     if (C < 1 || C > 2000) { err = "yn_draw_create: num_classes " + std::to_string(C) + " outside 1..2000"; return 1; }
     if (thickness < 1 || thickness > 8) { err = "yn_draw_create: thickness " + std::to_string(thickness) + " outside 1..8"; return 1; }
@@ -316,20 +312,20 @@ int draw_create(int device, int C, const uint8_t* colors, const char* const* lab
     auto* d = new DrawState;
     d->device = device; d->C = C; d->thickness = thickness; d->labelled = labels != nullptr;
     d->gw = labels ? gw : 0; d->gh = labels ? gh : 0;
-    hipError_t r = hipMalloc((void**)&d->colors, (size_t)C * sizeof(uint32_t));
-    if (r == hipSuccess) r = hipMemcpy(d->colors, packed.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (r == hipSuccess) r = hipMalloc((void**)&d->stat, 3 * sizeof(unsigned long long));
-    if (r == hipSuccess) r = hipMemset(d->stat, 0, 3 * sizeof(unsigned long long));
+    const size_t an = (size_t)95 * gh * gw;
+    int r = d->colors.reserve((size_t)C);
+    if (!r) r = d->stat.reserve(3);
+    if (!r && labels) r = d->labels.reserve(lab.size());
+    if (!r && labels) r = d->lens.reserve((size_t)C);
+    if (!r && labels) r = d->atlas.reserve(an);
+    if (!r) r = hipMemcpy(d->colors, packed.data(), (size_t)C * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (!r) r = hipMemset(d->stat, 0, 3 * sizeof(unsigned long long));
     if (labels) {
-        const size_t an = (size_t)95 * gh * gw;
-        if (r == hipSuccess) r = hipMalloc((void**)&d->labels, lab.size());
-        if (r == hipSuccess) r = hipMemcpy(d->labels, lab.data(), lab.size(), hipMemcpyHostToDevice);
-        if (r == hipSuccess) r = hipMalloc((void**)&d->lens, (size_t)C * sizeof(int32_t));
-        if (r == hipSuccess) r = hipMemcpy(d->lens, lens.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (r == hipSuccess) r = hipMalloc((void**)&d->atlas, an);
-        if (r == hipSuccess) r = hipMemcpy(d->atlas, atlas, an, hipMemcpyHostToDevice);
+        if (!r) r = hipMemcpy(d->labels, lab.data(), lab.size(), hipMemcpyHostToDevice);
+        if (!r) r = hipMemcpy(d->lens, lens.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (!r) r = hipMemcpy(d->atlas, atlas, an, hipMemcpyHostToDevice);
     }
-    if (r != hipSuccess) { err = std::string("yn_draw_create: ") + hipGetErrorString(r); draw_destroy(d); return 1; }
+    if (r) { err = std::string("yn_draw_create: ") + hipGetErrorString((hipError_t)r); draw_destroy(d); return 1; }
     *out = d;
     return 0;
 }
@@ -337,7 +333,6 @@ int draw_create(int device, int C, const uint8_t* colors, const char* const* lab
 int draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, const int32_t* geom, int space, const float* rec_dev,
                const int32_t* offsets_dev, int64_t rec_capacity, float vis_thresh, std::string& err)
 {
-    using evs::grow;
     if (B < 0) { err = "yn_draw_batch: negative batch"; return 1; }
     if (space != 0 && space != 1) { err = "yn_draw_batch: space " + std::to_string(space) + " is neither YN_DRAW_LETTERBOX nor YN_DRAW_PIXELS"; return 1; }
     if (rec_capacity < 0 || rec_capacity > ((int64_t)1 << 31) - 1) { err = "yn_draw_batch: rec_capacity outside 0..2^31 - 1"; return 1; }
@@ -375,13 +370,10 @@ int draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, const
             return 1;
         }
     }
-    if (grow(d->prims, d->prims_cap, (size_t)std::max<int64_t>(rec_capacity, 1) * DRAW_PRIM, err)) return 1;
-    if ((size_t)B > d->book_cap) {
-        size_t cap = 0;                                         // [2][cap]: both halves move, so start over
-        if (d->book) EVCHK(hipFree(d->book));
-        d->book = nullptr; d->book_cap = 0;
-        if (grow(d->book, cap, 2 * (size_t)std::max(B, DRAW_FRAMES), err)) return 1;
-        d->book_cap = cap / 2;
+    EVCHK(d->prims.reserve((size_t)std::max<int64_t>(rec_capacity, 1) * DRAW_PRIM, 1));
+    if ((size_t)B > d->frames()) {                              // [2][frames]: both halves move, so start over from one element
+        d->book.reset();
+        EVCHK(d->book.reserve(2 * (size_t)std::max(B, DRAW_FRAMES), 1));
     }
     EVCHK(hipMemsetAsync(d->stat, 0, 3 * sizeof(unsigned long long), s));
     DrawStyle st{d->colors, d->labels, d->lens, d->atlas, d->gw, d->gh, d->thickness, d->C};
@@ -397,9 +389,9 @@ int draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, const
             tiles += ((g[0] + DRAW_TW - 1) / DRAW_TW) * ((g[1] + DRAW_TH - 1) / DRAW_TH);      // at most 32 * 256 * 1024 = 2^23
         }
         for (int i = fr.m; i <= DRAW_FRAMES; ++i) fr.tile0[i] = tiles;
-        hipLaunchKernelGGL(draw_prims_kernel, dim3(fr.m), dim3(DRAW_THREADS), 0, s, fr, b0, B, (int)d->book_cap, rec_dev, offsets_dev,
+        hipLaunchKernelGGL(draw_prims_kernel, dim3(fr.m), dim3(DRAW_THREADS), 0, s, fr, b0, B, (int)d->frames(), rec_dev, offsets_dev,
                            (long long)rec_capacity, vis_thresh, space, d->C, d->prims, d->book, d->stat);
-        hipLaunchKernelGGL(draw_tile_kernel, dim3(tiles), dim3(DRAW_THREADS), 0, s, fr, b0, (int)d->book_cap, d->prims, d->book, st);
+        hipLaunchKernelGGL(draw_tile_kernel, dim3(tiles), dim3(DRAW_THREADS), 0, s, fr, b0, (int)d->frames(), d->prims, d->book, st);
     }
     EVCHK(hipGetLastError());
     d->last_B = B;
@@ -423,16 +415,16 @@ int draw_prims(DrawState* d, hipStream_t s, int32_t* host, int64_t cap, std::str
     if (d->last_B < 0) { err = "yn_draw_prims: no yn_draw_batch has run"; return 1; }
     const int B = d->last_B;
     if (B == 0) return 0;
-    std::vector<int32_t> book(2 * d->book_cap);
+    std::vector<int32_t> book(2 * d->frames());
     EVCHK(hipMemcpyAsync(book.data(), d->book, book.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     EVCHK(hipStreamSynchronize(s));
     int64_t n = 0;
-    for (int b = 0; b < B; ++b) n += book[d->book_cap + b];
+    for (int b = 0; b < B; ++b) n += book[d->frames() + b];
     if (n > cap) { err = "yn_draw_prims: " + std::to_string(n) + " primitives, room for " + std::to_string(cap); return 1; }
     std::vector<int32_t> tmp;
     int64_t at = 0;
     for (int b = 0; b < B; ++b) {
-        const int cnt = book[d->book_cap + b];
+        const int cnt = book[d->frames() + b];
         if (!cnt) continue;
         tmp.resize((size_t)cnt * DRAW_PRIM);
         EVCHK(hipMemcpyAsync(tmp.data(), d->prims + (size_t)book[b] * DRAW_PRIM, tmp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));

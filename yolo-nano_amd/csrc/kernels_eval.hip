@@ -322,25 +322,24 @@ __global__ __launch_bounds__(CT) void eval_curve_kernel(const uint64_t* __restri
 struct EvalState {
     int device = 0, C = 0;
     double ovthresh = 0.5;
-    int64_t n = 0, cap = 0;                    // records ingested / capacity of soa
-    int n_img = 0, img_cap = 0;
-    int32_t* soa = nullptr;                    // [7][cap]: img, cls, k, x1, y1, x2, y2 (tenths)
-    int32_t* img_first = nullptr;              // [img_cap]
-    int32_t* geom_dev = nullptr; int geom_cap = 0;
-    int32_t* pinned = nullptr; int pinned_cap = 0;   // offsets[B] read-back + geometry staging
-    int* err_dev = nullptr;
+    int64_t n = 0;                             // records ingested
+    int n_img = 0;
+    DevBuf<int32_t> soa;                       // [7][planes()]: img, cls, k, x1, y1, x2, y2 (tenths)
+    int64_t planes() const { return (int64_t)(soa.cap() / 7); }
+    DevBuf<int32_t> img_first;                 // [n_img]
+    DevBuf<int32_t> geom_dev;
+    PinnedBuf<int32_t> pinned;                 // offsets[B] read-back + geometry staging
+    DevBuf<int> err_dev;
     std::vector<int32_t> gt;                   // [G][5] grouped by (image, class), file order inside
     std::vector<int32_t> gt_seg{0};            // [n_img * C + 1]
     std::vector<int64_t> npos;                 // [C] non-difficult GT
     // finish
-    int64_t fin_cap = 0, fin_pow = 0;
-    uint64_t *keyA = nullptr, *keyB = nullptr;
-    uint8_t* flag = nullptr;
-    double *rec = nullptr, *prec = nullptr, *env = nullptr, *terms = nullptr, *ap = nullptr;
-    int32_t* pts = nullptr;
-    int64_t *npos_dev = nullptr, *cls_start = nullptr;
-    int32_t *gt_dev = nullptr, *gt_seg_dev = nullptr;
-    size_t gt_cap = 0, seg_cap = 0;
+    DevBuf<uint64_t> keyA, keyB;
+    DevBuf<uint8_t> flag;
+    DevBuf<double> rec, prec, env, terms, ap;
+    DevBuf<int32_t> pts;
+    DevBuf<int64_t> npos_dev, cls_start;
+    DevBuf<int32_t> gt_dev, gt_seg_dev;
     bool finished = false;
     std::vector<int64_t> starts;               // [C+1] class segments of the last finish
 };
@@ -352,11 +351,10 @@ int eval_create(int device, int C, double ovthresh, EvalState** out, std::string
     auto* e = new EvalState;
     e->device = device; e->C = C; e->ovthresh = ovthresh;
     e->npos.assign(C, 0);
-    hipError_t r = hipMalloc((void**)&e->err_dev, 16);
-    if (r == hipSuccess) r = hipMemset(e->err_dev, 0, 16);
-    if (r == hipSuccess) r = hipHostMalloc((void**)&e->pinned, 64 * sizeof(int32_t), hipHostMallocDefault);
-    if (r != hipSuccess) { err = std::string("yn_eval_create: ") + hipGetErrorString(r); eval_destroy(e); return 1; }
-    e->pinned_cap = 64;
+    int r = e->err_dev.reserve(4);
+    if (!r) r = e->pinned.reserve(64);
+    if (!r) r = hipMemset(e->err_dev, 0, 16);
+    if (r) { err = std::string("yn_eval_create: ") + hipGetErrorString((hipError_t)r); eval_destroy(e); return 1; }
     *out = e;
     return 0;
 }
@@ -367,13 +365,8 @@ void eval_destroy(EvalState* e)
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     (void)hipSetDevice(e->device);
-    void* dev[] = {e->soa, e->img_first, e->geom_dev, e->err_dev, e->keyA, e->keyB, e->flag, e->rec, e->prec, e->env, e->terms, e->ap,
-                   e->pts, e->npos_dev, e->cls_start, e->gt_dev, e->gt_seg_dev};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (prev >= 0) (void)hipSetDevice(prev);
     delete e;
+    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int eval_reset(EvalState* e, hipStream_t s, std::string& err)
@@ -411,12 +404,9 @@ int eval_add(EvalState* e, hipStream_t s, int B, const float* rec_dev, const int
             if (++cnt[g[4]] > EV_MAX_GT) { err = "yn_eval_add: more than 4096 ground-truth boxes of one class in one image"; return 1; }
         }
     }
-    if (e->pinned_cap < 1 + 7 * B) {
+    if (e->pinned.cap() < 1 + 7 * (size_t)B) {
         EVCHK(hipStreamSynchronize(s));
-        EVCHK(hipHostFree(e->pinned));
-        e->pinned = nullptr;
-        EVCHK(hipHostMalloc((void**)&e->pinned, (1 + 7 * (size_t)B) * sizeof(int32_t), hipHostMallocDefault));
-        e->pinned_cap = 1 + 7 * B;
+        EVCHK(e->pinned.reserve(1 + 7 * (size_t)B));
     }
     EVCHK(hipMemcpyAsync(e->pinned, offsets_dev + B, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     EVCHK(hipStreamSynchronize(s));            // also retires the previous batch's use of the geometry staging
@@ -424,38 +414,24 @@ int eval_add(EvalState* e, hipStream_t s, int B, const float* rec_dev, const int
     if (total < 0) { err = "yn_eval_add: offsets[B] is negative (split-f16 range mark): nothing added"; return 2; }
     if (e->n + total >= ((int64_t)1 << 31)) { err = "yn_eval_add: more than 2^31 - 1 records"; return 1; }
     // records: grow the SoA store (keeps what is there)
-    if (e->n + total > e->cap) {
-        int64_t nc = e->cap ? e->cap : 4096;
+    if (e->n + total > e->planes()) {
+        int64_t nc = e->planes() ? e->planes() : 4096;
         while (nc < e->n + total) nc *= 2;
-        int32_t* p = nullptr;
-        EVCHK(hipMalloc((void**)&p, (size_t)nc * 7 * sizeof(int32_t)));
+        DevBuf<int32_t> p;                     // the seven planes move apart: copied by hand, swapped in when all of it has arrived
+        EVCHK(p.reserve((size_t)nc * 7));
         if (e->n)
             for (int f = 0; f < 7; ++f)
-                EVCHK(hipMemcpyAsync(p + f * nc, e->soa + f * e->cap, (size_t)e->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+                EVCHK(hipMemcpyAsync(p + f * nc, e->soa + f * e->planes(), (size_t)e->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         EVCHK(hipStreamSynchronize(s));
-        if (e->soa) EVCHK(hipFree(e->soa));
-        e->soa = p; e->cap = nc;
+        e->soa = std::move(p);
     }
-    if (e->n_img + B > e->img_cap) {
-        int nc = e->img_cap ? e->img_cap : 1024;
-        while (nc < e->n_img + B) nc *= 2;
-        int32_t* p = nullptr;
-        EVCHK(hipMalloc((void**)&p, (size_t)nc * sizeof(int32_t)));
-        if (e->n_img) EVCHK(hipMemcpyAsync(p, e->img_first, (size_t)e->n_img * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        EVCHK(hipStreamSynchronize(s));
-        if (e->img_first) EVCHK(hipFree(e->img_first));
-        e->img_first = p; e->img_cap = nc;
-    }
-    if (e->geom_cap < 7 * B) {
-        size_t gc = e->geom_cap;
-        if (grow(e->geom_dev, gc, 7 * (size_t)B, err)) return 1;
-        e->geom_cap = (int)gc;
-    }
+    EVCHK(e->img_first.reserve_keep((size_t)e->n_img + B, (size_t)e->n_img, s, 1024));
+    EVCHK(e->geom_dev.reserve(7 * (size_t)B, 1));
     memcpy(e->pinned + 1, geom, 7 * (size_t)B * sizeof(int32_t));
     EVCHK(hipMemcpyAsync(e->geom_dev, e->pinned + 1, 7 * (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const int64_t threads = total > B ? total : B;
     hipLaunchKernelGGL(eval_ingest_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, rec_dev, offsets_dev, B,
-                       (const int32_t*)e->geom_dev, C, e->n, e->n_img, e->soa, e->cap, e->img_first, e->err_dev);
+                       (const int32_t*)e->geom_dev, C, e->n, e->n_img, e->soa, e->planes(), e->img_first, e->err_dev);
     EVCHK(hipGetLastError());
     // ground truth: per image, grouped by class in file order
     for (int b = 0; b < B; ++b) {
@@ -489,45 +465,32 @@ int eval_finish(EvalState* e, hipStream_t s, int use07, double* ap_host, int64_t
     const int64_t n = e->n;
     int64_t npow = EV_LOCAL;
     while (npow < n) npow *= 2;
-    if (npow > e->fin_pow) {
-        void* ps[] = {e->keyA, e->keyB};
-        for (void* p : ps) if (p) EVCHK(hipFree(p));
-        e->keyA = e->keyB = nullptr;
-        EVCHK(hipMalloc((void**)&e->keyA, npow * sizeof(uint64_t)));
-        EVCHK(hipMalloc((void**)&e->keyB, npow * sizeof(uint64_t)));
-        e->fin_pow = npow;
-    }
-    if (n + C > e->fin_cap) {
-        void* ps[] = {e->flag, e->rec, e->prec, e->env, e->terms, e->pts};
-        for (void* p : ps) if (p) EVCHK(hipFree(p));
-        const int64_t m = n + C;
-        EVCHK(hipMalloc((void**)&e->flag, m));
-        EVCHK(hipMalloc((void**)&e->rec, m * sizeof(double)));
-        EVCHK(hipMalloc((void**)&e->prec, m * sizeof(double)));
-        EVCHK(hipMalloc((void**)&e->env, m * sizeof(double)));
-        EVCHK(hipMalloc((void**)&e->terms, m * sizeof(double)));
-        EVCHK(hipMalloc((void**)&e->pts, m * sizeof(int32_t)));
-        e->fin_cap = m;
-    }
-    if (!e->ap) {
-        EVCHK(hipMalloc((void**)&e->ap, C * sizeof(double)));
-        EVCHK(hipMalloc((void**)&e->npos_dev, C * sizeof(int64_t)));
-        EVCHK(hipMalloc((void**)&e->cls_start, (C + 1) * sizeof(int64_t)));
-    }
-    if (grow(e->gt_dev, e->gt_cap, e->gt.size() + 5, err)) return 1;
-    if (grow(e->gt_seg_dev, e->seg_cap, e->gt_seg.size(), err)) return 1;
+    const size_t m = (size_t)(n + C);
+    EVCHK(e->keyA.reserve((size_t)npow));
+    EVCHK(e->keyB.reserve((size_t)npow));
+    EVCHK(e->flag.reserve(m));
+    EVCHK(e->rec.reserve(m));
+    EVCHK(e->prec.reserve(m));
+    EVCHK(e->env.reserve(m));
+    EVCHK(e->terms.reserve(m));
+    EVCHK(e->pts.reserve(m));
+    EVCHK(e->ap.reserve((size_t)C));
+    EVCHK(e->npos_dev.reserve((size_t)C));
+    EVCHK(e->cls_start.reserve((size_t)C + 1));
+    EVCHK(e->gt_dev.reserve(e->gt.size() + 5, 1));
+    EVCHK(e->gt_seg_dev.reserve(e->gt_seg.size(), 1));
     EVCHK(hipStreamSynchronize(s));
     if (!e->gt.empty()) EVCHK(hipMemcpyAsync(e->gt_dev, e->gt.data(), e->gt.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     EVCHK(hipMemcpyAsync(e->gt_seg_dev, e->gt_seg.data(), e->gt_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     EVCHK(hipMemcpyAsync(e->npos_dev, e->npos.data(), C * sizeof(int64_t), hipMemcpyHostToDevice, s));
     if (n > 0) {
-        hipLaunchKernelGGL(eval_keys_kernel, dim3((unsigned)((npow + 255) / 256)), dim3(256), 0, s, (const int32_t*)e->soa, e->cap,
+        hipLaunchKernelGGL(eval_keys_kernel, dim3((unsigned)((npow + 255) / 256)), dim3(256), 0, s, (const int32_t*)e->soa, e->planes(),
                            (const int32_t*)e->img_first, n, npow, e->keyA, e->keyB);
-        bitonic_sort(e->keyA, npow, s);
-        bitonic_sort(e->keyB, npow, s);
+        bitonic_sort(e->keyA.get(), npow, s);
+        bitonic_sort(e->keyB.get(), npow, s);
         const int64_t pairs = (int64_t)e->n_img * C;
         hipLaunchKernelGGL(eval_match_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, (const uint64_t*)e->keyB, n,
-                           (const int32_t*)e->soa, e->cap, (const int32_t*)e->img_first, (const int32_t*)e->gt_dev,
+                           (const int32_t*)e->soa, e->planes(), (const int32_t*)e->img_first, (const int32_t*)e->gt_dev,
                            (const int32_t*)e->gt_seg_dev, e->n_img, C, e->ovthresh, e->flag);
     }
     hipLaunchKernelGGL(eval_curve_kernel, dim3(C), dim3(CT), 0, s, (const uint64_t*)e->keyA, n, (const uint8_t*)e->flag,
@@ -567,7 +530,7 @@ int eval_records(EvalState* e, hipStream_t s, int32_t* host, int64_t cap, std::s
     int bits = 0;
     std::vector<int32_t> tmp((size_t)m * 7);
     for (int f = 0; f < 7 && m > 0; ++f)
-        EVCHK(hipMemcpyAsync(tmp.data() + f * m, e->soa + f * e->cap, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        EVCHK(hipMemcpyAsync(tmp.data() + f * m, e->soa + f * e->planes(), m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     EVCHK(hipMemcpyAsync(&bits, e->err_dev, sizeof(int), hipMemcpyDeviceToHost, s));
     EVCHK(hipStreamSynchronize(s));
     if (bits) { err = std::string("yn_eval_records: ") + err_text(bits); return 1; }

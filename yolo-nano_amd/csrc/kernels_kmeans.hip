@@ -392,12 +392,11 @@ struct KmeansState {
     int64_t capacity = 0;
     int max_k = 0, n = 0, k = 0;
     bool have_centroids = false;
-    double2* boxes = nullptr;
-    double* md = nullptr;
-    u64* block_sum = nullptr;
-    u64* slab = nullptr;
-    KmDev* st = nullptr;
-    KmDev* pinned = nullptr;
+    DevBuf<double2> boxes;
+    DevBuf<double> md;
+    DevBuf<u64> block_sum, slab;
+    DevBuf<KmDev> st;
+    PinnedBuf<KmDev> pinned;
     int64_t host_reads = 0, passes = 0;        // of the last yn_kmeans_run
 };
 
@@ -417,7 +416,7 @@ int read_state(KmeansState* e, hipStream_t s, std::string& err)        // the on
 
 void copy_result(const KmeansState* e, double* centroids, int64_t* counts, double* loss)
 {
-    const KmDev& p = *e->pinned;
+    const KmDev& p = e->pinned[0];
     if (centroids) memcpy(centroids, p.cent[p.slot], sizeof(double) * 2 * e->k);
     if (counts) memcpy(counts, p.count[p.slot], sizeof(int64_t) * e->k);
     if (loss) *loss = p.loss[p.slot];
@@ -447,14 +446,14 @@ int kmeans_create(int device, int64_t capacity, int max_k, KmeansState** out, st
     if (max_k < 1 || max_k > KM_MAX_K) { err = "yn_kmeans_create: max_k must be 1..32"; return 1; }
     auto* e = new KmeansState;
     e->device = device; e->capacity = capacity; e->max_k = max_k;
-    hipError_t r = hipMalloc((void**)&e->boxes, (size_t)capacity * sizeof(double2));
-    if (r == hipSuccess) r = hipMalloc((void**)&e->md, (size_t)capacity * sizeof(double));
-    if (r == hipSuccess) r = hipMalloc((void**)&e->block_sum, (size_t)seed_blocks((int)capacity) * sizeof(u64));
-    if (r == hipSuccess) r = hipMalloc((void**)&e->slab, (size_t)KM_PASS_BLOCKS * (KM_MAX_K * KM_COLS + 2) * sizeof(u64));
-    if (r == hipSuccess) r = hipMalloc((void**)&e->st, sizeof(KmDev));
-    if (r == hipSuccess) r = hipMemset(e->st, 0, sizeof(KmDev));
-    if (r == hipSuccess) r = hipHostMalloc((void**)&e->pinned, sizeof(KmDev), hipHostMallocDefault);
-    if (r != hipSuccess) { err = std::string("yn_kmeans_create: ") + hipGetErrorString(r); kmeans_destroy(e); return 1; }
+    int r = e->boxes.reserve((size_t)capacity);
+    if (!r) r = e->md.reserve((size_t)capacity);
+    if (!r) r = e->block_sum.reserve((size_t)seed_blocks((int)capacity));
+    if (!r) r = e->slab.reserve((size_t)KM_PASS_BLOCKS * (KM_MAX_K * KM_COLS + 2));
+    if (!r) r = e->st.reserve(1);
+    if (!r) r = e->pinned.reserve(1);
+    if (!r) r = hipMemset(e->st, 0, sizeof(KmDev));
+    if (r) { err = std::string("yn_kmeans_create: ") + hipGetErrorString((hipError_t)r); kmeans_destroy(e); return 1; }
     *out = e;
     return 0;
 }
@@ -465,12 +464,8 @@ void kmeans_destroy(KmeansState* e)
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     (void)hipSetDevice(e->device);
-    void* dev[] = {e->boxes, e->md, e->block_sum, e->slab, e->st};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (prev >= 0) (void)hipSetDevice(prev);
     delete e;
+    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int kmeans_set_boxes(KmeansState* e, hipStream_t s, const double* wh_dev, int64_t n, std::string& err)
@@ -482,8 +477,8 @@ int kmeans_set_boxes(KmeansState* e, hipStream_t s, const double* wh_dev, int64_
     hipLaunchKernelGGL(km_set_boxes_kernel, dim3(flat_blocks((int)n)), dim3(KM_THREADS), 0, s, (const double2*)wh_dev, e->boxes, (int)n, e->st);
     EVCHK(hipGetLastError());
     if (read_state(e, s, err)) return 1;
-    if (e->pinned->bad) {
-        err = "yn_kmeans_set_boxes: " + std::to_string(e->pinned->bad) + " of " + std::to_string(n) +
+    if (e->pinned[0].bad) {
+        err = "yn_kmeans_set_boxes: " + std::to_string(e->pinned[0].bad) + " of " + std::to_string(n) +
               " boxes are outside the domain 1 <= w, h < 65536 or not finite";
         return 1;
     }
@@ -508,7 +503,7 @@ int kmeans_seed(KmeansState* e, hipStream_t s, int k, int64_t first_index, const
         hipLaunchKernelGGL(km_seed_total_kernel, dim3(1), dim3(KM_THREADS), 0, s, e->block_sum, nb, e->st);
         EVCHK(hipGetLastError());
         if (read_state(e, s, err)) return 1;                           // sum_distance: the threshold needs it
-        const double thresh = e->pinned->sum_d * u_host[r - 1];
+        const double thresh = e->pinned[0].sum_d * u_host[r - 1];
         u64 t_hi, t_lo;
         floor_scaled53(thresh, &t_hi, &t_lo);
         hipLaunchKernelGGL(km_seed_select_kernel, dim3(1), dim3(KM_THREADS), 0, s, e->boxes, e->n, e->md, e->block_sum, nb, t_hi, t_lo, r, e->st);
@@ -516,8 +511,8 @@ int kmeans_seed(KmeansState* e, hipStream_t s, int k, int64_t first_index, const
     EVCHK(hipGetLastError());
     if (read_state(e, s, err)) return 1;
     e->k = k; e->have_centroids = true;
-    if (centroids_host) memcpy(centroids_host, e->pinned->cent[0], sizeof(double) * 2 * k);
-    if (picked_host) memcpy(picked_host, e->pinned->picked, sizeof(int32_t) * k);
+    if (centroids_host) memcpy(centroids_host, e->pinned[0].cent[0], sizeof(double) * 2 * k);
+    if (picked_host) memcpy(picked_host, e->pinned[0].picked, sizeof(int32_t) * k);
     return 0;
 }
 
@@ -528,7 +523,7 @@ int kmeans_set_centroids(KmeansState* e, hipStream_t s, const double* wh_host, i
     for (int i = 0; i < 2 * k; ++i)
         if (!(wh_host[i] >= 0.0 && wh_host[i] < 65536.0)) { err = "yn_kmeans_set_centroids: a centroid side is outside 0 <= v < 65536 or not finite"; return 1; }
     EVCHK(hipStreamSynchronize(s));                                    // the pinned record may still be the target of an earlier copy
-    KmDev& p = *e->pinned;
+    KmDev& p = e->pinned[0];
     memset(&p, 0, sizeof(KmDev));
     p.k = k;
     memcpy(p.cent[0], wh_host, sizeof(double) * 2 * k);
@@ -565,12 +560,12 @@ int kmeans_run(KmeansState* e, hipStream_t s, double loss_convergence, int iters
         sent += batch;
         if (read_state(e, s, err)) return 1;                           // one host read per batch
         ++e->host_reads;
-        if (e->pinned->done) break;
+        if (e->pinned[0].done) break;
     }
-    if (!e->pinned->done) { err = "yn_kmeans_run: the loop did not stop within its bound of passes"; return 1; }
-    e->passes = e->pinned->it;
+    if (!e->pinned[0].done) { err = "yn_kmeans_run: the loop did not stop within its bound of passes"; return 1; }
+    e->passes = e->pinned[0].it;
     copy_result(e, centroids_host, counts_host, loss_host);
-    if (iterations_host) *iterations_host = e->pinned->it;
+    if (iterations_host) *iterations_host = e->pinned[0].it;
     return 0;
 }
 

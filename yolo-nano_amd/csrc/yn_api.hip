@@ -29,8 +29,7 @@ std::mutex g_tune_mutex;
 std::map<std::vector<int>, int> g_pw_tuned;        // (device, M, K, N, strides...) -> fastest pointwise tile configuration
 
 struct Param {
-    void* dev = nullptr;
-    size_t bytes = 0;
+    DevBuf<float> dev;                     // [numel]
     size_t numel = 0;
     std::vector<int64_t> shape;
 };
@@ -40,21 +39,17 @@ enum { K_PW = 0, K_DW = 1, K_DENSE3 = 2, K_STEM = 3 };
 struct Layer {
     std::string name, conv, bn;
     int kind = 0, cin = 0, cout = 0, stride = 1, has_bias = 0, act = 0;
-    float* w_packed = nullptr;
-    float* b_packed = nullptr;
-    float* w_ref = nullptr;
-    float* b_ref = nullptr;
-    void* ws_hi = nullptr;                 // split-f16 packs of the folded weights (dense 3x3: conv3x3_split_kernel)
-    void* ws_lo = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<float> w_packed, b_packed, w_ref, b_ref;
+    DevBuf<_Float16> ws_hi, ws_lo;         // split-f16 packs of the folded weights (dense 3x3: conv3x3_split_kernel), equal sizes
+    size_t ws_bytes() const { return ws_hi.cap() * sizeof(_Float16); }
     size_t w_numel = 0;
     int Kp = 0, Npad = 0;
 };
 
-struct TrainPack { float* wp = nullptr; float* bias = nullptr; float* wp_bwd = nullptr; int Kb = 0, Npad_b = 0; };   // per-layer training weight packs
+struct TrainPack { DevBuf<float> wp, bias, wp_bwd; int Kb = 0, Npad_b = 0; };   // per-layer training weight packs
 
 // per-layer weight packs of the fp16 training step (yn_train_h16.inc): f16 GEMM packs (forward / input gradient), fp32 depthwise taps
-struct HPack { ynk::h16* wf = nullptr; ynk::h16* wb = nullptr; float* bias = nullptr; float* dwf = nullptr; float* dwb = nullptr; int Kp = 0, Npad = 0, Kpb = 0, Npadb = 0; };
+struct HPack { DevBuf<ynk::h16> wf, wb; DevBuf<float> bias, dwf, dwb; int Kp = 0, Npad = 0, Kpb = 0, Npadb = 0; };
 
 struct ProfRec {
     std::string name, kernel;
@@ -78,13 +73,13 @@ struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifet
 struct yn_tta {
     int device = 0, flip = 1, max_batch = 0, cap = 0, A = 0, C = 0, Nmax = 0, smax = 0;
     std::vector<int> scales;
-    float* xr = nullptr;                                             // the resized (+ mirrored) batch [nb][3][smax][smax], nb = flip ? 2 max_batch : max_batch
-    float* fb = nullptr; float* fs = nullptr; int32_t* fc = nullptr; int32_t* fcount = nullptr;      // yn_infer's outputs for one scale: [nb][Nmax]
-    float* lb = nullptr; float* ls = nullptr; int32_t* lc = nullptr;                                 // the merge lists [max_batch][cap]
-    int32_t* state = nullptr;                                        // [TTA_STATE + max_batch]: flags + cursors (tta_append_kernel)
-    int32_t* fstart = nullptr;                                       // [forwards][max_batch]
-    float* mb = nullptr; float* ms = nullptr; int32_t* mc = nullptr; int32_t* mcount = nullptr;      // the merge's kept rows [max_batch][cap]
-    float* rec = nullptr; int32_t* offsets = nullptr;                // yn_pack_detections layout: [max_batch * cap][6], [max_batch + 1]
+    ynk::DevBuf<float> xr;                                           // the resized (+ mirrored) batch [nb][3][smax][smax], nb = flip ? 2 max_batch : max_batch
+    ynk::DevBuf<float> fb, fs; ynk::DevBuf<int32_t> fc, fcount;      // yn_infer's outputs for one scale: [nb][Nmax]
+    ynk::DevBuf<float> lb, ls; ynk::DevBuf<int32_t> lc;              // the merge lists [max_batch][cap]
+    ynk::DevBuf<int32_t> state;                                      // [TTA_STATE + max_batch]: flags + cursors (tta_append_kernel)
+    ynk::DevBuf<int32_t> fstart;                                     // [forwards][max_batch]
+    ynk::DevBuf<float> mb, ms; ynk::DevBuf<int32_t> mc, mcount;      // the merge's kept rows [max_batch][cap]
+    ynk::DevBuf<float> rec; ynk::DevBuf<int32_t> offsets;            // yn_pack_detections layout: [max_batch * cap][6], [max_batch + 1]
     std::vector<int32_t> state_host;                                 // the one read-back of yn_tta_infer
     int last_B = -1;                                                 // images of the last successful yn_tta_infer, -1: none
     int lists_B = -1;                                                // images whose merge lists are valid (yn_tta_forwards), -1: none
@@ -110,46 +105,42 @@ struct yn_handle {
     int head_ch = 0;
     GridInfo grid;
     // arena
-    char* arena = nullptr;
-    size_t arena_bytes = 0, arena_used = 0;
+    DevBuf<char> arena;                   // the activations, then the sync words of stage_pipe_kernel
+    size_t arena_bytes = 0, arena_used = 0;       // bytes of the activation part / taken from it
     int arena_S = 0, arena_B = 0;
-    // NMS scratch + candidate buffers (sized max_batch * N)
-    float* cand_boxes = nullptr; float* cand_scores = nullptr; int32_t* cand_cls = nullptr;
-    NmsWork nms{};
-    size_t nms_cap = 0;           // elements B*N currently allocated
-    size_t nms_seg_cap = 0;       // B*(C+1)
-    size_t nms_m_cap = 0;         // uint64 words of suppression matrix
-    size_t nms_ps_cap = 0;        // uint64 words of the prefilter's slice sync
-    float* heads_int[3] = {nullptr, nullptr, nullptr};
-    size_t heads_cap = 0;
+    // candidate buffers + NMS scratch (ensure_post): per candidate [B*N], per segment [B*(C+1)], the suppression matrix, the prefilter's slice sync
+    DevBuf<float> cand_boxes, cand_scores, nms_sbox, nms_sbox2;
+    DevBuf<int32_t> cand_cls, nms_bucket, nms_keep, nms_bucket2;
+    DevBuf<int32_t> nms_seg[10];          // seg_count, seg_off, tile_off, large_list, seg_count2, tile_off2, seg_order, seg_sparse, work_off, ctr
+    DevBuf<unsigned long long> nms_matrix, nms_pre_sync;
+    NmsWork nms{};                        // the view of that scratch launch_nms_pipeline takes, filled by ensure_post
+    DevBuf<float> heads_buf;              // the three raw head tensors, one block
+    float* heads_int[3] = {nullptr, nullptr, nullptr};    // its split for the current grid (ensure_heads)
     float* fwd_only[3] = {nullptr, nullptr, nullptr};     // yn_train_forward: the training executors stop after the forward pass and copy the raw heads here
     float* tap_out[3] = {nullptr, nullptr, nullptr};      // yn_forward_taps: where run_network copies c3 / c4 / c5
-    float* loss_partial = nullptr;
-    size_t loss_partial_cap = 0;
+    DevBuf<float> loss_partial;
     // training (yn_train.inc): caller-owned flat buffers + per-layer packs + workspace
     float *tP = nullptr, *tG = nullptr, *tM = nullptr;
     int64_t tN = 0, tN_expected = 0;
     long train_steps = 0;
     std::map<std::string, size_t> toff;
     std::vector<TrainPack> tpacks;
-    float* zeros = nullptr;
-    float* train_losses = nullptr;        // device float[4]: the step's body writes its losses here (a fixed address for the graph), copied to the caller's buffer afterwards
+    DevBuf<float> zeros;
+    DevBuf<float> train_losses;           // device float[4]: the step's body writes its losses here (a fixed address for the graph), copied to the caller's buffer afterwards
     std::vector<TrainGraph> train_graphs; int train_graph_misses = 0; bool train_graph = false; int64_t train_graph_replays = 0;   // yn_train_graph
     int head_fork = -1, head_fork_now = 0, fork_trials = 0;      // -1: undecided (steps 3-6 time the step with and without the forks), else the choice
     hipEvent_t fork_ev[8] = {};           // timing events of the trials
     hipStream_t train_fork[2] = {nullptr, nullptr};      // the head towers of levels 3 / 4 (forward and backward) beside the main stream
     hipStream_t train_side = nullptr;     // the fp16 step's weight-gradient stream (lowest priority: the main stream is the critical path)
-    int* skip_flag = nullptr;             // device int[2]: [0] this step's gradient is non-finite, [1] number of skipped updates
+    DevBuf<int> skip_flag;                // device int[2]: [0] this step's gradient is non-finite, [1] number of skipped updates
     int train_dtype = 0;                  // 0 fp32, 1 fp16 storage + f16 MFMA (yn_train_precision)
     std::vector<HPack> hpacks;
     std::vector<ynk::HPackDesc> hpack_jobs;   // recorded while the first fp16 step packs layer by layer; later steps pack everything in one launch
-    ynk::HPackDesc* hpack_table = nullptr;     // device copy
-    int hpack_table_n = 0;
-    float* scale_state = nullptr;         // device float[8]: loss scale, its inverse, clean-step counter, local overflow flag, step-pending mark (kernels_h16.hip)
+    DevBuf<ynk::HPackDesc> hpack_table;        // device copy
+    DevBuf<float> scale_state;            // device float[8]: loss scale, its inverse, clean-step counter, local overflow flag, step-pending mark (kernels_h16.hip)
     float loss_scale_init = 0.0f, loss_scale_clean = 0.0f;   // yn_train_set_loss_scale before the first fp16 step (checkpoint resume)
     std::vector<hipEvent_t> train_events;
-    char* train_arena = nullptr;
-    size_t train_arena_bytes = 0;
+    DevBuf<char> train_arena;
     // graphs / profiling
     bool use_graph = false;
     bool tail_fuse = true;                 // yn_tail_fuse: off = layers .2+.3 and .4+decode of the heads as two grouped kernels instead of one (head_tail_group_kernel)
@@ -159,9 +150,9 @@ struct yn_handle {
     int fuse_decode_mode = 1;              // 1 = when the stride-8 head has >= 8192 pixels, 2 = always
     bool exact_f32 = false;                // yn_exact_f32: GEMM-shaped convs on the f32 MFMA only (no split-f16 operands)
     bool range_fallback = false;           // yn_fold_bn found a folded GEMM weight outside the split's range (|w| >= 65504): same effect as exact_f32
-    unsigned* range_host = nullptr;        // one word of pinned host memory: set by compact_kernel beside the negative counts (the range flag, out of band);
+    PinnedBuf<unsigned, hipHostMallocMapped | hipHostMallocCoherent> range_host;   // one word of pinned host memory: set by compact_kernel beside the negative counts (the range flag, out of band);
     unsigned* range_host_dev = nullptr;    // its device view.  While set, yn_infer / yn_pack_detections return YN_STATUS_RANGE; yn_range_status clears it
-    unsigned* range_flags = nullptr;       // device uint[3]: [0] weights out of range (fold_pack_kernel), [1] an activation >= 65504 was split
+    DevBuf<unsigned> range_flags;          // device uint[3]: [0] weights out of range (fold_pack_kernel), [1] an activation >= 65504 was split
                                            // (range_report, yn_device.h; read and cleared by yn_range_status), [2] the same as [0] for a yn_op_* call
     bool autotune = true;
     int force_pw_cfg = -1;                         // yn_set_pw_config (testing aid)
@@ -194,7 +185,7 @@ int fail(yn_handle* h, const char* fmt, ...)
 }
 
 // Every entry point runs with the handle's device current and restores the caller's afterwards (a handle created on
-// cuda:1 may be called while cuda:0 is current: its hipMallocs, launches and hipFuncSetAttributes must not land there).
+// cuda:1 may be called while cuda:0 is current: its allocations, launches and hipFuncSetAttributes must not land there).
 struct DevGuard {
     int prev = -1;
     explicit DevGuard(const yn_handle* h);
@@ -202,9 +193,9 @@ struct DevGuard {
 };
 #define YN_ENTER(h) if (!(h)) return 1; DevGuard dev_guard_(h)
 
-#define HIPCHK(h, expr)                                                                            \
+#define HIPCHK(h, expr)           /* a HIP call, or a DevBuf growth (its int is a hipError_t) */   \
     do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
+        hipError_t e_ = (hipError_t)(expr);                                                                 \
         if (e_ != hipSuccess) return fail((h), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
@@ -229,7 +220,7 @@ void add_layer(yn_handle* h, const std::string& name, const std::string& conv, c
     L.stride = stride; L.has_bias = has_bias; L.act = act;
     h->by_name[name] = (int)h->layers.size();
     h->by_conv[conv] = (int)h->layers.size();
-    h->layers.push_back(L);
+    h->layers.push_back(std::move(L));
 }
 
 // the 77 convolutions, same naming as yolo_nano_amd/arch.py conv_specs()
@@ -339,16 +330,19 @@ int ensure_arena(yn_handle* h, int B, int S)
 {
     const size_t need = network_arena_bytes(h, B, S);
     if (need <= h->arena_bytes) return 0;
-    if (h->arena) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->arena)); h->arena = nullptr; h->arena_bytes = 0; }
+    if (h->arena) HIPCHK(h, hipStreamSynchronize(h->stream));
     // behind the activations: the sync words of stage_pipe_kernel (kernels_stage.hip) for the largest stage (stage 2: B (S/8)^2 rows, 32-row tiles,
     // up to YN_STAGE_MAX units).  Zeroed HERE, once, on the handle's stream; every launch leaves them zero.
     const size_t sync_bytes = (stage_sync_words((int)((size_t)B * (S / 8) * (S / 8) / 32 + 1), YN_STAGE_MAX) * sizeof(unsigned) + 255) & ~(size_t)255;
-    HIPCHK(h, hipMalloc((void**)&h->arena, need + sync_bytes));
+    h->arena_bytes = 0; h->stage_sync = nullptr; h->stage_sync_bytes = 0;
+    bool moved = false;
+    const int rc = h->arena.reserve(need + sync_bytes, 0, &moved);
+    if (moved) drop_graphs(h);
+    if (rc) return fail(h, "activation arena of %zu bytes: %s", need + sync_bytes, hipGetErrorString((hipError_t)rc));
     h->arena_bytes = need;
     h->stage_sync = reinterpret_cast<unsigned*>(h->arena + need);
     h->stage_sync_bytes = sync_bytes;
     HIPCHK(h, hipMemsetAsync(h->stage_sync, 0, sync_bytes, h->stream));
-    drop_graphs(h);
     return 0;
 }
 
@@ -370,80 +364,55 @@ int ensure_post(yn_handle* h, int B, int N, int C)
         return fail(h, "NMS over %d candidates per image exceeds the supported segment size %d", N, nms_max_segment());
     const size_t need = (size_t)B * N, need_seg = (size_t)B * (C + 1);
     const size_t m_stride = nms_matrix_words_per_image(N, C);
-    const size_t need_m = m_stride * B;
-    if (need > h->nms_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        void** ptrs[] = {(void**)&h->cand_boxes, (void**)&h->cand_scores, (void**)&h->cand_cls,
-                         (void**)&h->nms.bucket, (void**)&h->nms.keep, (void**)&h->nms.sbox, (void**)&h->nms.bucket2, (void**)&h->nms.sbox2};
-        for (void** q : ptrs) if (*q) { HIPCHK(h, hipFree(*q)); *q = nullptr; }
-        HIPCHK(h, hipMalloc((void**)&h->cand_boxes, need * 4 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void**)&h->cand_scores, need * sizeof(float)));
-        HIPCHK(h, hipMalloc((void**)&h->cand_cls, need * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.bucket, need * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.keep, need * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.sbox, need * 4 * sizeof(float)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.bucket2, need * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.sbox2, need * 4 * sizeof(float)));
-        h->nms_cap = need;
-        drop_graphs(h);
-    }
-    if (need_seg > h->nms_seg_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        void** ptrs[] = {(void**)&h->nms.seg_count, (void**)&h->nms.seg_off, (void**)&h->nms.tile_off, (void**)&h->nms.large_list,
-                         (void**)&h->nms.seg_count2, (void**)&h->nms.tile_off2, (void**)&h->nms.seg_order, (void**)&h->nms.ctr, (void**)&h->nms.seg_sparse, (void**)&h->nms.work_off};
-        for (void** q : ptrs) if (*q) { HIPCHK(h, hipFree(*q)); *q = nullptr; }
-        HIPCHK(h, hipMalloc((void**)&h->nms.seg_count, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.seg_off, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.tile_off, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.large_list, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.seg_count2, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.tile_off2, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.seg_order, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.seg_sparse, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.work_off, need_seg * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc((void**)&h->nms.ctr, need_seg * sizeof(int32_t)));          // >= 2 * B ints
-        HIPCHK(h, hipMemsetAsync(h->nms.ctr, 0, need_seg * sizeof(int32_t), h->stream));
-        h->nms_seg_cap = need_seg;
-        drop_graphs(h);
-    }
-    if (need_m > h->nms_m_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->nms.matrix) { HIPCHK(h, hipFree(h->nms.matrix)); h->nms.matrix = nullptr; }
-        HIPCHK(h, hipMalloc(&h->nms.matrix, need_m * sizeof(unsigned long long)));
-        h->nms_m_cap = need_m;
-        drop_graphs(h);
-    }
     const size_t need_ps = nms_pre_sync_words(B, N);
-    if (need_ps > h->nms_ps_cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->nms.pre_sync) { HIPCHK(h, hipFree(h->nms.pre_sync)); h->nms.pre_sync = nullptr; }
-        HIPCHK(h, hipMalloc(&h->nms.pre_sync, need_ps * sizeof(unsigned long long)));
-        HIPCHK(h, hipMemsetAsync(h->nms.pre_sync, 0, need_ps * sizeof(unsigned long long), h->stream));
-        h->nms_ps_cap = need_ps;
-        drop_graphs(h);
-    }
-    h->nms.matrix_stride = m_stride;
-    h->nms.large_cap = (N / 1024 + 1) < C ? (N / 1024 + 1) : C;       // at most N/1024 segments can exceed 1024 items
+    // Every buffer answers for itself (a call that failed half way leaves each one empty or whole): the stream is drained before the first
+    // block of a group goes, the graphs are dropped whenever an address changed, and the view is refilled on every way out.
+    int rc = 0;
+    bool moved = false, drained = false;
+    auto take = [&](auto& buf, size_t n) {                  // true: buf is a new block
+        if (rc || n <= buf.cap()) return false;
+        if (!drained) { rc = (int)hipStreamSynchronize(h->stream); drained = true; }
+        if (!rc) rc = buf.reserve(n, 0, &moved);
+        return !rc;
+    };
+    take(h->cand_boxes, need * 4); take(h->cand_scores, need); take(h->cand_cls, need);
+    take(h->nms_bucket, need); take(h->nms_keep, need); take(h->nms_sbox, need * 4); take(h->nms_bucket2, need); take(h->nms_sbox2, need * 4);
+    drained = false;
+    bool zero_ctr = false;
+    for (DevBuf<int32_t>& b : h->nms_seg) zero_ctr = take(b, need_seg);          // ctr, the last one: >= 2 * B ints
+    if (zero_ctr) rc = (int)hipMemsetAsync(h->nms_seg[9], 0, need_seg * sizeof(int32_t), h->stream);
+    drained = false;
+    take(h->nms_matrix, m_stride * B);
+    drained = false;
+    if (take(h->nms_pre_sync, need_ps)) rc = (int)hipMemsetAsync(h->nms_pre_sync, 0, need_ps * sizeof(unsigned long long), h->stream);
+    NmsWork& w = h->nms;
+    w.bucket = h->nms_bucket; w.keep = h->nms_keep; w.sbox = h->nms_sbox; w.bucket2 = h->nms_bucket2; w.sbox2 = h->nms_sbox2;
+    int32_t** const seg[10] = {&w.seg_count, &w.seg_off, &w.tile_off, &w.large_list, &w.seg_count2, &w.tile_off2, &w.seg_order, &w.seg_sparse, &w.work_off, &w.ctr};
+    for (int i = 0; i < 10; ++i) *seg[i] = h->nms_seg[i];
+    w.matrix = h->nms_matrix; w.pre_sync = h->nms_pre_sync;
+    w.matrix_stride = m_stride;
+    w.large_cap = (N / 1024 + 1) < C ? (N / 1024 + 1) : C;       // at most N/1024 segments can exceed 1024 items
+    if (moved) drop_graphs(h);
+    if (rc) return fail(h, "NMS scratch for %d x %d candidates: %s", B, N, hipGetErrorString((hipError_t)rc));
     return 0;
 }
 
 int ensure_heads(yn_handle* h, int B)
 {
     const int hld = (h->head_ch + 3) & ~3;                  // internal heads: rows padded to 16 bytes => float4 stores
-    const size_t need = (size_t)B * (h->grid.hw[0] + h->grid.hw[1] + h->grid.hw[2]) * hld;
-    if (need <= h->heads_cap) {
-        // re-derive the split for the current grid
-        h->heads_int[1] = h->heads_int[0] + (size_t)B * h->grid.hw[0] * hld;
-        h->heads_int[2] = h->heads_int[1] + (size_t)B * h->grid.hw[1] * hld;
-        return 0;
+    const size_t need = (size_t)B * (h->grid.hw[0] + h->grid.hw[1] + h->grid.hw[2]) * hld + 256;      // + 1024 bytes of slack
+    bool moved = false;
+    int rc = 0;
+    if (need > h->heads_buf.cap()) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        rc = h->heads_buf.reserve(need, 0, &moved);
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->heads_int[0]) HIPCHK(h, hipFree(h->heads_int[0]));
-    HIPCHK(h, hipMalloc((void**)&h->heads_int[0], need * sizeof(float) + 1024));
-    h->heads_cap = need;
+    // re-derive the split for the current grid
+    h->heads_int[0] = h->heads_buf;
     h->heads_int[1] = h->heads_int[0] + (size_t)B * h->grid.hw[0] * hld;
     h->heads_int[2] = h->heads_int[1] + (size_t)B * h->grid.hw[1] * hld;
-    drop_graphs(h);
+    if (moved) drop_graphs(h);
+    if (rc) return fail(h, "raw head tensors for %d images: %s", B, hipGetErrorString((hipError_t)rc));
     return 0;
 }
 
@@ -1207,6 +1176,13 @@ int yn_abi_version(void) { return 2; }       // 2: + yn_range_status, yn_allredu
 
 const char* yn_last_error(yn_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+int yn_live_device_memory(int64_t* blocks, int64_t* bytes)
+{
+    if (blocks) *blocks = g_live_blocks.load();
+    if (bytes) *bytes = g_live_bytes.load();
+    return 0;
+}
+
 int yn_create(const yn_config* cfg, yn_handle** out)
 {
     if (!cfg || !out) return fail(nullptr, "yn_create: null argument");
@@ -1233,15 +1209,15 @@ int yn_create(const yn_config* cfg, yn_handle** out)
     if (set_grid_info(h, cfg->input_size)) { g_create_error = h->err; delete h; return 1; }
     // (hipMemsetAsync on the handle's stream, never hipMemset: ONE operation on the legacy null stream and every later launch of the
     // process on torch's streams serialises against it - measured 38.2 k -> 32.6 k images/s with four handles, single-stream unchanged)
-    if (hipMalloc((void**)&h->range_flags, 3 * sizeof(unsigned)) != hipSuccess ||
+    if (h->range_flags.reserve(3) ||
         hipMemsetAsync(h->range_flags, 0, 3 * sizeof(unsigned), h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
         g_create_error = "yn_create: out of device memory"; delete h; return 1;
     }
-    if (hipHostMalloc((void**)&h->range_host, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||      // coherent: the kernel's system-scope store is visible when it is made, not at kernel end (HIP_HOST_COHERENT=0)
-        hipHostGetDevicePointer((void**)&h->range_host_dev, h->range_host, 0) != hipSuccess) {
+    if (h->range_host.reserve(1) ||      // coherent: the kernel's system-scope store is visible when it is made, not at kernel end (HIP_HOST_COHERENT=0)
+        hipHostGetDevicePointer((void**)&h->range_host_dev, h->range_host.get(), 0) != hipSuccess) {
         g_create_error = "yn_create: no pinned host memory for the range flag"; delete h; return 1;
     }
-    *h->range_host = 0;
+    h->range_host[0] = 0;
     *out = h;
     return 0;
 }
@@ -1251,40 +1227,17 @@ void yn_destroy(yn_handle* h)
     if (!h) return;
     DevGuard dev_guard_(h);
     (void)hipStreamSynchronize(h->stream);
-    for (auto& kv : h->params) if (kv.second.dev) (void)hipFree(kv.second.dev);
-    for (Layer& l : h->layers) {
-        if (l.w_packed) (void)hipFree(l.w_packed);
-        if (l.b_packed) (void)hipFree(l.b_packed);
-        if (l.w_ref) (void)hipFree(l.w_ref);
-        if (l.b_ref) (void)hipFree(l.b_ref);
-        if (l.ws_hi) (void)hipFree(l.ws_hi);
-        if (l.ws_lo) (void)hipFree(l.ws_lo);
-    }
-    void* ptrs[] = {h->arena, h->cand_boxes, h->cand_scores, h->cand_cls, h->nms.bucket, h->nms.keep, h->nms.sbox,
-                    h->nms.seg_count, h->nms.seg_off, h->nms.tile_off, h->nms.large_list, h->nms.matrix, h->heads_int[0], h->loss_partial,
-                    h->nms.bucket2, h->nms.sbox2, h->nms.seg_count2, h->nms.tile_off2, h->nms.seg_order, h->nms.ctr, h->nms.seg_sparse, h->nms.work_off, h->nms.pre_sync};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     for (GraphEntry& g : h->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
     if (h->tune_e0) { (void)hipEventDestroy(h->tune_e0); (void)hipEventDestroy(h->tune_e1); }
     for (hipEvent_t e : h->fj_events) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) if (h->side[k]) (void)hipStreamDestroy(h->side[k]);
-    for (TrainPack& pk : h->tpacks) { if (pk.wp) (void)hipFree(pk.wp); if (pk.bias) (void)hipFree(pk.bias); if (pk.wp_bwd) (void)hipFree(pk.wp_bwd); }
-    if (h->range_flags) (void)hipFree(h->range_flags);
-    if (h->range_host) (void)hipHostFree(h->range_host);
-    if (h->zeros) (void)hipFree(h->zeros);
     for (TrainGraph& g : h->train_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (h->train_side) (void)hipStreamDestroy(h->train_side);
     for (int i = 0; i < 2; ++i) if (h->train_fork[i]) (void)hipStreamDestroy(h->train_fork[i]);
     for (int i = 0; i < 8; ++i) if (h->fork_ev[i]) (void)hipEventDestroy(h->fork_ev[i]);
-    if (h->train_losses) (void)hipFree(h->train_losses);
-    if (h->skip_flag) (void)hipFree(h->skip_flag);
-    if (h->scale_state) (void)hipFree(h->scale_state);
-    if (h->hpack_table) (void)hipFree(h->hpack_table);
-    for (HPack& pk : h->hpacks) { void* q[] = {pk.wf, pk.wb, pk.bias, pk.dwf, pk.dwb}; for (void* v : q) if (v) (void)hipFree(v); }
     for (hipEvent_t e : h->train_events) (void)hipEventDestroy(e);
-    if (h->train_arena) (void)hipFree(h->train_arena);
-    delete h;
+    delete h;                                // every buffer goes with its owning member, on the handle's device (dev_guard_)
 }
 
 int yn_set_grid(yn_handle* h, int input_size)
@@ -1396,7 +1349,7 @@ int yn_nms_prefilter(yn_handle* h, int mode)
 int yn_nms_sweep_segments(yn_handle* h, int B, int C)
 {
     YN_ENTER(h);
-    if (!h->nms.seg_sparse || B <= 0 || C <= 0 || (size_t)B * C > h->nms_seg_cap) return 0;
+    if (!h->nms.seg_sparse || B <= 0 || C <= 0 || (size_t)B * C > h->nms_seg[7].cap()) return 0;
     std::vector<int32_t> v((size_t)B * C);
     if (hipMemcpyAsync(v.data(), h->nms.seg_sparse, v.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -1;
     int k = 0;
@@ -1511,10 +1464,9 @@ static int load_param_impl(yn_handle* h, const char* key, const void* ptr, const
     if (numel != expect) return fail(h, "size mismatch for '%s': got %zu elements, expected %zu", key, numel, expect);
     Param& p = h->params[k];
     const size_t bytes = numel * sizeof(float);
-    if (p.bytes != bytes) {
-        if (p.dev) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(p.dev)); p.dev = nullptr; }
-        HIPCHK(h, hipMalloc(&p.dev, bytes));
-        p.bytes = bytes;
+    if (p.dev.cap() != numel) {
+        if (p.dev) { HIPCHK(h, hipStreamSynchronize(h->stream)); p.dev.reset(); }
+        HIPCHK(h, p.dev.reserve(numel));
     }
     p.numel = numel;
     p.shape.assign(shape, shape + ndim);
@@ -1571,23 +1523,20 @@ int yn_fold_bn(yn_handle* h)
             packed_floats = (size_t)l.Kp * l.Npad;
         }
         a.Kp = l.Kp; a.Npad = l.Npad;
-        if (!l.w_packed) {
-            HIPCHK(h, hipMalloc((void**)&l.w_packed, packed_floats * sizeof(float)));
-            HIPCHK(h, hipMalloc((void**)&l.b_packed, (size_t)((l.Npad + 31) & ~31) * sizeof(float)));
-            HIPCHK(h, hipMalloc((void**)&l.w_ref, w->numel * sizeof(float)));
-            HIPCHK(h, hipMalloc((void**)&l.b_ref, (size_t)l.cout * sizeof(float)));
-            l.w_numel = w->numel;
+        // (no-ops from the second fold on: a layer's sizes never change)
+        HIPCHK(h, l.w_packed.reserve(packed_floats));
+        HIPCHK(h, l.b_packed.reserve((size_t)((l.Npad + 31) & ~31)));
+        HIPCHK(h, l.w_ref.reserve(w->numel));
+        HIPCHK(h, l.b_ref.reserve((size_t)l.cout));
+        l.w_numel = w->numel;
+        if (l.kind == K_DENSE3 || l.kind == K_PW) {
+            const size_t halves = (size_t)(l.kind == K_DENSE3 ? 9 : 1) * ((l.cin + 7) / 8) * l.Npad * 8;
+            HIPCHK(h, l.ws_hi.reserve(halves));
+            HIPCHK(h, l.ws_lo.reserve(halves));
+            HIPCHK(h, hipMemsetAsync(l.ws_hi, 0, l.ws_bytes(), h->stream));
+            HIPCHK(h, hipMemsetAsync(l.ws_lo, 0, l.ws_bytes(), h->stream));
         }
-        if ((l.kind == K_DENSE3 || l.kind == K_PW) && !l.ws_hi) {
-            l.ws_bytes = (size_t)(l.kind == K_DENSE3 ? 9 : 1) * ((l.cin + 7) / 8) * l.Npad * 8 * sizeof(_Float16);
-            HIPCHK(h, hipMalloc(&l.ws_hi, l.ws_bytes));
-            HIPCHK(h, hipMalloc(&l.ws_lo, l.ws_bytes));
-        }
-        if (l.ws_hi) {
-            HIPCHK(h, hipMemsetAsync(l.ws_hi, 0, l.ws_bytes, h->stream));
-            HIPCHK(h, hipMemsetAsync(l.ws_lo, 0, l.ws_bytes, h->stream));
-        }
-        a.ws_hi = l.ws_hi; a.ws_lo = l.ws_lo; a.w_ovf = h->range_flags;
+        a.ws_hi = l.ws_hi.get(); a.ws_lo = l.ws_lo.get(); a.w_ovf = h->range_flags;
         HIPCHK(h, hipMemsetAsync(l.w_packed, 0, packed_floats * sizeof(float), h->stream));
         HIPCHK(h, hipMemsetAsync(l.b_packed, 0, (size_t)((l.Npad + 31) & ~31) * sizeof(float), h->stream));
         a.w_ref = l.w_ref; a.b_ref = l.b_ref; a.w_packed = l.w_packed; a.b_packed = l.b_packed;
@@ -1611,7 +1560,7 @@ int yn_fold_bn(yn_handle* h)
 static int range_pending(yn_handle* h, const char* who)
 {
     // (not under yn_exact_f32: the f32-MFMA family cannot raise the flag, and running again under it IS the documented recovery - ADVICE r5)
-    if (!exact(h) && h->range_host && __atomic_load_n(h->range_host, __ATOMIC_RELAXED)) {
+    if (!exact(h) && h->range_host && __atomic_load_n(h->range_host.get(), __ATOMIC_RELAXED)) {
         fail(h, "%s: an earlier yn_infer split an activation >= 65504 (split-f16 range): its results are invalid - call yn_range_status to acknowledge, "
                 "then yn_exact_f32(h, 1) and run again", who);
         return YN_STATUS_RANGE;
@@ -1626,7 +1575,7 @@ int yn_range_status(yn_handle* h, int* weights_exceed_f16, int* activation_overf
     HIPCHK(h, hipMemcpyAsync(&f, h->range_flags + 1, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (f) HIPCHK(h, hipMemsetAsync(h->range_flags + 1, 0, sizeof(unsigned), h->stream));
-    if (h->range_host) __atomic_store_n(h->range_host, 0u, __ATOMIC_RELAXED);      // acknowledged (the stream is idle: no compact_kernel can still set it)
+    if (h->range_host) __atomic_store_n(h->range_host.get(), 0u, __ATOMIC_RELAXED);      // acknowledged (the stream is idle: no compact_kernel can still set it)
     if (h->stage_sync) {                                                            // stage_pipe_kernel's bounded waits (kernels_stage.hip): an expired one marks the launch
         unsigned tmo = 0;
         HIPCHK(h, hipMemcpyAsync(&tmo, h->stage_sync + STAGE_TIMEOUT, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
@@ -1904,12 +1853,10 @@ int yn_pack_detections(yn_handle* h, const float* out_boxes, const float* out_sc
 static int ensure_loss(yn_handle* h, int B)
 {
     const size_t need = (size_t)loss_num_blocks(h->grid, B) * 4;
-    if (need <= h->loss_partial_cap) return 0;
+    if (need <= h->loss_partial.cap()) return 0;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     drop_train_graphs(h);                                   // a captured fp16 step carries loss_partial's address (launch_loss_h16)
-    if (h->loss_partial) HIPCHK(h, hipFree(h->loss_partial));
-    HIPCHK(h, hipMalloc((void**)&h->loss_partial, need * sizeof(float)));
-    h->loss_partial_cap = need;
+    HIPCHK(h, h->loss_partial.reserve(need));
     return 0;
 }
 
@@ -1972,7 +1919,7 @@ int yn_sgd_step(yn_handle* h, float* params, const float* grads, float* momentum
     if (n < 0 || !params || !grads || !momentum_buf) return fail(h, "yn_sgd_step: bad arguments");
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) return fail(h, "yn_sgd_step: buffers must be 16-byte aligned");
     if (!h->skip_flag) {
-        HIPCHK(h, hipMalloc((void**)&h->skip_flag, 2 * sizeof(int)));
+        HIPCHK(h, h->skip_flag.reserve(2));
         HIPCHK(h, hipMemsetAsync(h->skip_flag, 0, 2 * sizeof(int), h->stream));
     }
     launch_sgd(params, grads, momentum_buf, (long)n, lr, momentum, weight_decay, grad_scale, first_step, h->skip_flag, h->stream);
@@ -2029,16 +1976,16 @@ struct TmpLayer {
         else { a.kind = 0; a.kk = kind == K_DENSE3 ? 9 : 1; const int K = cin * a.kk; l.Kp = (K + 1) & ~1; l.Npad = (cout + 31) & ~31; packed = (size_t)l.Kp * l.Npad; }
         a.Kp = l.Kp; a.Npad = l.Npad;
         const size_t bfl = (size_t)((l.Npad + 31) & ~31);
-        if (hipMalloc((void**)&l.w_packed, packed * sizeof(float)) != hipSuccess || hipMalloc((void**)&l.b_packed, bfl * sizeof(float)) != hipSuccess) { rc = 1; return; }
+        if (l.w_packed.reserve(packed) || l.b_packed.reserve(bfl)) { rc = 1; return; }
         (void)hipMemsetAsync(l.w_packed, 0, packed * sizeof(float), h->stream);
         (void)hipMemsetAsync(l.b_packed, 0, bfl * sizeof(float), h->stream);
         a.w_packed = l.w_packed; a.b_packed = l.b_packed;
         if (kind == K_DENSE3 || kind == K_PW) {             // the split-f16 packs the network's GEMM-shaped layers run on
-            l.ws_bytes = (size_t)(kind == K_DENSE3 ? 9 : 1) * ((cin + 7) / 8) * l.Npad * 8 * sizeof(_Float16);
-            if (hipMalloc(&l.ws_hi, l.ws_bytes) != hipSuccess || hipMalloc(&l.ws_lo, l.ws_bytes) != hipSuccess) { rc = 1; return; }
-            (void)hipMemsetAsync(l.ws_hi, 0, l.ws_bytes, h->stream);
-            (void)hipMemsetAsync(l.ws_lo, 0, l.ws_bytes, h->stream);
-            a.ws_hi = l.ws_hi; a.ws_lo = l.ws_lo; a.w_ovf = h->range_flags + 2;
+            const size_t halves = (size_t)(kind == K_DENSE3 ? 9 : 1) * ((cin + 7) / 8) * l.Npad * 8;
+            if (l.ws_hi.reserve(halves) || l.ws_lo.reserve(halves)) { rc = 1; return; }
+            (void)hipMemsetAsync(l.ws_hi, 0, l.ws_bytes(), h->stream);
+            (void)hipMemsetAsync(l.ws_lo, 0, l.ws_bytes(), h->stream);
+            a.ws_hi = l.ws_hi.get(); a.ws_lo = l.ws_lo.get(); a.w_ovf = h->range_flags + 2;
             (void)hipMemsetAsync(h->range_flags + 2, 0, sizeof(unsigned), h->stream);
         }
         launch_fold_pack(a, h->stream);
@@ -2046,17 +1993,10 @@ struct TmpLayer {
             unsigned wflag = 0;
             (void)hipMemcpyAsync(&wflag, h->range_flags + 2, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream);
             if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = 1; return; }
-            if (wflag) { (void)hipFree(l.ws_hi); (void)hipFree(l.ws_lo); l.ws_hi = l.ws_lo = nullptr; }
+            if (wflag) { l.ws_hi.reset(); l.ws_lo.reset(); }
         }
     }
-    ~TmpLayer()
-    {
-        (void)hipStreamSynchronize(h->stream);
-        if (l.w_packed) (void)hipFree(l.w_packed);
-        if (l.b_packed) (void)hipFree(l.b_packed);
-        if (l.ws_hi) (void)hipFree(l.ws_hi);
-        if (l.ws_lo) (void)hipFree(l.ws_lo);
-    }
+    ~TmpLayer() { (void)hipStreamSynchronize(h->stream); }      // then the packs go with l
 };
 }  // namespace
 
@@ -2141,12 +2081,12 @@ int yn_op_shuffle_block(yn_handle* h, const char* block, const float* x, int B, 
     const int Cin = s2 ? pw1.cin : C;
     const int Ho = s2 ? (H - 1) / 2 + 1 : H, Wo = s2 ? (W - 1) / 2 + 1 : W;
     const long Mi = (long)B * H * W, Mo = (long)B * Ho * Wo;
-    float *t1 = nullptr, *t2 = nullptr, *tdw = nullptr, *tb1 = nullptr;
-    HIPCHK(h, hipMalloc((void**)&t1, Mi * bf * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&t2, Mo * bf * sizeof(float)));
+    DevBuf<float> t1, t2, tdw, tb1;
+    HIPCHK(h, t1.reserve((size_t)Mi * bf));
+    HIPCHK(h, t2.reserve((size_t)Mo * bf));
     if (s2) {
-        HIPCHK(h, hipMalloc((void**)&tdw, Mo * Cin * sizeof(float)));
-        HIPCHK(h, hipMalloc((void**)&tb1, Mo * bf * sizeof(float)));
+        HIPCHK(h, tdw.reserve((size_t)Mo * Cin));
+        HIPCHK(h, tb1.reserve((size_t)Mo * bf));
         run_dw(h, L(h, P + ".b1.dw"), x, Cin, 0, B, H, W, tdw, Cin, 0);
         run_pw(h, L(h, P + ".b1.pw"), tdw, Cin, 0, Mo, tb1, bf, 0, nullptr, 0, 0);
         run_pw(h, pw1, x, Cin, 0, Mi, t1, bf, 0, nullptr, 0, 0);
@@ -2157,9 +2097,6 @@ int yn_op_shuffle_block(yn_handle* h, const char* block, const float* x, int B, 
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(t1); (void)hipFree(t2);
-    if (tdw) (void)hipFree(tdw);
-    if (tb1) (void)hipFree(tb1);
     return 0;
 }
 
@@ -2475,10 +2412,8 @@ void yn_tta_destroy(yn_tta* t)
     int prev = -1;
     const bool moved = hipGetDevice(&prev) == hipSuccess && prev != t->device && hipSetDevice(t->device) == hipSuccess;
     if (t->last_stream || t->lists_B >= 0) (void)hipDeviceSynchronize();
-    void* ptrs[] = {t->xr, t->fb, t->fs, t->fc, t->fcount, t->lb, t->ls, t->lc, t->state, t->fstart, t->mb, t->ms, t->mc, t->mcount, t->rec, t->offsets};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (moved) (void)hipSetDevice(prev);
     delete t;
+    if (moved) (void)hipSetDevice(prev);
 }
 
 int yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip, int max_batch, int list_capacity, yn_tta** out)
@@ -2503,20 +2438,20 @@ int yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip,
     const size_t nb = (size_t)(t->flip ? 2 : 1) * max_batch, fN = nb * t->Nmax, lN = (size_t)max_batch * t->cap;
     const size_t forwards = (size_t)(t->flip ? 2 : 1) * num_scales;
     t->state_host.resize(TTA_STATE + max_batch);
-    struct { void** p; size_t bytes; } req[] = {
-        {(void**)&t->xr, nb * 3 * t->smax * t->smax * sizeof(float)},
-        {(void**)&t->fb, fN * 4 * sizeof(float)}, {(void**)&t->fs, fN * sizeof(float)}, {(void**)&t->fc, fN * sizeof(int32_t)}, {(void**)&t->fcount, nb * sizeof(int32_t)},
-        {(void**)&t->lb, lN * 4 * sizeof(float)}, {(void**)&t->ls, lN * sizeof(float)}, {(void**)&t->lc, lN * sizeof(int32_t)},
-        {(void**)&t->state, (TTA_STATE + max_batch) * sizeof(int32_t)}, {(void**)&t->fstart, forwards * max_batch * sizeof(int32_t)},
-        {(void**)&t->mb, lN * 4 * sizeof(float)}, {(void**)&t->ms, lN * sizeof(float)}, {(void**)&t->mc, lN * sizeof(int32_t)}, {(void**)&t->mcount, max_batch * sizeof(int32_t)},
-        {(void**)&t->rec, lN * 6 * sizeof(float)}, {(void**)&t->offsets, (max_batch + 1) * sizeof(int32_t)}};
-    for (auto& r : req) {
-        if (hipMalloc(r.p, r.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            yn_tta_destroy(t);
-            return fail(h, "yn_tta_create: out of device memory (%zu bytes for %d images, %d scales up to %d, %d rows per list)", r.bytes, max_batch, num_scales,
-                        t->smax, t->cap);
-        }
+    size_t failed = 0;                                  // bytes of the first allocation that failed
+    auto take = [&](auto& buf, size_t n) { if (!failed && buf.reserve(n)) failed = n * sizeof(buf[0]); };
+    take(t->xr, nb * 3 * t->smax * t->smax);
+    take(t->fb, fN * 4); take(t->fs, fN); take(t->fc, fN); take(t->fcount, nb);
+    take(t->lb, lN * 4); take(t->ls, lN); take(t->lc, lN);
+    take(t->state, (size_t)TTA_STATE + max_batch); take(t->fstart, forwards * max_batch);
+    take(t->mb, lN * 4); take(t->ms, lN); take(t->mc, lN); take(t->mcount, (size_t)max_batch);
+    take(t->rec, lN * 6); take(t->offsets, (size_t)max_batch + 1);
+    if (failed) {
+        (void)hipGetLastError();
+        const int smax = t->smax;
+        yn_tta_destroy(t);
+        return fail(h, "yn_tta_create: out of device memory (%zu bytes for %d images, %d scales up to %d, %d rows per list)", failed, max_batch, num_scales,
+                    smax, list_capacity);
     }
     // the lists' unused rows are never candidates (class -1, set per call), but the NMS kernels may load them: finite values once
     if (hipMemsetAsync(t->lb, 0, lN * 4 * sizeof(float), h->stream) != hipSuccess || hipMemsetAsync(t->ls, 0, lN * sizeof(float), h->stream) != hipSuccess ||

@@ -1,6 +1,6 @@
 // yn_eval_shared.h — what the two metric files (kernels_eval.hip: VOC mAP, kernels_coco.hip: COCO box AP) have in common: the
-// evaluators' un-letterboxing of a detection box, a bitonic sort of unique keys, a block scan, a lower bound and the host-side error /
-// growth plumbing.  Both files are built with -ffp-contract=off.  Everything here is `static` or a template: each file gets its own copy.
+// evaluators' un-letterboxing of a detection box, a bitonic sort of unique keys, a block scan, a lower bound and the host-side error
+// check (device memory is owned by DevBuf members, yn_devbuf.h).  Both files are built with -ffp-contract=off.  Everything here is `static` or a template: each file gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,22 +124,9 @@ __device__ __forceinline__ T block_scan_incl(T v, Op op, T* lds)
 // ---- host plumbing ----------------------------------------------------------------------------------------------------------------
 #define EVCHK(expr)                                                                                         \
     do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
+        const hipError_t e_ = (hipError_t)(expr);      /* a HIP call, or a DevBuf growth (its int is a hipError_t) */ \
         if (e_ != hipSuccess) { err = std::string(#expr " failed: ") + hipGetErrorString(e_); return 1; }   \
     } while (0)
-
-template <typename T>
-static int grow(T*& p, size_t& cap, size_t need, std::string& err)   // drops the old contents
-{
-    if (need <= cap) return 0;
-    size_t nc = cap ? cap : 1;
-    while (nc < need) nc *= 2;
-    if (p) EVCHK(hipFree(p));
-    p = nullptr;
-    EVCHK(hipMalloc((void**)&p, nc * sizeof(T)));
-    cap = nc;
-    return 0;
-}
 
 }  // namespace evs
 }  // namespace ynk

@@ -5,6 +5,8 @@
 
 #include <string>
 
+#include "yn_devbuf.h"
+
 namespace ynk {
 
 // Every launch of the library goes through this form of hipLaunchKernelGGL: with YN_LOG_LDS=1 in the environment each distinct (kernel, dynamic

@@ -68,12 +68,12 @@ int alloc_packs(yn_handle* h, Layer& l, TrainPack& pk)
         if (l.kind == K_DENSE3) pk.Kb = l.cout;              // conv3x3 launcher takes Cin', not 9*Cin'
     }
     l.Kp = d.Kp; l.Npad = d.Npad;                              // the same values yn_fold_bn derives
-    HIPCHK(h, hipMalloc((void**)&pk.wp, fwd * sizeof(float)));
-    HIPCHK(h, hipMalloc((void**)&pk.bias, nbias * sizeof(float)));
+    HIPCHK(h, pk.wp.reserve(fwd));
+    HIPCHK(h, pk.bias.reserve(nbias));
     HIPCHK(h, hipMemsetAsync(pk.wp, 0, fwd * sizeof(float), h->stream));
     HIPCHK(h, hipMemsetAsync(pk.bias, 0, nbias * sizeof(float), h->stream));
     if (bwd) {
-        HIPCHK(h, hipMalloc((void**)&pk.wp_bwd, bwd * sizeof(float)));
+        HIPCHK(h, pk.wp_bwd.reserve(bwd));
         HIPCHK(h, hipMemsetAsync(pk.wp_bwd, 0, bwd * sizeof(float), h->stream));
     }
     return 0;
@@ -177,7 +177,7 @@ void even_channels_to(const float* g, int C, long M, View dst, hipStream_t st) {
 int zeros_ready(yn_handle* h)
 {
     if (!h->zeros) {
-        HIPCHK(h, hipMalloc((void**)&h->zeros, 4096 * sizeof(float)));
+        HIPCHK(h, h->zeros.reserve(4096));
         HIPCHK(h, hipMemsetAsync(h->zeros, 0, 4096 * sizeof(float), h->stream));
     }
     return 0;

@@ -54,7 +54,7 @@ struct HTrainer : StepBase<HRec> {
             for (int i = 0; i < 8; ++i) sq.fev[i] = h->train_events[NEV + 1 + i];
         }
         if (carve_scratch(h, ar, HACC_SLOTS, st, sc)) return 1;
-        if (h->hpack_table) launch_hpack_all(h->hpack_table, h->hpack_table_n, st);
+        if (h->hpack_table) launch_hpack_all(h->hpack_table, (int)h->hpack_table.cap(), st);
         return 0;
     }
 
@@ -67,8 +67,7 @@ struct HTrainer : StepBase<HRec> {
         const float* b = l.has_bias ? P(l.conv + ".bias") : nullptr;
         if (l.kind == K_DW) {
             if (!pk.dwf) {
-                if (hipMalloc((void**)&pk.dwf, (size_t)9 * x.Cp * sizeof(float)) != hipSuccess || hipMalloc((void**)&pk.dwb, (size_t)9 * x.Cp * sizeof(float)) != hipSuccess ||
-                    hipMalloc((void**)&pk.bias, (size_t)x.Cp * sizeof(float)) != hipSuccess) return 1;
+                if (pk.dwb.reserve((size_t)9 * x.Cp) || pk.bias.reserve((size_t)x.Cp) || pk.dwf.reserve((size_t)9 * x.Cp)) return 1;     // dwf last: it marks the set as made
                 (void)hipMemsetAsync(pk.dwf, 0, (size_t)9 * x.Cp * sizeof(float), st);
                 (void)hipMemsetAsync(pk.dwb, 0, (size_t)9 * x.Cp * sizeof(float), st);
                 (void)hipMemsetAsync(pk.bias, 0, (size_t)x.Cp * sizeof(float), st);
@@ -78,7 +77,7 @@ struct HTrainer : StepBase<HRec> {
             if (l.stride == 1) launch_hpack_dw(w, nullptr, l.cout, x.half, x.gap, x.Cp, 1, pk.dwb, nullptr, st);
             h->hpack_jobs.push_back(HPackDesc{w, b, 1, l.cout, l.cin, 9, x.half, x.gap, x.Cp, 0, 0, 0, nullptr, nullptr, pk.bias, pk.dwf, l.stride == 1 ? pk.dwb : nullptr});
         } else if (l.kind == K_STEM) {
-            if (!pk.dwf) { if (hipMalloc((void**)&pk.dwf, (size_t)27 * 24 * sizeof(float)) != hipSuccess) return 1; }
+            if (pk.dwf.reserve((size_t)27 * 24)) return 1;
             launch_hpack_stem(w, pk.dwf, st);
             h->hpack_jobs.push_back(HPackDesc{w, nullptr, 2, 24, 3, 9, 3, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, pk.dwf, nullptr});
         } else {
@@ -86,8 +85,7 @@ struct HTrainer : StepBase<HRec> {
             if (!pk.wf) {
                 pk.Kp = x.Cp; pk.Npad = r32(l.cout); pk.Kpb = r8(l.cout); pk.Npadb = r32(x.Cp);
                 const size_t nf = (size_t)taps * pk.Kp * pk.Npad, nb = (size_t)taps * pk.Kpb * pk.Npadb;
-                if (hipMalloc((void**)&pk.wf, nf * sizeof(h16)) != hipSuccess || hipMalloc((void**)&pk.wb, nb * sizeof(h16)) != hipSuccess ||
-                    hipMalloc((void**)&pk.bias, (size_t)pk.Npad * sizeof(float)) != hipSuccess) return 1;
+                if (pk.wb.reserve(nb) || pk.bias.reserve((size_t)pk.Npad) || pk.wf.reserve(nf)) return 1;     // wf last: it marks the set as made
                 (void)hipMemsetAsync(pk.wf, 0, nf * sizeof(h16), st);
                 (void)hipMemsetAsync(pk.wb, 0, nb * sizeof(h16), st);
                 (void)hipMemsetAsync(pk.bias, 0, (size_t)pk.Npad * sizeof(float), st);
@@ -208,10 +206,9 @@ struct HTrainer : StepBase<HRec> {
     int forward_done()
     {
         if (h->hpack_table || h->hpack_jobs.empty()) return 0;
-        HIPCHK(h, hipMalloc((void**)&h->hpack_table, h->hpack_jobs.size() * sizeof(HPackDesc)));
+        HIPCHK(h, h->hpack_table.reserve(h->hpack_jobs.size()));
         HIPCHK(h, hipMemcpyAsync(h->hpack_table, h->hpack_jobs.data(), h->hpack_jobs.size() * sizeof(HPackDesc), hipMemcpyHostToDevice, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        h->hpack_table_n = (int)h->hpack_jobs.size();
         return 0;
     }
     // (+ scaled gradient w.r.t. the raw heads)

@@ -4,10 +4,15 @@
 namespace {
 
 // scratch of the op-level entry points (yn_op_h16_*, yn_op_f32_*), filled with the byte `fill` (zero; 0xff makes every float a NaN), freed on scope exit
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes, hipStream_t st, int fill = 0) { if (hipMalloc(&p, bytes ? bytes : 16) == hipSuccess) (void)hipMemsetAsync(p, fill, bytes ? bytes : 16, st); else p = nullptr; }
-    ~DevBuf() { if (p) (void)hipFree(p); }
+struct Scratch {
+    DevBuf<char> buf;
+    void* p = nullptr;                                      // null: the allocation failed
+    explicit Scratch(size_t bytes, hipStream_t st, int fill = 0)
+    {
+        if (buf.reserve(bytes ? bytes : 16)) return;
+        p = buf;
+        (void)hipMemsetAsync(p, fill, buf.cap(), st);
+    }
     template <class T> T* as() { return (T*)p; }
 };
 
@@ -33,11 +38,11 @@ int yn_op_h16_conv(yn_handle* h, int kind, const float* x, int B, int H, int W, 
     const long Mi = (long)B * H * W, Mo = (long)B * Ho * Wo;
     const int taps = kind == 2 ? 9 : 1;
     const int oC = Cout, Np = kind == 1 ? Cp : r8(Cout), ohalf = kind == 1 ? half : Cout, ogap = kind == 1 ? gap : 0;
-    DevBuf xb((size_t)Mi * Cp * sizeof(h16), st), yb((size_t)Mo * Np * sizeof(h16), st), dyb((size_t)Mo * Np * sizeof(h16), st), dxb((size_t)Mi * Cp * sizeof(h16), st);
+    Scratch xb((size_t)Mi * Cp * sizeof(h16), st), yb((size_t)Mo * Np * sizeof(h16), st), dyb((size_t)Mo * Np * sizeof(h16), st), dxb((size_t)Mi * Cp * sizeof(h16), st);
     const int Npad = r32(Cout), Kpb = r8(Cout), Npadb = r32(Cp);
-    DevBuf wf((size_t)taps * Cp * Npad * sizeof(h16), st), wb((size_t)taps * Kpb * Npadb * sizeof(h16), st), bb((size_t)(Npad > Cp ? Npad : Cp) * sizeof(float), st);
-    DevBuf dwf((size_t)9 * Cp * sizeof(float), st), dwbk((size_t)9 * Cp * sizeof(float), st);
-    DevBuf part((size_t)(4 << 20) * sizeof(float), st), slots((size_t)GRAD_SLOTS * Cout * 9 * sizeof(float), st);
+    Scratch wf((size_t)taps * Cp * Npad * sizeof(h16), st), wb((size_t)taps * Kpb * Npadb * sizeof(h16), st), bb((size_t)(Npad > Cp ? Npad : Cp) * sizeof(float), st);
+    Scratch dwf((size_t)9 * Cp * sizeof(float), st), dwbk((size_t)9 * Cp * sizeof(float), st);
+    Scratch part((size_t)(4 << 20) * sizeof(float), st), slots((size_t)GRAD_SLOTS * Cout * 9 * sizeof(float), st);
     if (!xb.p || !yb.p || !dyb.p || !dxb.p || !wf.p || !wb.p || !bb.p || !dwf.p || !dwbk.p || !part.p || !slots.p) return fail(h, "yn_op_h16_conv: out of memory");
     launch_hstage(x, Cin, xb.as<h16>(), Cp, half, gap, Mi, st);
     if (kind == 1) {
@@ -105,9 +110,9 @@ int yn_op_h16_gemm_stats(yn_handle* h, int kind, const float* x, int B, int H, i
     const int half = gapped ? Cin / 2 : Cin, gap = gapped ? r8(half) - half : 0, Cp = gapped ? 2 * r8(half) : r8(Cin);
     const long M = (long)B * H * W;
     const int taps = kind == 2 ? 9 : 1, Np = r8(Cout), Npad = r32(Cout), Kpb = r8(Cout), Npadb = r32(Cp);
-    DevBuf xb((size_t)M * Cp * sizeof(h16), st), yb((size_t)M * Np * sizeof(h16), st), dyb((size_t)M * Np * sizeof(h16), st), dxb((size_t)M * Cp * sizeof(h16), st), ybb((size_t)M * Cp * sizeof(h16), st);
-    DevBuf wf((size_t)taps * Cp * Npad * sizeof(h16), st), wb((size_t)taps * Kpb * Npadb * sizeof(h16), st);
-    DevBuf accf((size_t)2 * HACC_SLOTS * Cout * sizeof(double), st), accb((size_t)2 * HACC_SLOTS * Cin * sizeof(double), st);
+    Scratch xb((size_t)M * Cp * sizeof(h16), st), yb((size_t)M * Np * sizeof(h16), st), dyb((size_t)M * Np * sizeof(h16), st), dxb((size_t)M * Cp * sizeof(h16), st), ybb((size_t)M * Cp * sizeof(h16), st);
+    Scratch wf((size_t)taps * Cp * Npad * sizeof(h16), st), wb((size_t)taps * Kpb * Npadb * sizeof(h16), st);
+    Scratch accf((size_t)2 * HACC_SLOTS * Cout * sizeof(double), st), accb((size_t)2 * HACC_SLOTS * Cin * sizeof(double), st);
     if (!xb.p || !yb.p || !dyb.p || !dxb.p || !ybb.p || !wf.p || !wb.p || !accf.p || !accb.p) return fail(h, "yn_op_h16_gemm_stats: out of memory");
     launch_hstage(x, Cin, xb.as<h16>(), Cp, half, gap, M, st);
     launch_hpack_gemm(w, Cout, Cin, taps, half, gap, Cp, Npad, 0, wf.as<h16>(), st);
@@ -147,8 +152,8 @@ int yn_op_h16_bn(yn_handle* h, const float* y, const float* dz, int64_t M, int C
     if (dz && (!dy || !dgamma || !dbeta)) return fail(h, "yn_op_h16_bn: the backward pass needs dy, dgamma and dbeta");
     hipStream_t st = h->stream;
     const int Cp = r8(C);
-    DevBuf yb((size_t)M * Cp * sizeof(h16), st), zb((size_t)M * Cp * sizeof(h16), st), dzb((size_t)M * Cp * sizeof(h16), st), dyb((size_t)M * Cp * sizeof(h16), st);
-    DevBuf acc((size_t)4 * HACC_SLOTS * C * sizeof(double), st), mi((size_t)2 * C * sizeof(float), st);
+    Scratch yb((size_t)M * Cp * sizeof(h16), st), zb((size_t)M * Cp * sizeof(h16), st), dzb((size_t)M * Cp * sizeof(h16), st), dyb((size_t)M * Cp * sizeof(h16), st);
+    Scratch acc((size_t)4 * HACC_SLOTS * C * sizeof(double), st), mi((size_t)2 * C * sizeof(float), st);
     if (!yb.p || !zb.p || !dzb.p || !dyb.p || !acc.p || !mi.p) return fail(h, "yn_op_h16_bn: out of memory");
     launch_hstage(y, C, yb.as<h16>(), Cp, C, 0, (long)M, st);
     HRedArgs q{};
@@ -179,9 +184,9 @@ int yn_op_h16_bn_unit(yn_handle* h, const float* y, const float* pass, const flo
     if (dunit && (!dy || !deven || !dgamma || !dbeta)) return fail(h, "yn_op_h16_bn_unit: the backward pass needs dy, deven, dgamma and dbeta");
     hipStream_t st = h->stream;
     const int Cp = r8(C), gap = Cp - C, Up = 2 * Cp;
-    DevBuf yb((size_t)M * Cp * sizeof(h16), st), pb((size_t)M * Cp * sizeof(h16), st), ub((size_t)M * Up * sizeof(h16), st), dub((size_t)M * Up * sizeof(h16), st);
-    DevBuf dyb((size_t)M * Cp * sizeof(h16), st), evb((size_t)M * Cp * sizeof(h16), st);
-    DevBuf acc((size_t)4 * HACC_SLOTS * C * sizeof(double), st), mi((size_t)2 * C * sizeof(float), st);
+    Scratch yb((size_t)M * Cp * sizeof(h16), st), pb((size_t)M * Cp * sizeof(h16), st), ub((size_t)M * Up * sizeof(h16), st), dub((size_t)M * Up * sizeof(h16), st);
+    Scratch dyb((size_t)M * Cp * sizeof(h16), st), evb((size_t)M * Cp * sizeof(h16), st);
+    Scratch acc((size_t)4 * HACC_SLOTS * C * sizeof(double), st), mi((size_t)2 * C * sizeof(float), st);
     if (!yb.p || !pb.p || !ub.p || !dub.p || !dyb.p || !evb.p || !acc.p || !mi.p) return fail(h, "yn_op_h16_bn_unit: out of memory");
     launch_hstage(y, C, yb.as<h16>(), Cp, C, 0, (long)M, st);
     launch_hstage(pass, C, pb.as<h16>(), Cp, C, 0, (long)M, st);

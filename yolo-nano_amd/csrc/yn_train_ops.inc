@@ -15,13 +15,7 @@ struct TmpTrainLayer {
         l.name = "op"; l.kind = kind; l.cin = cin; l.cout = cout; l.stride = stride; l.has_bias = has_bias;
         rc = alloc_packs(h, l, pk);
     }
-    ~TmpTrainLayer()
-    {
-        (void)hipStreamSynchronize(h->stream);
-        if (pk.wp) (void)hipFree(pk.wp);
-        if (pk.bias) (void)hipFree(pk.bias);
-        if (pk.wp_bwd) (void)hipFree(pk.wp_bwd);
-    }
+    ~TmpTrainLayer() { (void)hipStreamSynchronize(h->stream); }     // then the packs go with pk
 };
 
 }  // namespace
@@ -66,8 +60,8 @@ int yn_op_f32_conv(yn_handle* h, int kind, const float* x, int B, int H, int W, 
     if (dy) {
         // a flat gradient buffer of this one layer, [weight][bias], with its GRAD_SLOTS slot copies; the scratch starts as NaNs: the step's is not zeroed either
         const size_t n = wn + (size_t)Cout;
-        DevBuf g(n * sizeof(float), st), slots((size_t)GRAD_SLOTS * n * sizeof(float), st);
-        DevBuf part((dw || dbias) ? cap * sizeof(float) : 0, st, 0xff), tmp(dx && accumulate ? (size_t)r.Mi * Cin * sizeof(float) : 0, st, 0xff);
+        Scratch g(n * sizeof(float), st), slots((size_t)GRAD_SLOTS * n * sizeof(float), st);
+        Scratch part((dw || dbias) ? cap * sizeof(float) : 0, st, 0xff), tmp(dx && accumulate ? (size_t)r.Mi * Cin * sizeof(float) : 0, st, 0xff);
         if (!g.p || !slots.p || !part.p || !tmp.p) return fail(h, "yn_op_f32_conv: out of memory");
         if (dw || dbias) {
             GradPtrs gp{};
@@ -101,7 +95,7 @@ int yn_op_f32_bn(yn_handle* h, const float* y, int64_t M, int C, const float* ga
     hipStream_t st = h->stream;
     Layer l;
     l.name = "op"; l.kind = K_PW; l.cin = l.cout = C; l.act = act;
-    DevBuf acc((size_t)4 * ACC_SLOTS * C * sizeof(double), st);
+    Scratch acc((size_t)4 * ACC_SLOTS * C * sizeof(double), st);
     if (!acc.p) return fail(h, "yn_op_f32_bn: out of memory");
     TRec r;
     r.l = &l; r.Mo = (long)M; r.y = const_cast<float*>(y); r.y_ld = C; r.mean = mean; r.invstd = invstd; r.acc = acc.as<double>();

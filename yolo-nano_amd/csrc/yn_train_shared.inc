@@ -65,7 +65,7 @@ template <class Rec> struct StepBase {
     StepArena ar;
     StepScratch sc;
     std::vector<Rec> recs;
-    StepBase(yn_handle* h_, int B_, const TrainSwitches& sw_) : h(h_), B(B_), S(h_->grid.S), st(h_->stream), sw(sw_), ar{h_->train_arena, h_->train_arena_bytes} { recs.reserve(h->layers.size() + 4); }
+    StepBase(yn_handle* h_, int B_, const TrainSwitches& sw_) : h(h_), B(B_), S(h_->grid.S), st(h_->stream), sw(sw_), ar{h_->train_arena, h_->train_arena.cap()} { recs.reserve(h->layers.size() + 4); }
     float* P(const std::string& k) { return h->tP + h->toff.at(k); }
     float* G(const std::string& k) { return h->tG + h->toff.at(k); }
     float* GS(const std::string& k) { return sc.gslots + h->toff.at(k); }   // slot 0; slot s is h->tN floats further
@@ -127,12 +127,10 @@ int ensure_train_events(yn_handle* h, size_t n)
 int ensure_train_arena(yn_handle* h, int B, int S, int factor)
 {
     const size_t need = network_arena_bytes(h, B, S) * factor + ((size_t)256 << 20);
-    if (need <= h->train_arena_bytes) return 0;
+    if (need <= h->train_arena.cap()) return 0;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     drop_train_graphs(h);                                   // captured steps bake the arena's addresses in
-    if (h->train_arena) HIPCHK(h, hipFree(h->train_arena));
-    HIPCHK(h, hipMalloc((void**)&h->train_arena, need));
-    h->train_arena_bytes = need;
+    HIPCHK(h, h->train_arena.reserve(need));
     return 0;
 }
 
@@ -140,7 +138,7 @@ int ensure_train_arena(yn_handle* h, int B, int S, int factor)
 int optimiser_tail(yn_handle* h, float lr, float momentum, float weight_decay, float grad_scale, hipStream_t st)
 {
     if (!h->skip_flag) {
-        HIPCHK(h, hipMalloc((void**)&h->skip_flag, 2 * sizeof(int)));
+        HIPCHK(h, h->skip_flag.reserve(2));
         HIPCHK(h, hipMemsetAsync(h->skip_flag, 0, 2 * sizeof(int), st));
     }
     launch_sgd(h->tP, h->tG, h->tM, (long)h->tN, lr, momentum, weight_decay, grad_scale, 0, h->skip_flag, st);   // momentum starts at zero: no first-step case

@@ -116,7 +116,7 @@ int train_tape(X& T, const float* x_dev, const float* target_dev, float* losses_
     head_fwd(2, nullptr);
     for (int i = 0; i < 2; ++i)
         if (fk[i]) { (void)hipEventRecord(fev[2 + i], fk[i]); (void)hipStreamWaitEvent(st, fev[2 + i], 0); }
-    if (T.ar.oom) return fail(h, "training workspace exhausted (%zu bytes)", h->train_arena_bytes);
+    if (T.ar.oom) return fail(h, "training workspace exhausted (%zu bytes)", h->train_arena.cap());
     if (T.forward_done()) return 1;
     if (h->fwd_only[0]) {                                  // yn_train_forward: raw heads as dense fp32 rows, nothing else
         for (int k = 0; k < 3; ++k) launch_rows_to_f32(raw[k].v, X::is_h16, HCp, h->fwd_only[k], h->head_ch, raw[k].M, st);
