@@ -118,3 +118,19 @@ def test_device_memory_is_allocated_and_freed_in_one_header():
             if found:
                 calls[f] = found
     assert calls == {"yn_devbuf.h": {"hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree"}}
+
+
+def test_split_f16_arithmetic_is_written_in_one_header():
+    """The split-f16 step has one definition, csrc/yn_split.h: no other inference source names the f16 MFMA builtin or the join's
+    constant, and the per-file aliases of the _Float16 vectors are gone.  kernels_h16.hip (fp16 training) is a different scheme."""
+    csrc = os.path.join(ROOT, "yolo-nano_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".inc")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        for alias in ("c3h16", "uch16", "ph16", "sh16"):
+            assert alias not in text, "%s: %s" % (f, alias)
+        if f in ("yn_split.h", "kernels_h16.hip"):
+            continue
+        assert "mfma_f32_32x32x16_f16" not in text, f
+        assert "1.0f / 2048.0f" not in text, f

@@ -331,10 +331,6 @@ __global__ __launch_bounds__(256, 2) void unit_chain_kernel(ChainArgs a)
 // (memory) phase plus two short matrix phases, so ONE launch per unit beats three again.  LDS: the depthwise output / x2' as two
 // planes of halves P[2][BM][PS] (A operands); the weights go through registers.
 // -------------------------------------------------------------------------------------------------
-typedef _Float16 uch16;
-typedef _Float16 uch16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 uch16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 uch16x2 __attribute__((ext_vector_type(2)));
 
 // -------------------------------------------------------------------------------------------------
 // unit_chain2_kernel (round 3).  What changed against the round-2 form, and why (tools/phase_timing.sh chain2: of a block's ~50 k
@@ -363,8 +359,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN != 4 ? 1 : ((NT == 1 && V ==
     extern __shared__ __attribute__((aligned(16))) float uc2_smem[];
     const int bf = a.bf, W = a.W, H = a.H, HW = H * W;
     const int KQ = (bf + 7) >> 3, PS = plane_stride(bf), S = (KQ + 1) >> 1;     // S: 16-deep k-steps of a GEMM
-    uch16* Ph = reinterpret_cast<uch16*>(uc2_smem);                     // [BM][PS]
-    uch16* Pl = Ph + BM * PS;
+    h16* Ph = reinterpret_cast<h16*>(uc2_smem);                     // [BM][PS]
+    h16* Pl = Ph + BM * PS;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int wm = wave % WM, wn = wave / WM;
@@ -384,10 +380,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN != 4 ? 1 : ((NT == 1 && V ==
     // chunk barriers, no staging pass, half the LDS (the first form walked K in chunks of 64 through LDS: two barrier rounds of ~2 k
     // cycles per GEMM whatever they multiplied, and a 2.3 k staging pass between the GEMMs).  Same k order (16-deep steps in sequence):
     // the same bits.
-    uch16x8 bq[D][NT][2];
-    auto load_b = [&](const void* Wh_, const void* Wl_, int s, uch16x8 (&dst)[NT][2]) {
-        const uch16* Wh = reinterpret_cast<const uch16*>(Wh_);
-        const uch16* Wl = reinterpret_cast<const uch16*>(Wl_);
+    h16x8 bq[D][NT][2];
+    auto load_b = [&](const void* Wh_, const void* Wl_, int s, h16x8 (&dst)[NT][2]) {
+        const h16* Wh = reinterpret_cast<const h16*>(Wh_);
+        const h16* Wl = reinterpret_cast<const h16*>(Wl_);
         // NO masks (round 5): a masked load is USED where it is issued - eight v_and per fragment - and hipcc then waits for it there: every k-step
         // of the walk drained the vector-memory counter (vmcnt(3) ... vmcnt(0) in front of its MFMAs) and cost a full L2 round trip, D deep or
         // not.  Clamped addresses instead: an octet past K (kq = KQ, odd octet counts) meets the planes' zero K tail, a column past Npad is
@@ -397,22 +393,22 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN != 4 ? 1 : ((NT == 1 && V ==
         for (int nt = 0; nt < NT; ++nt) {
             const int n = min(wn * NT * 32 + nt * 32 + l31, a.Npad - 1);
             const size_t off = ((size_t)kq * a.Npad + n) * 8;
-            dst[nt][0] = *reinterpret_cast<const uch16x8*>(Wh + off);
-            dst[nt][1] = *reinterpret_cast<const uch16x8*>(Wl + off);
+            dst[nt][0] = *reinterpret_cast<const h16x8*>(Wh + off);
+            dst[nt][1] = *reinterpret_cast<const h16x8*>(Wl + off);
         }
     };
     auto prime_b = [&](const void* Wh, const void* Wl) {
 #pragma unroll
         for (int j = 0; j < D; ++j) load_b(Wh, Wl, j, bq[j]);
     };
-    float amax = 0.0f;                                                   // range guard (yn_device.h)
+    float amax = 0.0f;                                                   // range guard (yn_split.h)
     auto split_store = [&](int r, int c, float v0, float v1) {           // two adjacent channels of row r -> both planes
-        uch16x2 hi, lo;
+        h16x2 hi, lo;
         amax = range_track(range_track(amax, v0), v1);
-        hi[0] = (uch16)v0; hi[1] = (uch16)v1;
-        lo[0] = (uch16)((v0 - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((v1 - (float)hi[1]) * 2048.0f);
-        *reinterpret_cast<uch16x2*>(Ph + r * PS + c) = hi;
-        *reinterpret_cast<uch16x2*>(Pl + r * PS + c) = lo;
+        hi[0] = (h16)v0; hi[1] = (h16)v1;
+        lo[0] = split_lo(v0, hi[0]); lo[1] = split_lo(v1, hi[1]);
+        *reinterpret_cast<h16x2*>(Ph + r * PS + c) = hi;
+        *reinterpret_cast<h16x2*>(Pl + r * PS + c) = lo;
     };
 
     float bias2[NT], bias1n[NT];
@@ -509,7 +505,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN != 4 ? 1 : ((NT == 1 && V ==
         x1_prefetch();
         // K tail: the columns [bf, PS) of both planes are zero (they meet zero weight rows, but must not be NaN bit patterns)
         const int padn = PS - bf;
-        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = bf + i - r * padn; Ph[r * PS + c2] = (uch16)0.0f; Pl[r * PS + c2] = (uch16)0.0f; }
+        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = bf + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
     }
     __syncthreads();
     YN_TS();
@@ -527,22 +523,18 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN != 4 ? 1 : ((NT == 1 && V ==
             for (int j = 0; j < D; ++j) {
                 const int s = s0 + j;
                 const int a_col = s < S ? s * 16 + h * 8 : PS - 8;      // past the walk: the last 16 bytes of the row's zero K tail (plane_stride)
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ph + (wm * 32 + l31) * PS + a_col);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(Pl + (wm * 32 + l31) * PS + a_col);
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(Ph + (wm * 32 + l31) * PS + a_col);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(Pl + (wm * 32 + l31) * PS + a_col);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bq[j][nt][0], acc0[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bq[j][nt][1], acc1[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bq[j][nt][0], acc1[nt], 0, 0, 0);
+                    split_mfma(ah, al, bq[j][nt][0], bq[j][nt][1], acc0[nt], acc1[nt]);
                 }
                 load_b(Wh, Wl, s + D, bq[j]);                   // (clamped beyond the last step)
                 __builtin_amdgcn_sched_barrier(0);              // HERE, behind the MFMAs that freed the slot: hipcc sank all D steps' loads to the end of
             }                                                   // the unrolled group, where the next group needs them at once (a round trip per group)
         }
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[nt][r] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]);
+        for (int nt = 0; nt < NT; ++nt) split_join(acc0[nt], acc1[nt]);
     };
     gemm(a.Ws2h, a.Ws2l);
     YN_TS();
@@ -709,18 +701,18 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     extern __shared__ __attribute__((aligned(16))) float du_smem[];
     const int bf = a.bf, CS = bf + 2;
     // region 1: A1 planes [RT1*32][AST1] x 2 + B1 [4][BN][8] x 2   (GEMM 1), later A2 planes [32][AST2] x 2 + B2 [8][BN][8] x 2 (GEMM 2)
-    uch16* A1h = reinterpret_cast<uch16*>(du_smem);
-    uch16* A1l = A1h + RT1 * 32 * AST1;
-    uch16* B1 = A1l + RT1 * 32 * AST1;                      // hi plane, then lo plane
+    h16* A1h = reinterpret_cast<h16*>(du_smem);
+    h16* A1l = A1h + RT1 * 32 * AST1;
+    h16* B1 = A1l + RT1 * 32 * AST1;                      // hi plane, then lo plane
     constexpr int R1_HALVES_A = 2 * RT1 * 32 * AST1 + 2 * 4 * BN * 8;
     constexpr int R1_HALVES_B = 2 * NO * AST2 + 2 * 8 * BN * 8 + 2 * NO * AST1 + 2 * 4 * BN * 8;      // A2, B2, then branch 1's A3 [32][AST1] x 2 and B3 [4][BN][8] x 2
     constexpr int R1_HALVES = R1_HALVES_A > R1_HALVES_B ? R1_HALVES_A : R1_HALVES_B;
-    uch16* A2h = reinterpret_cast<uch16*>(du_smem);
-    uch16* A2l = A2h + NO * AST2;
-    uch16* B2 = A2l + NO * AST2;
-    uch16* A3h = B2 + 2 * 8 * BN * 8;
-    uch16* A3l = A3h + NO * AST1;
-    uch16* B3 = A3l + NO * AST1;
+    h16* A2h = reinterpret_cast<h16*>(du_smem);
+    h16* A2l = A2h + NO * AST2;
+    h16* B2 = A2l + NO * AST2;
+    h16* A3h = B2 + 2 * 8 * BN * 8;
+    h16* A3l = A3h + NO * AST1;
+    h16* B3 = A3l + NO * AST1;
     float* T32 = du_smem + (R1_HALVES + 1) / 2;             // [RT1*32][CS] (rows >= NPIX are written as zeros, never read)
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
@@ -732,7 +724,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     const int oy0 = (trem / tx_n) * TH, ox0 = (trem % tx_n) * TW;
     const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;         // input pixel of window position (0, 0)
     const int KQ1 = (a.cin + 7) >> 3, KQ2 = (bf + 7) >> 3;
-    float amax = 0.0f;                                      // range guard (yn_device.h): largest |value| this thread has split
+    float amax = 0.0f;                                      // range guard (yn_split.h): largest |value| this thread has split
 
 #ifdef YN_EXP_TIMING
     long long TS[8]; int tsn = 0;
@@ -763,7 +755,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     constexpr int NI1 = 2;                                  // 32 output pixels over >= 16 pixel lanes (cin <= 32)
     float2 x1w[NI1][9], w1d[9], b1d = make_float2(0.0f, 0.0f);
     constexpr int B3_PER = (2 * 4 * BN + 255) / 256;
-    uch16x8 b3_reg[B3_PER];
+    h16x8 b3_reg[B3_PER];
     float bias3v = 0.0f;
 #pragma unroll
     for (int k = 0; k < 9; ++k) w1d[k] = *reinterpret_cast<const float2*>(a.wdw1 + k * a.cin + c1);
@@ -784,10 +776,10 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
         const int g = t + 256 * i;
         const int pl = g / (4 * BN), r = g - pl * (4 * BN);
         const int o = r / BN, n = r - o * BN;
-        uch16x8 v;
+        h16x8 v;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-        if (g < 2 * 4 * BN && o < KQ1 && n < a.Npad3) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.W3l : a.W3h) + ((size_t)o * a.Npad3 + n) * 8);
+        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
+        if (g < 2 * 4 * BN && o < KQ1 && n < a.Npad3) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W3l : a.W3h) + ((size_t)o * a.Npad3 + n) * 8);
         b3_reg[i] = v;
     }
     if (wave >= NP && wave < 2 * NP && (wave - NP) * 32 + l31 < bf) bias3v = a.b3[(wave - NP) * 32 + l31];
@@ -807,37 +799,37 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
         }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
-            uch16x8 hi, lo;
+            h16x8 hi, lo;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float x0 = v[o * 4 + j].x, x1 = v[o * 4 + j].y;
-                hi[2 * j] = (uch16)x0; hi[2 * j + 1] = (uch16)x1;
-                lo[2 * j] = (uch16)((x0 - (float)hi[2 * j]) * 2048.0f); lo[2 * j + 1] = (uch16)((x1 - (float)hi[2 * j + 1]) * 2048.0f);
+                hi[2 * j] = (h16)x0; hi[2 * j + 1] = (h16)x1;
+                lo[2 * j] = split_lo(x0, hi[2 * j]); lo[2 * j + 1] = split_lo(x1, hi[2 * j + 1]);
             }
-            *reinterpret_cast<uch16x8*>(A1h + p * AST1 + o * 8) = hi;
-            *reinterpret_cast<uch16x8*>(A1l + p * AST1 + o * 8) = lo;
+            *reinterpret_cast<h16x8*>(A1h + p * AST1 + o * 8) = hi;
+            *reinterpret_cast<h16x8*>(A1l + p * AST1 + o * 8) = lo;
         }
     }
     for (int g = t; g < 2 * 4 * BN; g += 256) {             // W1: plane, octet, column
         const int pl = g / (4 * BN), r = g - pl * (4 * BN);
         const int o = r / BN, n = r - o * BN;
-        uch16x8 v;
+        h16x8 v;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-        if (o < KQ1 && n < a.Npad1) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.W1l : a.W1h) + ((size_t)o * a.Npad1 + n) * 8);
-        *reinterpret_cast<uch16x8*>(B1 + (size_t)g * 8) = v;
+        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
+        if (o < KQ1 && n < a.Npad1) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W1l : a.W1h) + ((size_t)o * a.Npad1 + n) * 8);
+        *reinterpret_cast<h16x8*>(B1 + (size_t)g * 8) = v;
     }
     constexpr int B2_PER = (2 * 8 * BN + 255) / 256;
-    uch16x8 b2_reg[B2_PER];
+    h16x8 b2_reg[B2_PER];
 #pragma unroll
     for (int i = 0; i < B2_PER; ++i) {
         const int g = t + 256 * i;
         const int pl = g / (8 * BN), r = g - pl * (8 * BN);
         const int o = r / BN, n = r - o * BN;
-        uch16x8 v;
+        h16x8 v;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-        if (g < 2 * 8 * BN && o < KQ2 && n < a.Npad2) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.W2l : a.W2h) + ((size_t)o * a.Npad2 + n) * 8);
+        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
+        if (g < 2 * 8 * BN && o < KQ2 && n < a.Npad2) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W2l : a.W2h) + ((size_t)o * a.Npad2 + n) * 8);
         b2_reg[i] = v;
     }
     __syncthreads();
@@ -850,19 +842,17 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
         f32x16 acc0, acc1;
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const uch16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
-        const uch16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
-        const uch16* Bhb = B1 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const uch16* Blb = Bhb + 4 * BN * 8;
+        const h16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
+        const h16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
+        const h16* Bhb = B1 + (size_t)(h * BN + nt * 32 + l31) * 8;
+        const h16* Blb = Bhb + 4 * BN * 8;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-            const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-            const uch16x8 bh = *reinterpret_cast<const uch16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const uch16x8 bl = *reinterpret_cast<const uch16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
+            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
+            split_mfma(ah, al, bh, bl, acc0, acc1);
         }
         unsigned in16 = 0;                                  // inside flags of this lane's 16 rows
 #pragma unroll
@@ -875,7 +865,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int p = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float v = apply_act(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias, a.act1);
+                const float v = apply_act(split_join(acc0[r], acc1[r]) + bias, a.act1);
                 T32[p * CS + n] = __uint_as_float(__float_as_uint(v) & (0u - ((in16 >> r) & 1u)));
             }
         }
@@ -887,12 +877,12 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
 #pragma unroll
     for (int i = 0; i < B2_PER; ++i) {
         const int g = t + 256 * i;
-        if (g < 2 * 8 * BN) *reinterpret_cast<uch16x8*>(B2 + (size_t)g * 8) = b2_reg[i];
+        if (g < 2 * 8 * BN) *reinterpret_cast<h16x8*>(B2 + (size_t)g * 8) = b2_reg[i];
     }
 #pragma unroll
     for (int i = 0; i < B3_PER; ++i) {
         const int g = t + 256 * i;
-        if (g < 2 * 4 * BN) *reinterpret_cast<uch16x8*>(B3 + (size_t)g * 8) = b3_reg[i];
+        if (g < 2 * 4 * BN) *reinterpret_cast<h16x8*>(B3 + (size_t)g * 8) = b3_reg[i];
     }
     if (p1 < p1_n) {
 #pragma unroll
@@ -904,16 +894,16 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
                 for (int k = 0; k < 9; ++k) vfma(acc, x1w[i][k], w1d[k]);
                 acc = vact(acc, a.dw1_act);
                 amax = range_track(range_track(amax, acc.x), acc.y);
-                uch16x2 hi, lo;
-                hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
-                lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
-                *reinterpret_cast<uch16x2*>(A3h + op * AST1 + c1) = hi;
-                *reinterpret_cast<uch16x2*>(A3l + op * AST1 + c1) = lo;
+                h16x2 hi, lo;
+                hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
+                lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
+                *reinterpret_cast<h16x2*>(A3h + op * AST1 + c1) = hi;
+                *reinterpret_cast<h16x2*>(A3l + op * AST1 + c1) = lo;
             }
         }
     }
     const int pad1 = AST1 - a.cin;                          // K tail of branch 1's planes: zero
-    for (int i = t; i < NO * pad1; i += 256) { const int r = i / pad1, c2 = a.cin + i - r * pad1; A3h[r * AST1 + c2] = (uch16)0.0f; A3l[r * AST1 + c2] = (uch16)0.0f; }
+    for (int i = t; i < NO * pad1; i += 256) { const int r = i / pad1, c2 = a.cin + i - r * pad1; A3h[r * AST1 + c2] = (h16)0.0f; A3l[r * AST1 + c2] = (h16)0.0f; }
     if (dworker) {
         for (int op = dpl; op < NO; op += ppl) {
             const int dy = op / TW, dx = op - dy * TW;
@@ -925,16 +915,16 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
                     vfma(acc, *reinterpret_cast<const float2*>(T32 + ((2 * dy + ky) * WW + 2 * dx + kx) * CS + dc), wd[ky * 3 + kx]);
             acc = vact(acc, a.dw_act);
             amax = range_track(range_track(amax, acc.x), acc.y);
-            uch16x2 hi, lo;
-            hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
-            lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
-            *reinterpret_cast<uch16x2*>(A2h + op * AST2 + dc) = hi;
-            *reinterpret_cast<uch16x2*>(A2l + op * AST2 + dc) = lo;
+            h16x2 hi, lo;
+            hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
+            lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
+            *reinterpret_cast<h16x2*>(A2h + op * AST2 + dc) = hi;
+            *reinterpret_cast<h16x2*>(A2l + op * AST2 + dc) = lo;
         }
     }
     {
         const int padn = AST2 - bf;                         // K tail of both planes: zero
-        for (int i = t; i < NO * padn; i += 256) { const int r = i / padn, c2 = bf + i - r * padn; A2h[r * AST2 + c2] = (uch16)0.0f; A2l[r * AST2 + c2] = (uch16)0.0f; }
+        for (int i = t; i < NO * padn; i += 256) { const int r = i / padn, c2 = bf + i - r * padn; A2h[r * AST2 + c2] = (h16)0.0f; A2l[r * AST2 + c2] = (h16)0.0f; }
     }
     __syncthreads();
     YN_TS();
@@ -947,39 +937,35 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
     for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
     if (wave >= NP && wave < 2 * NP) {
         const int nt = wave - NP;
-        const uch16* Ahb = A3h + l31 * AST1 + h * 8;
-        const uch16* Alb = A3l + l31 * AST1 + h * 8;
-        const uch16* Bhb = B3 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const uch16* Blb = Bhb + 4 * BN * 8;
+        const h16* Ahb = A3h + l31 * AST1 + h * 8;
+        const h16* Alb = A3l + l31 * AST1 + h * 8;
+        const h16* Bhb = B3 + (size_t)(h * BN + nt * 32 + l31) * 8;
+        const h16* Blb = Bhb + 4 * BN * 8;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-            const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-            const uch16x8 bh = *reinterpret_cast<const uch16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const uch16x8 bl = *reinterpret_cast<const uch16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
+            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
+            split_mfma(ah, al, bh, bl, acc0, acc1);
         }
         const int n = nt * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            PT[((r & 3) + 8 * (r >> 2) + 4 * h) * (BN + 1) + n] = apply_act(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias3v, a.act3);
+            PT[((r & 3) + 8 * (r >> 2) + 4 * h) * (BN + 1) + n] = apply_act(split_join(acc0[r], acc1[r]) + bias3v, a.act3);
     }
     if (wave < NP) {                                        // pw2: one wavefront per 32 output columns
         const int nt = wave;
-        const uch16* Ahb = A2h + l31 * AST2 + h * 8;
-        const uch16* Alb = A2l + l31 * AST2 + h * 8;
-        const uch16* Bhb = B2 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const uch16* Blb = Bhb + 8 * BN * 8;
+        const h16* Ahb = A2h + l31 * AST2 + h * 8;
+        const h16* Alb = A2l + l31 * AST2 + h * 8;
+        const h16* Bhb = B2 + (size_t)(h * BN + nt * 32 + l31) * 8;
+        const h16* Blb = Bhb + 8 * BN * 8;
         for (int ks = 0; ks < 2 * ((KQ2 + 3) >> 2); ++ks) {                 // gemm_split_tile's chunks of 32: whole chunks, zero-padded
-            const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-            const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-            const uch16x8 bh = *reinterpret_cast<const uch16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const uch16x8 bl = *reinterpret_cast<const uch16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
+            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
+            split_mfma(ah, al, bh, bl, acc0, acc1);
         }
     }
     __syncthreads();                                        // branch 1's tile is complete
@@ -1004,7 +990,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if ((okm >> r) & 1u) {
-                    const float v = apply_act(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias, a.act2);
+                    const float v = apply_act(split_join(acc0[r], acc1[r]) + bias, a.act2);
                     *reinterpret_cast<float2*>(a.out + mrow[r] * (2 * bf) + 2 * n) = make_float2(pv[r], v);
                 }
             }
@@ -1038,12 +1024,12 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     constexpr int BN = 32 * NP, AST1 = 32 + 8, AST2 = BN + 8, NO = TW * TH, NLD = 5, KS2 = 2 * NP;
     extern __shared__ __attribute__((aligned(16))) float du_smem[];
     const int bf = a.bf, CS = bf + 2, cin = a.cin, cq = cin >> 2;
-    uch16* A1h = reinterpret_cast<uch16*>(du_smem);                  // [RT1*32][AST1] x 2: pw1's operand planes
-    uch16* A1l = A1h + RT1 * 32 * AST1;
-    uch16* A2h = A1h;                                                // behind GEMM 1: [NO][AST2] x 2 (pw2), then [NO][AST1] x 2 (branch 1)
-    uch16* A2l = A2h + NO * AST2;
-    uch16* A3h = A2l + NO * AST2;
-    uch16* A3l = A3h + NO * AST1;
+    h16* A1h = reinterpret_cast<h16*>(du_smem);                  // [RT1*32][AST1] x 2: pw1's operand planes
+    h16* A1l = A1h + RT1 * 32 * AST1;
+    h16* A2h = A1h;                                                // behind GEMM 1: [NO][AST2] x 2 (pw2), then [NO][AST1] x 2 (branch 1)
+    h16* A2l = A2h + NO * AST2;
+    h16* A3h = A2l + NO * AST2;
+    h16* A3l = A3h + NO * AST1;
     float* X32 = du_smem + RT1 * 32 * AST1;                          // [RT1*32][cin]: the window in fp32 (zero outside the image)
     float* T32 = X32 + RT1 * 32 * cin;                               // [RT1*32][CS]: y1 (zero outside the image), later branch 1's tile
     unsigned char* inside = reinterpret_cast<unsigned char*>(T32 + RT1 * 32 * CS);      // [RT1*32]
@@ -1086,16 +1072,16 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     const int nt1 = (NP == 2) ? (it0 & 1) : 0;                       // the stride 4 is even: a wavefront's column tile never changes
     const bool pw2_wave = wave < NP, b1_wave = wave >= NP && wave < 2 * NP;
     const int nt2 = pw2_wave ? wave : wave - NP;
-    auto frag = [&](const void* Wh_, const void* Wl_, int ks, int KQ, int n, bool use, uch16x8& bh, uch16x8& bl) {
+    auto frag = [&](const void* Wh_, const void* Wl_, int ks, int KQ, int n, bool use, h16x8& bh, h16x8& bl) {
         const int kq = ks * 2 + h;
         const bool ok = use && kq < KQ;
         const size_t off = ((size_t)(ok ? kq : 0) * BN + (ok ? n : 0)) * 8;      // Npad1 = Npad2 = Npad3 = BN (down_unit_covers)
         const unsigned mk = opaque_mask(ok);
-        uint4 vh = *reinterpret_cast<const uint4*>(reinterpret_cast<const uch16*>(Wh_) + off), vl = *reinterpret_cast<const uint4*>(reinterpret_cast<const uch16*>(Wl_) + off);
+        uint4 vh = *reinterpret_cast<const uint4*>(reinterpret_cast<const h16*>(Wh_) + off), vl = *reinterpret_cast<const uint4*>(reinterpret_cast<const h16*>(Wl_) + off);
         vh.x &= mk; vh.y &= mk; vh.z &= mk; vh.w &= mk; vl.x &= mk; vl.y &= mk; vl.z &= mk; vl.w &= mk;
-        bh = *reinterpret_cast<uch16x8*>(&vh); bl = *reinterpret_cast<uch16x8*>(&vl);
+        bh = *reinterpret_cast<h16x8*>(&vh); bl = *reinterpret_cast<h16x8*>(&vl);
     };
-    uch16x8 g1h[2], g1l[2], g2h[KS2], g2l[KS2];
+    h16x8 g1h[2], g1l[2], g2h[KS2], g2l[KS2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) frag(a.W1h, a.W1l, ks, KQ1, nt1 * 32 + l31, true, g1h[ks], g1l[ks]);
 #pragma unroll
@@ -1137,7 +1123,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     };
     request(tbase + tl);
     if (t < RT1 * 32 - NPIX) inside[NPIX + t] = 0;                   // pad rows of the last row tile: never inside
-    float amax = 0.0f;                                               // range guard (yn_device.h): largest |value| this thread has split
+    float amax = 0.0f;                                               // range guard (yn_split.h): largest |value| this thread has split
     float* PT = T32;                                                 // [32][BN + 1]: branch 1's output tile
 
     // ---- 1. the window: fp32 copy + split planes; K tail of the planes (run for the NEXT tile in front of the current tile's stores: the wait
@@ -1151,11 +1137,11 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                 const float4 v = vmask(pre[i], 0u - ((pok >> i) & 1u));
                 *reinterpret_cast<float4*>(X32 + p * cin + c4) = v;
                 const float x4[4] = {v.x, v.y, v.z, v.w};
-                uch16x4 hi, lo;
+                h16x4 hi, lo;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (uch16)x4[j]; lo[j] = (uch16)((x4[j] - (float)hi[j]) * 2048.0f); }
-                *reinterpret_cast<uch16x4*>(A1h + p * AST1 + c4) = hi;
-                *reinterpret_cast<uch16x4*>(A1l + p * AST1 + c4) = lo;
+                for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+                *reinterpret_cast<h16x4*>(A1h + p * AST1 + c4) = hi;
+                *reinterpret_cast<h16x4*>(A1l + p * AST1 + c4) = lo;
                 if (c4 == 0) inside[p] = (unsigned char)((pok >> i) & 1u);
             }
         }
@@ -1185,25 +1171,23 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
             f32x16 acc0, acc1;
 #pragma unroll
             for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-            const uch16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
-            const uch16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
+            const h16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
+            const h16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
             int inw[4];                                              // inside flags of this lane's 16 rows: four bytes per word
 #pragma unroll
             for (int g = 0; g < 4; ++g) inw[g] = *reinterpret_cast<const int*>(inside + rt * 32 + 8 * g + 4 * h);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g1h[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g1l[ks], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, g1h[ks], acc1, 0, 0, 0);
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+                split_mfma(ah, al, &g1h[ks], &g1l[ks], acc0, acc1);
             }
             const int n = nt1 * 32 + l31;
             if (n < bf) {
                 float* trow = T32 + (rt * 32 + 4 * h) * CS + n;      // row (r & 3) + 8 (r >> 2) of this lane's half: a wave-uniform offset
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float v = act_pw(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias1, a.act1);
+                    const float v = act_pw(split_join(acc0[r], acc1[r]) + bias1, a.act1);
                     trow[((r & 3) + 8 * (r >> 2)) * CS] = __uint_as_float(__float_as_uint(v) & (unsigned)__builtin_amdgcn_sbfe(inw[r >> 2], 8 * (r & 3), 1));
                 }
             }
@@ -1224,11 +1208,11 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                     for (int k = 0; k < 9; ++k) vfma(acc, *reinterpret_cast<const float2*>(xw + ((k / 3) * WW + k % 3) * cin), w1d[k]);
                     if (!RELU) acc = vact(acc, a.dw1_act);
                     amax = range_track(range_track(amax, acc.x), acc.y);
-                    uch16x2 hi, lo;
-                    hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
-                    lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
-                    *reinterpret_cast<uch16x2*>(A3h + op * AST1 + c1) = hi;
-                    *reinterpret_cast<uch16x2*>(A3l + op * AST1 + c1) = lo;
+                    h16x2 hi, lo;
+                    hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
+                    lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
+                    *reinterpret_cast<h16x2*>(A3h + op * AST1 + c1) = hi;
+                    *reinterpret_cast<h16x2*>(A3l + op * AST1 + c1) = lo;
                 }
             }
         }
@@ -1252,11 +1236,11 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                         vfma(acc, *reinterpret_cast<const float2*>(yw + (ky * WW + kx) * CS), wd[ky * 3 + kx]);
                 if (!RELU) acc = vact(acc, a.dw_act);
                 amax = range_track(range_track(amax, acc.x), acc.y);
-                uch16x2 hi, lo;
-                hi[0] = (uch16)acc.x; hi[1] = (uch16)acc.y;
-                lo[0] = (uch16)((acc.x - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((acc.y - (float)hi[1]) * 2048.0f);
-                *reinterpret_cast<uch16x2*>(A2h + op * AST2 + dc) = hi;
-                *reinterpret_cast<uch16x2*>(A2l + op * AST2 + dc) = lo;
+                h16x2 hi, lo;
+                hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
+                lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
+                *reinterpret_cast<h16x2*>(A2h + op * AST2 + dc) = hi;
+                *reinterpret_cast<h16x2*>(A2l + op * AST2 + dc) = lo;
             }
         }
         {
@@ -1275,31 +1259,27 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
         if (b1_wave) {
-            const uch16* Ahb = A3h + l31 * AST1 + h * 8;
-            const uch16* Alb = A3l + l31 * AST1 + h * 8;
+            const h16* Ahb = A3h + l31 * AST1 + h * 8;
+            const h16* Alb = A3l + l31 * AST1 + h * 8;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g2h[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g2l[ks], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, g2h[ks], acc1, 0, 0, 0);
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+                split_mfma(ah, al, &g2h[ks], &g2l[ks], acc0, acc1);
             }
             float* prow = PT + (4 * h) * (BN + 1) + nt2 * 32 + l31;
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                prow[((r & 3) + 8 * (r >> 2)) * (BN + 1)] = act_pw(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias23, a.act3);
+                prow[((r & 3) + 8 * (r >> 2)) * (BN + 1)] = act_pw(split_join(acc0[r], acc1[r]) + bias23, a.act3);
         }
         if (pw2_wave) {                                              // pw2: one wavefront per 32 output columns, gemm_split_tile's chunks of 32 (whole chunks, zero-padded)
-            const uch16* Ahb = A2h + l31 * AST2 + h * 8;
-            const uch16* Alb = A2l + l31 * AST2 + h * 8;
+            const h16* Ahb = A2h + l31 * AST2 + h * 8;
+            const h16* Alb = A2l + l31 * AST2 + h * 8;
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks) {
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g2h[ks], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, g2l[ks], acc1, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, g2h[ks], acc1, 0, 0, 0);
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+                split_mfma(ah, al, &g2h[ks], &g2l[ks], acc0, acc1);
             }
         }
         __syncthreads();                                             // branch 1's tile is complete; nobody reads the planes, the fp32 window or the flags any more
@@ -1320,7 +1300,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                 const int dy = r >> 2, dxu = r & 3;
                 if (oy0 + dy < Ho) {
                     if (n < bf && ox0 + dxu + 4 * h < Wo) {
-                        const float v = act_pw(__builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]) + bias23, a.act2);
+                        const float v = act_pw(split_join(acc0[r], acc1[r]) + bias23, a.act2);
                         *reinterpret_cast<float2*>(obase + (lane_off + (unsigned)((dy * Wo + dxu) * 2 * bf) * 4u)) = make_float2(pv[r], v);
                     }
                 }
@@ -1416,10 +1396,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
     const int KQ2 = (bf + 7) >> 3, KQ1 = (cin + 7) >> 3, PS2 = plane_stride(bf), PS1 = plane_stride(cin);
     const int S2 = (KQ2 + 1) >> 1, S1 = (KQ1 + 1) >> 1, S = S2 + S1;    // 16-deep k-steps of pw2, of branch 1's pointwise conv
     const bool chain = a.W1nh != nullptr;                               // + the next unit's pw1 (K = bf: S2 steps more, after the store)
-    uch16* A2h = reinterpret_cast<uch16*>(d2_smem);                     // [BM][PS2]
-    uch16* A2l = A2h + BM * PS2;
-    uch16* A1h = A2l + BM * PS2;                                        // [BM][PS1]
-    uch16* A1l = A1h + BM * PS1;
+    h16* A2h = reinterpret_cast<h16*>(d2_smem);                     // [BM][PS2]
+    h16* A2l = A2h + BM * PS2;
+    h16* A1h = A2l + BM * PS2;                                        // [BM][PS1]
+    h16* A1l = A1h + BM * PS1;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1, HWo = Ho * Wo, Mo = a.B * HWo;
@@ -1444,13 +1424,13 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
     // stood inside every unrolled step, D copies of the store epilogue: a 50-100 KB loop body the instruction cache could not hold - a k-step
     // cost ~900 cycles for 192 cycles of MFMAs even with six workgroups on an idle chip).  A padded step multiplies the zero K tail: exact zeros.
     const int G2 = (S2 + D - 1) / D * D, G1 = (S1 + D - 1) / D * D;
-    uch16x8 bq[D][NT][2];
-    auto load_b = [&](int s, uch16x8 (&dst)[NT][2]) {          // s: padded step
+    h16x8 bq[D][NT][2];
+    auto load_b = [&](int s, h16x8 (&dst)[NT][2]) {          // s: padded step
         const bool second = s >= G2, third = s >= G2 + G1;
         const int ks = third ? s - (G2 + G1) : (second ? s - G2 : s), KQ = (second && !third) ? KQ1 : KQ2;
         // (without a next unit the steps >= S are masked loads at a clamped address: the base must still be a real pointer)
-        const uch16* Wh = reinterpret_cast<const uch16*>((third && chain) ? a.W1nh : ((second && !third) ? a.W3h : a.W2h));
-        const uch16* Wl = reinterpret_cast<const uch16*>((third && chain) ? a.W1nl : ((second && !third) ? a.W3l : a.W2l));
+        const h16* Wh = reinterpret_cast<const h16*>((third && chain) ? a.W1nh : ((second && !third) ? a.W3h : a.W2h));
+        const h16* Wl = reinterpret_cast<const h16*>((third && chain) ? a.W1nl : ((second && !third) ? a.W3l : a.W2l));
         // no masks (unit_chain2_kernel's load_b: a masked load is waited for where it is issued - the walk then paid a memory round trip per
         // k-step): clamped octet / column, and the steps past the walk take their A fragment from the planes' zero K tail
         const int kq = min(ks * 2 + h, KQ - 1);
@@ -1458,15 +1438,15 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
         for (int nt = 0; nt < NT; ++nt) {
             const int n = min((wave * NT + nt) * 32 + l31, a.Npad - 1);
             const size_t off = ((size_t)kq * a.Npad + n) * 8;
-            dst[nt][0] = *reinterpret_cast<const uch16x8*>(Wh + off);
-            dst[nt][1] = *reinterpret_cast<const uch16x8*>(Wl + off);
+            dst[nt][0] = *reinterpret_cast<const h16x8*>(Wh + off);
+            dst[nt][1] = *reinterpret_cast<const h16x8*>(Wl + off);
         }
     };
 #pragma unroll
     for (int j = 0; j < D; ++j) load_b(j, bq[j]);                        // requested first: they return before the window loads below
     // ---- 1. both depthwise convs (stride 2, dwconv3x3_kernel's fma chain) -> the split planes of their branch ---------------------------
-    float amax = 0.0f;                                                   // range guard (yn_device.h)
-    auto dw_branch = [&](const float* __restrict__ src, int C, const float* __restrict__ wd, const float* __restrict__ bd, int act, uch16* Ph, uch16* Pl, int PS) {
+    float amax = 0.0f;                                                   // range guard (yn_split.h)
+    auto dw_branch = [&](const float* __restrict__ src, int C, const float* __restrict__ wd, const float* __restrict__ bd, int act, h16* Ph, h16* Pl, int PS) {
         const int cqn = C >> 2, ppl = 256 / cqn;
         const int cq = t % cqn, pl = t / cqn, c = cq * 4;
         if (pl < ppl) {
@@ -1504,22 +1484,22 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
                         for (int k = 0; k < 9; ++k) vfma(acc, win[u][k], w[k]);
                         acc = vact(acc, act);
                         const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
-                        uch16x4 hi, lo;
+                        h16x4 hi, lo;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (uch16)x4[j]; lo[j] = (uch16)((x4[j] - (float)hi[j]) * 2048.0f); }
-                        *reinterpret_cast<uch16x4*>(Ph + r * PS + c) = hi;
-                        *reinterpret_cast<uch16x4*>(Pl + r * PS + c) = lo;
+                        for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+                        *reinterpret_cast<h16x4*>(Ph + r * PS + c) = hi;
+                        *reinterpret_cast<h16x4*>(Pl + r * PS + c) = lo;
                     }
                 }
             }
         }
         // K tail [C, PS) of every row and the idle rows [nrows, BM): zeros (they meet zero weight rows / are never stored, but must not be NaN bit patterns)
         const int padn = PS - C;
-        for (int i = t; i < BM * padn; i += 256) { const int r = i / padn, c2 = C + i - r * padn; Ph[r * PS + c2] = (uch16)0.0f; Pl[r * PS + c2] = (uch16)0.0f; }
+        for (int i = t; i < BM * padn; i += 256) { const int r = i / padn, c2 = C + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
         for (int i = t; i < (BM - nrows) * (C >> 2); i += 256) {
             const int r = nrows + i / (C >> 2), c2 = (i % (C >> 2)) * 4;
-            uch16x4 z; z[0] = z[1] = z[2] = z[3] = (uch16)0.0f;
-            *reinterpret_cast<uch16x4*>(Ph + r * PS + c2) = z; *reinterpret_cast<uch16x4*>(Pl + r * PS + c2) = z;
+            h16x4 z; z[0] = z[1] = z[2] = z[3] = (h16)0.0f;
+            *reinterpret_cast<h16x4*>(Ph + r * PS + c2) = z; *reinterpret_cast<h16x4*>(Pl + r * PS + c2) = z;
         }
     };
     dw_branch(a.y1, bf, a.wdw, a.bdw, a.dw_act, A2h, A2l, PS2);
@@ -1561,36 +1541,34 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float z = apply_act(__builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]) + bias3[nt], a.act3);
+                    const float z = apply_act(split_join(acc0[nt][r], acc1[nt][r]) + bias3[nt], a.act3);
                     if (row < nrows) *reinterpret_cast<float2*>(out_base + (unsigned)(row * 2 * bf + 2 * n) * 4u) = make_float2(z, y3[nt][r]);
                     if (to_plane) {                                     // (idle rows carry finite values of zero operands: never stored)
                         const float v0 = z, v1 = y3[nt][r];
-                        uch16x2 hi, lo;
+                        h16x2 hi, lo;
                         amax = range_track(range_track(amax, v0), v1);
-                        hi[0] = (uch16)v0; hi[1] = (uch16)v1;
-                        lo[0] = (uch16)((v0 - (float)hi[0]) * 2048.0f); lo[1] = (uch16)((v1 - (float)hi[1]) * 2048.0f);
-                        *reinterpret_cast<uch16x2*>(A2h + row * PS2 + 2 * (n - jhi)) = hi;
-                        *reinterpret_cast<uch16x2*>(A2l + row * PS2 + 2 * (n - jhi)) = lo;
+                        hi[0] = (h16)v0; hi[1] = (h16)v1;
+                        lo[0] = split_lo(v0, hi[0]); lo[1] = split_lo(v1, hi[1]);
+                        *reinterpret_cast<h16x2*>(A2h + row * PS2 + 2 * (n - jhi)) = hi;
+                        *reinterpret_cast<h16x2*>(A2l + row * PS2 + 2 * (n - jhi)) = lo;
                     }
                 }
             }
         }
     };
-    auto run_gemm = [&](const uch16* Ah_, const uch16* Al_, int PS, int Sn, int p0, int p1) {     // padded steps [p0, p1) of one GEMM (Sn real k-steps)
-        const uch16* ahp = Ah_ + l31 * PS + h * 8;
-        const uch16* alp = Al_ + l31 * PS + h * 8;
+    auto run_gemm = [&](const h16* Ah_, const h16* Al_, int PS, int Sn, int p0, int p1) {     // padded steps [p0, p1) of one GEMM (Sn real k-steps)
+        const h16* ahp = Ah_ + l31 * PS + h * 8;
+        const h16* alp = Al_ + l31 * PS + h * 8;
         for (int s0 = p0; s0 < p1; s0 += D) {
 #pragma unroll
             for (int j = 0; j < D; ++j) {
                 const int ks = s0 + j - p0;
                 const int a_col = ks < Sn ? ks * 16 : PS - 8 - h * 8;  // padded step: the last 16 bytes of the row's zero K tail
-                const uch16x8 ah = *reinterpret_cast<const uch16x8*>(ahp + a_col);
-                const uch16x8 al = *reinterpret_cast<const uch16x8*>(alp + a_col);
+                const h16x8 ah = *reinterpret_cast<const h16x8*>(ahp + a_col);
+                const h16x8 al = *reinterpret_cast<const h16x8*>(alp + a_col);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bq[j][nt][0], acc0[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bq[j][nt][1], acc1[nt], 0, 0, 0);
-                    acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bq[j][nt][0], acc1[nt], 0, 0, 0);
+                    split_mfma(ah, al, bq[j][nt][0], bq[j][nt][1], acc0[nt], acc1[nt]);
                 }
                 load_b(s0 + j + D, bq[j]);                              // (clamped beyond the walk)
             }
@@ -1601,7 +1579,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            y3[nt][r] = apply_act(__builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]) + bias2[nt], a.act2);
+            y3[nt][r] = apply_act(split_join(acc0[nt][r], acc1[nt][r]) + bias2[nt], a.act2);
             acc0[nt][r] = 0.0f; acc1[nt][r] = 0.0f;
         }
     run_gemm(A1h, A1l, PS1, S1, G2, G2 + G1);                           // branch 1's pointwise conv
@@ -1622,9 +1600,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 1) void down2_kernel(Down2Args a
     } else {
         // the next unit's pw1 -> t1n (gemm_split_kernel's epilogue: 16-byte stores through the in-quad transpose)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[nt][r] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]);
+        for (int nt = 0; nt < NT; ++nt) split_join(acc0[nt], acc1[nt]);
         GemmArgs e{};
         e.out = a.t1n; e.out_ld = bf; e.out_off = 0; e.M = m0 + nrows; e.N = bf; e.Npad = a.Npad; e.bias = a.b1n; e.act = a.act1n; e.pass = nullptr;
         gemm_epilogue<NT>(e, acc0, m0, wave * NT * 32, true, lane, bias1n);
@@ -1674,12 +1650,12 @@ void launch_down2(const Down2Args& a, hipStream_t s)
 // gemm_split_kernel.  LDS 50 KB: three workgroups per CU.
 // -------------------------------------------------------------------------------------------------
 template <int TH>                                           // tile height: 8 x TH pixels per workgroup, TH / 4 runs per thread
-__device__ __forceinline__ void dwpw_block(const DwPwArgs& a, uch16* smem, unsigned bid, unsigned nblocks)
+__device__ __forceinline__ void dwpw_block(const DwPwArgs& a, h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int TW = 8, NO = TW * TH, C = 96, KQ = C / 8, BN = 96, AST = C + 8, R = 4, NR = TH / 4;
-    uch16* Ah = smem;                                       // [NO][AST]
-    uch16* Al = Ah + NO * AST;
-    uch16* Bs = Al + NO * AST;                              // [2][KQ][BN][8]
+    h16* Ah = smem;                                       // [NO][AST]
+    h16* Al = Ah + NO * AST;
+    h16* Bs = Al + NO * AST;                              // [2][KQ][BN][8]
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH;
     const int tile = (int)xcd_block(bid, nblocks);
@@ -1714,22 +1690,22 @@ __device__ __forceinline__ void dwpw_block(const DwPwArgs& a, uch16* smem, unsig
         bd = *reinterpret_cast<const float4*>(a.bdw + c);
     }
     constexpr int B_PER = (2 * KQ * BN + 255) / 256;        // 9 granules of 16 bytes per thread
-    uch16x8 b_reg[B_PER];
+    h16x8 b_reg[B_PER];
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
         const int g = t + 256 * i;                          // plane, octet, column
         const int pl = g / (KQ * BN), r = g - pl * (KQ * BN);
         const int o = r / BN, n = r - o * BN;
-        uch16x8 v;
+        h16x8 v;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (uch16)0.0f;
-        if (g < 2 * KQ * BN) v = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(pl ? a.Wl : a.Wh) + ((size_t)o * a.Npad + n) * 8);
+        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
+        if (g < 2 * KQ * BN) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.Wl : a.Wh) + ((size_t)o * a.Npad + n) * 8);
         b_reg[i] = v;
     }
     const float gbias = (wave < 3) ? a.bias[wave * 32 + l31] : 0.0f;
 
     // ---- 2. depthwise (dwconv3x3_kernel's chain) -> split planes; weights -> LDS -------------------------------------------------------
-    float amax = 0.0f;                                      // range guard (yn_device.h)
+    float amax = 0.0f;                                      // range guard (yn_split.h)
     if (worker) {
 #pragma unroll
         for (int i = 0; i < NR; ++i)
@@ -1743,18 +1719,18 @@ __device__ __forceinline__ void dwpw_block(const DwPwArgs& a, uch16* smem, unsig
             acc = vact(acc, a.dw_act);
             const int op = (ry + 4 * i) * TW + rx + o;
             const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
-            uch16x4 hi, lo;
+            h16x4 hi, lo;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (uch16)x4[j]; lo[j] = (uch16)((x4[j] - (float)hi[j]) * 2048.0f); }
-            *reinterpret_cast<uch16x4*>(Ah + op * AST + c) = hi;
-            *reinterpret_cast<uch16x4*>(Al + op * AST + c) = lo;
+            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+            *reinterpret_cast<h16x4*>(Ah + op * AST + c) = hi;
+            *reinterpret_cast<h16x4*>(Al + op * AST + c) = lo;
         }
         range_report(a.ovf, amax);
     }
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
         const int g = t + 256 * i;
-        if (g < 2 * KQ * BN) *reinterpret_cast<uch16x8*>(Bs + (size_t)g * 8) = b_reg[i];
+        if (g < 2 * KQ * BN) *reinterpret_cast<h16x8*>(Bs + (size_t)g * 8) = b_reg[i];
     }
     __syncthreads();
 
@@ -1765,28 +1741,26 @@ __device__ __forceinline__ void dwpw_block(const DwPwArgs& a, uch16* smem, unsig
         f32x16 acc0, acc1;
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const uch16* Ahb = Ah + (rt * 32 + l31) * AST + h * 8;
-        const uch16* Alb = Al + (rt * 32 + l31) * AST + h * 8;
-        const uch16* Bhb = Bs + (size_t)(h * BN + wave * 32 + l31) * 8;
-        const uch16* Blb = Bhb + (size_t)KQ * BN * 8;
+        const h16* Ahb = Ah + (rt * 32 + l31) * AST + h * 8;
+        const h16* Alb = Al + (rt * 32 + l31) * AST + h * 8;
+        const h16* Bhb = Bs + (size_t)(h * BN + wave * 32 + l31) * 8;
+        const h16* Blb = Bhb + (size_t)KQ * BN * 8;
 #pragma unroll
         for (int ks = 0; ks < KQ / 2; ++ks) {
-            const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-            const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-            const uch16x8 bh = *reinterpret_cast<const uch16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const uch16x8 bl = *reinterpret_cast<const uch16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
+            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
+            split_mfma(ah, al, bh, bl, acc0, acc1);
         }
         const int j = lane & 3;
         const int nq = wave * 32 + (l31 & ~3);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            float v0 = apply_act(__builtin_fmaf(acc1[4 * g + 0], 1.0f / 2048.0f, acc0[4 * g + 0]) + gbias, a.act);
-            float v1 = apply_act(__builtin_fmaf(acc1[4 * g + 1], 1.0f / 2048.0f, acc0[4 * g + 1]) + gbias, a.act);
-            float v2 = apply_act(__builtin_fmaf(acc1[4 * g + 2], 1.0f / 2048.0f, acc0[4 * g + 2]) + gbias, a.act);
-            float v3 = apply_act(__builtin_fmaf(acc1[4 * g + 3], 1.0f / 2048.0f, acc0[4 * g + 3]) + gbias, a.act);
+            float v0 = apply_act(split_join(acc0[4 * g + 0], acc1[4 * g + 0]) + gbias, a.act);
+            float v1 = apply_act(split_join(acc0[4 * g + 1], acc1[4 * g + 1]) + gbias, a.act);
+            float v2 = apply_act(split_join(acc0[4 * g + 2], acc1[4 * g + 2]) + gbias, a.act);
+            float v3 = apply_act(split_join(acc0[4 * g + 3], acc1[4 * g + 3]) + gbias, a.act);
             {   // 2x2 blocks, then 4x4: lane j of the quad ends up with row j x 4 columns (gemm_epilogue's transpose)
                 const float s0 = (j & 1) ? v0 : v1, s1 = (j & 1) ? v2 : v3;
                 const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
@@ -1812,7 +1786,7 @@ __global__ __launch_bounds__(256, (TH == 4 ? 3 : 2)) void dwpw_group_kernel(Grou
     extern __shared__ __attribute__((aligned(16))) float dwpw_smem[];
     unsigned local, nb;
     const int p = group_problem(g.first, blockIdx.x, local, nb);
-    dwpw_block<TH>(g.a[p], reinterpret_cast<uch16*>(dwpw_smem), local, nb);
+    dwpw_block<TH>(g.a[p], reinterpret_cast<h16*>(dwpw_smem), local, nb);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1822,11 +1796,11 @@ __global__ __launch_bounds__(256, (TH == 4 ? 3 : 2)) void dwpw_group_kernel(Grou
 // depthwise windows right behind the barrier that ends the depthwise phase - the round trip runs under the GEMM and the stores.  Same
 // arithmetic in the same order: bit-identical (test_dwpw_fused_is_bit_identical).
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, unsigned bid, unsigned nblocks)
+__device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int TW = 8, TH = 4, NO = TW * TH, C = 96, KQ = C / 8, KS = KQ / 2, AST = C + 8, R = 4;
-    uch16* Ah = smem;                                       // [NO][AST]
-    uch16* Al = Ah + NO * AST;
+    h16* Ah = smem;                                       // [NO][AST]
+    h16* Al = Ah + NO * AST;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
     const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH, per_img = tx_n * ty_n;
     const int tiles = a.B * per_img;
@@ -1842,12 +1816,12 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, 
 #pragma unroll
     for (int k = 0; k < 9; ++k) wd[k] = *reinterpret_cast<const float4*>(a.wdw + k * C + c);
     const float4 bd = *reinterpret_cast<const float4*>(a.bdw + c);
-    uch16x8 gh[KS], gl[KS];
+    h16x8 gh[KS], gl[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         const size_t off = ((size_t)(ks * 2 + h) * a.Npad + wave * 32 + l31) * 8;
-        gh[ks] = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(a.Wh) + off);
-        gl[ks] = *reinterpret_cast<const uch16x8*>(reinterpret_cast<const uch16*>(a.Wl) + off);
+        gh[ks] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(a.Wh) + off);
+        gl[ks] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(a.Wl) + off);
     }
     const float gbias = a.bias[wave * 32 + l31];
     float4 win[3][R + 2];
@@ -1872,7 +1846,7 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, 
         }
     };
     request(tbase + tl);
-    float amax = 0.0f;                                      // range guard (yn_device.h)
+    float amax = 0.0f;                                      // range guard (yn_split.h)
     const int j4 = lane & 3;
     const int nq = wave * 32 + (l31 & ~3);
 
@@ -1895,11 +1869,11 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, 
             acc = vact(acc, a.dw_act);
             const int op = ry * TW + rx + o;
             const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
-            uch16x4 hi, lo;
+            h16x4 hi, lo;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (uch16)x4[j]; lo[j] = (uch16)((x4[j] - (float)hi[j]) * 2048.0f); }
-            *reinterpret_cast<uch16x4*>(Ah + op * AST + c) = hi;
-            *reinterpret_cast<uch16x4*>(Al + op * AST + c) = lo;
+            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+            *reinterpret_cast<h16x4*>(Ah + op * AST + c) = hi;
+            *reinterpret_cast<h16x4*>(Al + op * AST + c) = lo;
         }
         __syncthreads();
         const bool more = tl + GL < TL && tbase + tl + GL < tiles;
@@ -1909,15 +1883,13 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, 
         f32x16 acc0, acc1;
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const uch16* Ahb = Ah + l31 * AST + h * 8;
-        const uch16* Alb = Al + l31 * AST + h * 8;
+        const h16* Ahb = Ah + l31 * AST + h * 8;
+        const h16* Alb = Al + l31 * AST + h * 8;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const uch16x8 ah = *reinterpret_cast<const uch16x8*>(Ahb + ks * 16);
-            const uch16x8 al = *reinterpret_cast<const uch16x8*>(Alb + ks * 16);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gh[ks], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, gl[ks], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, gh[ks], acc1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            split_mfma(ah, al, gh[ks], gl[ks], acc0, acc1);
         }
         // tile pixel of accumulator group g, lane (h, j4): row g, column 4 h + j4 - a wave-uniform row offset + one lane offset, 32-bit
         char* obase = reinterpret_cast<char*>(a.out);
@@ -1925,10 +1897,10 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, uch16* smem, 
         const bool xin = ox0 + 4 * h + j4 < a.W;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            float v0 = apply_act(__builtin_fmaf(acc1[4 * g + 0], 1.0f / 2048.0f, acc0[4 * g + 0]) + gbias, a.act);
-            float v1 = apply_act(__builtin_fmaf(acc1[4 * g + 1], 1.0f / 2048.0f, acc0[4 * g + 1]) + gbias, a.act);
-            float v2 = apply_act(__builtin_fmaf(acc1[4 * g + 2], 1.0f / 2048.0f, acc0[4 * g + 2]) + gbias, a.act);
-            float v3 = apply_act(__builtin_fmaf(acc1[4 * g + 3], 1.0f / 2048.0f, acc0[4 * g + 3]) + gbias, a.act);
+            float v0 = apply_act(split_join(acc0[4 * g + 0], acc1[4 * g + 0]) + gbias, a.act);
+            float v1 = apply_act(split_join(acc0[4 * g + 1], acc1[4 * g + 1]) + gbias, a.act);
+            float v2 = apply_act(split_join(acc0[4 * g + 2], acc1[4 * g + 2]) + gbias, a.act);
+            float v3 = apply_act(split_join(acc0[4 * g + 3], acc1[4 * g + 3]) + gbias, a.act);
             {   // 2x2 blocks, then 4x4: lane j of the quad ends up with row j x 4 columns (gemm_epilogue's transpose)
                 const float s0 = (j4 & 1) ? v0 : v1, s1 = (j4 & 1) ? v2 : v3;
                 const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
@@ -1954,7 +1926,7 @@ __global__ __launch_bounds__(192, 2) void dwpw_pipe_group_kernel(Group<DwPwArgs>
     extern __shared__ __attribute__((aligned(16))) float dwpw_smem[];
     unsigned local, nb;
     const int p = group_problem(g.first, blockIdx.x, local, nb);
-    dwpw_pipe_block(g.a[p], reinterpret_cast<uch16*>(dwpw_smem), local, nb);
+    dwpw_pipe_block(g.a[p], reinterpret_cast<h16*>(dwpw_smem), local, nb);
 }
 
 bool dwpw_group_ok(const DwPwArgs* a, int n)

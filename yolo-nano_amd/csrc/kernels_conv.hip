@@ -744,10 +744,10 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
     extern __shared__ __attribute__((aligned(16))) float c3s_smem[];
     const int W = a.W, H = a.H, HW = H * W;
     const int npix = BM + 2 * W + 2;
-    c3h16* Hh = reinterpret_cast<c3h16*>(c3s_smem);                                   // [npix][CSH]
-    c3h16* Hl = Hh + (size_t)npix * CSH;
-    c3h16* Bh = Hl + (size_t)npix * CSH;                                              // TPS x { [KQ][BN][8] hi, then lo }
-    c3h16* Bl = Bh + WCH;
+    h16* Hh = reinterpret_cast<h16*>(c3s_smem);                                   // [npix][CSH]
+    h16* Hl = Hh + (size_t)npix * CSH;
+    h16* Bh = Hl + (size_t)npix * CSH;                                              // TPS x { [KQ][BN][8] hi, then lo }
+    h16* Bl = Bh + WCH;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l31 = lane & 31, h = lane >> 5;
@@ -755,8 +755,8 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
     if (p0 >= a.M) return;
     const int n0 = blockIdx.y * BN;
     const int base = p0 - W - 1;
-    const c3h16* Wsh = reinterpret_cast<const c3h16*>(a.Wsh);
-    const c3h16* Wsl = reinterpret_cast<const c3h16*>(a.Wsl);
+    const h16* Wsh = reinterpret_cast<const h16*>(a.Wsh);
+    const h16* Wsl = reinterpret_cast<const h16*>(a.Wsl);
 
 #ifdef YN_EXP_TIMING
     long long TS[8]; int tsn = 0;
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
 #define YN_TS()
 #endif
     YN_TS();
-    c3h16x8 b_reg[TPS][B_PER];
+    h16x8 b_reg[TPS][B_PER];
     auto prefetch_b = [&](int step) {                                                 // step = (half * 9 + first tap) / TPS
         const int half = (step * TPS) / 9, tap0 = step * TPS - half * 9;
 #pragma unroll
@@ -775,10 +775,10 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
                 const int g = t + 256 * i;                                            // granule: plane (hi / lo), octet o, column n
                 const int pl = g / (KQ * BN), r = g - pl * (KQ * BN);
                 const int o = r / BN, n = r - o * BN;
-                c3h16x8 v;
+                h16x8 v;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (c3h16)0.0f;
-                if (g < 2 * KQ * BN) v = *reinterpret_cast<const c3h16x8*>((pl ? Wsl : Wsh) + (((size_t)(tap0 + tt) * KQT + half * KQ + o) * a.Npad + n0 + n) * 8);
+                for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
+                if (g < 2 * KQ * BN) v = *reinterpret_cast<const h16x8*>((pl ? Wsl : Wsh) + (((size_t)(tap0 + tt) * KQT + half * KQ + o) * a.Npad + n0 + n) * 8);
                 b_reg[tt][i] = v;
             }
     };
@@ -788,7 +788,7 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
 #pragma unroll
             for (int i = 0; i < B_PER; ++i) {
                 const int g = t + 256 * i;
-                if (g < 2 * KQ * BN) *reinterpret_cast<c3h16x8*>(Bh + (size_t)tt * 2 * WCH + (size_t)g * 8) = b_reg[tt][i];      // Bl follows Bh: plane 1 lands there
+                if (g < 2 * KQ * BN) *reinterpret_cast<h16x8*>(Bh + (size_t)tt * 2 * WCH + (size_t)g * 8) = b_reg[tt][i];      // Bl follows Bh: plane 1 lands there
             }
     };
     prefetch_b(0);
@@ -797,7 +797,7 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
     //      smooth_1: W = 52, one block per CU): halo 19 k cycles, nine taps 31.7 k (486 MFMAs = 15.5 k), epilogue 9 k per 128-pixel tile.
     //      The halo phase is BANDWIDTH-bound, not latency-bound: 180 KB per tile (halo factor 1.83 at W = 52 + the up2 source) at the
     //      ~10 B/clk/CU every CU gets when all of them stream at once; 24 loads in flight per thread instead of 8 changed nothing ----
-    float amax = 0.0f;                                                                // range guard (yn_device.h): largest |value| this thread has split
+    float amax = 0.0f;                                                                // range guard (yn_split.h): largest |value| this thread has split
     auto load_halo = [&](int half) {
         constexpr int U = 8, CQ = HC / 4, PPL = 256 / CQ;
         const int cq = t % CQ, pl = t / CQ;
@@ -828,11 +828,11 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
                     const int i = i0 + u * PPL;
                     if (i < npix) {
                         const float x4[4] = {v[u].x + u2[u].x, v[u].y + u2[u].y, v[u].z + u2[u].z, v[u].w + u2[u].w};
-                        c3h16x4 hi, lo;
+                        h16x4 hi, lo;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (c3h16)x4[j]; lo[j] = (c3h16)((x4[j] - (float)hi[j]) * 2048.0f); }
-                        *reinterpret_cast<c3h16x4*>(Hh + (size_t)i * CSH + 4 * cq) = hi;
-                        *reinterpret_cast<c3h16x4*>(Hl + (size_t)i * CSH + 4 * cq) = lo;
+                        for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+                        *reinterpret_cast<h16x4*>(Hh + (size_t)i * CSH + 4 * cq) = hi;
+                        *reinterpret_cast<h16x4*>(Hl + (size_t)i * CSH + 4 * cq) = lo;
                     }
                 }
             }
@@ -871,23 +871,21 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
         const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
         const bool ok = (tapmask >> tap) & 1u;
         const size_t arow = (size_t)(W + 1 + r + dy * W + dx) * CSH + h * 8 + (NH == 1 ? ((step * TPS) / 9) * CH : 0);
-        const c3h16* Bhb = Bh + (size_t)tt * 2 * WCH + (size_t)(h * BN + l31) * 8;
-        const c3h16* Blb = Bl + (size_t)tt * 2 * WCH + (size_t)(h * BN + l31) * 8;
+        const h16* Bhb = Bh + (size_t)tt * 2 * WCH + (size_t)(h * BN + l31) * 8;
+        const h16* Blb = Bl + (size_t)tt * 2 * WCH + (size_t)(h * BN + l31) * 8;
 #pragma unroll
         for (int ks = 0; ks < KQ / 2; ++ks) {
-            c3h16x8 ah = *reinterpret_cast<const c3h16x8*>(Hh + arow + ks * 16);
-            c3h16x8 al = *reinterpret_cast<const c3h16x8*>(Hl + arow + ks * 16);
+            h16x8 ah = *reinterpret_cast<const h16x8*>(Hh + arow + ks * 16);
+            h16x8 al = *reinterpret_cast<const h16x8*>(Hl + arow + ks * 16);
             if (!ok) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { ah[j] = (c3h16)0.0f; al[j] = (c3h16)0.0f; }
+                for (int j = 0; j < 8; ++j) { ah[j] = (h16)0.0f; al[j] = (h16)0.0f; }
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                const c3h16x8 bh = *reinterpret_cast<const c3h16x8*>(Bhb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                const c3h16x8 bl = *reinterpret_cast<const c3h16x8*>(Blb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[nt], 0, 0, 0);
+                const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN + nt * 32) * 8);
+                const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN + nt * 32) * 8);
+                split_mfma(ah, al, bh, bl, acc0[nt], acc1[nt]);
             }
         }
         }
@@ -912,7 +910,7 @@ __global__ __launch_bounds__(256, NH) void conv3x3_split_kernel(GemmArgs a)
         for (int g = 0; g < 4; ++g) {
             float vv[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) vv[e] = apply_act(__builtin_fmaf(acc1[nt][4 * g + e], 1.0f / 2048.0f, acc0[nt][4 * g + e]) + bias, a.act);
+            for (int e = 0; e < 4; ++e) vv[e] = apply_act(split_join(acc0[nt][4 * g + e], acc1[nt][4 * g + e]) + bias, a.act);
             float v0 = vv[0], v1 = vv[1], v2 = vv[2], v3 = vv[3];
             {
                 const float s0 = (j & 1) ? v0 : v1, s1 = (j & 1) ? v2 : v3;
@@ -961,7 +959,7 @@ static size_t conv3x3_halo_lds(int W, int Cin, int NT)
 // to the f32-MFMA family, which rounds once per product-add; against float64 the split form is the more accurate of the two).
 // -------------------------------------------------------------------------------------------------
 template <int WM, int WN, int NT, int KC>
-__device__ __forceinline__ void gemm_split_block(const GemmArgs& a, c3h16* smem, unsigned bid, unsigned nblocks)
+__device__ __forceinline__ void gemm_split_block(const GemmArgs& a, h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int BM = 32 * WM, BN = 32 * NT * WN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -980,14 +978,14 @@ __device__ __forceinline__ void gemm_split_block(const GemmArgs& a, c3h16* smem,
 template <int WM, int WN, int NT, int KC>
 __global__ __launch_bounds__(256) void gemm_split_kernel(GemmArgs a)
 {
-    __shared__ __attribute__((aligned(16))) c3h16 smem[gemm_split_smem_halves(32 * WM, 32 * NT * WN, KC)];
+    __shared__ __attribute__((aligned(16))) h16 smem[gemm_split_smem_halves(32 * WM, 32 * NT * WN, KC)];
     gemm_split_block<WM, WN, NT, KC>(a, smem, blockIdx.x, gridDim.x);
 }
 
 template <int WM, int WN, int NT, int KC>
 __global__ __launch_bounds__(256) void gemm_split_group_kernel(Group<GemmArgs> g)
 {
-    __shared__ __attribute__((aligned(16))) c3h16 smem[gemm_split_smem_halves(32 * WM, 32 * NT * WN, KC)];
+    __shared__ __attribute__((aligned(16))) h16 smem[gemm_split_smem_halves(32 * WM, 32 * NT * WN, KC)];
     unsigned local, nb;
     const int p = group_problem(g.first, blockIdx.x, local, nb);
     gemm_split_block<WM, WN, NT, KC>(g.a[p], smem, local, nb);
@@ -1678,7 +1676,7 @@ __global__ void fold_pack_kernel(FoldArgs a)
         a.w_packed[((size_t)(k >> 1) * a.Npad + co) * 2 + (k & 1)] = v;
         if (a.ws_hi) {                          // the same weight as an exact-to-2^-22 pair of halves: v = hi + lo * 2^-11
             if (a.w_ovf && !(fabsf(v) < 65504.0f)) atomicOr(a.w_ovf, 1u);      // does not fit the split (or is not finite): the caller drops to the f32-MFMA family
-            const _Float16 hi = (_Float16)v, lo = (_Float16)((v - (float)hi) * 2048.0f);
+            const _Float16 hi = (_Float16)v, lo = split_lo(v, hi);
             const size_t o = (((size_t)tap * ((a.Cin + 7) >> 3) + (ci >> 3)) * a.Npad + co) * 8 + (ci & 7);
             reinterpret_cast<_Float16*>(a.ws_hi)[o] = hi;
             reinterpret_cast<_Float16*>(a.ws_lo)[o] = lo;

@@ -19,16 +19,12 @@
 // Every sum runs in the order of the separate kernels (same fma chain per depthwise output, same 16-deep k-steps per accumulator):
 // bit-identical to unit_chain2_kernel and to the three-kernel path (tests/test_gpu_parity.py::test_unit_chain_bit_identical_...).
 #include "yn_internal.h"
-#include "yn_device.h"
+#include "yn_unit_tile.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace ynk {
-
-typedef _Float16 ph16;
-typedef _Float16 ph16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ph16x4 __attribute__((ext_vector_type(4)));
 
 // BF = branch width, compile-time: with run-time strides (bf, the plane stride, out_ld) every unrolled LDS / global access of the
 // epilogues needs its own address register, and the optimiser hoists ~80 of them out of the tile loop - into the registers the weights
@@ -61,13 +57,14 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
     constexpr bool last = LAST;
     constexpr int out_ld = LAST ? 2 * BF : BF;
     const unsigned win_bytes = (unsigned)(BM + 2 * W + 2) * ROWB;
-    const unsigned win_lds = (win_bytes + 8u + 15u) & ~15u;             // + the lead-in, in whole pieces
+    const unsigned win_lds = (win_bytes + 8u + 15u) & ~15u;             // + the lead-in, in whole pieces = pipe_window_lds(BF, W, BM, 8) in 32 bits (the 64-bit form compiles to other code)
     unsigned char* win = up_smem;                                       // fp32 window image: flat pixels [m0 - W - 1, m0 + BM + W + 1) x bf, from byte `sh`
     float* x1s = reinterpret_cast<float*>(up_smem + win_lds);           // pass-through rows [BM][X1S]
-    ph16* Ph = reinterpret_cast<ph16*>(up_smem + win_lds + (unsigned)BM * X1S * 4u);   // operand planes [BM][PS]
-    ph16* Pl = Ph + BM * PS;
+    h16* Ph = reinterpret_cast<h16*>(up_smem + win_lds + (unsigned)BM * X1S * 4u);   // operand planes [BM][PS]
+    h16* Pl = Ph + BM * PS;
     int* mtab = reinterpret_cast<int*>(Pl + BM * PS);                   // [BM] nine tap-valid bits per tile row
     float* taps = reinterpret_cast<float*>(mtab + BM);                  // depthwise weights [9][bf] + bias [bf] (registers are for the GEMM weights)
+    static_assert((size_t)BM * X1S * 4 + (size_t)2 * BM * PS * 2 + BM * 4 + 10 * BF * 4 == unit_pipe_lds_fixed(BF, BM), "the launcher's LDS size (yn_stage_form.h) ends where taps ends");
     const unsigned lds_win = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)up_smem;
     const unsigned lds_x1 = lds_win + win_lds;
 
@@ -82,24 +79,9 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
     int tile = (int)(blockIdx.x & 7u) * TX + (int)(blockIdx.x >> 3);
     if (tile >= tend) return;
 
-    // Address arithmetic of the DMA pieces: recomputed per tile from an OPAQUE copy of the thread index - as loop invariants the optimiser
-    // hoists one register per piece (14 of them) out of the tile loop and spills them around the GEMMs, and a scratch reload is a vector-memory
-    // load: its s_waitcnt vmcnt(0) retires the DMA pieces in flight
-    const int t1_lim = ((a.M * (int)ROWB + 15) & ~15) - 16;             // last piece that holds a byte of t1 (M * bf * 8 < 2^32 is a launch condition)
-    auto win_lead = [&](int tl) { return ROWB % 16u == 0 ? 0 : (((tl * BM - W - 1) * (int)ROWB) & 15); };        // 0, or 8 for channel pairs and an odd first pixel
-    auto issue_window = [&](int tl) {
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-        const int g0 = (tl * BM - W - 1) * (int)ROWB;                   // first byte of the window (negative / past the end at the tensor's ends:
-        const int sh = ROWB % 16u == 0 ? 0 : (g0 & 15);                 //  clamped - those pixels' taps are masked)
-        const int gs = g0 - sh + tt * 16;
-        const int nch = (int)((win_bytes + (unsigned)sh + 15u) >> 4);
-        for (int c0 = 0; c0 < nch; c0 += NTHR) {
-            int src = gs + c0 * 16;
-            src = src < 0 ? 0 : (src > t1_lim ? t1_lim : src);
-            if (c0 + tt < nch) dma16(a.t1, (unsigned)src, lds_win + (unsigned)(c0 + wave * 64) * 16u);
-        }
-    };
+    const int t1_lim = window_t1_lim<BF>(a.M);
+    auto win_lead = [&](int tl) { return window_lead<BF>(tl * BM, W); };       // 0, or 8 for channel pairs and an odd first pixel
+    auto issue_window = [&](int tl) { issue_window_pieces<BF, NTHR, false>(a.t1, t1_lim, tl * BM, W, win_bytes, lds_win, t, wave); };
     auto issue_x1 = [&](int tl) {
         int tt = t;
         asm volatile("" : "+v"(tt));
@@ -132,23 +114,18 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
         tapv[q] = *reinterpret_cast<const float2*>((k < 9 ? a.wdw + k * bf : a.bdw) + 2 * c2);
     }
     // ---- loop invariants: both GEMMs' B fragments of this wavefront's columns ----
-    ph16x8 bw2[SMAX][NT][2], bw1[STREAM ? 1 : SMAX][NT][2];
-    // No masks on the fragment loads (a masked load is USED - waited for - where it is issued): the octet past the matrix (the last half k-step
-    // of an odd octet count) and the columns past Npad read the nearest valid ones instead.  Finite weights against the planes' zero K tail add
-    // exact zeros; accumulator columns >= bf are never stored.
-    auto load_step = [&](const void* Wh_, const void* Wl_, int s, ph16x8 (&dst)[NT][2]) {   // the fragments of k-step s
+    h16x8 bw2[SMAX][NT][2], bw1[STREAM ? 1 : SMAX][NT][2];
+    auto load_step = [&](const void* Wh_, const void* Wl_, int s, h16x8 (&dst)[NT][2]) {   // the fragments of k-step s (no masks: frag_off)
         const char* Wh = reinterpret_cast<const char*>(Wh_);
         const char* Wl = reinterpret_cast<const char*>(Wl_);
-        const int kq = s * 2 + h < KQ ? s * 2 + h : KQ - 1;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const int n = wn * NT * 32 + nt * 32 + l31;
-            const unsigned off = ((unsigned)kq * (unsigned)a.Npad + (unsigned)(n < a.Npad ? n : a.Npad - 1)) * 16u;
-            dst[nt][0] = *reinterpret_cast<const ph16x8*>(Wh + off);
-            dst[nt][1] = *reinterpret_cast<const ph16x8*>(Wl + off);
+            const unsigned off = frag_off<KQ>(s, h, wn * NT * 32 + nt * 32 + l31, a.Npad);
+            dst[nt][0] = *reinterpret_cast<const h16x8*>(Wh + off);
+            dst[nt][1] = *reinterpret_cast<const h16x8*>(Wl + off);
         }
     };
-    auto load_w = [&](const void* Wh, const void* Wl, ph16x8 (&dst)[SMAX][NT][2]) {
+    auto load_w = [&](const void* Wh, const void* Wl, h16x8 (&dst)[SMAX][NT][2]) {
 #pragma unroll
         for (int s = 0; s < SMAX; ++s) load_step(Wh, Wl, s, dst[s]);
     };
@@ -181,9 +158,9 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
     // K tail of both planes: zero once (nothing below writes columns >= bf)
     {
         const int padn = PS - bf;
-        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = bf + i - r * padn; Ph[r * PS + c2] = (ph16)0.0f; Pl[r * PS + c2] = (ph16)0.0f; }
+        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = bf + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
     }
-    float amax = 0.0f;                                                  // range guard (yn_device.h)
+    float amax = 0.0f;                                                  // range guard (yn_split.h)
     const int jhi = bf >> 1;
     f32x16 acc0[NT], acc1[NT];
 
@@ -192,7 +169,7 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
     // refill != null (STREAM): k-step s of that matrix replaces the fragments the MFMAs of step s have just read
     const unsigned lane_w = ((unsigned)h * (WN * 32u) + (unsigned)wn * 32u + (unsigned)l31) * 16u;      // byte offset of this lane's fragment inside a k-step of a pack
     // which: 0 = no refill, 1 = refill with the next pointwise conv's matrix, 2 = with pw2 (for the next tile); do_refill: wave-uniform
-    auto gemm = [&](ph16x8 (&bw)[SMAX][NT][2], auto which, bool refill) {
+    auto gemm = [&](h16x8 (&bw)[SMAX][NT][2], auto which, bool refill) {
         const char* refill_h = reinterpret_cast<const char*>(decltype(which)::value == 1 ? a.Ws1h : a.Ws2h);
         const char* refill_l = reinterpret_cast<const char*>(decltype(which)::value == 1 ? a.Ws1l : a.Ws2l);
         unsigned lw = lane_w;                                           // (opaque per call: as loop invariants the per-step addresses are hoisted out of the tile loop)
@@ -201,35 +178,22 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
         for (int i = 0; i < NT; ++i)
 #pragma unroll
             for (int k = 0; k < 16; ++k) { acc0[i][k] = 0.0f; acc1[i][k] = 0.0f; }
-        const ph16* ahp = Ph + (wm * 32 + l31) * PS + h * 8;
-        const ph16* alp = Pl + (wm * 32 + l31) * PS + h * 8;
+        const h16* ahp = Ph + (wm * 32 + l31) * PS + h * 8;
+        const h16* alp = Pl + (wm * 32 + l31) * PS + h * 8;
 #pragma unroll
         for (int s = 0; s < SMAX; ++s) {
-            const ph16x8 ah = *reinterpret_cast<const ph16x8*>(ahp + s * 16);
-            const ph16x8 al = *reinterpret_cast<const ph16x8*>(alp + s * 16);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][nt][0], acc0[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][nt][1], acc1[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bw[s][nt][0], acc1[nt], 0, 0, 0);
-            }
+            for (int nt = 0; nt < NT; ++nt) panel_step(ahp, alp, s, bw[s][nt][0], bw[s][nt][1], acc0[nt], acc1[nt]);      // (NT = 1)
             if constexpr (STREAM && decltype(which)::value != 0) {
-                // No mask on this path (a masked load needs a temporary per load in flight: 120 registers), and ONE lane offset for all k-steps
-                // (wave-uniform base + s * 8 KB: per-step 64-bit lane addresses are 60 loop-invariant registers - hoisted, spilled and reloaded
-                // through vmcnt(0) in the first form).  The one octet past the matrix (the last half k-step of an odd octet count) reads the last
-                // valid octet instead: finite weights against the planes' zero K tail.
-                if (refill) {
-                    const unsigned kq = (s * 2 + 1 < KQ) ? (unsigned)(s * 2 + h) : (unsigned)(s * 2 + h < KQ ? s * 2 + h : KQ - 1);
-                    const unsigned off = (s * 2 + 1 < KQ) ? lw + (unsigned)s * (2u * WN * 32u * 16u) : lw - (unsigned)h * (WN * 32u * 16u) + kq * (WN * 32u * 16u);
-                    bw[s][0][0] = *reinterpret_cast<const ph16x8*>(refill_h + off);
-                    bw[s][0][1] = *reinterpret_cast<const ph16x8*>(refill_l + off);
+                if (refill) {                                           // (no mask, ONE lane offset for all k-steps: frag_step_off)
+                    const unsigned off = frag_step_off<KQ, WN * 32u>(lw, s, h);
+                    bw[s][0][0] = *reinterpret_cast<const h16x8*>(refill_h + off);
+                    bw[s][0][1] = *reinterpret_cast<const h16x8*>(refill_l + off);
                 }
             }
         }
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[nt][r] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]);
+        for (int nt = 0; nt < NT; ++nt) split_join(acc0[nt], acc1[nt]);
     };
     // STREAM: hipcc is TOLD where the streamed panel has landed (an empty asm that reads and writes its 30 fragment registers: its own wait for the
     // refill loads goes HERE - behind the hand-placed drain - instead of in front of the next tile's first GEMM's
@@ -242,38 +206,14 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
 #undef YN_P2
         }
     };
-    auto split2 = [&](int r, int c, float v0, float v1) {               // two adjacent channels of row r -> both planes
-        amax = range_track(range_track(amax, v0), v1);
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        h2 hi, lo;
-        hi[0] = (ph16)v0; hi[1] = (ph16)v1;
-        lo[0] = (ph16)((v0 - (float)hi[0]) * 2048.0f); lo[1] = (ph16)((v1 - (float)hi[1]) * 2048.0f);
-        *reinterpret_cast<h2*>(Ph + r * PS + c) = hi;
-        *reinterpret_cast<h2*>(Pl + r * PS + c) = lo;
-    };
+    auto split2 = [&](int r, int c, float v0, float v1) { ynk::split2<PS>(Ph, Pl, r, c, v0, v1, amax); };
 
     // tap-valid bits of a tile's rows (zero padding of the 3 x 3 window; idle rows: nothing valid) -> mtab; written one tile ahead, behind the
     // barrier that ends the depthwise phase (the only reader)
     auto write_mtab = [&](int tl) {
         int tq = threadIdx.x;                                           // (opaque: as a loop invariant the mtab address is one more register held across the GEMMs -
         asm volatile("" : "+v"(tq));                                    //  the eight-wavefront form of width 116 spilled it, and a scratch reload's vmcnt(0) retires the DMA pieces in flight)
-        if (tq < BM) {
-            const int t = tq;
-            const int m0 = tl * BM;
-            const int rem0 = m0 % HW;                                   // wave-uniform
-            const int y0 = rem0 / W, x0 = rem0 - y0 * W;
-            const int q = x0 + t;
-            const int dy = (int)(((float)q + 0.5f) * inv_w);            // q / W (exact: q < 2^16)
-            const int x = q - dy * W;
-            const int yy = y0 + dy;
-            const int y = yy - (int)(((float)yy + 0.5f) * inv_h) * H;   // rows past the image's last one continue in the next image
-            const int yb = (y >= 1 ? 1 : 0) | 2 | (y + 1 < H ? 4 : 0), xb = (x >= 1 ? 1 : 0) | 2 | (x + 1 < W ? 4 : 0);
-            int bits = 0;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-                if ((yb >> ky) & 1) bits |= xb << (3 * ky);
-            mtab[t] = m0 + t < a.M ? bits : 0;
-        }
+        write_tap_bits<BM>(mtab, tl * BM, tq, a.M, H, W, HW, inv_w, inv_h);
     };
     write_mtab(tile);
 #ifdef YN_EXP_TIMING
@@ -339,20 +279,16 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
                 float o[VEC];
                 if constexpr (VEC == 4) { o[0] = acc[i].x; o[1] = acc[i].y; o[2] = acc[i].z; o[3] = acc[i].w; }
                 else { o[0] = acc[i].x; o[1] = acc[i].y; }
-                typedef _Float16 hv __attribute__((ext_vector_type(VEC)));
-                hv hi, lo;
+                typename H16Vec<VEC>::type hi, lo;
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
-                    // the fp32 value is the result: without this the optimiser folds the last fma and the conversion below into v_fma_mixlo_f16 -
-                    // ONE rounding, straight to f16 - and a value that lies exactly between two f16 neighbours once the fma has been rounded to fp32
-                    // gets the other hi (hi + lo * 2^-11 is the same number either way; bit-identity with the other kernels is not: 1 pixel of 200)
-                    asm volatile("" : "+v"(o[j]));
+                    asm volatile("" : "+v"(o[j]));                       // the fp32 value is the result (no v_fma_mixlo_f16: yn_split.h)
                     amax = range_track(amax, o[j]);
-                    hi[j] = (ph16)o[j];
-                    lo[j] = (ph16)((o[j] - (float)hi[j]) * 2048.0f);
+                    hi[j] = (h16)o[j];
+                    lo[j] = split_lo(o[j], hi[j]);
                 }
-                *reinterpret_cast<hv*>(Ph + (r0 + i) * PS + VEC * cq) = hi;
-                *reinterpret_cast<hv*>(Pl + (r0 + i) * PS + VEC * cq) = lo;
+                *reinterpret_cast<typename H16Vec<VEC>::type*>(Ph + (r0 + i) * PS + VEC * cq) = hi;
+                *reinterpret_cast<typename H16Vec<VEC>::type*>(Pl + (r0 + i) * PS + VEC * cq) = lo;
             }
         }
         YN_TS();
@@ -446,12 +382,6 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
 #endif
 }
 
-static size_t unit_pipe_lds(int bf, int W, int BM)
-{
-    const size_t win = (((size_t)(BM + 2 * W + 2) * bf * 4 + 8 + 15) & ~(size_t)15), x1row = (((size_t)bf * 4 + 15) / 16) * 16;
-    return win + (size_t)BM * x1row + (size_t)2 * BM * plane_stride(bf) * 2 + (size_t)BM * 4 + (size_t)10 * bf * 4;
-}
-
 // The persistent form of a stride-1 unit where it applies: split-f16 family, an instantiated branch width, ReLU pointwise / linear depthwise
 // convs, dense depthwise input, whole row groups of eight, a workgroup small enough for two per CU, 32-bit byte offsets, enough tiles to
 // walk.  false = not launched (the caller runs unit_chain2_kernel).
@@ -530,9 +460,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
     static_assert(KK % 2 == 0 && S <= (NW * OCC == 16 ? 8 : 15) && NPAD <= 32 * NW && WM >= 1, "register-resident B fragments");
     extern __shared__ __attribute__((aligned(16))) unsigned char pp_smem[];
     float* raw = reinterpret_cast<float*>(pp_smem);                     // [BM][X1S] fp32 input rows
-    ph16* Ph = reinterpret_cast<ph16*>(pp_smem + (unsigned)BM * X1S * 4u);      // operand planes [BM][PS]
-    ph16* Pl = Ph + BM * PS;
+    h16* Ph = reinterpret_cast<h16*>(pp_smem + (unsigned)BM * X1S * 4u);      // operand planes [BM][PS]
+    h16* Pl = Ph + BM * PS;
     const unsigned lds_raw = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)pp_smem;
+    static_assert((size_t)BM * X1S * 4 + (size_t)2 * BM * PS * 2 == pw_pipe_lds(KK, BM), "the launcher's LDS size (yn_stage_form.h) ends where the planes end");
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
     const int wm = wave % WM, wn = wave / WM;
@@ -557,22 +488,21 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
         }
     };
     issue_rows(tile);
-    ph16x8 bw[S][2];
+    h16x8 bw[S][2];
     {
         const int n = wn * 32 + l31;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const int kq = s * 2 + h < KQ ? s * 2 + h : KQ - 1;        // (no masks: unit_pipe_kernel's load_step)
-            const unsigned off = ((unsigned)kq * (unsigned)a.Npad + (unsigned)(n < a.Npad ? n : a.Npad - 1)) * 16u;
-            bw[s][0] = *reinterpret_cast<const ph16x8*>(reinterpret_cast<const char*>(a.Wsh) + off);
-            bw[s][1] = *reinterpret_cast<const ph16x8*>(reinterpret_cast<const char*>(a.Wsl) + off);
+            const unsigned off = frag_off<KQ>(s, h, n, a.Npad);          // (no masks)
+            bw[s][0] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(a.Wsh) + off);
+            bw[s][1] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(a.Wsl) + off);
         }
     }
     float bias1[1];
     { const int n = wn * 32 + l31; bias1[0] = n < a.N ? a.bias[n] : 0.0f; }
     {
         constexpr int padn = PS - KK;
-        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = KK + i - r * padn; Ph[r * PS + c2] = (ph16)0.0f; Pl[r * PS + c2] = (ph16)0.0f; }
+        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = KK + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
     }
     float amax = 0.0f;
     const bool vecO = ((a.N | a.out_ld | a.out_off) & 3) == 0;
@@ -592,12 +522,11 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
                     const vec v = *reinterpret_cast<const vec*>(raw + r * X1S + VEC * cq);
                     float o[VEC];
                     if constexpr (VEC == 4) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; } else { o[0] = v.x; o[1] = v.y; }
-                    typedef _Float16 hv __attribute__((ext_vector_type(VEC)));
-                    hv hi, lo;
+                    typename H16Vec<VEC>::type hi, lo;
 #pragma unroll
-                    for (int j = 0; j < VEC; ++j) { amax = range_track(amax, o[j]); hi[j] = (ph16)o[j]; lo[j] = (ph16)((o[j] - (float)hi[j]) * 2048.0f); }
-                    *reinterpret_cast<hv*>(Ph + r * PS + VEC * cq) = hi;
-                    *reinterpret_cast<hv*>(Pl + r * PS + VEC * cq) = lo;
+                    for (int j = 0; j < VEC; ++j) { amax = range_track(amax, o[j]); hi[j] = (h16)o[j]; lo[j] = split_lo(o[j], hi[j]); }
+                    *reinterpret_cast<typename H16Vec<VEC>::type*>(Ph + r * PS + VEC * cq) = hi;
+                    *reinterpret_cast<typename H16Vec<VEC>::type*>(Pl + r * PS + VEC * cq) = lo;
                 }
             }
         }
@@ -609,19 +538,14 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
         {
             int ll = threadIdx.x & 63;
             asm volatile("" : "+v"(ll));
-            const ph16* ahp = Ph + (wm * 32 + (ll & 31)) * PS + (ll >> 5) * 8;
-            const ph16* alp = Pl + (wm * 32 + (ll & 31)) * PS + (ll >> 5) * 8;
+            const h16* ahp = Ph + (wm * 32 + (ll & 31)) * PS + (ll >> 5) * 8;
+            const h16* alp = Pl + (wm * 32 + (ll & 31)) * PS + (ll >> 5) * 8;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                const ph16x8 ah = *reinterpret_cast<const ph16x8*>(ahp + s * 16);
-                const ph16x8 al = *reinterpret_cast<const ph16x8*>(alp + s * 16);
-                acc0[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][0], acc0[0], 0, 0, 0);
-                acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][1], acc1[0], 0, 0, 0);
-                acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bw[s][0], acc1[0], 0, 0, 0);
+                panel_step(ahp, alp, s, bw[s][0], bw[s][1], acc0[0], acc1[0]);
             }
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[0][r] = __builtin_fmaf(acc1[0][r], 1.0f / 2048.0f, acc0[0][r]);
+        split_join(acc0[0], acc1[0]);
         vm_drain();         // the next tile's pieces - BEFORE this tile's stores, which need not be waited for
         gemm_epilogue_impl<1, false>(a, acc0, m0 + wm * 32, wn * 32, vecO, threadIdx.x & 63, bias1);     // (no pass-through form: its loads would make hipcc drain the memory counter - stores included - at the top of every tile)
     };
@@ -649,7 +573,7 @@ bool launch_pw_pipe(const GemmArgs& a, hipStream_t s)
     if (a.K == Kv && a.Npad == Nv) {                                                                                     \
         constexpr int BM = 32 * (NWv / (Nv <= 32 ? 1 : (Nv <= 64 ? 2 : (Nv <= 128 ? 4 : 8))));                            \
         const int tiles = (a.M + BM - 1) / BM;                                                                           \
-        const size_t lds = (size_t)BM * (((size_t)Kv * 4 + 15) / 16) * 16 + (size_t)2 * BM * plane_stride(Kv) * 2;        \
+        const size_t lds = pw_pipe_lds(Kv, BM);                                                                          \
         unsigned g = xcd_grid((unsigned)tiles);                                                                          \
         if (g > (unsigned)wg_cap) g = (unsigned)wg_cap;                                                                  \
         if (g > 256u * OCCv) g = 256u * OCCv;                                                                            \

@@ -259,7 +259,7 @@ template <int NT> struct HeadDecodeLds {
 template <int NT, int KMAX>
 __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridInfo& g, int scale, float conf_thresh,
                                                   float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls,
-                                                  c3h16* smem, unsigned bid, unsigned nblocks)
+                                                  h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int BM = 32, BN = 128 * NT, LD = BN + 4;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -332,7 +332,7 @@ template <int NT, int KMAX>
 __global__ __launch_bounds__(256) void head_decode_kernel(GemmArgs a, GridInfo g, int scale, float conf_thresh,
                                                            float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls)
 {
-    __shared__ __attribute__((aligned(16))) c3h16 smem[HeadDecodeLds<NT>::HALVES];
+    __shared__ __attribute__((aligned(16))) h16 smem[HeadDecodeLds<NT>::HALVES];
     head_decode_block<NT, KMAX>(a, g, scale, conf_thresh, boxes, scores, cls, smem, blockIdx.x, gridDim.x);
 }
 
@@ -341,7 +341,7 @@ template <int NT, int KMAX>
 __global__ __launch_bounds__(256) void head_decode_group_kernel(Group<GemmArgs> q, GridInfo g, float conf_thresh,
                                                                  float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls)
 {
-    __shared__ __attribute__((aligned(16))) c3h16 smem[HeadDecodeLds<NT>::HALVES];
+    __shared__ __attribute__((aligned(16))) h16 smem[HeadDecodeLds<NT>::HALVES];
     unsigned local, nb;
     const int p = group_problem(q.first, blockIdx.x, local, nb);
     head_decode_block<NT, KMAX>(q.a[p], g, p, conf_thresh, boxes, scores, cls, smem, local, nb);
@@ -426,12 +426,12 @@ void launch_head_decode_group(const GemmArgs* a, int n, const GridInfo& g, float
 template <int KMAX>
 __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const GridInfo& g, int scale, float conf_thresh,
                                                 float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls,
-                                                c3h16* smem, unsigned bid, unsigned nblocks)
+                                                h16* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int TW = 8, TH = 4, NO = TW * TH, C = 96, KQ = C / 8, BN1 = 96, AST = C + 8, R = 4, BN2 = 256, LD = BN2 + 4;
-    c3h16* Ah = smem;                                       // [NO][AST]
-    c3h16* Al = Ah + NO * AST;
-    c3h16* Bs = Al + NO * AST;                              // [2][KQ][BN1][8], then chunks [2][4][BN2][8], then the raw tile
+    h16* Ah = smem;                                       // [NO][AST]
+    h16* Al = Ah + NO * AST;
+    h16* Bs = Al + NO * AST;                              // [2][KQ][BN1][8], then chunks [2][4][BN2][8], then the raw tile
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
     const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH;
     const int tile = (int)(((bid & 7u) * (nblocks >> 3)) + (bid >> 3));
@@ -453,7 +453,7 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
     {
         constexpr int NP1 = 2 * KQ * BN1;                   // pieces: plane (hi / lo), octet, column
         static_assert(NP1 % 256 == 0 && (KQ * BN1) % 64 == 0, "whole wavefronts per plane");
-        const unsigned lds_bs = (unsigned)(size_t)(__attribute__((address_space(3))) c3h16*)Bs;
+        const unsigned lds_bs = (unsigned)(size_t)(__attribute__((address_space(3))) h16*)Bs;
 #pragma unroll
         for (int i = 0; i < NP1 / 256; ++i) {
             const int g0 = 256 * i + 64 * wave;             // this wavefront's first piece (wave-uniform)
@@ -492,7 +492,7 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
     }
     const float gbias = (wave < 3) ? a.bias[wave * 32 + l31] : 0.0f;
     constexpr int B2_PER = 2 * 4 * BN2 / 256;               // 8 granules per thread and chunk
-    c3h16x8 b2_reg[B2_PER];
+    h16x8 b2_reg[B2_PER];
     auto prefetch_b2 = [&](int chunk) {
 #pragma unroll
         for (int i = 0; i < B2_PER; ++i) {
@@ -501,19 +501,19 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
             const int o = r / BN2, n = r - o * BN2;
             // (no select on the loaded value: it would be a USE where the load is issued, and hipcc then waits for every load of the prefetch
             // in turn, inside the MFMA section it is meant to hide under.  A column past Npad reads column Npad - 1: never decoded.)
-            b2_reg[i] = *reinterpret_cast<const c3h16x8*>(reinterpret_cast<const c3h16*>(pl ? a.Wfl : a.Wfh) + ((size_t)(chunk * 4 + o) * a.Npad + (n < a.Npad ? n : a.Npad - 1)) * 8);
+            b2_reg[i] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.Wfl : a.Wfh) + ((size_t)(chunk * 4 + o) * a.Npad + (n < a.Npad ? n : a.Npad - 1)) * 8);
         }
     };
     auto stage_b2 = [&]() {
 #pragma unroll
-        for (int i = 0; i < B2_PER; ++i) *reinterpret_cast<c3h16x8*>(Bs + (size_t)(t + 256 * i) * 8) = b2_reg[i];
+        for (int i = 0; i < B2_PER; ++i) *reinterpret_cast<h16x8*>(Bs + (size_t)(t + 256 * i) * 8) = b2_reg[i];
     };
     float fbias[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) { const int n = wave * 64 + nt * 32 + l31; fbias[nt] = a.fbias[n < a.Npad ? n : 0]; }
 
     // ---- 2. depthwise -> split planes; W -> LDS; 96 -> 96 GEMM on three wavefronts -----------------------------------------------------
-    float amax = 0.0f;                                      // range guard (yn_device.h): largest |value| this thread has split
+    float amax = 0.0f;                                      // range guard (yn_split.h): largest |value| this thread has split
     if (worker) {
 #pragma unroll
         for (int o = 0; o < R; ++o) {
@@ -525,11 +525,11 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
             acc = vact(acc, a.dw_act);
             const int op = ry * TW + rx + o;
             const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
-            c3h16x4 hi, lo;
+            h16x4 hi, lo;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (c3h16)x4[j]; lo[j] = (c3h16)((x4[j] - (float)hi[j]) * 2048.0f); }
-            *reinterpret_cast<c3h16x4*>(Ah + op * AST + c) = hi;
-            *reinterpret_cast<c3h16x4*>(Al + op * AST + c) = lo;
+            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
+            *reinterpret_cast<h16x4*>(Ah + op * AST + c) = hi;
+            *reinterpret_cast<h16x4*>(Al + op * AST + c) = lo;
         }
     }
     vm_drain();                                             // the weight pieces (issued a depthwise phase ago)
@@ -540,19 +540,17 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
 #pragma unroll
     for (int k = 0; k < 16; ++k) { m0[k] = 0.0f; m1[k] = 0.0f; }
     if (wave < 3) {
-        const c3h16* Ahb = Ah + l31 * AST + h * 8;
-        const c3h16* Alb = Al + l31 * AST + h * 8;
-        const c3h16* Bhb = Bs + (size_t)(h * BN1 + wave * 32 + l31) * 8;
-        const c3h16* Blb = Bhb + (size_t)KQ * BN1 * 8;
+        const h16* Ahb = Ah + l31 * AST + h * 8;
+        const h16* Alb = Al + l31 * AST + h * 8;
+        const h16* Bhb = Bs + (size_t)(h * BN1 + wave * 32 + l31) * 8;
+        const h16* Blb = Bhb + (size_t)KQ * BN1 * 8;
 #pragma unroll
         for (int ks = 0; ks < KQ / 2; ++ks) {
-            const c3h16x8 ah = *reinterpret_cast<const c3h16x8*>(Ahb + ks * 16);
-            const c3h16x8 al = *reinterpret_cast<const c3h16x8*>(Alb + ks * 16);
-            const c3h16x8 bh = *reinterpret_cast<const c3h16x8*>(Bhb + (size_t)(ks * 2 * BN1) * 8);
-            const c3h16x8 bl = *reinterpret_cast<const c3h16x8*>(Blb + (size_t)(ks * 2 * BN1) * 8);
-            m0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, m0, 0, 0, 0);
-            m1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, m1, 0, 0, 0);
-            m1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, m1, 0, 0, 0);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN1) * 8);
+            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN1) * 8);
+            split_mfma(ah, al, bh, bl, m0, m1);
         }
     }
     __syncthreads();                                        // every operand read of the first GEMM is done: planes and weight space are free
@@ -564,11 +562,11 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = apply_act(__builtin_fmaf(m1[r], 1.0f / 2048.0f, m0[r]) + gbias, a.act);
+            const float v = apply_act(split_join(m0[r], m1[r]) + gbias, a.act);
             amax = range_track(amax, v);
-            const c3h16 hi = (c3h16)v;
+            const h16 hi = (h16)v;
             Ah[row * AST + n] = hi;
-            Al[row * AST + n] = (c3h16)((v - (float)hi) * 2048.0f);
+            Al[row * AST + n] = split_lo(v, hi);
         }
     }
     range_report(a.ovf, amax);                              // both split sites of this workgroup are behind it
@@ -585,21 +583,19 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
         for (int k = 0; k < 16; ++k) { acc0[nt][k] = 0.0f; acc1[nt][k] = 0.0f; }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const c3h16* Ahb = Ah + l31 * AST + ch * 32 + h * 8;
-        const c3h16* Alb = Al + l31 * AST + ch * 32 + h * 8;
-        const c3h16* Bhb = Bs + (size_t)(h * BN2 + wave * 64 + l31) * 8;
-        const c3h16* Blb = Bhb + (size_t)4 * BN2 * 8;
+        const h16* Ahb = Ah + l31 * AST + ch * 32 + h * 8;
+        const h16* Alb = Al + l31 * AST + ch * 32 + h * 8;
+        const h16* Bhb = Bs + (size_t)(h * BN2 + wave * 64 + l31) * 8;
+        const h16* Blb = Bhb + (size_t)4 * BN2 * 8;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const c3h16x8 ah = *reinterpret_cast<const c3h16x8*>(Ahb + ks * 16);
-            const c3h16x8 al = *reinterpret_cast<const c3h16x8*>(Alb + ks * 16);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                const c3h16x8 bh = *reinterpret_cast<const c3h16x8*>(Bhb + (size_t)(ks * 2 * BN2 + nt * 32) * 8);
-                const c3h16x8 bl = *reinterpret_cast<const c3h16x8*>(Blb + (size_t)(ks * 2 * BN2 + nt * 32) * 8);
-                acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[nt], 0, 0, 0);
+                const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN2 + nt * 32) * 8);
+                const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN2 + nt * 32) * 8);
+                split_mfma(ah, al, bh, bl, acc0[nt], acc1[nt]);
             }
         }
         __syncthreads();                                    // every wavefront is done with this chunk's weights (and, after the last one, with the planes)
@@ -618,7 +614,7 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
         const int n = wave * 64 + nt * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            raw[((r & 3) + 8 * (r >> 2) + 4 * h) * LD + n] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]) + fbias[nt];
+            raw[((r & 3) + 8 * (r >> 2) + 4 * h) * LD + n] = split_join(acc0[nt][r], acc1[nt][r]) + fbias[nt];
     }
     int* rowinfo = reinterpret_cast<int*>(raw + NO * LD + NO * 16);     // [32][4]: first candidate, gx, gy, inside the image
     if (t < NO) {
@@ -716,7 +712,7 @@ void head_tail_group_kernel(Group<HeadTailArgs> q, GridInfo g, float conf_thresh
     extern __shared__ __attribute__((aligned(16))) float head_tail_smem[];
     unsigned local, nb;
     const int p = group_problem(q.first, blockIdx.x, local, nb);
-    head_tail_block<KMAX>(q.a[p], g, p, conf_thresh, boxes, scores, cls, reinterpret_cast<c3h16*>(head_tail_smem), local, nb);
+    head_tail_block<KMAX>(q.a[p], g, p, conf_thresh, boxes, scores, cls, reinterpret_cast<h16*>(head_tail_smem), local, nb);
 }
 
 bool head_tail_ok(const HeadTailArgs* q, int n, const GridInfo& g)

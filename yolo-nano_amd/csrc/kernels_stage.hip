@@ -25,30 +25,20 @@
 //   * the polled words (queue heads, flags, exit count) are zero between launches: the last workgroup to leave resets them (they are zeroed
 //     once when the handle allocates them) - no memset node per launch, legal under graph replay.
 // Arithmetic: the tile body is unit_pipe_kernel's (same fma chains, same k order, same epilogues): bit-identical to the per-unit launches.
+// The pieces both kernels call are in yn_unit_tile.h; the depthwise phase, the first epilogue, the pass-through rows' DMA loop and the K-tail
+// zeroing are written out in both files, line for line the same (why: yn_unit_tile.h) - a change to one is a change to the other.
 // The LAST unit of a stage (whole shuffled rows to global, no next pw1) stays a unit_pipe_kernel launch.
 #include "yn_internal.h"
-#include "yn_device.h"
+#include "yn_unit_tile.h"
 
 #include <cstdlib>
 
 namespace ynk {
 
-typedef _Float16 sh16;
-typedef _Float16 sh16x8 __attribute__((ext_vector_type(8)));
-typedef float sf32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) unsigned gu32s;
 
 #define YN_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-// LDS-DMA piece with sc1: bypasses this CU's L1 (another workgroup's write-through rows are read from L2 / memory, never from a stale L1 line)
-__device__ __forceinline__ void dma16_sc1(const void* gbase, unsigned goff, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(goff), "s"(gbase), "s"(lds_dst)
-                 : "memory");
-}
 template <int BF, int NW, bool PUB_EARLY>
 __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
 {
@@ -61,15 +51,16 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char sp_smem[];
     const int W = a.W, H = a.H, HW = H * W, tiles = a.tiles, nunits = a.nunits;
     const unsigned win_bytes = (unsigned)(BM + 2 * W + 2) * ROWB;
-    const unsigned win_lds = (win_bytes + 15u) & ~15u;
+    const unsigned win_lds = (win_bytes + 15u) & ~15u;                  // = pipe_window_lds(BF, W, BM, 0) in 32 bits (the 64-bit form compiles to other code)
     unsigned char* win = sp_smem;                                        // fp32 window image: flat pixels [m0 - W - 1, m0 + BM + W + 1) x bf
     float* x1s = reinterpret_cast<float*>(sp_smem + win_lds);           // pass-through rows [BM][BF]
-    sh16* Ph = reinterpret_cast<sh16*>(sp_smem + win_lds + (unsigned)BM * X1S * 4u);   // operand planes [BM][PS]
-    sh16* Pl = Ph + BM * PS;
+    h16* Ph = reinterpret_cast<h16*>(sp_smem + win_lds + (unsigned)BM * X1S * 4u);   // operand planes [BM][PS]
+    h16* Pl = Ph + BM * PS;
     int* mtab = reinterpret_cast<int*>(Pl + BM * PS);                   // [BM] nine tap-valid bits per tile row
     float* taps = reinterpret_cast<float*>(mtab + BM);                  // depthwise weights [9][BF] + bias [BF] of the unit in work
     float* biasl = taps + 10 * BF;                                      // [2][2][BF]: (b2, b1n) of the unit in work / of the next item's unit
     int* ctl = reinterpret_cast<int*>(biasl + 4 * BF);                  // [0] next item, [1] its flags were up at the depthwise phase, [2] ... at the first GEMM, [3] scratch
+    static_assert((size_t)BM * X1S * 4 + (size_t)2 * BM * PS * 2 + BM * 4 + 14 * BF * 4 + 64 + 192 == stage_pipe_lds_fixed(BF, BM), "the launcher's LDS size (yn_stage_form.h) ends behind ctl (16 words) and the timing sums");
     const unsigned lds_win = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)sp_smem;
     const unsigned lds_x1 = lds_win + win_lds;
     const unsigned lds_taps = lds_x1 + (unsigned)BM * X1S * 4u + 2u * BM * PS * 2u + BM * 4u;
@@ -145,20 +136,11 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
         }
     };
 
-    // ---- DMA issue helpers (addresses from an OPAQUE copy of the thread index: unit_pipe_kernel) ----
-    const int t1_lim = ((a.M * (int)ROWB + 15) & ~15) - 16;
+    // ---- DMA issue helpers (sc1 pieces: the rows come from another workgroup of this launch; addresses from an OPAQUE copy of the thread
+    //      index: yn_unit_tile.h) ----
+    const int t1_lim = window_t1_lim<BF>(a.M);
     auto issue_window = [&](int item) {
-        const int tl = item & 0xfffff;
-        const float* t1 = a.u[item >> 20].t1;
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-        const int gs = (tl * BM - W - 1) * (int)ROWB + tt * 16;
-        const int nch = (int)((win_bytes + 15u) >> 4);
-        for (int c0 = 0; c0 < nch; c0 += NTHR) {
-            int src = gs + c0 * 16;
-            src = src < 0 ? 0 : (src > t1_lim ? t1_lim : src);
-            if (c0 + tt < nch) dma16_sc1(t1, (unsigned)src, lds_win + (unsigned)(c0 + wave * 64) * 16u);
-        }
+        issue_window_pieces<BF, NTHR, true>(a.u[item >> 20].t1, t1_lim, (item & 0xfffff) * BM, W, win_bytes, lds_win, t, wave);
     };
     auto issue_x1 = [&](int item) {
         const int tl = item & 0xfffff;
@@ -175,7 +157,7 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
             const int j = c - row * X1C;
             const int m = m0 + row < a.M ? m0 + row : a.M - 1;
             const unsigned src = (unsigned)m * x1_ld * 4u + (unsigned)j * 16u;
-            if (c < nch) dma16_sc1(x1, src, lds_x1 + (unsigned)(c0 + wave * 64) * 16u);
+            if (c < nch) dma16<true>(x1, src, lds_x1 + (unsigned)(c0 + wave * 64) * 16u);
         }
     };
     // depthwise taps + bias -> taps; (b2, b1n) -> biasl[par]: whole 16-byte pieces (BF % 4 == 0), plain loads (weights are read-only)
@@ -206,14 +188,11 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
     issue_x1(cur);
     issue_taps(cur >> 20, 0);
 
-    // ---- both GEMMs' B fragments of this wavefront's columns (unit_pipe_kernel's load_step: no masks, clamped octet / column) ----
-    sh16x8 bw2[S][2], bw1[S][2];
+    // ---- both GEMMs' B fragments of this wavefront's columns (no masks, clamped octet / column: frag_step_off) ----
+    h16x8 bw2[S][2], bw1[S][2];
     const int ncol = wn * 32 + l31;
     const unsigned lane_w = ((unsigned)h * NPAD + (unsigned)(ncol < NPAD ? ncol : NPAD - 1)) * 16u;   // byte offset of this lane's fragment inside k-step 0 of a pack
-    auto step_off = [&](unsigned lw, int s) {
-        const unsigned kq = (unsigned)(s * 2 + h < KQ ? s * 2 + h : KQ - 1);
-        return (s * 2 + 1 < KQ) ? lw + (unsigned)s * (2u * NPAD * 16u) : lw - (unsigned)h * (NPAD * 16u) + kq * (NPAD * 16u);
-    };
+    auto step_off = [&](unsigned lw, int s) { return frag_step_off<KQ, NPAD>(lw, s, h); };
     // Everything this wavefront has issued so far - ticket atomics, flag polls, the first item's DMA pieces - is OLDER than the 4 S fragment loads
     // between the two asm statements below (side-effecting asm: the loads cannot be scheduled across either), so the counted wait behind them
     // retires exactly the DMA pieces and leaves the fragments in flight under the first depthwise phase.  Explicit: nothing here relies on
@@ -223,13 +202,13 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
         const StageUnit& u = a.u[cur >> 20];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            bw2[s][0] = *reinterpret_cast<const sh16x8*>(reinterpret_cast<const char*>(u.Ws2h) + step_off(lane_w, s));
-            bw2[s][1] = *reinterpret_cast<const sh16x8*>(reinterpret_cast<const char*>(u.Ws2l) + step_off(lane_w, s));
+            bw2[s][0] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(u.Ws2h) + step_off(lane_w, s));
+            bw2[s][1] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(u.Ws2l) + step_off(lane_w, s));
         }
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            bw1[s][0] = *reinterpret_cast<const sh16x8*>(reinterpret_cast<const char*>(u.Ws1h) + step_off(lane_w, s));
-            bw1[s][1] = *reinterpret_cast<const sh16x8*>(reinterpret_cast<const char*>(u.Ws1l) + step_off(lane_w, s));
+            bw1[s][0] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(u.Ws1h) + step_off(lane_w, s));
+            bw1[s][1] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(u.Ws1l) + step_off(lane_w, s));
         }
     }
     asm volatile("; YN_STAGE_FRAG_END\n\ts_waitcnt vmcnt(%0)" ::"i"(4 * S) : "memory");
@@ -237,7 +216,7 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
     const bool worker = pl < BM / RUN;
     {   // K tail of both planes: zero once
         constexpr int padn = PS - BF;
-        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = BF + i - r * padn; Ph[r * PS + c2] = (sh16)0.0f; Pl[r * PS + c2] = (sh16)0.0f; }
+        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = BF + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
     }
     float amax = 0.0f;
     constexpr int jhi = BF >> 1;
@@ -246,7 +225,7 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
 
     // refill: k-step s of (rh, rl) replaces the fragments the MFMAs of step s have just read (wave-uniform switch)
     // refill2 (with refill): the OTHER panel `bo` (idle during this GEMM) takes k-step s of (qh, ql) at the same place
-    auto gemm = [&](sh16x8 (&bw)[S][2], const void* rh_, const void* rl_, bool refill, sh16x8 (&bo)[S][2], const void* qh_, const void* ql_) {
+    auto gemm = [&](h16x8 (&bw)[S][2], const void* rh_, const void* rl_, bool refill, h16x8 (&bo)[S][2], const void* qh_, const void* ql_) {
         const char* rh = reinterpret_cast<const char*>(rh_);
         const char* rl = reinterpret_cast<const char*>(rl_);
         const char* qh = reinterpret_cast<const char*>(qh_);
@@ -255,53 +234,23 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
         asm volatile("" : "+v"(lw));
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const sh16* ahp = Ph + (wm * 32 + l31) * PS + h * 8;
-        const sh16* alp = Pl + (wm * 32 + l31) * PS + h * 8;
+        const h16* ahp = Ph + (wm * 32 + l31) * PS + h * 8;
+        const h16* alp = Pl + (wm * 32 + l31) * PS + h * 8;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const sh16x8 ah = *reinterpret_cast<const sh16x8*>(ahp + s * 16);
-            const sh16x8 al = *reinterpret_cast<const sh16x8*>(alp + s * 16);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bw[s][1], acc1, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bw[s][0], acc1, 0, 0, 0);
+            panel_step(ahp, alp, s, bw[s][0], bw[s][1], acc0, acc1);
             if (refill) {
                 const unsigned off = step_off(lw, s);
-                bo[s][0] = *reinterpret_cast<const sh16x8*>(qh + off);
-                bo[s][1] = *reinterpret_cast<const sh16x8*>(ql + off);
-                bw[s][0] = *reinterpret_cast<const sh16x8*>(rh + off);
-                bw[s][1] = *reinterpret_cast<const sh16x8*>(rl + off);
+                bo[s][0] = *reinterpret_cast<const h16x8*>(qh + off);
+                bo[s][1] = *reinterpret_cast<const h16x8*>(ql + off);
+                bw[s][0] = *reinterpret_cast<const h16x8*>(rh + off);
+                bw[s][1] = *reinterpret_cast<const h16x8*>(rl + off);
             }
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[r] = __builtin_fmaf(acc1[r], 1.0f / 2048.0f, acc0[r]);
+        split_join(acc0, acc1);
     };
-    auto split2 = [&](int r, int c, float v0, float v1) {
-        amax = range_track(range_track(amax, v0), v1);
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        h2 hi, lo;
-        hi[0] = (sh16)v0; hi[1] = (sh16)v1;
-        lo[0] = (sh16)((v0 - (float)hi[0]) * 2048.0f); lo[1] = (sh16)((v1 - (float)hi[1]) * 2048.0f);
-        *reinterpret_cast<h2*>(Ph + r * PS + c) = hi;
-        *reinterpret_cast<h2*>(Pl + r * PS + c) = lo;
-    };
-    auto write_mtab = [&](int item) {
-        if (t < BM) {
-            const int m0 = (item & 0xfffff) * BM;
-            const int rem0 = m0 % HW;
-            const int y0 = rem0 / W, x0 = rem0 - y0 * W;
-            const int q = x0 + t;
-            const int dy = (int)(((float)q + 0.5f) * a.inv_w);
-            const int x = q - dy * W;
-            const int yy = y0 + dy;
-            const int y = yy - (int)(((float)yy + 0.5f) * a.inv_h) * H;
-            const int yb = (y >= 1 ? 1 : 0) | 2 | (y + 1 < H ? 4 : 0), xb = (x >= 1 ? 1 : 0) | 2 | (x + 1 < W ? 4 : 0);
-            int bits = 0;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-                if ((yb >> ky) & 1) bits |= xb << (3 * ky);
-            mtab[t] = m0 + t < a.M ? bits : 0;
-        }
-    };
+    auto split2 = [&](int r, int c, float v0, float v1) { ynk::split2<PS>(Ph, Pl, r, c, v0, v1, amax); };
+    auto write_mtab = [&](int item) { write_tap_bits<BM>(mtab, (item & 0xfffff) * BM, t, a.M, H, W, HW, a.inv_w, a.inv_h); };
     write_mtab(cur);
     auto publish = [&](int item) {                                       // every storing wavefront has drained and passed a barrier
         if (t == 0) __hip_atomic_store(flags + (item >> 20) * tiles + (item & 0xfffff), 1u, YN_RLX_AGENT);
@@ -364,17 +313,16 @@ __global__ __launch_bounds__(64 * NW, 2) void stage_pipe_kernel(StageArgs a)
 #pragma unroll
             for (int i = 0; i < RUN; ++i) {
                 float o[4] = {acc[i].x, acc[i].y, acc[i].z, acc[i].w};
-                typedef _Float16 hv __attribute__((ext_vector_type(4)));
-                hv hi, lo;
+                h16x4 hi, lo;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    asm volatile("" : "+v"(o[j]));                       // the fp32 value is the result (no v_fma_mixlo_f16: DESIGN 4.1)
+                    asm volatile("" : "+v"(o[j]));                       // the fp32 value is the result (no v_fma_mixlo_f16: yn_split.h)
                     amax = range_track(amax, o[j]);
-                    hi[j] = (sh16)o[j];
-                    lo[j] = (sh16)((o[j] - (float)hi[j]) * 2048.0f);
+                    hi[j] = (h16)o[j];
+                    lo[j] = split_lo(o[j], hi[j]);
                 }
-                *reinterpret_cast<hv*>(Ph + (r0 + i) * PS + 4 * cq) = hi;
-                *reinterpret_cast<hv*>(Pl + (r0 + i) * PS + 4 * cq) = lo;
+                *reinterpret_cast<h16x4*>(Ph + (r0 + i) * PS + 4 * cq) = hi;
+                *reinterpret_cast<h16x4*>(Pl + (r0 + i) * PS + 4 * cq) = lo;
             }
         }
         YN_TS(1);

@@ -1,31 +1,13 @@
-// yn_device.h — device-side helpers shared by the kernel translation units (kernels_conv.hip, kernels_chain.hip):
-// activation, the opaque-mask load idiom, the GEMM epilogue of the f32 MFMA accumulator layout, the split-f16 GEMM tile, small vector helpers.
+// yn_device.h — device-side helpers shared by the inference kernel translation units (kernels_conv / chain / pipe / stage / post .hip): activation,
+// quad exchanges, the opaque-mask load idiom, the GEMM epilogue of the f32 MFMA accumulator layout, the split-f16 pointwise GEMM tile, LDS-DMA
+// pieces and their barriers, raw-buffer stores, small vector helpers.  The split-f16 arithmetic itself is yn_split.h (included here); the
+// shared pieces of the persistent stride-1 unit kernels' tile body are yn_unit_tile.h.
 #pragma once
 #include "yn_internal.h"
 #include "yn_stage_form.h"
+#include "yn_split.h"
 
 namespace ynk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// ---- range guard of the split-f16 family ----------------------------------------------------------------------------------
-// x = hi + lo * 2^-11 takes hi = (f16)x: finite only for |x| < 65520.  Beyond that hi = +-inf, lo = -+inf, the three-MFMA sum is
-// NaN (and a ReLU epilogue turns that NaN into 0), where the reference's fp32 conv is finite.  Every kernel that splits
-// activations keeps the running max |x| of what it splits (one v_max_f32 per element, next to the five VALU ops of the split itself)
-// and raises the handle's flag once per wavefront at its end; yn_range_status() reports it and the host shim re-runs on the f32-MFMA
-// family (yn_exact_f32).  Folded WEIGHTS are checked once, at yn_fold_bn (fold_pack_kernel).  Tiny values need no guard: below the f16
-// normal range hi loses bits (or flushes to 0) but lo = (x - hi) * 2^11 still carries x exactly to 11 bits more, i.e. an absolute
-// error <= 2^-25 * 2^-11 - far below the fp32 round-off of any accumulation that also holds O(1) terms.
-#ifdef YN_EXP_NO_RANGE                                      // timing experiment only: the guard compiled out
-__device__ __forceinline__ float range_track(float amax, float) { return amax; }
-__device__ __forceinline__ void range_report(unsigned*, float) {}
-#else
-__device__ __forceinline__ float range_track(float amax, float x) { return __builtin_fmaxf(amax, __builtin_fabsf(x)); }
-__device__ __forceinline__ void range_report(unsigned* ovf, float amax)
-{
-    if (ovf && amax >= 65504.0f) atomicOr(ovf, 1u);         // +inf included; a NaN input is NaN in the reference too
-}
-#endif
 
 // Activation without control flow: with a run-time `act` an if-chain compiles to branches PER VALUE in the unrolled epilogues (three
 // per accumulator register, ~250 in one pointwise-GEMM kernel).  x > 0 ? x : (act 1: +0, act 2: 0.1 x, act 0: 1.0 x = x); NaN takes
@@ -156,32 +138,28 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
 //      32 x (32*NT) block (rows m0 + 32*wm.., columns n0 + 32*NT*wn..) BEFORE bias; the MFMA sequence per accumulator only
 //      depends on K, so every caller / tile shape gives bit-identical sums.  Ends with all waves past their last LDS read
 //      only after the caller's next __syncthreads().
-typedef _Float16 c3h16;
-typedef _Float16 c3h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 c3h16x4 __attribute__((ext_vector_type(4)));
-
 __host__ __device__ constexpr int gemm_split_smem_halves(int BM, int BN, int KC = 32) { return 2 * BM * (KC + 8) + 2 * (KC / 8) * BN * 8; }
 
 // KC = K per chunk (32, or 64: half the barrier rounds for the small-M / long-K layers; zero-padded chunks add exact zeros, same bits)
 template <int WM, int WN, int NT, int KC = 32>
-__device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, int m0, int n0, f32x16 (&acc0)[NT])
+__device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, h16* smem, int m0, int n0, f32x16 (&acc0)[NT])
 {
     constexpr int BM = 32 * WM, BN = 32 * NT * WN, AST = KC + 8, OQ = KC / 8;
     constexpr int A_PER = (BM * OQ + 255) / 256;            // (row, octet) granules per thread per chunk
     constexpr int B_PER = (2 * OQ * BN + 255) / 256;        // 16-byte granules per thread per chunk (hi and lo planes)
-    c3h16* Ah = smem;
-    c3h16* Al = smem + BM * AST;
-    c3h16* Bh = smem + 2 * BM * AST;                        // [OQ][BN][8], then the lo plane
+    h16* Ah = smem;
+    h16* Al = smem + BM * AST;
+    h16* Bh = smem + 2 * BM * AST;                        // [OQ][BN][8], then the lo plane
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int wm = wave % WM, wn = wave / WM;
     const int KQ = (a.K + 7) >> 3, nchunks = (a.K + KC - 1) / KC;
     const bool vecA = ((a.K | a.in_ld | a.in_off) & 3) == 0;
-    const c3h16* Wsh = reinterpret_cast<const c3h16*>(a.Wsh);
-    const c3h16* Wsl = reinterpret_cast<const c3h16*>(a.Wsl);
+    const h16* Wsh = reinterpret_cast<const h16*>(a.Wsh);
+    const h16* Wsl = reinterpret_cast<const h16*>(a.Wsl);
 
     float4 a_reg[A_PER][2];
-    c3h16x8 b_reg[B_PER];
+    h16x8 b_reg[B_PER];
     float amax = 0.0f;                                      // range guard: largest |activation| this thread has split
     // prefetch(): NOTHING but loads (round 5).  The round-2 form masked every loaded value where it was loaded (vmask on A, a select on B): a
     // use at the point of issue, so hipcc waited for each load in turn - vmcnt(3) ... vmcnt(0) behind every group of four - BEFORE the MFMAs
@@ -213,7 +191,7 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
             const int pl = g / (OQ * BN), r = g - pl * (OQ * BN);
             const int o = r / BN, n = r - o * BN;
             const int kq = min(c * (KC / 8) + o, KQ - 1), nn = min(n0 + n, a.Npad - 1);
-            b_reg[i] = *reinterpret_cast<const c3h16x8*>(((pl & 1) ? Wsl : Wsh) + ((size_t)kq * a.Npad + nn) * 8);
+            b_reg[i] = *reinterpret_cast<const h16x8*>(((pl & 1) ? Wsl : Wsh) + ((size_t)kq * a.Npad + nn) * 8);
         }
     };
     auto stage = [&](int c) {
@@ -225,17 +203,17 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
                 float x8[8] = {a_reg[i][0].x, a_reg[i][0].y, a_reg[i][0].z, a_reg[i][0].w, a_reg[i][1].x, a_reg[i][1].y, a_reg[i][1].z, a_reg[i][1].w};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x8[j] = (k + (vecA ? (j & 4) : (j & 6)) < a.K) ? x8[j] : 0.0f;
-                c3h16x8 hi, lo;
+                h16x8 hi, lo;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { amax = range_track(amax, x8[j]); hi[j] = (c3h16)x8[j]; lo[j] = (c3h16)((x8[j] - (float)hi[j]) * 2048.0f); }
-                *reinterpret_cast<c3h16x8*>(Ah + (g / OQ) * AST + (g % OQ) * 8) = hi;
-                *reinterpret_cast<c3h16x8*>(Al + (g / OQ) * AST + (g % OQ) * 8) = lo;
+                for (int j = 0; j < 8; ++j) { amax = range_track(amax, x8[j]); hi[j] = (h16)x8[j]; lo[j] = split_lo(x8[j], hi[j]); }
+                *reinterpret_cast<h16x8*>(Ah + (g / OQ) * AST + (g % OQ) * 8) = hi;
+                *reinterpret_cast<h16x8*>(Al + (g / OQ) * AST + (g % OQ) * 8) = lo;
             }
         }
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const int g = t + 256 * i;
-            if (g < 2 * OQ * BN) *reinterpret_cast<c3h16x8*>(Bh + (size_t)g * 8) = b_reg[i];
+            if (g < 2 * OQ * BN) *reinterpret_cast<h16x8*>(Bh + (size_t)g * 8) = b_reg[i];
         }
     };
     f32x16 acc1[NT];
@@ -249,21 +227,19 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
         if (c + 1 < nchunks) prefetch(c + 1);
-        const c3h16* Ahb = Ah + (wm * 32 + l31) * AST + h * 8;
-        const c3h16* Alb = Al + (wm * 32 + l31) * AST + h * 8;
-        const c3h16* Bhb = Bh + (size_t)(h * BN + wn * NT * 32 + l31) * 8;
-        const c3h16* Blb = Bhb + OQ * BN * 8;
+        const h16* Ahb = Ah + (wm * 32 + l31) * AST + h * 8;
+        const h16* Alb = Al + (wm * 32 + l31) * AST + h * 8;
+        const h16* Bhb = Bh + (size_t)(h * BN + wn * NT * 32 + l31) * 8;
+        const h16* Blb = Bhb + OQ * BN * 8;
 #pragma unroll
         for (int ks = 0; ks < KC / 16; ++ks) {
-            const c3h16x8 ah = *reinterpret_cast<const c3h16x8*>(Ahb + ks * 16);
-            const c3h16x8 al = *reinterpret_cast<const c3h16x8*>(Alb + ks * 16);
+            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                const c3h16x8 bh = *reinterpret_cast<const c3h16x8*>(Bhb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                const c3h16x8 bl = *reinterpret_cast<const c3h16x8*>(Blb + (size_t)(ks * 2 * BN + nt * 32) * 8);
-                acc0[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[nt], 0, 0, 0);
-                acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[nt], 0, 0, 0);
+                const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN + nt * 32) * 8);
+                const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN + nt * 32) * 8);
+                split_mfma(ah, al, bh, bl, acc0[nt], acc1[nt]);
             }
         }
         if (c + 1 < nchunks) {
@@ -273,9 +249,7 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
         }
     }
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc0[nt][r] = __builtin_fmaf(acc1[nt][r], 1.0f / 2048.0f, acc0[nt][r]);
+    for (int nt = 0; nt < NT; ++nt) split_join(acc0[nt], acc1[nt]);
     range_report(a.ovf, amax);
 }
 
@@ -284,13 +258,16 @@ __device__ __forceinline__ void gemm_split_tile(const GemmArgs& a, c3h16* smem, 
 // ---- LDS-DMA (global_load_lds_dwordx4) and the barriers that go with it (unit_pipe_kernel, head_tail_pipe_group_kernel) -----------------
 // One LDS-DMA piece: 64 lanes x 16 bytes, global (wave-uniform base + 32-bit lane offset) -> LDS (wave-uniform byte address + lane * 16).
 // Invisible to hipcc's s_waitcnt bookkeeping (cdna_hip_programming.md 5.x "What hipcc does not do"): completion is counted by hand below.
+// SC1: the piece bypasses this CU's L1 (another workgroup's write-through rows are read from L2 / memory, never from a stale L1 line: the
+// hand-off inside a launch, kernels_stage.hip)
+template <bool SC1 = false>
 __device__ __forceinline__ void dma16(const void* gbase, unsigned goff, unsigned lds_dst)
 {
     unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(goff), "s"(gbase), "s"(lds_dst)
-                 : "memory");
+#define YN_DMA16(AUX) asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" AUX "\n\ts_mov_b32 m0, %0" \
+                                   : "=&s"(keep) : "v"(goff), "s"(gbase), "s"(lds_dst) : "memory")
+    if constexpr (SC1) YN_DMA16(" sc1"); else YN_DMA16("");
+#undef YN_DMA16
 }
 // barriers that do NOT drain the vector-memory counter (a __syncthreads() may: its fence waits for this wavefront's global stores, and the
 // in-order counter then retires the DMA pieces in front of them too)
