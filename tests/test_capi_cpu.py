@@ -87,7 +87,6 @@ def test_shim_state_dict_matches_reference_keys():
 # The only environment variables the library reads at run time: test hooks and an output-neutral launch log.  Anything
 # else that could change a run's kernels or results belongs behind a C-ABI setter, where a caller states it.
 RUNTIME_ENV = {
-    "YN_DOWN_PIPE", "YN_DWPW_PIPE",                                  # one-tile-per-workgroup reference forms (tools/ab_hash.py)
     "YN_TRAIN_POISON", "YN_TRAIN_FUSE_STATS", "YN_TRAIN_FUSE_SUMS",  # training-step test hooks
     "YN_TRAIN_STEM_FUSE", "YN_LOSS_SCALE",
     "YN_LOG_LDS",                                                    # launch shapes to stderr (tools/concurrency.py)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""sha1 of the raw heads and detections of one seeded call - for A/Bs of environment switches that a process reads once (YN_DWPW_PIPE,
-YN_DOWN_PIPE, ...): run it under both settings and compare the lines.   python3 tools/ab_hash.py <S> <B> [backbone] [classes]"""
+"""sha1 of the raw heads and detections of one seeded call - for build-against-build comparisons: run it in both source trees (each
+with its own built library) and compare the lines.   python3 tools/ab_hash.py <S> <B> [backbone] [classes]"""
 import hashlib
 import os
 import sys

@@ -684,338 +684,23 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
 //     branch 1:  z1 = dw3x3_s2(x)  ->  z2 = relu(pw(z1))                                  out = shuffle(cat(z2, y3))
 // y1 is the largest tensor of the network (stage 2: 104 x 104 x 58 per image, 80 MB per 32-image step written and read back once) and the
 // launches around it cost their full duration even with four streams (profiles/r06_ablation_4stream.txt: the big-tensor regions do not overlap with
-// anything).  One workgroup = an 8 x 4 tile of OUTPUT pixels of one image: pw1 on the 17 x 9 input pixels the tile's depthwise
-// windows cover (20 % recomputed on tile borders; K = cin <= 32 is one chunk), y1 in an fp32 LDS tile (zero outside the image: the
-// depthwise conv pads its INPUT), depthwise -> split planes, pw2 (K = bf <= 64: two chunks) on wavefronts 0..NP-1 while wavefronts
-// NP..2NP-1 run branch 1's pointwise conv (its depthwise inputs come straight from global into registers at kernel start), and the
-// concat + shuffle is the store.  x is read once (x 1.2) and `out` written once: 80 MB per step instead of 360 MB in five launches.
-// Every sum runs in the order of gemm_split_kernel / dwconv3x3_kernel: bit-identical to the five launches
-// (test_down_unit_is_bit_identical).  LDS 76 KB: two workgroups per CU.  94 us of launches -> 75 us; 33.3 -> 35.2 k images/s together
-// with the branch-free activation this kernel led to (three branches per accumulator value in the first version's epilogue).
-// -------------------------------------------------------------------------------------------------
-template <int NP>                                           // Npad / 32 of both GEMMs (bf <= 32 * NP)
-__global__ __launch_bounds__(256, 2) void down_unit_kernel(DownArgs a)
-{
-    constexpr int TW = 8, TH = 4, WW = 2 * TW + 1, WH = 2 * TH + 1, NPIX = WW * WH, RT1 = (NPIX + 31) / 32;      // 17 x 9 = 153 window pixels, 5 row tiles
-    constexpr int BN = 32 * NP, AST1 = 32 + 8, AST2 = BN + 8, NO = TW * TH;
-    extern __shared__ __attribute__((aligned(16))) float du_smem[];
-    const int bf = a.bf, CS = bf + 2;
-    // region 1: A1 planes [RT1*32][AST1] x 2 + B1 [4][BN][8] x 2   (GEMM 1), later A2 planes [32][AST2] x 2 + B2 [8][BN][8] x 2 (GEMM 2)
-    h16* A1h = reinterpret_cast<h16*>(du_smem);
-    h16* A1l = A1h + RT1 * 32 * AST1;
-    h16* B1 = A1l + RT1 * 32 * AST1;                      // hi plane, then lo plane
-    constexpr int R1_HALVES_A = 2 * RT1 * 32 * AST1 + 2 * 4 * BN * 8;
-    constexpr int R1_HALVES_B = 2 * NO * AST2 + 2 * 8 * BN * 8 + 2 * NO * AST1 + 2 * 4 * BN * 8;      // A2, B2, then branch 1's A3 [32][AST1] x 2 and B3 [4][BN][8] x 2
-    constexpr int R1_HALVES = R1_HALVES_A > R1_HALVES_B ? R1_HALVES_A : R1_HALVES_B;
-    h16* A2h = reinterpret_cast<h16*>(du_smem);
-    h16* A2l = A2h + NO * AST2;
-    h16* B2 = A2l + NO * AST2;
-    h16* A3h = B2 + 2 * 8 * BN * 8;
-    h16* A3l = A3h + NO * AST1;
-    h16* B3 = A3l + NO * AST1;
-    float* T32 = du_smem + (R1_HALVES + 1) / 2;             // [RT1*32][CS] (rows >= NPIX are written as zeros, never read)
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
-    const int Ho = a.H >> 1, Wo = a.W >> 1;
-    const int tx_n = (Wo + TW - 1) / TW, ty_n = (Ho + TH - 1) / TH;
-    const int tile = (int)xcd_block(blockIdx.x, gridDim.x);
-    if (tile >= a.B * ty_n * tx_n) return;
-    const int b = tile / (ty_n * tx_n), trem = tile - b * (ty_n * tx_n);
-    const int oy0 = (trem / tx_n) * TH, ox0 = (trem % tx_n) * TW;
-    const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;         // input pixel of window position (0, 0)
-    const int KQ1 = (a.cin + 7) >> 3, KQ2 = (bf + 7) >> 3;
-    float amax = 0.0f;                                      // range guard (yn_split.h): largest |value| this thread has split
-
-#ifdef YN_EXP_TIMING
-    long long TS[8]; int tsn = 0;
-#define YN_TS() TS[tsn++] = __builtin_readcyclecounter()
-#else
-#define YN_TS()
-#endif
-    YN_TS();
-    // ---- 1. x window -> split planes; W1 -> LDS; W2, the depthwise taps and biases -> registers --------------------------------------
-    unsigned char* inside = reinterpret_cast<unsigned char*>(T32 + RT1 * 32 * CS);      // [RT1*32] window pixel lies inside the image
-    // depthwise work split: thread = (channel pair cp, pixel lane pl); its nine taps and bias stay in registers
-    const int cp_n = bf >> 1, ppl = 256 / cp_n;
-    const int cp = t % cp_n, dpl = t / cp_n, dc = cp * 2;
-    const bool dworker = dpl < ppl;
-    // biases of both GEMMs for this lane's columns: requested now, used after the MFMAs (a load inside the epilogue is a full wait)
-    float bias1[NP], bias2v = 0.0f;
-#pragma unroll
-    for (int nt = 0; nt < NP; ++nt) bias1[nt] = (nt * 32 + l31 < bf) ? a.b1[nt * 32 + l31] : 0.0f;
-    if (wave < NP && wave * 32 + l31 < bf) bias2v = a.b2[wave * 32 + l31];
-    float2 wd[9], bd = make_float2(0.0f, 0.0f);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) wd[k] = dworker ? *reinterpret_cast<const float2*>(a.wdw + k * bf + dc) : make_float2(0.0f, 0.0f);
-    if (dworker) bd = *reinterpret_cast<const float2*>(a.bdw + dc);
-    // branch 1: thread = (channel pair c1, pixel lane p1) -> its <= 2 output pixels' 3x3 stride-2 windows of x, straight from global (the
-    // lines are the ones the window load below brings in), nine taps and the bias in registers; W3 -> registers
-    const int c1_n = a.cin >> 1, p1_n = 256 / c1_n;
-    const int c1 = (t % c1_n) * 2, p1 = t / c1_n;
-    constexpr int NI1 = 2;                                  // 32 output pixels over >= 16 pixel lanes (cin <= 32)
-    float2 x1w[NI1][9], w1d[9], b1d = make_float2(0.0f, 0.0f);
-    constexpr int B3_PER = (2 * 4 * BN + 255) / 256;
-    h16x8 b3_reg[B3_PER];
-    float bias3v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) w1d[k] = *reinterpret_cast<const float2*>(a.wdw1 + k * a.cin + c1);
-    b1d = *reinterpret_cast<const float2*>(a.bdw1 + c1);
-#pragma unroll
-    for (int i = 0; i < NI1; ++i) {
-        const int op = p1 + i * p1_n;
-        const int dy = op / TW, dx = op - dy * TW;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int iy = 2 * (oy0 + dy) - 1 + k / 3, ix = 2 * (ox0 + dx) - 1 + k % 3;
-            const bool ok = op < NO && p1 < p1_n && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            x1w[i][k] = vmask(*reinterpret_cast<const float2*>(a.x + ((size_t)(b * a.H + (ok ? iy : 0)) * a.W + (ok ? ix : 0)) * a.cin + c1), opaque_mask(ok));
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < B3_PER; ++i) {
-        const int g = t + 256 * i;
-        const int pl = g / (4 * BN), r = g - pl * (4 * BN);
-        const int o = r / BN, n = r - o * BN;
-        h16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
-        if (g < 2 * 4 * BN && o < KQ1 && n < a.Npad3) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W3l : a.W3h) + ((size_t)o * a.Npad3 + n) * 8);
-        b3_reg[i] = v;
-    }
-    if (wave >= NP && wave < 2 * NP && (wave - NP) * 32 + l31 < bf) bias3v = a.b3[(wave - NP) * 32 + l31];
-    if (t < RT1 * 32) {                                     // one window pixel per thread: all of its (<= 32) input channels
-        const int p = t;
-        const int wy = p / WW, wx = p - wy * WW;
-        const int iy = iy0 + wy, ix = ix0 + wx;
-        const bool ok = p < NPIX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        inside[p] = ok ? 1 : 0;
-        const float* px = a.x + ((size_t)(b * a.H + (ok ? iy : 0)) * a.W + (ok ? ix : 0)) * a.cin;
-        float2 v[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const bool kj = 2 * j < a.cin;
-            v[j] = vmask(*reinterpret_cast<const float2*>(px + (kj ? 2 * j : 0)), opaque_mask(ok && kj));
-            amax = range_track(range_track(amax, v[j].x), v[j].y);
-        }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            h16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float x0 = v[o * 4 + j].x, x1 = v[o * 4 + j].y;
-                hi[2 * j] = (h16)x0; hi[2 * j + 1] = (h16)x1;
-                lo[2 * j] = split_lo(x0, hi[2 * j]); lo[2 * j + 1] = split_lo(x1, hi[2 * j + 1]);
-            }
-            *reinterpret_cast<h16x8*>(A1h + p * AST1 + o * 8) = hi;
-            *reinterpret_cast<h16x8*>(A1l + p * AST1 + o * 8) = lo;
-        }
-    }
-    for (int g = t; g < 2 * 4 * BN; g += 256) {             // W1: plane, octet, column
-        const int pl = g / (4 * BN), r = g - pl * (4 * BN);
-        const int o = r / BN, n = r - o * BN;
-        h16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
-        if (o < KQ1 && n < a.Npad1) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W1l : a.W1h) + ((size_t)o * a.Npad1 + n) * 8);
-        *reinterpret_cast<h16x8*>(B1 + (size_t)g * 8) = v;
-    }
-    constexpr int B2_PER = (2 * 8 * BN + 255) / 256;
-    h16x8 b2_reg[B2_PER];
-#pragma unroll
-    for (int i = 0; i < B2_PER; ++i) {
-        const int g = t + 256 * i;
-        const int pl = g / (8 * BN), r = g - pl * (8 * BN);
-        const int o = r / BN, n = r - o * BN;
-        h16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
-        if (g < 2 * 8 * BN && o < KQ2 && n < a.Npad2) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.W2l : a.W2h) + ((size_t)o * a.Npad2 + n) * 8);
-        b2_reg[i] = v;
-    }
-    __syncthreads();
-    YN_TS();
-
-    // ---- 2. y1 = act(pw1) on the window pixels -> T32 (zero outside the image): RT1 x NP (row tile, 32-column tile) items over the four
-    //      wavefronts (10 items: 3, 3, 2, 2 - whole row tiles would be 2, 1, 1, 1 with twice the work each) -----------------------------
-    for (int it = wave; it < RT1 * NP; it += 4) {
-        const int rt = it / NP, nt = it - rt * NP;
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const h16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
-        const h16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
-        const h16* Bhb = B1 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const h16* Blb = Bhb + 4 * BN * 8;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
-            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
-            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            split_mfma(ah, al, bh, bl, acc0, acc1);
-        }
-        unsigned in16 = 0;                                  // inside flags of this lane's 16 rows
-#pragma unroll
-        for (int r = 0; r < 16; ++r) in16 |= (unsigned)inside[rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] << r;
-        const int n = nt * 32 + l31;
-        float bias = 0.0f;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) bias = (q == nt) ? bias1[q] : bias;
-        if (n < bf) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const float v = apply_act(split_join(acc0[r], acc1[r]) + bias, a.act1);
-                T32[p * CS + n] = __uint_as_float(__float_as_uint(v) & (0u - ((in16 >> r) & 1u)));
-            }
-        }
-    }
-    __syncthreads();                                        // y1 complete; region 1 is free
-    YN_TS();
-
-    // ---- 3. depthwise 3x3 stride 2 (dwconv3x3_kernel's fma chain) -> split planes A2; W2 -> LDS ---------------------------------
-#pragma unroll
-    for (int i = 0; i < B2_PER; ++i) {
-        const int g = t + 256 * i;
-        if (g < 2 * 8 * BN) *reinterpret_cast<h16x8*>(B2 + (size_t)g * 8) = b2_reg[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B3_PER; ++i) {
-        const int g = t + 256 * i;
-        if (g < 2 * 4 * BN) *reinterpret_cast<h16x8*>(B3 + (size_t)g * 8) = b3_reg[i];
-    }
-    if (p1 < p1_n) {
-#pragma unroll
-        for (int i = 0; i < NI1; ++i) {
-            const int op = p1 + i * p1_n;
-            if (op < NO) {
-                float2 acc = b1d;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) vfma(acc, x1w[i][k], w1d[k]);
-                acc = vact(acc, a.dw1_act);
-                amax = range_track(range_track(amax, acc.x), acc.y);
-                h16x2 hi, lo;
-                hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
-                lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
-                *reinterpret_cast<h16x2*>(A3h + op * AST1 + c1) = hi;
-                *reinterpret_cast<h16x2*>(A3l + op * AST1 + c1) = lo;
-            }
-        }
-    }
-    const int pad1 = AST1 - a.cin;                          // K tail of branch 1's planes: zero
-    for (int i = t; i < NO * pad1; i += 256) { const int r = i / pad1, c2 = a.cin + i - r * pad1; A3h[r * AST1 + c2] = (h16)0.0f; A3l[r * AST1 + c2] = (h16)0.0f; }
-    if (dworker) {
-        for (int op = dpl; op < NO; op += ppl) {
-            const int dy = op / TW, dx = op - dy * TW;
-            float2 acc = bd;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-                    vfma(acc, *reinterpret_cast<const float2*>(T32 + ((2 * dy + ky) * WW + 2 * dx + kx) * CS + dc), wd[ky * 3 + kx]);
-            acc = vact(acc, a.dw_act);
-            amax = range_track(range_track(amax, acc.x), acc.y);
-            h16x2 hi, lo;
-            hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
-            lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
-            *reinterpret_cast<h16x2*>(A2h + op * AST2 + dc) = hi;
-            *reinterpret_cast<h16x2*>(A2l + op * AST2 + dc) = lo;
-        }
-    }
-    {
-        const int padn = AST2 - bf;                         // K tail of both planes: zero
-        for (int i = t; i < NO * padn; i += 256) { const int r = i / padn, c2 = bf + i - r * padn; A2h[r * AST2 + c2] = (h16)0.0f; A2l[r * AST2 + c2] = (h16)0.0f; }
-    }
-    __syncthreads();
-    YN_TS();
-    range_report(a.ovf, amax);                              // every split of this workgroup is done
-
-    // ---- 4. branch 1's pointwise conv on wavefronts NP..2NP-1 (-> an LDS tile in the free T32 space) while wavefronts 0..NP-1 run pw2 --
-    float* PT = T32;                                        // [32][BN + 1]
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-    if (wave >= NP && wave < 2 * NP) {
-        const int nt = wave - NP;
-        const h16* Ahb = A3h + l31 * AST1 + h * 8;
-        const h16* Alb = A3l + l31 * AST1 + h * 8;
-        const h16* Bhb = B3 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const h16* Blb = Bhb + 4 * BN * 8;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
-            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
-            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            split_mfma(ah, al, bh, bl, acc0, acc1);
-        }
-        const int n = nt * 32 + l31;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            PT[((r & 3) + 8 * (r >> 2) + 4 * h) * (BN + 1) + n] = apply_act(split_join(acc0[r], acc1[r]) + bias3v, a.act3);
-    }
-    if (wave < NP) {                                        // pw2: one wavefront per 32 output columns
-        const int nt = wave;
-        const h16* Ahb = A2h + l31 * AST2 + h * 8;
-        const h16* Alb = A2l + l31 * AST2 + h * 8;
-        const h16* Bhb = B2 + (size_t)(h * BN + nt * 32 + l31) * 8;
-        const h16* Blb = Bhb + 8 * BN * 8;
-        for (int ks = 0; ks < 2 * ((KQ2 + 3) >> 2); ++ks) {                 // gemm_split_tile's chunks of 32: whole chunks, zero-padded
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
-            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
-            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            split_mfma(ah, al, bh, bl, acc0, acc1);
-        }
-    }
-    __syncthreads();                                        // branch 1's tile is complete
-    // ---- 5. concat + shuffle store: out[2n] = branch 1, out[2n+1] = branch 2 -------------------------------------------------------
-    if (wave < NP) {
-        const int n = wave * 32 + l31;
-        if (n < bf) {
-            const float bias = bias2v;
-            // the 16 branch-1 values of this lane are read together, before any store
-            float pv[16];
-            size_t mrow[16];
-            unsigned okm = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int op = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int oy = oy0 + op / TW, ox = ox0 + op % TW;
-                const bool ok = oy < Ho && ox < Wo;
-                okm |= (ok ? 1u : 0u) << r;
-                mrow[r] = ((size_t)b * Ho + (ok ? oy : 0)) * Wo + (ok ? ox : 0);
-                pv[r] = PT[op * (BN + 1) + n];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if ((okm >> r) & 1u) {
-                    const float v = apply_act(split_join(acc0[r], acc1[r]) + bias, a.act2);
-                    *reinterpret_cast<float2*>(a.out + mrow[r] * (2 * bf) + 2 * n) = make_float2(pv[r], v);
-                }
-            }
-        }
-    }
-#ifdef YN_EXP_TIMING
-    YN_TS();
-    if (t == 0 && (blockIdx.x % 331) == 7) printf("downunit blk %d load+split %lld gemm1 %lld dw %lld gemm2+store %lld total %lld\n", (int)blockIdx.x, TS[1] - TS[0], TS[2] - TS[1], TS[3] - TS[2], TS[4] - TS[3], TS[4] - TS[0]);
-#endif
-#undef YN_TS
-}
-
-// -------------------------------------------------------------------------------------------------
-// down_unit_kernel as a software pipeline (round 4).  `tools/phase_timing.sh downunit` on the one-tile-per-workgroup form above: 25 k
-// cycles per workgroup, 10 k of them the load phase (one memory round trip, 34 eight-byte loads per thread with a cache line per lane),
-// at two workgroups of four wavefronts per CU - nothing to hide it behind.  This form keeps the arithmetic and its order (same bits,
-// test_down_unit_is_bit_identical) and changes where the operands come from:
+// anything).  One tile = 8 x 4 OUTPUT pixels of one image: pw1 on the 17 x 9 input pixels the tile's depthwise windows cover (20 %
+// recomputed on tile borders; K = cin <= 32 is one chunk), y1 in an fp32 LDS tile (zero outside the image: the depthwise conv pads its
+// INPUT), depthwise -> split planes, pw2 (K = bf <= 64: two chunks) on wavefronts 0..NP-1 while wavefronts NP..2NP-1 run branch 1's
+// pointwise conv, and the concat + shuffle is the store.  x is read once (x 1.2) and `out` written once: 80 MB per step instead of
+// 360 MB in five launches.  Every sum runs in the order of gemm_split_kernel / dwconv3x3_kernel: bit-identical to the five launches
+// (test_down_unit_is_bit_identical).
+// The kernel is a software pipeline (round 4).  With one tile per workgroup the load phase was 10 k of a workgroup's 25 k cycles (one
+// memory round trip, 34 eight-byte loads per thread with a cache line per lane) at two workgroups of four wavefronts per CU - nothing to
+// hide it behind.  So:
 //   * a workgroup WALKS tiles (XCD-contiguous: workgroup i of XCD x takes tiles x*TL + i, + G/8, ...) and requests the next tile's input
 //     window right after the barrier that frees the registers of the current one: the round trip runs under phases 2-5;
 //   * the window is loaded as what it is - nine contiguous runs of 17 pixels x cin floats - with 16-byte loads (4-5 per thread, eight
 //     cache lines per wavefront instruction instead of 64), split into the A planes AND kept as fp32 in LDS: branch 1's depthwise conv
-//     reads its stride-2 windows there (18 more global loads per thread in the old form);
+//     reads its stride-2 windows there;
 //   * every weight is loop-invariant: the B fragments of a wavefront's columns (16 contiguous bytes of the pre-split pack per lane and
 //     k-step - down2_kernel's register-direct form) are loaded ONCE per workgroup into 48 registers, like the depthwise taps.  No
-//     weight ever passes through LDS: 76 -> 78 KB with the fp32 window (two workgroups per CU either way).
+//     weight ever passes through LDS.  LDS 78 KB with the fp32 window: two workgroups per CU.
 // -------------------------------------------------------------------------------------------------
 template <int NP, bool RELU>                                 // RELU: the three pointwise convs end in ReLU, the depthwise convs in nothing (ShuffleNetV2)
 __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int tiles)
@@ -1324,17 +1009,10 @@ static size_t down_unit_pipe_lds(int bf, int cin)
     return ((size_t)160 * 40 + (size_t)160 * cin + (size_t)160 * (bf + 2)) * sizeof(float) + 160;
 }
 
-static size_t down_unit_lds(int bf, int NP)
-{
-    const int BN = 32 * NP, RT1 = 5, NO = 32;
-    const size_t r1a = (size_t)2 * RT1 * 32 * 40 + (size_t)2 * 4 * BN * 8, r1b = (size_t)2 * NO * (BN + 8) + (size_t)2 * 8 * BN * 8 + (size_t)2 * NO * 40 + (size_t)2 * 4 * BN * 8;
-    const size_t r1 = r1a > r1b ? r1a : r1b;
-    return ((r1 + 1) / 2) * sizeof(float) + (size_t)160 * (bf + 2) * sizeof(float) + 160;       // + the window's inside flags
-}
-
+// what down_unit_pipe_kernel takes: channel quads (its window pieces are 16 bytes), one K chunk of cin, at most two column tiles, 32-bit byte offsets
 bool down_unit_covers(const DownArgs& a)
 {
-    return a.W1h && a.W1l && a.W2h && a.W2l && a.cin <= 32 && !(a.cin & 1) && a.bf <= 64 && !(a.bf & 1) && a.Npad1 == a.Npad2 && a.Npad1 <= 64 &&
+    return a.W1h && a.W1l && a.W2h && a.W2l && a.cin <= 32 && !(a.cin & 3) && a.bf <= 64 && !(a.bf & 1) && a.Npad1 == a.Npad2 && a.Npad1 <= 64 &&
            !(a.H & 1) && !(a.W & 1) && a.B > 0 && a.cin >= 16 && (size_t)a.B * a.H * a.W * (size_t)(a.cin > a.bf / 2 ? a.cin : a.bf / 2) < ((size_t)1 << 30) &&      // 32-bit byte offsets
            a.wdw1 && a.bdw1 && a.W3h && a.W3l && a.b3 && a.Npad3 == a.Npad1;
 }
@@ -1344,37 +1022,27 @@ void launch_down_unit(const DownArgs& a, hipStream_t s)
     const int Ho = a.H >> 1, Wo = a.W >> 1;
     const unsigned tiles = (unsigned)a.B * ((Ho + 3) / 4) * ((Wo + 7) / 8);
     const int NP = a.Npad1 / 32;
-    const size_t lds = down_unit_lds(a.bf, NP);
     static unsigned long long attr = 0;
     if (attr_pending(attr)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    // the pipelined form (a workgroup walks tiles), channel quads (YN_DOWN_PIPE=0: one tile per workgroup, the test reference)
-    static const int pipe = getenv("YN_DOWN_PIPE") ? atoi(getenv("YN_DOWN_PIPE")) : 1;
     constexpr unsigned pipe_g = 1024;   // walking workgroups (a multiple of 8): ~3 tiles each at bs = 32 (512 / 768 / 1024 / 1456 / one per tile measured within 1 % of each other)
-    if (pipe && !(a.cin & 3)) {
-        const size_t plds = down_unit_pipe_lds(a.bf, a.cin);
-        unsigned g = xcd_grid(tiles);
-        if (g > pipe_g) g = pipe_g;
-        const bool relu = a.act1 == 1 && a.act2 == 1 && a.act3 == 1 && a.dw_act == 0 && a.dw1_act == 0;
+    const size_t plds = down_unit_pipe_lds(a.bf, a.cin);
+    unsigned g = xcd_grid(tiles);
+    if (g > pipe_g) g = pipe_g;
+    const bool relu = a.act1 == 1 && a.act2 == 1 && a.act3 == 1 && a.dw_act == 0 && a.dw1_act == 0;
 #define YN_DUP(np, rl) { set_last_kernel_name("down_unit_pipe_kernel<" #np "," #rl ">"); hipLaunchKernelGGL((down_unit_pipe_kernel<np, rl>), dim3(g), dim3(256), plds, s, a, (int)tiles); }
-        if (NP == 1) { if (relu) YN_DUP(1, true) else YN_DUP(1, false) }
-        else         { if (relu) YN_DUP(2, true) else YN_DUP(2, false) }
+    if (NP == 1) { if (relu) YN_DUP(1, true) else YN_DUP(1, false) }
+    else         { if (relu) YN_DUP(2, true) else YN_DUP(2, false) }
 #undef YN_DUP
-        return;
-    }
-    if (NP == 1) { set_last_kernel_name("down_unit_kernel<1>"); hipLaunchKernelGGL(down_unit_kernel<1>, dim3(xcd_grid(tiles)), dim3(256), lds, s, a); }
-    else         { set_last_kernel_name("down_unit_kernel<2>"); hipLaunchKernelGGL(down_unit_kernel<2>, dim3(xcd_grid(tiles)), dim3(256), lds, s, a); }
 }
 
 // -------------------------------------------------------------------------------------------------
 // The stride-2 ShuffleV2 units of stages 3 and 4 (backbone/shufflenetv2.py:42-49, 53-63, 73-74; cin = bf = 116 / 232): too wide for
-// down_unit_kernel's window form (pw1 on the 17 x 9 halo needs the whole K = cin of 153 pixels in LDS).  The unit is cut where the chain
+// down_unit_pipe_kernel's window form (pw1 on the 17 x 9 halo needs the whole K = cin of 153 pixels in LDS).  The unit is cut where the chain
 // kernels cut theirs - at the depthwise convs, after which everything is pixel-local:
 //     launch 1 (gemm_split_kernel):  y1 = relu(pw1(x))                                          [B][H][W][bf]
 //     launch 2 (down2_kernel):       y3 = relu(pw2(dw_s2(y1))),  z2 = relu(pw(dw_s2(x))),  out = shuffle(cat(z2, y3))
@@ -1643,158 +1311,14 @@ void launch_down2(const Down2Args& a, hipStream_t s)
 // -------------------------------------------------------------------------------------------------
 // Depthwise 3x3 + pointwise conv of a detection head (models/yolo_nano.py:60-82: Conv(96, 96, k=3, g=96) -> Conv(96, 96, k=1)) as one
 // kernel, for up to three pyramid levels per launch (Group<>).  The depthwise output of the stride-8 head is 33 MB per 32-image step,
-// written by one launch and read back by the next; here it goes from registers into the GEMM's LDS operand planes.  Workgroup = an 8 x 4
-// tile of pixels of one image: thread = (4 channels, a run of 4 pixels along x) with its 3 x 6 window in ONE batch of clamped, masked
-// loads (dwconv3x3_kernel's thread, the same fma chain), the whole 96 x 96 pre-split weight matrix in LDS (no K-chunk barriers), three
-// wavefronts = the three 32-column tiles, 16-byte stores through the in-quad transpose.  Bit-identical to dwconv3x3_kernel +
-// gemm_split_kernel.  LDS 50 KB: three workgroups per CU.
-// -------------------------------------------------------------------------------------------------
-template <int TH>                                           // tile height: 8 x TH pixels per workgroup, TH / 4 runs per thread
-__device__ __forceinline__ void dwpw_block(const DwPwArgs& a, h16* smem, unsigned bid, unsigned nblocks)
-{
-    constexpr int TW = 8, NO = TW * TH, C = 96, KQ = C / 8, BN = 96, AST = C + 8, R = 4, NR = TH / 4;
-    h16* Ah = smem;                                       // [NO][AST]
-    h16* Al = Ah + NO * AST;
-    h16* Bs = Al + NO * AST;                              // [2][KQ][BN][8]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
-    const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH;
-    const int tile = (int)xcd_block(bid, nblocks);
-    if (tile >= a.B * ty_n * tx_n) return;
-    const int b = tile / (ty_n * tx_n), trem = tile - b * (ty_n * tx_n);
-    const int oy0 = (trem / tx_n) * TH, ox0 = (trem % tx_n) * TW;
-
-    // ---- 1. every load of the workgroup in one batch: depthwise windows, taps, bias; the weight matrix; the GEMM bias ------------------
-    const int cq = t % (C / 4), run = t / (C / 4);          // 24 channel quads x 8 runs (2 per tile row, rows run/2 + 4 i) = 192 workers
-    const bool worker = run < 8;
-    const int c = cq * 4, ry = run >> 1, rx = (run & 1) * R;
-    float4 win[NR][3][R + 2], wd[9], bd = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (worker) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int oy = oy0 + ry + 4 * i;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int iy = oy - 1 + ky;
-                const bool yok = oy < a.H && iy >= 0 && iy < a.H;
-                const float* rowp = a.in + ((size_t)(b * a.H + (yok ? iy : 0)) * a.W) * C + c;
-#pragma unroll
-                for (int j = 0; j < R + 2; ++j) {
-                    const int ix = ox0 + rx - 1 + j;
-                    const bool ok = yok && ix >= 0 && ix < a.W;
-                    win[i][ky][j] = vmask(*reinterpret_cast<const float4*>(rowp + (size_t)(ok ? ix : 0) * C), opaque_mask(ok));
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) wd[k] = *reinterpret_cast<const float4*>(a.wdw + k * C + c);
-        bd = *reinterpret_cast<const float4*>(a.bdw + c);
-    }
-    constexpr int B_PER = (2 * KQ * BN + 255) / 256;        // 9 granules of 16 bytes per thread
-    h16x8 b_reg[B_PER];
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-        const int g = t + 256 * i;                          // plane, octet, column
-        const int pl = g / (KQ * BN), r = g - pl * (KQ * BN);
-        const int o = r / BN, n = r - o * BN;
-        h16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (h16)0.0f;
-        if (g < 2 * KQ * BN) v = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(pl ? a.Wl : a.Wh) + ((size_t)o * a.Npad + n) * 8);
-        b_reg[i] = v;
-    }
-    const float gbias = (wave < 3) ? a.bias[wave * 32 + l31] : 0.0f;
-
-    // ---- 2. depthwise (dwconv3x3_kernel's chain) -> split planes; weights -> LDS -------------------------------------------------------
-    float amax = 0.0f;                                      // range guard (yn_split.h)
-    if (worker) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i)
-#pragma unroll
-        for (int o = 0; o < R; ++o) {
-            float4 acc = bd;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) vfma(acc, win[i][ky][o + kx], wd[ky * 3 + kx]);
-            acc = vact(acc, a.dw_act);
-            const int op = (ry + 4 * i) * TW + rx + o;
-            const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
-            h16x4 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
-            *reinterpret_cast<h16x4*>(Ah + op * AST + c) = hi;
-            *reinterpret_cast<h16x4*>(Al + op * AST + c) = lo;
-        }
-        range_report(a.ovf, amax);
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i) {
-        const int g = t + 256 * i;
-        if (g < 2 * KQ * BN) *reinterpret_cast<h16x8*>(Bs + (size_t)g * 8) = b_reg[i];
-    }
-    __syncthreads();
-
-    // ---- 3. pointwise conv: three wavefronts, 32 x 32 each, K = 96 in gemm_split_tile's order; bias, activation, 16-byte stores -----------
-    if (wave < 3) {
-#pragma unroll
-        for (int rt = 0; rt < NO / 32; ++rt) {
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-        const h16* Ahb = Ah + (rt * 32 + l31) * AST + h * 8;
-        const h16* Alb = Al + (rt * 32 + l31) * AST + h * 8;
-        const h16* Bhb = Bs + (size_t)(h * BN + wave * 32 + l31) * 8;
-        const h16* Blb = Bhb + (size_t)KQ * BN * 8;
-#pragma unroll
-        for (int ks = 0; ks < KQ / 2; ++ks) {
-            const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
-            const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
-            const h16x8 bh = *reinterpret_cast<const h16x8*>(Bhb + (size_t)(ks * 2 * BN) * 8);
-            const h16x8 bl = *reinterpret_cast<const h16x8*>(Blb + (size_t)(ks * 2 * BN) * 8);
-            split_mfma(ah, al, bh, bl, acc0, acc1);
-        }
-        const int j = lane & 3;
-        const int nq = wave * 32 + (l31 & ~3);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float v0 = apply_act(split_join(acc0[4 * g + 0], acc1[4 * g + 0]) + gbias, a.act);
-            float v1 = apply_act(split_join(acc0[4 * g + 1], acc1[4 * g + 1]) + gbias, a.act);
-            float v2 = apply_act(split_join(acc0[4 * g + 2], acc1[4 * g + 2]) + gbias, a.act);
-            float v3 = apply_act(split_join(acc0[4 * g + 3], acc1[4 * g + 3]) + gbias, a.act);
-            {   // 2x2 blocks, then 4x4: lane j of the quad ends up with row j x 4 columns (gemm_epilogue's transpose)
-                const float s0 = (j & 1) ? v0 : v1, s1 = (j & 1) ? v2 : v3;
-                const float r0 = quad_xor1(s0), r1 = quad_xor1(s1);
-                if (j & 1) { v0 = r0; v2 = r1; } else { v1 = r0; v3 = r1; }
-            }
-            {
-                const float s0 = (j & 2) ? v0 : v2, s1 = (j & 2) ? v1 : v3;
-                const float r0 = quad_xor2(s0), r1 = quad_xor2(s1);
-                if (j & 2) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
-            }
-            const int op = rt * 32 + 8 * g + 4 * h + j;
-            const int py = oy0 + op / TW, px = ox0 + op % TW;
-            if (py < a.H && px < a.W)
-                *reinterpret_cast<float4*>(a.out + (((size_t)b * a.H + py) * a.W + px) * C + nq) = make_float4(v0, v1, v2, v3);
-        }
-        }
-    }
-}
-
-template <int TH>
-__global__ __launch_bounds__(256, (TH == 4 ? 3 : 2)) void dwpw_group_kernel(Group<DwPwArgs> g)
-{
-    extern __shared__ __attribute__((aligned(16))) float dwpw_smem[];
-    unsigned local, nb;
-    const int p = group_problem(g.first, blockIdx.x, local, nb);
-    dwpw_block<TH>(g.a[p], reinterpret_cast<h16*>(dwpw_smem), local, nb);
-}
-
-// -------------------------------------------------------------------------------------------------
-// dwpw_block as a tile walk (round 4, after down_unit_pipe_kernel): 192 threads (the fourth wavefront of dwpw_block only helped staging
-// the weight matrix), the 96 x 96 split weights register-resident (a lane's B fragments of its wavefront's 32 columns: 48 registers, loaded
-// once per workgroup - nothing of them in LDS: 50 -> 13 KB), a workgroup walks ~3 tiles (XCD-contiguous) and requests the next tile's
-// depthwise windows right behind the barrier that ends the depthwise phase - the round trip runs under the GEMM and the stores.  Same
-// arithmetic in the same order: bit-identical (test_dwpw_fused_is_bit_identical).
+// written by one launch and read back by the next; here it goes from registers into the GEMM's LDS operand planes.  One tile = 8 x 4
+// pixels of one image: thread = (4 channels, a run of 4 pixels along x) with its 3 x 6 window in ONE batch of clamped loads, masked where
+// they are consumed (dwconv3x3_kernel's thread, the same fma chain); 192 threads = three wavefronts = the three 32-column tiles of the
+// GEMM, 16-byte stores through the in-quad transpose.  The 96 x 96 split weights are register-resident (a lane's B fragments of its
+// wavefront's 32 columns: 48 registers, loaded once per workgroup - nothing of them in LDS: 13 KB), a workgroup walks ~3 tiles
+// (XCD-contiguous, after down_unit_pipe_kernel) and requests the next tile's depthwise windows right behind the barrier that ends the
+// depthwise phase - the round trip runs under the GEMM and the stores.  Bit-identical to dwconv3x3_kernel + gemm_split_kernel
+// (test_grouped_launches_are_bit_identical).
 // -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, unsigned bid, unsigned nblocks)
 {
@@ -1932,8 +1456,10 @@ __global__ __launch_bounds__(192, 2) void dwpw_pipe_group_kernel(Group<DwPwArgs>
 bool dwpw_group_ok(const DwPwArgs* a, int n)
 {
     if (n < 1 || n > YN_GROUP_MAX) return false;
-    for (int p = 0; p < n; ++p)
+    for (int p = 0; p < n; ++p) {
         if (a[p].C != 96 || a[p].Npad != 96 || !a[p].Wh || !a[p].Wl || a[p].B <= 0) return false;
+        if ((size_t)a[p].B * a[p].H * a[p].W * 96 >= ((size_t)1 << 30)) return false;      // 32-bit byte offsets
+    }
     return true;
 }
 
@@ -1941,35 +1467,14 @@ void launch_dwpw_group(const DwPwArgs* a, int n, hipStream_t s)
 {
     Group<DwPwArgs> g{};
     unsigned tot = 0;
-    // the tile-walking form (YN_DWPW_PIPE=0: one tile per workgroup, the test reference)
-    static const int pipe = getenv("YN_DWPW_PIPE") ? atoi(getenv("YN_DWPW_PIPE")) : 1;
-    if (pipe) {
-        bool fits = true;
-        for (int p = 0; p < n; ++p) fits = fits && (size_t)a[p].B * a[p].H * a[p].W * 96 < ((size_t)1 << 30);      // 32-bit byte offsets
-        if (fits) {
-            constexpr unsigned per = 3;                     // tiles per walking workgroup
-            for (int p = 0; p < YN_GROUP_MAX; ++p) {
-                g.first[p] = tot;
-                if (p < n) { g.a[p] = a[p]; const unsigned tiles = (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8); tot += xcd_grid((tiles + per - 1) / per); }
-            }
-            g.first[YN_GROUP_MAX] = tot;
-            set_last_kernel_name("dwpw_pipe_group_kernel");
-            hipLaunchKernelGGL(dwpw_pipe_group_kernel, dim3(tot), dim3(192), (size_t)2 * 32 * 104 * 2, s, g);
-            return;
-        }
-    }
-    // one 8 x 4 tile per workgroup (8 x 8 tiles, half the weight traffic, measured the same end to end: 43 vs 39 us alone)
-    constexpr int TH = 4;
+    constexpr unsigned per = 3;                             // tiles per walking workgroup
     for (int p = 0; p < YN_GROUP_MAX; ++p) {
         g.first[p] = tot;
-        if (p < n) { g.a[p] = a[p]; tot += xcd_grid((unsigned)a[p].B * ((a[p].H + TH - 1) / TH) * ((a[p].W + 7) / 8)); }
+        if (p < n) { g.a[p] = a[p]; const unsigned tiles = (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8); tot += xcd_grid((tiles + per - 1) / per); }
     }
     g.first[YN_GROUP_MAX] = tot;
-    const size_t lds = ((size_t)2 * 8 * TH * 104 + (size_t)2 * 12 * 96 * 8) * 2;
-    static unsigned long long attr = 0;
-    if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwpw_group_kernel<TH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    set_last_kernel_name("dwpw_group_kernel<4>");
-    hipLaunchKernelGGL(dwpw_group_kernel<TH>, dim3(tot), dim3(256), lds, s, g);
+    set_last_kernel_name("dwpw_pipe_group_kernel");
+    hipLaunchKernelGGL(dwpw_pipe_group_kernel, dim3(tot), dim3(192), (size_t)2 * 32 * 104 * 2, s, g);
 }
 
 bool launch_unit_chain(const ChainArgs& a, hipStream_t s) { return unit_chain_dispatch(a, s, false); }

@@ -387,8 +387,8 @@ __global__ __launch_bounds__(64 * NW, 2) void unit_pipe_kernel(ChainArgs a, int 
 // walk.  false = not launched (the caller runs unit_chain2_kernel).
 bool launch_unit_pipe(const ChainArgs& a, hipStream_t s, bool dry)
 {
-    // the form is the handle's choice (yn_chain_pipe -> ChainArgs::pipe_mode: 0 by the size rule, 1 never, 2 also for few tiles)
-    const int mode = a.pipe_mode == 1 ? 0 : (a.pipe_mode == 2 ? 2 : 1);
+    // the form is the handle's choice (yn_chain_pipe -> ChainArgs::pipe_mode: 0 never, 1 by the size rule, 2 also for few tiles)
+    const int mode = a.pipe_mode;
     // size rule: the walk pays from about one tile per workgroup slot; the streamed wide form (a workgroup's whole-panel prefetch instead of three
     // k-steps of look-ahead) at every size: one 608 x 608 image 0.652 -> 0.639 ms
     const int min_tiles = a.bf > 128 ? 1 : 256;

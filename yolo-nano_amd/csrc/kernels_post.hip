@@ -412,9 +412,11 @@ void launch_head_decode_group(const GemmArgs* a, int n, const GridInfo& g, float
 
 // -------------------------------------------------------------------------------------------------
 // The tail of a detection head in ONE kernel (models/yolo_nano.py:60-82, 299-330, 362-367): depthwise 3x3 + pointwise conv (layers .2 and
-// .3: dwpw_group_kernel's tile and thread roles), the last conv (.4) on the tile while it is still in LDS, and the candidate decode of
-// head_decode_kernel.  Against dwpw_group_kernel + head_decode_group_kernel the 96-channel activation of layer .3 (44 MB per 32-image step
-// at 416 x 416) is neither written nor read back, and a chip-filling launch disappears.  Workgroup = an 8 x 4 pixel tile of one image.
+// .3), the last conv (.4) on the tile while it is still in LDS, and the candidate decode of head_decode_kernel.  Against
+// dwpw_pipe_group_kernel + head_decode_group_kernel the 96-channel activation of layer .3 (44 MB per 32-image step at 416 x 416) is
+// neither written nor read back, and a chip-filling launch disappears.  Workgroup = an 8 x 4 pixel tile of one image; in the depthwise
+// phase thread = (4 channels, a run of 4 pixels along x) with its 3 x 6 window in one batch of clamped, masked loads (192 of the 256
+// threads), in the 96 -> 96 GEMM wavefront = one 32-column tile (three of the four).
 //   1. depthwise windows, taps, biases, the 96 x 96 split weight matrix and the first weight chunk of the last conv: one batch of loads
 //   2. depthwise -> split planes A [32][104] x 2; W -> LDS; three wavefronts run the 96 -> 96 GEMM (K in gemm_split_tile's order)
 //   3. barrier; activation, split -> the SAME planes (now the last conv's A operand); last conv's chunk 0 -> the weight space

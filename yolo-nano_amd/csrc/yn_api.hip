@@ -144,7 +144,7 @@ struct yn_handle {
     // graphs / profiling
     bool use_graph = false;
     bool tail_fuse = true;                 // yn_tail_fuse: off = layers .2+.3 and .4+decode of the heads as two grouped kernels instead of one (head_tail_group_kernel)
-    bool down_fuse = true;                 // yn_down_fuse: the main branch of a stride-2 unit as one kernel (down_unit_kernel)
+    bool down_fuse = true;                 // yn_down_fuse: the main branch of a stride-2 unit as one kernel (down_unit_pipe_kernel)
     bool group_launch = true;              // yn_group_launch: the three heads' layers (and the laterals) as grouped launches
     bool fuse_decode = true;               // yn_fuse_decode: yn_infer's last head conv + candidate decode as one kernel
     int fuse_decode_mode = 1;              // 1 = when the stride-8 head has >= 8192 pixels, 2 = always
@@ -626,7 +626,7 @@ int run_unit_chain(yn_handle* h, int stage, int R, float* oA, int B, int H, int 
             a.out = final_out; a.out_ld = C;
         }
         a.B = B; a.H = H; a.W = W; a.bf = bf; a.Npad = pw2.Npad; a.M = (int)M;
-        a.pipe_mode = h->chain_pipe == 1 ? 0 : (h->chain_pipe == 0 ? 1 : 2);
+        a.pipe_mode = h->chain_pipe;
         a.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
         ua.push_back(a);
         x1 = a.out; x1_ld = bf;
@@ -861,7 +861,6 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             d.W1h = lp1.ws_hi; d.W1l = lp1.ws_lo; d.b1 = lp1.b_packed; d.act1 = lp1.act; d.Npad1 = lp1.Npad;
             d.wdw = ldw.w_packed; d.bdw = ldw.b_packed; d.dw_act = ldw.act;
             d.W2h = lp2.ws_hi; d.W2l = lp2.ws_lo; d.b2 = lp2.b_packed; d.act2 = lp2.act; d.Npad2 = lp2.Npad;
-            d.pass = nullptr;
             d.wdw1 = l1d.w_packed; d.bdw1 = l1d.b_packed; d.dw1_act = l1d.act;
             d.W3h = l1p.ws_hi; d.W3l = l1p.ws_lo; d.b3 = l1p.b_packed; d.act3 = l1p.act; d.Npad3 = l1p.Npad;
             d.out = oA; d.B = B; d.H = curH; d.W = curH; d.bf = bf;

@@ -35,9 +35,7 @@ struct GemmArgs {
     const float* pass; int pass_ld; int pass_off; // shuffle mode: out[m][2n] = pass[m][n], out[m][2n+1] = res
     int M, K, N, Npad, act;
     int cfg;                                    // pointwise tile configuration index, -1 = heuristic
-    const float* dw_w; const float* dw_b;       // fused depthwise prologue (dwpw kernel): [9][K], [K]
-    int dw_act;                                 // activation between the depthwise and the pointwise conv
-    int dw_stride;                              // dwpw_tile_kernel: stride of the depthwise conv (H, W = its INPUT extent, M = output pixels)
+    int dw_act; int dw_stride;                  // unused; kept: without these 8 bytes hipcc merges two kernarg loads in conv3x3_split_kernel<1,*> and pw_pipe_kernel
     const void* Wsh; const void* Wsl;           // split-f16 packs of the same weights (hi, lo * 2^11): [taps][ceil(Cin/8)][Npad][8] halves, or null.
                                                 // INVARIANT the kernels rely on (their prefetches carry no masks): every value of every octet
                                                 // < ceil(Cin/8) and every column < Npad is FINITE (fold_pack_kernel checks what it packs and zero-fills the
@@ -68,7 +66,7 @@ struct ChainArgs {
     float* t1n;                                 // next unit's depthwise input [M][bf]
     int B, H, W, bf, Npad, M;
     unsigned* ovf;                              // split-f16 range guard flag or null
-    int pipe_mode;                              // unit_pipe_kernel: 0 by the size rule, 1 never, 2 also for few tiles (yn_chain_pipe)
+    int pipe_mode;                              // unit_pipe_kernel: 0 never, 1 by the size rule, 2 also for few tiles (yn_chain_pipe's argument)
 };
 // The stride-1 units of a stage (all but the last) as ONE persistent launch (kernels_stage.hip, stage_pipe_kernel): work items = (unit, tile)
 // handed out by ticket, tile-level ready flags between the units.
@@ -100,14 +98,13 @@ bool launch_stage_pipe(StageArgs a, int bf, int pub_early, int min_tiles, size_t
 bool launch_unit_chain(const ChainArgs& a, hipStream_t s);
 bool launch_unit_pipe(const ChainArgs& a, hipStream_t s, bool dry = false);   // kernels_pipe.hip: the persistent tile walk; false = not applicable, nothing launched
 
-// The main branch of a stride-2 ShuffleV2 unit as ONE kernel (kernels_chain.hip, down_unit_kernel): pw1 -> depthwise 3x3 stride 2 ->
+// The main branch of a stride-2 ShuffleV2 unit as ONE kernel (kernels_chain.hip, down_unit_pipe_kernel): pw1 -> depthwise 3x3 stride 2 ->
 // pw2 -> concat + shuffle with the other branch's output.
 struct DownArgs {
     const float* x; int cin;                    // unit input [B][H][W][cin] (dense)
     const void *W1h, *W1l; const float* b1; int act1, Npad1;       // pw1: split packs [ceil(cin/8)][Npad1][8], bias, activation
     const float* wdw; const float* bdw; int dw_act;                // depthwise [9][bf], [bf]
     const void *W2h, *W2l; const float* b2; int act2, Npad2;       // pw2: split packs [ceil(bf/8)][Npad2][8]
-    const float* pass;                          // unused, null (keeps down_unit_pipe_kernel's argument layout); branch 1 is computed here
     const float* wdw1; const float* bdw1; int dw1_act;             // branch 1 depthwise (stride 2, on x): [9][cin], [cin]
     const void *W3h, *W3l; const float* b3; int act3, Npad3;       // branch 1 pointwise cin -> bf
     float* out;                                 // [B][Ho][Wo][2*bf]: out[2n] = branch 1, out[2n+1] = pw2[n]
@@ -131,7 +128,7 @@ struct Down2Args {
 };
 bool down2_covers(const Down2Args& a);
 void launch_down2(const Down2Args& a, hipStream_t s);
-// depthwise 3x3 (stride 1) + pointwise conv of a detection head as one kernel (kernels_chain.hip, dwpw_group_kernel): C = Cout = 96
+// depthwise 3x3 (stride 1) + pointwise conv of a detection head as one kernel (kernels_chain.hip, dwpw_pipe_group_kernel): C = Cout = 96
 struct DwPwArgs {
     const float* in;                            // [B][H][W][C] dense
     const float* wdw; const float* bdw; int dw_act;                // depthwise [9][C], [C]
