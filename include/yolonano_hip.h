@@ -646,6 +646,41 @@ int  yn_op_f32_maxpool(yn_handle* h, const float* x, int B, int H, int W, int C,
  * mode 2  out[B,H/2,W/2] += the four children of a[B,H,W]     mode 3  out[B,2H,2W] at the even pixels += a[B,H,W]          (b unused) */
 int  yn_op_f32_resample(yn_handle* h, int mode, const float* a, const float* b, float* out, int B, int H, int W, int C);
 
+/* ---- baseline JPEG decode: Huffman stage on the host, everything after it on the device --------------------------------------------
+ * Files as cv2.imread / PIL read them with libjpeg's defaults (JDCT_ISLOW, fancy upsampling), byte for byte: SOF0 / SOF1 with 8-bit
+ * samples, one interleaved scan, 1 component or 3 with luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma, restart intervals, 8- and 16-bit
+ * quantisation tables.  Anything else (progressive, arithmetic, lossless, 12-bit, 4 components, other samplings, several scans) is
+ * YN_JPEG_UNSUPPORTED; a file that breaks its own syntax (truncated, codes outside a table, runs past coefficient 63, bad restart markers,
+ * undefined tables, a dimension of 0) is YN_JPEG_CORRUPT; a side above 16384, or a coefficient buffer that is too small, YN_JPEG_TOO_LARGE. */
+typedef struct yn_jpeg yn_jpeg;
+#define YN_JPEG_OK 0
+#define YN_JPEG_UNSUPPORTED 1
+#define YN_JPEG_CORRUPT 2
+#define YN_JPEG_TOO_LARGE 3
+/* Host only, no handle, no GPU needed.  info8 = w, h, components, h_samp, v_samp (of the luma), restart interval, SOF marker, status.
+ * Returns the status. */
+int  yn_jpeg_info(const uint8_t* data, int64_t len, int32_t* info8);
+/* Host only: the entropy stage alone.  coef_host [cap] int16 receives the coefficients, 64 per block in natural order, per component
+ * block-row-major over the MCU-padded block grid, component after component; qt_host [3][64] the components' quantisation tables in
+ * natural order; grid_host [3][2] the block grids (blocks high, blocks wide; 0 for absent components).  Returns the status, also in *status. */
+int  yn_jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef_host, int64_t cap, uint16_t* qt_host, int32_t* grid_host, int32_t* status);
+/* A decoder for the handle's device: two pinned staging slots of staging_bytes each (int16 coefficients: 2 bytes per sample, 3 bytes
+ * per pixel at 4:2:0), 1.5 x staging_bytes on the device.  A batch is cut into chunks of max_batch (1..1024) images, one upload and two
+ * kernel launches each; the host decodes a chunk with up to `threads` (>= 1, capped at 16) workers. */
+int  yn_jpeg_create(yn_handle* h, int max_batch, int64_t staging_bytes, int threads, yn_jpeg** out);
+void yn_jpeg_destroy(yn_jpeg* j);
+/* n files (host pointers / lengths) -> frames_host[i]: a DEVICE pointer to uint8 [h_i][w_i][3] BGR, sized by yn_jpeg_info.  Returns once
+ * the work is enqueued on the handle's stream (the entropy stage has run by then: the files may be released).  status_host[i] is the
+ * YN_JPEG_ status of image i and *failed the number that are not OK: such a frame is left untouched (and may be null), the others are
+ * decoded.  A chunk whose coefficients exceed staging_bytes fails the call (1) before anything is launched; the error names the bytes needed. */
+int  yn_jpeg_decode_batch(yn_handle* h, yn_jpeg* j, int n, const uint8_t* const* data_host, const int64_t* len_host, uint8_t* const* frames_host,
+                          int32_t* status_host, int32_t* failed);
+/* Why image i of the last batch was refused ("" if it was not).  j == NULL: the reason of the calling thread's last yn_jpeg_info /
+ * yn_jpeg_coefficients. */
+const char* yn_jpeg_reason(yn_jpeg* j, int i);
+/* Measurement (synchronises): ms3 = host entropy stage of the last batch (wall clock), upload and kernels of its last chunk (HIP events). */
+int  yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every kernel launch of yn_forward_raw / yn_infer is bracketed by a pair of HIP
  * events recorded on the handle's stream (graph replay is bypassed while enabled).  After the

@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in ("Visualizer", "class_colors", "default_font"):
         from . import draw                                    # numpy only until a Visualizer is made
         return getattr(draw, name)
+    if name in ("JPEGDecoder", "imread", "imread_batch"):
+        from . import jpeg                                    # files -> device frames (yn_jpeg_*)
+        return getattr(jpeg, name)
     if name in ("Handle", "YnError", "YnRangeError", "load_library"):
         from . import capi
         return getattr(capi, name)

@@ -150,6 +150,13 @@ SIGNATURES = {
     "yn_draw_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, ctypes.c_int64, _f32]),
     "yn_draw_status": (_i32, [_vp, _vp, _i64p, _i64p, ctypes.POINTER(_i32)]),
     "yn_draw_prims": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
+    "yn_jpeg_info": (_i32, [_vp, ctypes.c_int64, _vp]),
+    "yn_jpeg_coefficients": (_i32, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, ctypes.POINTER(_i32)]),
+    "yn_jpeg_create": (_i32, [_vp, _i32, ctypes.c_int64, _i32, ctypes.POINTER(_vp)]),
+    "yn_jpeg_destroy": (None, [_vp]),
+    "yn_jpeg_decode_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
+    "yn_jpeg_reason": (ctypes.c_char_p, [_vp, _i32]),
+    "yn_jpeg_timing": (_i32, [_vp, _vp, _vp]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

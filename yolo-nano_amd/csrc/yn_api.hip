@@ -68,6 +68,7 @@ struct GraphEntry {
 struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
+struct yn_jpeg { ynk::JpegState* st; };      // likewise (kernels_jpeg.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
 // test-time augmentation for whole batches (kernels_tta.hip): every buffer is allocated once, for max_batch images and the largest scale
 struct yn_tta {
@@ -2565,6 +2566,64 @@ int yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_ho
             HIPCHK(h, hipMemcpyAsync(forward_start_host + f * B, t->fstart + f * t->max_batch, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// ---- baseline JPEG decode: entropy stage on the host, the rest on the device (yn_jpeg_host.h, kernels_jpeg.hip) --------------------------
+static_assert(YN_JPEG_OK == 0 && YN_JPEG_UNSUPPORTED == 1 && YN_JPEG_CORRUPT == 2 && YN_JPEG_TOO_LARGE == 3, "yn_jpeg statuses (yn_jpeg_host.h)");
+static thread_local std::string g_jpeg_reason;      // of the calling thread's last yn_jpeg_info / yn_jpeg_coefficients
+
+int yn_jpeg_info(const uint8_t* data, int64_t len, int32_t* info8)
+{
+    int32_t scratch[8];
+    g_jpeg_reason.clear();
+    return ynk::jpeg_info(data, len, info8 ? info8 : scratch, g_jpeg_reason);
+}
+
+int yn_jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef_host, int64_t cap, uint16_t* qt_host, int32_t* grid_host, int32_t* status)
+{
+    int64_t needed = 0;
+    g_jpeg_reason.clear();
+    const int st = ynk::jpeg_coefficients(data, len, coef_host, cap, qt_host, grid_host, &needed, g_jpeg_reason);
+    if (status) *status = st;
+    return st;
+}
+
+int yn_jpeg_create(yn_handle* h, int max_batch, int64_t staging_bytes, int threads, yn_jpeg** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_jpeg_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::JpegState* st = nullptr;
+    if (ynk::jpeg_create(h->cfg.device, max_batch, staging_bytes, threads, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_jpeg{st};
+    return 0;
+}
+
+void yn_jpeg_destroy(yn_jpeg* j)
+{
+    if (!j) return;
+    ynk::jpeg_destroy(j->st);
+    delete j;
+}
+
+int yn_jpeg_decode_batch(yn_handle* h, yn_jpeg* j, int n, const uint8_t* const* data_host, const int64_t* len_host, uint8_t* const* frames_host,
+                         int32_t* status_host, int32_t* failed)
+{
+    YN_ENTER(h);
+    if (!j) return fail(h, "yn_jpeg_decode_batch: null object");
+    if (ynk::jpeg_device(j->st) != h->cfg.device)
+        return fail(h, "yn_jpeg_decode_batch: the object was made for device %d, the handle is on device %d", ynk::jpeg_device(j->st), h->cfg.device);
+    YN_EVAL_CALL(ynk::jpeg_decode_batch(j->st, h->stream, n, data_host, len_host, frames_host, status_host, failed, err));
+}
+
+const char* yn_jpeg_reason(yn_jpeg* j, int i) { return j ? ynk::jpeg_reason(j->st, i) : g_jpeg_reason.c_str(); }
+
+int yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3)
+{
+    YN_ENTER(h);
+    if (!j || !ms3) return fail(h, "yn_jpeg_timing: null argument");
+    YN_EVAL_CALL(ynk::jpeg_timing(j->st, ms3, err));
 }
 
 }  // extern "C"

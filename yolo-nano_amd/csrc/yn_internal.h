@@ -287,6 +287,19 @@ int  draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, cons
 int  draw_status(DrawState* d, hipStream_t s, int64_t* drawn, int64_t* skipped, int* range_mark, std::string& err);
 int  draw_prims(DrawState* d, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
 
+// ---- baseline JPEG decode (kernels_jpeg.hip, yn_jpeg_host.h): the state behind yn_jpeg; 0 = ok, 1 = error (text in err) -------------------
+struct JpegState;
+int  jpeg_create(int device, int max_batch, int64_t staging_bytes, int threads, JpegState** out, std::string& err);
+void jpeg_destroy(JpegState* j);
+int  jpeg_device(const JpegState* j);
+int  jpeg_decode_batch(JpegState* j, hipStream_t s, int n, const uint8_t* const* data, const int64_t* len, uint8_t* const* frames, int32_t* status,
+                       int32_t* failed, std::string& err);
+const char* jpeg_reason(const JpegState* j, int i);
+int  jpeg_timing(JpegState* j, float* ms3, std::string& err);
+// host only; they return the YN_JPEG_ status and the reason of a refusal
+int  jpeg_info(const uint8_t* data, int64_t len, int32_t* info8, std::string& reason);
+int  jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef, int64_t cap, uint16_t* qt, int32_t* grid, int64_t* needed, std::string& reason);
+
 // ---- training loss (kernels_train.hip) --------------------------------------------------------------
 int  loss_num_blocks(const GridInfo& g, int B);
 void launch_loss(const float* conf, const float* cls, const float* t, const float* const head[3], float* const ghead[3],

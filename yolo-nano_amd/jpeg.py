@@ -1,0 +1,189 @@
+"""Baseline JPEG files -> uint8 [h,w,3] BGR frames on the device, byte for byte what cv2.imread returns (yn_jpeg_*).
+
+    frame = imread("000001.jpg")                       # the stand-in for cv2.imread in data/voc.py:pull_image and data/coco.py
+    frames = JPEGDecoder(max_batch=32).batch(blobs)    # blobs: bytes objects; one upload and two kernel launches per 32 files
+
+The Huffman stage runs on the host, threaded over the files of a batch; dequantisation, the inverse DCT, chroma upsampling and the colour
+conversion run on the device.  The frames go straight into ValTransforms.batch / TrainTransforms.batch / Mosaic.batch / evaluate /
+Visualizer.batch, which take CUDA uint8 frames as they are.  Files outside the baseline subset (progressive, arithmetic, 12-bit, CMYK,
+unusual sampling factors) are refused with a reason; there is no host decoder to fall back to.  `info` and `coefficients` need no GPU."""
+import ctypes
+import os
+
+import numpy as np
+
+from . import capi
+
+OK, UNSUPPORTED, CORRUPT, TOO_LARGE = 0, 1, 2, 3
+STATUS_NAMES = {OK: "ok", UNSUPPORTED: "unsupported", CORRUPT: "corrupt", TOO_LARGE: "too large"}
+
+
+def _buffer(blob):
+    """bytes-like -> (object that keeps the memory alive, address, length)."""
+    a = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    return a, a.ctypes.data, int(a.size)
+
+
+def info(blob):
+    """Header fields of one file (yn_jpeg_info; host only): dict(w, h, components, h_samp, v_samp, restart_interval, sof, status, reason)."""
+    lib = capi.load_library()
+    keep, ptr, n = _buffer(blob)
+    out = np.zeros(8, dtype=np.int32)
+    st = lib.yn_jpeg_info(ptr, n, out.ctypes.data)
+    return dict(w=int(out[0]), h=int(out[1]), components=int(out[2]), h_samp=int(out[3]), v_samp=int(out[4]), restart_interval=int(out[5]),
+                sof=int(out[6]), status=int(st), reason=lib.yn_jpeg_reason(None, 0).decode() if st else "")
+
+
+def coefficient_count(meta):
+    """int16 elements yn_jpeg_coefficients writes for a file with these header fields (the MCU-padded block grids, 64 per block)."""
+    mw = -(-meta["w"] // (8 * meta["h_samp"]))
+    mh = -(-meta["h"] // (8 * meta["v_samp"]))
+    blocks = mw * mh * (meta["h_samp"] * meta["v_samp"] + (2 if meta["components"] == 3 else 0))
+    return 64 * blocks
+
+
+def coefficients(blob):
+    """The entropy stage alone (yn_jpeg_coefficients; host only) -> dict(status, reason, coef = [int16 [bh, bw, 64] per component],
+    qt uint16 [3, 64] natural order, grid int32 [3, 2])."""
+    lib = capi.load_library()
+    meta = info(blob)
+    if meta["status"]:
+        return dict(status=meta["status"], reason=meta["reason"], coef=[], qt=None, grid=None)
+    keep, ptr, n = _buffer(blob)
+    cap = coefficient_count(meta)
+    flat = np.zeros(cap, dtype=np.int16)
+    qt = np.zeros((3, 64), dtype=np.uint16)
+    grid = np.zeros((3, 2), dtype=np.int32)
+    st = ctypes.c_int()
+    lib.yn_jpeg_coefficients(ptr, n, flat.ctypes.data, cap, qt.ctypes.data, grid.ctypes.data, ctypes.byref(st))
+    coef, off = [], 0
+    for c in range(meta["components"]):
+        k = int(grid[c, 0]) * int(grid[c, 1]) * 64
+        coef.append(flat[off:off + k].reshape(int(grid[c, 0]), int(grid[c, 1]), 64))
+        off += k
+    return dict(status=int(st.value), reason=lib.yn_jpeg_reason(None, 0).decode() if st.value else "", coef=coef, qt=qt, grid=grid)
+
+
+class JPEGDecoder(object):
+    """A yn_jpeg object: two pinned staging slots, so the host decodes one chunk while the previous one uploads and runs.
+    threads=None: min(16, $OMP_NUM_THREADS or 8) host workers.  Staging grows by itself (the object is recreated)."""
+
+    def __init__(self, max_batch=32, threads=None, handle=None, device=None, staging_bytes=None):
+        self.lib = capi.load_library()
+        self.max_batch = int(max_batch)
+        self.threads = int(threads) if threads is not None else min(16, int(os.environ.get("OMP_NUM_THREADS", 8)))
+        self._handle, self._device = handle, device
+        self.j = None
+        self.staging_bytes = 0
+        self._create(int(staging_bytes) if staging_bytes else self.max_batch * 640 * 480 * 3)       # 4:2:0 VGA frames to begin with
+
+    def _h(self, handle=None):
+        if handle is not None:
+            return handle
+        if self._handle is None:                               # a bare handle: only its stream / error plumbing is used
+            import torch
+            from . import arch
+            dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._handle = capi.Handle(32, 1, arch.MULTI_ANCHOR_SIZE, "1.0x", device=dev)
+        return self._handle
+
+    def _create(self, staging_bytes):
+        h = self._h()
+        self.close()
+        j = ctypes.c_void_p()
+        h._ck(self.lib.yn_jpeg_create(h.h, self.max_batch, int(staging_bytes), self.threads, ctypes.byref(j)), "yn_jpeg_create")
+        self.j, self.staging_bytes = j, int(staging_bytes)
+
+    def close(self):
+        if getattr(self, "j", None):
+            self.lib.yn_jpeg_destroy(self.j)
+            self.j = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    info = staticmethod(info)
+
+    def reason(self, i):
+        return self.lib.yn_jpeg_reason(self.j, int(i)).decode()
+
+    def timing(self, handle=None):
+        """{'host_ms', 'h2d_ms', 'kernel_ms'} of the last batch (yn_jpeg_timing; synchronises): the host entropy stage of the whole batch,
+        upload and kernels of its last chunk."""
+        h = self._h(handle)
+        ms = (ctypes.c_float * 3)()
+        h._ck(self.lib.yn_jpeg_timing(h.h, self.j, ctypes.cast(ms, ctypes.c_void_p)), "yn_jpeg_timing")
+        return {"host_ms": float(ms[0]), "h2d_ms": float(ms[1]), "kernel_ms": float(ms[2])}
+
+    def decode_into(self, blobs, frames, handle=None):
+        """yn_jpeg_decode_batch as it is: frames[i] a contiguous CUDA uint8 [h,w,3] tensor or None -> (statuses int32 [n], failed).
+        Raises capi.YnError when the batch does not fit the staging slots."""
+        h = self._h(handle)
+        n = len(blobs)
+        keep = [_buffer(b) for b in blobs]
+        data = (ctypes.c_void_p * max(n, 1))(*[k[1] for k in keep])
+        lens = np.array([k[2] for k in keep] + [0], dtype=np.int64)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[None if f is None else f.data_ptr() for f in frames])
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        failed = ctypes.c_int()
+        h._ck(self.lib.yn_jpeg_decode_batch(h.h, self.j, n, ctypes.cast(data, ctypes.c_void_p), lens.ctypes.data, ctypes.cast(ptrs, ctypes.c_void_p),
+                                            status.ctypes.data, ctypes.byref(failed)), "yn_jpeg_decode_batch")
+        return status[:n], int(failed.value)
+
+    def batch(self, blobs, errors="raise", handle=None):
+        """A list of JPEG files (bytes-like) -> a list of CUDA uint8 [h,w,3] BGR tensors.  A refused file raises ValueError naming its
+        index and the reason; with errors="none" its entry is None and the others are decoded.  Asynchronous on the handle's stream."""
+        import torch
+        assert errors in ("raise", "none")
+        h = self._h(handle)
+        h.follow_current_stream()
+        metas = [info(b) for b in blobs]
+        if errors == "raise":
+            for i, m in enumerate(metas):
+                if m["status"]:
+                    raise ValueError("JPEG %d is %s: %s" % (i, STATUS_NAMES.get(m["status"], "refused"), m["reason"]))
+        need = 0
+        for c0 in range(0, len(blobs), self.max_batch):
+            need = max(need, sum(2 * coefficient_count(m) for m in metas[c0:c0 + self.max_batch] if not m["status"]))
+        if need > self.staging_bytes:
+            self._create(max(need, 2 * self.staging_bytes))
+        frames = [None if m["status"] else torch.empty((m["h"], m["w"], 3), dtype=torch.uint8, device=h.device) for m in metas]
+        status, failed = self.decode_into(blobs, frames, handle=h)
+        if failed:
+            bad = [i for i in range(len(blobs)) if status[i]]
+            if errors == "raise":
+                raise ValueError("JPEG %d is %s: %s" % (bad[0], STATUS_NAMES.get(int(status[bad[0]]), "refused"), self.reason(bad[0])))
+            for i in bad:
+                frames[i] = None
+        return frames
+
+
+_default = {}
+
+
+def _decoder(device=None):
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev not in _default:
+        _default[dev] = JPEGDecoder(device=dev)
+    return _default[dev]
+
+
+def _read(src):
+    if isinstance(src, (bytes, bytearray, memoryview, np.ndarray)):
+        return src
+    with open(src, "rb") as f:
+        return f.read()
+
+
+def imread(path_or_bytes, device=None):
+    """cv2.imread(path) on the device: one uint8 [h,w,3] BGR CUDA tensor.  Raises ValueError for a file the decoder refuses."""
+    return _decoder(device).batch([_read(path_or_bytes)])[0]
+
+
+def imread_batch(paths, device=None, errors="raise"):
+    """imread for a list of paths (or bytes objects), decoded together."""
+    return _decoder(device).batch([_read(p) for p in paths], errors=errors)

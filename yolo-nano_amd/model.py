@@ -591,13 +591,18 @@ class ValTransforms(object):
 
 
     def batch(self, images, out=None):
-        """A list of uint8 HxWx3 BGR arrays (any sizes) -> (x float32 [n,3,size,size] on the device, scales, offsets): the loop
-        of benchmark.py:58 / vocapi_evaluator.py:64 over a batch, one kernel launch per 32 images."""
+        """A list of uint8 HxWx3 BGR frames (any sizes; numpy arrays, or CUDA uint8 tensors such as jpeg.imread's, which skip the
+        upload) -> (x float32 [n,3,size,size] on the device, scales, offsets): the loop of benchmark.py:58 / vocapi_evaluator.py:64
+        over a batch, one kernel launch per 32 images."""
         hd = self._h()
         dev_imgs, geoms, scales, offsets = [], [], [], []
         for im in images:
             rw, rh, left, top, scale, offset = self.geometry(im.shape[0], im.shape[1])
-            dev_imgs.append(torch.as_tensor(np.ascontiguousarray(im, dtype=np.uint8)).to(hd.device, non_blocking=True))
+            if isinstance(im, torch.Tensor):
+                assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "frames are uint8 [h,w,3]"
+                dev_imgs.append(im.to(hd.device, non_blocking=True).contiguous())
+            else:
+                dev_imgs.append(torch.as_tensor(np.ascontiguousarray(im, dtype=np.uint8)).to(hd.device, non_blocking=True))
             geoms.append((rw, rh, left, top)); scales.append(scale); offsets.append(offset)
         return hd.preprocess_batch(dev_imgs, geoms, self.size, self.mean, self.std, out=out), scales, offsets
 
