@@ -583,6 +583,10 @@ int  yn_op_conv3x3(yn_handle* h, const float* x, const float* x2, int resample, 
 /* stem: x NCHW [B,3,H,W] -> y NHWC [B,Ho,Wo,Cout], 3x3 stride 2 pad 1 (backbone/shufflenetv2.py:109) */
 int  yn_op_stem(yn_handle* h, const float* x_nchw, int B, int H, int W, int Cout,
                 const float* w, const float* bias, int act, float* y);
+/* the stem as the network runs it: conv + activation + max pool 3x3 stride 2 pad 1 in one kernel (stem_pool_kernel),
+ * x NCHW [B,3,H,W] -> y NHWC [B,Hp,Wp,Cout], Hp = ((H-1)/2+1 - 1)/2 + 1 */
+int  yn_op_stem_pool(yn_handle* h, const float* x_nchw, int B, int H, int W, int Cout,
+                     const float* w, const float* bias, int act, float* y);
 int  yn_op_maxpool3x3s2(yn_handle* h, const float* x, int B, int H, int W, int C, float* y);
 /* ShuffleV2Block (backbone/shufflenetv2.py:31-78), weights taken from the handle's loaded params:
  * block = "backbone.stage2.1" etc.  x [B,H,W,Cin] -> y [B,H/stride,W/stride,Cout]. */

@@ -103,6 +103,7 @@ SIGNATURES = {
     "yn_op_pwconv_shuffle": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_conv3x3": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_stem": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "yn_op_stem_pool": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_maxpool3x3s2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_shuffle_block": (_i32, [_vp, ctypes.c_char_p, _vp, _i32, _i32, _i32, _vp]),
     "yn_op_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
@@ -816,6 +817,16 @@ class Handle:
         y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout), dtype=torch.float32, device=x_nchw.device)
         self._ck(self.lib.yn_op_stem(self.h, _ptr(self._in(x_nchw)), B, H, W, Cout, _ptr(self._in(w)),
                                      _ptr(self._in(bias)) if bias is not None else None, act, y.data_ptr()), "yn_op_stem")
+        return y
+
+    def op_stem_pool(self, x_nchw, w, bias, act=0):
+        """The network's fused stem: conv 3x3 s2 + activation + max pool 3x3 s2, NCHW in, pooled NHWC out."""
+        B, _, H, W = x_nchw.shape
+        Cout = w.shape[0]
+        Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((B, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, Cout), dtype=torch.float32, device=x_nchw.device)
+        self._ck(self.lib.yn_op_stem_pool(self.h, _ptr(self._in(x_nchw)), B, H, W, Cout, _ptr(self._in(w)),
+                                          _ptr(self._in(bias)) if bias is not None else None, act, y.data_ptr()), "yn_op_stem_pool")
         return y
 
     def op_maxpool(self, x):

@@ -2054,7 +2054,24 @@ int yn_op_stem(yn_handle* h, const float* x, int B, int H, int W, int Cout, cons
     if (Cout != 24) return fail(h, "yn_op_stem: Cout must be 24");
     TmpLayer t(h, K_STEM, 3, Cout, 2, act, w, bias);
     if (t.rc) return fail(h, "yn_op_stem: out of memory");
-    launch_stem(x, B, H, W, t.l.w_packed, t.l.b_packed, Cout, act, y, h->stream);
+    {
+        Bracket br(h, "op.stem", 2.0 * B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 27 * Cout, 0.0);
+        launch_stem(x, B, H, W, t.l.w_packed, t.l.b_packed, Cout, act, y, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int yn_op_stem_pool(yn_handle* h, const float* x, int B, int H, int W, int Cout, const float* w, const float* bias, int act, float* y)
+{
+    YN_ENTER(h);
+    if (Cout != 24) return fail(h, "yn_op_stem_pool: Cout must be 24");
+    TmpLayer t(h, K_STEM, 3, Cout, 2, act, w, bias);
+    if (t.rc) return fail(h, "yn_op_stem_pool: out of memory");
+    {
+        Bracket br(h, "op.stem+maxpool", 2.0 * B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 27 * Cout, 0.0);
+        launch_stem_pool(x, B, H, W, t.l.w_packed, t.l.b_packed, Cout, act, y, h->stream);
+    }
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -2063,7 +2080,11 @@ int yn_op_maxpool3x3s2(yn_handle* h, const float* x, int B, int H, int W, int C,
 {
     YN_ENTER(h);
     if (C % 4) return fail(h, "yn_op_maxpool3x3s2: C must be a multiple of 4");
-    launch_maxpool(x, B, H, W, C, y, h->stream);
+    h->cur = h->stream;
+    {
+        Bracket br(h, "op.maxpool", 0.0, 0.0);
+        launch_maxpool(x, B, H, W, C, y, h->stream);
+    }
     HIPCHK(h, hipGetLastError());
     return 0;
 }
