@@ -556,7 +556,9 @@ int  yn_train_head_fork(yn_handle* h, int force, int* decision_host);
  * YN_F16: activations and activation gradients are STORED as fp16 (channel-padded NHWC, half the HBM bytes), every GEMM-shaped
  * conv (forward, input gradient, weight gradient) runs on the f16 MFMA with fp32 accumulation, BatchNorm statistics / parameter
  * gradients / the optimiser stay fp32 on the fp32 master weights, and the loss gradient is multiplied by a dynamic loss scale
- * kept on the device (halved when a step's gradients overflow — that step is skipped — doubled after 2000 clean steps). */
+ * kept on the device (halved when a step's gradients overflow — that step is skipped — doubled after 2000 clean steps).
+ * YN_F16 is refused, with a message, for a network with a BatchNorm, depthwise or biased layer above 256 padded channels (the 1.5x and
+ * 2.0x backbones: bf = 352 / 488): the step's reducing and BatchNorm kernels combine at most 32 channel octets.  Those train in fp32. */
 int  yn_train_precision(yn_handle* h, int dtype);
 /* Opt-in: the fp16 step replays everything between its host-side preparation and the optimiser (~540 launches on two streams) from a
  * hipGraph once the same (x, target, batch, grid) has been seen twice on a handle with a stream of its own; callers whose tensors'
@@ -601,6 +603,44 @@ int  yn_op_nhwc_to_nchw(yn_handle* h, const float* x, int B, int C, int H, int W
  * (stride 1|2), 2 dense 3x3; w / dw in the reference layouts; y = conv(x) + bias, dx / dw = the gradients for dy (null = skip). */
 int  yn_op_h16_conv(yn_handle* h, int kind, const float* x, int B, int H, int W, int Cin, int gapped, const float* w, const float* bias,
                     int Cout, int stride, const float* dy, float* y, float* dx, float* dw);
+/* yn_op_h16_conv with the argument forms the step itself uses.  Every launch under test runs inside a profile bracket of its own
+ * (yn_profile_enable: the records then name the kernels that ran, in order: forward, dx, dbias, dw, the combine).
+ *   x [B,H,W,x_ld], channels [x_off, x_off + Cin): the whole row (x_ld = Cin, x_off = 0), or one plane of an ungapped two-plane unit
+ *   tensor (x_ld = 2 Cin, x_off = 0 | Cin: staged as [x1 | pad][x2 | pad], the conv reads its plane in place); other slices are refused.
+ *   dx [B,H,W,dx_ld], in and out, same two forms: its contents are staged first, the input gradient is written (accumulate != 0: added)
+ *   into the conv's channels and the whole tensor comes back (fp16-rounded).
+ *   partial_cap: floats of weight-gradient scratch the launcher may use (0 = the entry's 4 Mi; at least one packed copy of dw).
+ *   dbias [Cout]: column sums of dy through hcol_reduce_kernel<3> into the gradient slots; dw and dbias are combined from the slots by
+ *   hgrad_finish_kernel (S = 1) as at the end of a step.  dw of a depthwise conv and dbias need at most 256 padded channels.
+ *   stat (depthwise stride 1, at most 256 padded channels): 1 = sums_fwd[0][c] = sum y, [1][c] = sum y^2 of the stored fp16 output;
+ *   2 = with the complete dense dx, sums_bwd as yn_op_h16_gemm_stats (y_below [B,H,W,Cin] in x's channel map).  Host double [2][Cin]. */
+int  yn_op_h16_conv2(yn_handle* h, int kind, const float* x, int B, int H, int W, int Cin, int gapped, int x_ld, int x_off,
+                     const float* w, const float* bias, int Cout, int stride, const float* dy, int accumulate, int dx_ld, int dx_off,
+                     int64_t partial_cap, int stat, const float* y_below, const float* mean, const float* invstd, const float* gamma,
+                     const float* beta, int act, float* y, float* dx, float* dw, float* dbias, double* sums_fwd, double* sums_bwd);
+/* The fp16 step's stem conv (3 -> 24, 3x3 stride 2 pad 1) over x [B,3,H,W] fp32 NCHW: y [B,Ho,Wo,24] (null = skip); with dy also
+ * dw [24][3][3][3] = hstem_wgrad_kernel's sums in zeroed gradient slots, combined by hgrad_finish_kernel (S = 1).  bias [24] or null. */
+int  yn_op_h16_stem(yn_handle* h, const float* x_nchw, int B, int H, int W, const float* w, const float* bias, const float* dy, float* y, float* dw);
+/* The fp16 step's 3x3 stride-2 max pool over x [B,H,W,C] (C a multiple of 8): y, idx [B,Ho,Wo,C] (one byte per element: the window
+ * position ky * 3 + kx of the first maximum in scan order); with dy also dx [B,H,W,C]. */
+int  yn_op_h16_maxpool(yn_handle* h, const float* x, int B, int H, int W, int C, const float* dy, float* y, uint8_t* idx, float* dx);
+/* The stem's BatchNorm + activation + max pool as the fp16 step fuses them, from the stem conv's output y [B,H,W,24]: statistics
+ * (hcol_reduce_kernel<0>), then hstem_apply_pool_kernel -> out, idx [B,Ho,Wo,24] (as yn_op_h16_maxpool), mean, invstd [24] (device);
+ * with the pooled tensor's gradient g1 [B,Ho,Wo,24]: hstem_bwd_kernel<0> and <1> -> dy [B,H,W,24], dgamma, dbeta [24]. */
+int  yn_op_h16_stem_pool(yn_handle* h, const float* y, int B, int H, int W, const float* gamma, const float* beta, int act, const float* g1,
+                         float* out, uint8_t* idx, float* mean, float* invstd, float* dy, float* dgamma, float* dbeta);
+/* hresample_kernel: the modes of yn_op_f32_resample on fp16 tensors (modes 2 / 3 add into the prior contents of out; H, W even for
+ * modes 0 / 2). */
+int  yn_op_h16_resample(yn_handle* h, int mode, const float* a, const float* b, float* out, int B, int H, int W, int C);
+/* hgather_kernel with every map argument of launch_hgather: dst[m][dp(j)] = src[m][sp(j)] for j < n, 0 for n <= j < npad, where
+ * sp(j) = l + (l >= src_half ? src_gap : 0), l = src_off + j * src_cs (dp alike).  src [M][src_ld] and dst [M][dst_ld] (in and out)
+ * are PHYSICAL rows, pads included.  A map that leaves a row is refused. */
+int  yn_op_h16_gather(yn_handle* h, const float* src, int src_ld, int src_off, int src_cs, int src_half, int src_gap,
+                      float* dst, int dst_ld, int dst_off, int dst_cs, int dst_half, int dst_gap, int64_t M, int n, int npad);
+/* The end of an fp16 backward pass: hgrad_finish_kernel (g[n] = (g + the 8 slot copies slots[8][n]) / S, overflow scan), then
+ * hscale_update_kernel (update 0: not run; 1: settles from the local flag; 2: from global_flag, as yn_sgd_step passes its
+ * bucket-wide one).  state: five 32-bit words on the HOST, in and out: S, 1 / S, clean steps, the overflow flag (an integer), pending. */
+int  yn_op_h16_grad_finish(yn_handle* h, float* g, const float* slots, int64_t n, float* state, int update, int global_flag);
 /* The column sums the fp16 step takes in its GEMM epilogues instead of separate reduction launches, on their own (kind 0 pointwise,
  * 2 dense 3x3; layouts as yn_op_h16_conv): y = conv(x) with sums_fwd[0][c] = sum y, sums_fwd[1][c] = sum y^2 over the STORED fp16
  * values (the train-mode BatchNorm statistics, utils/modules.py:12-21);  and, when dy is given, dx = the input gradient with
@@ -610,9 +650,12 @@ int  yn_op_h16_conv(yn_handle* h, int kind, const float* x, int B, int H, int W,
 int  yn_op_h16_gemm_stats(yn_handle* h, int kind, const float* x, int B, int H, int W, int Cin, int gapped, const float* w, int Cout,
                           float* y, double* sums_fwd, const float* dy, const float* y_below, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, int act, float* dx, double* sums_bwd);
-/* Train-mode BatchNorm (+ activation) forward over y [M][C] and, when dz is given, its backward: z, dy [M][C], dgamma, dbeta [C]. */
+/* Train-mode BatchNorm (+ activation) forward over y [M][C] and, when dz is given, its backward: z, dy [M][C], dgamma, dbeta [C].
+ * yn_op_h16_bn2 also returns the saved statistics mean, invstd [C] (device; null = skip).  C <= 256. */
 int  yn_op_h16_bn(yn_handle* h, const float* y, const float* dz, int64_t M, int C, const float* gamma, const float* beta, int act,
                   float* z, float* dy, float* dgamma, float* dbeta);
+int  yn_op_h16_bn2(yn_handle* h, const float* y, const float* dz, int64_t M, int C, const float* gamma, const float* beta, int act,
+                   float* z, float* dy, float* dgamma, float* dbeta, float* mean, float* invstd);
 /* The same BatchNorm as the last layer of a ShuffleV2 unit (backbone/shufflenetv2.py:69-78 with :14-28): forward writes the unit
  * output unit[m][2c] = pass[m][c], unit[m][2c+1] = act(BN(y))[m][c]  ([M][2C]: concat + channel_shuffle(2));  backward takes the unit
  * output's gradient dunit [M][2C] and returns dy [M][C] (through activation and BatchNorm), deven [M][C] = dunit[:, 0::2] (the

@@ -109,6 +109,15 @@ SIGNATURES = {
     "yn_op_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_h16_conv": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "yn_op_h16_conv2": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.c_int64,
+                               _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_op_h16_stem": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "yn_op_h16_maxpool": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "yn_op_h16_stem_pool": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_op_h16_resample": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
+    "yn_op_h16_gather": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_int64, _i32, _i32]),
+    "yn_op_h16_grad_finish": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _i32]),
+    "yn_op_h16_bn2": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_op_h16_bn": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "yn_op_h16_gemm_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "yn_op_h16_bn_unit": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -864,6 +873,17 @@ class Handle:
                                        int(act), z.data_ptr(), _ptr(dy), _ptr(dg), _ptr(db)), "yn_op_h16_bn")
         return z, dy, dg, db
 
+    def op_h16_bn2(self, y, gamma, beta, act=0, dz=None):
+        """op_h16_bn with the saved statistics: -> (z, dy, dgamma, dbeta, mean, invstd)."""
+        M, C = y.shape
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y.device)
+        z, mean, invstd = torch.empty_like(y), mk(C), mk(C)
+        dy, dg, db = (torch.empty_like(y), mk(C), mk(C)) if dz is not None else (None, None, None)
+        keep = [self._in(y), self._in(dz) if dz is not None else None]
+        self._ck(self.lib.yn_op_h16_bn2(self.h, keep[0].data_ptr(), _ptr(keep[1]), M, C, gamma.data_ptr(), beta.data_ptr(), int(act), z.data_ptr(),
+                                        _ptr(dy), _ptr(dg), _ptr(db), mean.data_ptr(), invstd.data_ptr()), "yn_op_h16_bn2")
+        return z, dy, dg, db, mean, invstd
+
     def train_graph(self, enable=None):
         """Switch the fp16 step's hipGraph replay (None: leave); -> number of steps served from a graph so far."""
         n = ctypes.c_int64(0)
@@ -895,6 +915,112 @@ class Handle:
         self._ck(self.lib.yn_op_h16_bn_unit(self.h, yc.data_ptr(), pc.data_ptr(), _ptr(dc), M, C, gamma.data_ptr(), beta.data_ptr(), int(act),
                                             unit.data_ptr(), _ptr(dy), _ptr(dev), _ptr(dg), _ptr(db)), "yn_op_h16_bn_unit")
         return unit, dy, dev, dg, db
+
+    def op_h16_conv2(self, kind, x, w, bias=None, stride=1, dy=None, gapped=False, x_off=0, cin=None, dx=None, dx_off=0, accumulate=False, partial_cap=0,
+                     stat=0, below=None, want=("dx", "dw", "dbias")):
+        """op_h16_conv with the step's own argument forms (include/yolonano_hip.h): x [B,H,W,x_ld] read at channels [x_off, x_off + cin); `dx`
+        given: the tensor [B,H,W,dx_ld] the input gradient is written (accumulate: added) into at [dx_off, dx_off + cin), else a zeroed one like
+        the conv's input; stat 1 / 2: the depthwise run kernel's statistics (below = (y_below, mean, invstd, gamma, beta, act) for 2).
+        -> dict y and, with dy, those of dx, dw, dbias named in `want`; sums_fwd / sums_bwd (numpy double [2][C])."""
+        import numpy as np
+        x = self._in(x)
+        B, H, W, x_ld = x.shape
+        Cin = int(cin) if cin is not None else x_ld - int(x_off)
+        Cout = w.shape[0]
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        out = {"y": mk(B, Ho, Wo, Cout)}
+        keep = [self._in(t) if t is not None else None for t in (w, bias, dy)]
+        if dy is not None:
+            if "dx" in want:
+                out["dx"] = torch.zeros((B, H, W, Cin), dtype=torch.float32, device=x.device) if dx is None else dx
+            if "dw" in want:
+                out["dw"] = torch.empty_like(keep[0])
+            if "dbias" in want:
+                out["dbias"] = mk(Cout)
+        sf = np.zeros((2, Cin), np.float64) if stat == 1 else None
+        sb = np.zeros((2, Cin), np.float64) if stat == 2 else None
+        bl = [self._in(t) for t in below[:5]] if below is not None else [None] * 5
+        act = int(below[5]) if below is not None else 0
+        dxt = out.get("dx")
+        self._ck(self.lib.yn_op_h16_conv2(self.h, int(kind), x.data_ptr(), B, H, W, Cin, int(bool(gapped)), x_ld, int(x_off), keep[0].data_ptr(), _ptr(keep[1]),
+                                          Cout, int(stride), _ptr(keep[2]), int(bool(accumulate)), dxt.shape[3] if dxt is not None else Cin, int(dx_off),
+                                          int(partial_cap), int(stat), _ptr(bl[0]), _ptr(bl[1]), _ptr(bl[2]), _ptr(bl[3]), _ptr(bl[4]), act,
+                                          out["y"].data_ptr(), _ptr(dxt), _ptr(out.get("dw")), _ptr(out.get("dbias")),
+                                          sf.ctypes.data if sf is not None else None, sb.ctypes.data if sb is not None else None), "yn_op_h16_conv2")
+        if sf is not None:
+            out["sums_fwd"] = sf
+        if sb is not None:
+            out["sums_bwd"] = sb
+        return out
+
+    def op_h16_stem(self, x_nchw, w, bias=None, dy=None):
+        """The fp16 step's stem conv over x [B,3,H,W] -> (y [B,Ho,Wo,24], dw like w or None)."""
+        x = self._in(x_nchw)
+        B, _, H, W = x.shape
+        y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 24), dtype=torch.float32, device=x.device)
+        keep = [self._in(t) if t is not None else None for t in (w, bias, dy)]
+        dw = torch.empty_like(keep[0]) if dy is not None else None
+        self._ck(self.lib.yn_op_h16_stem(self.h, x.data_ptr(), B, H, W, keep[0].data_ptr(), _ptr(keep[1]), _ptr(keep[2]), y.data_ptr(), _ptr(dw)), "yn_op_h16_stem")
+        return y, dw
+
+    def op_h16_maxpool(self, x, dy=None):
+        """The fp16 step's max pool over x [B,H,W,C]: -> (y, idx uint8 window positions, dx or None)."""
+        x = self._in(x)
+        B, H, W, C = x.shape
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+        idx = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=x.device)
+        dx = torch.empty_like(x) if dy is not None else None
+        dyc = self._in(dy) if dy is not None else None
+        self._ck(self.lib.yn_op_h16_maxpool(self.h, x.data_ptr(), B, H, W, C, _ptr(dyc), y.data_ptr(), idx.data_ptr(), _ptr(dx)), "yn_op_h16_maxpool")
+        return y, idx, dx
+
+    def op_h16_stem_pool(self, y, gamma, beta, act=1, g1=None):
+        """The fused stem BatchNorm + activation + max pool of the fp16 step over the conv output y [B,H,W,24] -> dict out, idx, mean, invstd and,
+        with g1 (the pooled tensor's gradient), dy, dgamma, dbeta."""
+        y = self._in(y)
+        B, H, W, C = y.shape
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=y.device)
+        out = {"out": mk(B, Ho, Wo, C), "idx": torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=y.device), "mean": mk(C), "invstd": mk(C)}
+        if g1 is not None:
+            out.update(dy=mk(B, H, W, C), dgamma=mk(C), dbeta=mk(C))
+        keep = [self._in(t) if t is not None else None for t in (gamma, beta, g1)]
+        if C != 24:
+            raise YnError("yn_op_h16_stem_pool: the stem has 24 channels")
+        self._ck(self.lib.yn_op_h16_stem_pool(self.h, y.data_ptr(), B, H, W, keep[0].data_ptr(), keep[1].data_ptr(), int(act), _ptr(keep[2]),
+                                              out["out"].data_ptr(), out["idx"].data_ptr(), out["mean"].data_ptr(), out["invstd"].data_ptr(),
+                                              _ptr(out.get("dy")), _ptr(out.get("dgamma")), _ptr(out.get("dbeta"))), "yn_op_h16_stem_pool")
+        return out
+
+    def op_h16_resample(self, mode, a, b=None, out=None):
+        """hresample_kernel's four modes (as op_f32_resample); modes 2 / 3 add into `out`.  H, W are those of `a`."""
+        B, H, W, C = a.shape
+        if out is None:
+            out = torch.empty_like(a)
+        keep = [self._in(a), self._in(b) if b is not None else None]
+        self._ck(self.lib.yn_op_h16_resample(self.h, int(mode), keep[0].data_ptr(), _ptr(keep[1]), out.data_ptr(), B, H, W, C), "yn_op_h16_resample")
+        return out
+
+    def op_h16_gather(self, src, dst, n, npad, src_off=0, src_cs=1, src_half=None, src_gap=0, dst_off=0, dst_cs=1, dst_half=None, dst_gap=0):
+        """hgather_kernel over physical rows src [M,src_ld] -> dst [M,dst_ld] (written in place, returned)."""
+        src = self._in(src)
+        M, src_ld = src.shape
+        dst_ld = dst.shape[1]
+        self._ck(self.lib.yn_op_h16_gather(self.h, src.data_ptr(), src_ld, int(src_off), int(src_cs), int(src_ld if src_half is None else src_half), int(src_gap),
+                                           dst.data_ptr(), dst_ld, int(dst_off), int(dst_cs), int(dst_ld if dst_half is None else dst_half), int(dst_gap),
+                                           M, int(n), int(npad)), "yn_op_h16_gather")
+        return dst
+
+    def op_h16_grad_finish(self, g, slots, state, update=0, global_flag=0):
+        """hgrad_finish_kernel (+ hscale_update_kernel: update 1 local flag, 2 global_flag) on g [n] (in place), slots [8,n]; state: numpy float32 [5]
+        (word 3 is an integer flag: read it through .view(np.uint32)) -> the state afterwards."""
+        import numpy as np
+        st = np.ascontiguousarray(state, dtype=np.float32).copy()
+        assert st.shape == (5,) and slots.shape == (8, g.numel()) and slots.is_contiguous() and g.is_contiguous()
+        self._ck(self.lib.yn_op_h16_grad_finish(self.h, g.data_ptr(), slots.data_ptr(), g.numel(), st.ctypes.data, int(update), int(global_flag)), "yn_op_h16_grad_finish")
+        return st
 
     def op_f32_conv(self, kind, x, w, bias=None, stride=1, dy=None, x_off=0, cin=None, y_ld=None, dx=None, accumulate=False, partial_cap=0,
                     want=("dx", "dw", "dbias")):

@@ -80,6 +80,20 @@ __device__ __forceinline__ f32x2 act_grad2(f32x2 g, f32x2 z, float negslope)
     m.y = z.y > 0.0f ? 1.0f : negslope;
     return g * m;
 }
+// act_grad2 for the BatchNorm backward APPLY (hbn_bwd_kernel, hstem_bwd_kernel<1>): the product is formed with contraction off, a rounded value of
+// its own.  Contracted into the subtraction of the batch mean of d that follows, it is the UNROUNDED product against a mean of rounded ones: a batch
+// of one row (a 1 x 1 map at batch 1) came back as the product's rounding residue times gamma * invstd (316 at zero variance) instead of zero under
+// LeakyReLU.  The SUM passes (hcol_reduce_kernel<2>, hstem_bwd_kernel<0>, the HColStat epilogues) keep act_grad2 and may fold the product into their
+// accumulate: their sum of d is then the sum of unrounded products, rounded once per add - the same value for one row, closer to exact for many;
+// the two phases agree to the rounding of one product per element, which the apply's fp32 arithmetic has anyway.
+__device__ __forceinline__ f32x2 act_grad2_rounded(f32x2 g, f32x2 z, float negslope)
+{
+#pragma clang fp contract(off)
+    f32x2 m;
+    m.x = z.x > 0.0f ? 1.0f : negslope;
+    m.y = z.y > 0.0f ? 1.0f : negslope;
+    return g * m;
+}
 __device__ __forceinline__ float act_negslope(int act) { return act == 1 ? 0.0f : (act == 2 ? 0.1f : 1.0f); }
 
 // =================================================================================================
@@ -91,7 +105,8 @@ __device__ __forceinline__ float act_negslope(int act) { return act == 1 ? 0.0f 
 // Block = 4 waves, each owning 32 rows x (32*NT) columns in NT 32x32 f32 accumulators; the block walks K in chunks of 32
 // (one A chunk = 128 rows x 4 octets, one B chunk = 4 octets x BN columns, staged through LDS with the next chunk's global
 // loads in flight during the MFMAs).  Epilogue through LDS: whole 16-byte row segments leave the block, optionally added to
-// what is already there (dX accumulation).  MFMA operand convention: lane l supplies row/column l%32 and the k-octet l/32 of
+// what is already there (dX accumulation).  The LDS tile is fp16, so an accumulated dX is rounded TWICE: the conv result to fp16, then its sum
+// with the prior value (the depthwise kernels add in fp32 and round once); tests/test_gpu_train_h16_ops.py gives those cases the second half spacing.  MFMA operand convention: lane l supplies row/column l%32 and the k-octet l/32 of
 // a 16-deep step for both A and B, so the k-sum is consistent whatever order the hardware walks the octet in.
 // =================================================================================================
 template <int NT, int TAPS, int STAT>       // STAT: 0 none, 1 forward statistics of the output, 2 BatchNorm-backward sums of the layer below (HColStat)
@@ -308,6 +323,12 @@ static void launch_hgemm_nt(const HGemmArgs& a, hipStream_t s)
     const int BN = 32 * NT;
     const dim3 grid(xcd_grid((unsigned)((a.M + 127) / 128)) * (unsigned)(a.Npad / BN));
     const int stat = !a.st.acc ? 0 : (a.st.y ? 2 : 1);
+    static const char* const names[4][2][3] = {
+        {{"hgemm_kernel<1,1,0>", "hgemm_kernel<1,1,1>", "hgemm_kernel<1,1,2>"}, {"hgemm_kernel<1,9,0>", "hgemm_kernel<1,9,1>", "hgemm_kernel<1,9,2>"}},
+        {{"hgemm_kernel<2,1,0>", "hgemm_kernel<2,1,1>", "hgemm_kernel<2,1,2>"}, {"hgemm_kernel<2,9,0>", "hgemm_kernel<2,9,1>", "hgemm_kernel<2,9,2>"}},
+        {{"hgemm_kernel<3,1,0>", "hgemm_kernel<3,1,1>", "hgemm_kernel<3,1,2>"}, {"hgemm_kernel<3,9,0>", "hgemm_kernel<3,9,1>", "hgemm_kernel<3,9,2>"}},
+        {{"hgemm_kernel<4,1,0>", "hgemm_kernel<4,1,1>", "hgemm_kernel<4,1,2>"}, {"hgemm_kernel<4,9,0>", "hgemm_kernel<4,9,1>", "hgemm_kernel<4,9,2>"}}};
+    set_last_kernel_name(names[NT - 1][a.taps == 9 ? 1 : 0][stat]);
     if (a.taps == 9) {
         if (stat == 0) hipLaunchKernelGGL((hgemm_kernel<NT, 9, 0>), grid, dim3(256), 0, s, a);
         else if (stat == 1) hipLaunchKernelGGL((hgemm_kernel<NT, 9, 1>), grid, dim3(256), 0, s, a);
@@ -612,12 +633,13 @@ void launch_hwgrad(const HWgradArgs& a, hipStream_t s)
     if ((long)slices * nk > (long)a.partial_cap) slices = (int)((long)a.partial_cap / nk);
     if (slices < 1) slices = 1;
     const dim3 grid(gn, gk, slices);
-#define YN_WG2(taps_, tn, tk) hipLaunchKernelGGL((hwgrad2_kernel<taps_, tn, tk>), grid, dim3(256), 0, s, a)
-    if (TN == 2 && TK == 2) { if (a.taps == 9) YN_WG2(9, 2, 2); else YN_WG2(1, 2, 2); }
-    else if (TN == 2) { if (a.taps == 9) YN_WG2(9, 2, 1); else YN_WG2(1, 2, 1); }
-    else if (TK == 2) { if (a.taps == 9) YN_WG2(9, 1, 2); else YN_WG2(1, 1, 2); }
-    else if (a.taps == 9) hipLaunchKernelGGL(hwgrad_kernel<9>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(hwgrad_kernel<1>, grid, dim3(256), 0, s, a);
+    // (the name covers both launches: the slice kernel and the reduction that follows it)
+#define YN_WG2(taps_, tn, tk) { set_last_kernel_name("hwgrad2_kernel<" #taps_ "," #tn "," #tk ">+hwgrad_reduce_kernel"); hipLaunchKernelGGL((hwgrad2_kernel<taps_, tn, tk>), grid, dim3(256), 0, s, a); }
+    if (TN == 2 && TK == 2) { if (a.taps == 9) YN_WG2(9, 2, 2) else YN_WG2(1, 2, 2) }
+    else if (TN == 2) { if (a.taps == 9) YN_WG2(9, 2, 1) else YN_WG2(1, 2, 1) }
+    else if (TK == 2) { if (a.taps == 9) YN_WG2(9, 1, 2) else YN_WG2(1, 1, 2) }
+    else if (a.taps == 9) { set_last_kernel_name("hwgrad_kernel<9>+hwgrad_reduce_kernel"); hipLaunchKernelGGL(hwgrad_kernel<9>, grid, dim3(256), 0, s, a); }
+    else { set_last_kernel_name("hwgrad_kernel<1>+hwgrad_reduce_kernel"); hipLaunchKernelGGL(hwgrad_kernel<1>, grid, dim3(256), 0, s, a); }
 #undef YN_WG2
     const long total = (long)a.N * a.taps * a.Kp;
     hipLaunchKernelGGL(hwgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(1024), 0, s, a.partial, slices, a.Np, a.Kp, a.taps,
@@ -823,11 +845,13 @@ void launch_hdw(const HDwArgs& a, hipStream_t s)
         const int NR = (int)((nb1 + cap - 1) / cap);
         const dim3 g2(xcd_grid((unsigned)((nb1 + NR - 1) / NR)));
         const int stat = !a.st.acc ? 0 : (a.st.y ? 2 : 1);
+        set_last_kernel_name(stat == 0 ? "hdw_run_kernel<0>" : (stat == 1 ? "hdw_run_kernel<1>" : "hdw_run_kernel<2>"));
         if (stat == 0) hipLaunchKernelGGL(hdw_run_kernel<0>, g2, dim3(256), 0, s, a, NR);
         else if (stat == 1) hipLaunchKernelGGL(hdw_run_kernel<1>, g2, dim3(256), 0, s, a, NR);
         else hipLaunchKernelGGL(hdw_run_kernel<2>, g2, dim3(256), 0, s, a, NR);
         return;
     }
+    set_last_kernel_name(a.stride == 1 ? "hdw_kernel<1>" : "hdw_kernel<2>");
     if (a.stride == 1) hipLaunchKernelGGL(hdw_kernel<1>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(hdw_kernel<2>, grid, dim3(256), 0, s, a);
 }
@@ -883,6 +907,7 @@ __global__ __launch_bounds__(256) void hdw_dgrad_s2_kernel(const h16* __restrict
 void launch_hdw_dgrad_s2(const h16* dy, int dy_ld, const float* w, int B, int H, int W, int Cp, h16* dx, int dx_ld, int dx_off, int accumulate, hipStream_t s)
 {
     const long total = (long)B * H * W * (Cp >> 3);
+    set_last_kernel_name("hdw_dgrad_s2_kernel");
     hipLaunchKernelGGL(hdw_dgrad_s2_kernel, dim3(xcd_grid((unsigned)((total + 255) / 256))), dim3(256), 0, s, dy, dy_ld, w, B, H, W, Cp, dx, dx_ld, dx_off, accumulate);
 }
 
@@ -1121,6 +1146,7 @@ void launch_hcol_reduce(const HRedArgs& a0, int mode, hipStream_t s)
     // (cross-wave combine + 2*C fp64 atomics) outweighs the extra loads in flight
     constexpr int gmax = 256;
     const dim3 grid(hreduce_blocks(a.M, 256 / a.lanes, gmax));
+    set_last_kernel_name(mode == 0 ? "hcol_reduce_kernel<0>" : (mode == 2 ? "hcol_reduce_kernel<2>" : "hcol_reduce_kernel<3>"));
     if (mode == 0) hipLaunchKernelGGL(hcol_reduce_kernel<0>, grid, dim3(256), 0, s, a);
     else if (mode == 2) hipLaunchKernelGGL(hcol_reduce_kernel<2>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(hcol_reduce_kernel<3>, grid, dim3(256), 0, s, a);
@@ -1250,6 +1276,7 @@ void launch_hbn_apply(const HBnApplyArgs& a0, hipStream_t s)
 {
     HBnApplyArgs a = a0;
     a.lanes = hlanes_for(a.Cp);
+    set_last_kernel_name("hbn_apply_kernel");
     hipLaunchKernelGGL(hbn_apply_kernel, dim3((unsigned)hstream_blocks(a.M, 256 / a.lanes)), dim3(256), 0, s, a);
 }
 
@@ -1320,7 +1347,7 @@ __global__ __launch_bounds__(256) void hbn_bwd_kernel(HRedArgs a, h16* dy /* may
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const f32x2 xh = bn_xhat2(pair_of(v, p), mu[p], is[p]);
-            const f32x2 d = act_grad2(pair_of(g, p), bn_value2(xh, ga[p], be[p]), negslope);
+            const f32x2 d = act_grad2_rounded(pair_of(g, p), bn_value2(xh, ga[p], be[p]), negslope);
             const f32x2 o = (ga[p] * is[p]) * (d - m0[p] - xh * m1[p]);
             r[2 * p] = (h16)o.x; r[2 * p + 1] = (h16)o.y;
         }
@@ -1381,6 +1408,7 @@ void launch_hbn_bwd(const HRedArgs& a0, h16* dy, float* dgamma, float* dbeta, hi
     if (!sums_done) launch_hcol_reduce(a0, 2, s);
     HRedArgs a = a0;
     a.lanes = hlanes_for(a.Cp);
+    set_last_kernel_name(sums_done ? "hbn_bwd_kernel" : "hcol_reduce_kernel<2>+hbn_bwd_kernel");
     hipLaunchKernelGGL(hbn_bwd_kernel, dim3((unsigned)hstream_blocks(a.M, 256 / a.lanes)), dim3(256), 0, s, a, dy, dgamma, dbeta);
 }
 
@@ -1504,6 +1532,9 @@ void launch_hdw_wgrad(const h16* dy, int dy_ld, const h16* x, int x_ld, int x_of
     if (G > gmax) G = gmax;
     if ((size_t)G * C * 9 > part_cap) G = (long)(part_cap / ((size_t)C * 9));
     if (G < 1) G = 1;
+    // (both launches, and the second one's grid rows)
+    set_last_kernel_name(stride == 1 ? (G >= 64 ? "hdw_wgrad_kernel<1>+hdw_wgrad_sum_kernel[16]" : "hdw_wgrad_kernel<1>+hdw_wgrad_sum_kernel[1]")
+                                     : (G >= 64 ? "hdw_wgrad_kernel<2>+hdw_wgrad_sum_kernel[16]" : "hdw_wgrad_kernel<2>+hdw_wgrad_sum_kernel[1]"));
     if (stride == 1) hipLaunchKernelGGL(hdw_wgrad_kernel<1>, dim3((unsigned)G), dim3(256), 0, s, dy, dy_ld, x, x_ld, x_off, B, H, W, C, Cp, half, gap, part, OL);
     else hipLaunchKernelGGL(hdw_wgrad_kernel<2>, dim3((unsigned)G), dim3(256), 0, s, dy, dy_ld, x, x_ld, x_off, B, H, W, C, Cp, half, gap, part, OL);
     const int n = C * 9;
@@ -1563,6 +1594,7 @@ __global__ __launch_bounds__(256) void hstem_kernel(const float* __restrict__ x,
 void launch_hstem(const float* x, int B, int H, int W, const float* w, const float* bias, h16* y, hipStream_t s)
 {
     const long total = (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+    set_last_kernel_name("hstem_kernel");
     hipLaunchKernelGGL(hstem_kernel, dim3(xcd_grid((unsigned)((total + 255) / 256))), dim3(256), 0, s, x, B, H, W, w, bias, y);
 }
 
@@ -1680,6 +1712,7 @@ void launch_hstem_wgrad(const h16* dy, const float* x, int B, int H, int W, floa
     constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
     if (G < 1) G = 1;
+    set_last_kernel_name("hstem_wgrad_kernel");
     hipLaunchKernelGGL(hstem_wgrad_kernel, dim3((unsigned)G), dim3(256), 0, s, dy, x, B, H, W, dw_slots, slot_stride);
 }
 
@@ -1774,11 +1807,13 @@ __global__ __launch_bounds__(256) void hmaxpool_bwd_kernel(const h16* __restrict
 void launch_hmaxpool_idx(const h16* x, int B, int H, int W, int Cp, h16* y, uint8_t* idx, hipStream_t s)
 {
     const long total = (long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (Cp >> 3);
+    set_last_kernel_name("hmaxpool_idx_kernel");
     hipLaunchKernelGGL(hmaxpool_idx_kernel, dim3(xcd_grid((unsigned)((total + 255) / 256))), dim3(256), 0, s, x, B, H, W, Cp, y, idx);
 }
 void launch_hmaxpool_bwd(const h16* dy, const uint8_t* idx, int B, int H, int W, int Cp, h16* dx, hipStream_t s)
 {
     const long total = (long)B * H * W * (Cp >> 3);
+    set_last_kernel_name("hmaxpool_bwd_kernel");
     hipLaunchKernelGGL(hmaxpool_bwd_kernel, dim3(xcd_grid((unsigned)((total + 255) / 256))), dim3(256), 0, s, dy, idx, B, H, W, Cp, dx);
 }
 
@@ -1891,6 +1926,7 @@ void launch_hstem_apply_pool(const HBnApplyArgs& a, int B, int H, int W, h16* ou
     long G = (npix + 84) / 85;
     constexpr int gmax = 2048;
     if (G > gmax) G = gmax;
+    set_last_kernel_name("hstem_apply_pool_kernel");
     hipLaunchKernelGGL(hstem_apply_pool_kernel, dim3((unsigned)(G < 1 ? 1 : G)), dim3(256), 0, s, a, B, H, W, out, idx);
 }
 
@@ -1977,9 +2013,9 @@ __global__ __launch_bounds__(256) void hstem_bwd_kernel(HRedArgs a, const h16* _
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const f32x2 xh = bn_xhat2(pair_of(v, p), k.mu[p], k.is[p]);
-                const f32x2 d = act_grad2(pair_of(g, p), bn_value2(xh, k.ga[p], k.be[p]), negslope);
-                if (PHASE == 0) { t0[p] += d; t1[p] = __builtin_elementwise_fma(d, xh, t1[p]); }
-                else { const f32x2 o = (k.ga[p] * k.is[p]) * (d - m0[p] - xh * m1[p]); r[2 * p] = (h16)o.x; r[2 * p + 1] = (h16)o.y; }
+                const f32x2 zz = bn_value2(xh, k.ga[p], k.be[p]);
+                if (PHASE == 0) { const f32x2 d = act_grad2(pair_of(g, p), zz, negslope); t0[p] += d; t1[p] = __builtin_elementwise_fma(d, xh, t1[p]); }
+                else { const f32x2 d = act_grad2_rounded(pair_of(g, p), zz, negslope); const f32x2 o = (k.ga[p] * k.is[p]) * (d - m0[p] - xh * m1[p]); r[2 * p] = (h16)o.x; r[2 * p + 1] = (h16)o.y; }
             }
             if (PHASE == 1) sth8(dy + (size_t)pi * C + oc * 8, r);
             else if (++batch == 4) {                            // fp32 over four pixels, then into the double accumulators (hcol_reduce_kernel's batches)
@@ -2023,6 +2059,7 @@ void launch_hstem_bwd(const HRedArgs& a, const h16* g1, const uint8_t* idx, int 
     constexpr long g0 = 2048, g1n = 2048;
     long G = (npix + 84) / 85;
     const long G0 = G > g0 ? g0 : G, G1 = G > g1n ? g1n : G;
+    set_last_kernel_name("hstem_bwd_kernel<0>+hstem_bwd_kernel<1>");
     hipLaunchKernelGGL(hstem_bwd_kernel<0>, dim3((unsigned)G0), dim3(256), 0, s, a, g1, idx, B, H, W, dy, dgamma, dbeta);
     hipLaunchKernelGGL(hstem_bwd_kernel<1>, dim3((unsigned)G1), dim3(256), 0, s, a, g1, idx, B, H, W, dy, dgamma, dbeta);
 }
@@ -2081,6 +2118,7 @@ void launch_hresample(const h16* a, const h16* b, h16* out, int B, int H, int W,
     long blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
+    set_last_kernel_name("hresample_kernel");
     hipLaunchKernelGGL(hresample_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, b, out, B, H, W, Cp, mode);
 }
 
@@ -2111,6 +2149,7 @@ void launch_hgather(const h16* src, int src_ld, int src_off, int src_cs, int src
     long blocks = (M * npad + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
+    set_last_kernel_name("hgather_kernel");
     hipLaunchKernelGGL(hgather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, src_ld, src_off, src_cs, src_half, src_gap,
                        dst, dst_ld, dst_off, dst_cs, dst_half, dst_gap, M, n, npad);
 }
@@ -2186,20 +2225,24 @@ __global__ __launch_bounds__(256) void hpack_all_kernel(const HPackDesc* __restr
 }
 void launch_hpack_all(const HPackDesc* table_dev, int n, hipStream_t s)
 {
+    set_last_kernel_name("hpack_all_kernel");
     hipLaunchKernelGGL(hpack_all_kernel, dim3(16, (unsigned)n), dim3(256), 0, s, table_dev);
 }
 
 void launch_hpack_gemm(const float* w, int Cout, int Cin, int taps, int in_half, int in_gap, int Kp, int Npad, int backward, h16* out, hipStream_t s)
 {
     const long total = (long)Cout * Cin * taps;
+    set_last_kernel_name("hpack_gemm_kernel");
     hipLaunchKernelGGL(hpack_gemm_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, Cout, Cin, taps, in_half, in_gap, Kp, Npad, backward, out);
 }
 void launch_hpack_dw(const float* w, const float* bias, int C, int half, int gap, int Cp, int flip, float* out, float* bias_out, hipStream_t s)
 {
+    set_last_kernel_name("hpack_dw_kernel");
     hipLaunchKernelGGL(hpack_dw_kernel, dim3((unsigned)((C * 9 + 255) / 256)), dim3(256), 0, s, w, bias, C, half, gap, Cp, flip, out, bias_out);
 }
 void launch_hpack_stem(const float* w, float* out, hipStream_t s)
 {
+    set_last_kernel_name("hpack_stem_kernel");
     hipLaunchKernelGGL(hpack_stem_kernel, dim3(3), dim3(256), 0, s, w, out);
 }
 
@@ -2225,11 +2268,13 @@ __global__ __launch_bounds__(256) void hunstage_kernel(const h16* __restrict__ s
 void launch_hstage(const float* src, int C, h16* dst, int ld, int half, int gap, long M, hipStream_t s)
 {
     long blocks = (M * C + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    set_last_kernel_name("hstage_kernel");
     hipLaunchKernelGGL(hstage_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, C, dst, ld, half, gap, M);
 }
 void launch_hunstage(const h16* src, int ld, int half, int gap, float* dst, int C, long M, hipStream_t s)
 {
     long blocks = (M * C + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    set_last_kernel_name("hunstage_kernel");
     hipLaunchKernelGGL(hunstage_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, ld, half, gap, dst, C, M);
 }
 
@@ -2248,6 +2293,7 @@ void launch_rows_to_f32(const void* src, int is_h16, int src_ld, float* dst, int
     long blocks = (M * n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
+    set_last_kernel_name(is_h16 ? "rows_to_f32_kernel<h16>" : "rows_to_f32_kernel<float>");
     if (is_h16) hipLaunchKernelGGL(rows_to_f32_kernel<h16>, dim3((unsigned)blocks), dim3(256), 0, s, (const h16*)src, src_ld, dst, n, M);
     else hipLaunchKernelGGL(rows_to_f32_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)src, src_ld, dst, n, M);
 }
@@ -2298,11 +2344,13 @@ void launch_hgrad_finish(float* g, const float* slots, long n, size_t stride, fl
 {
     long blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
+    set_last_kernel_name("hgrad_finish_kernel");
     hipLaunchKernelGGL(hgrad_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, slots, n, stride, state);
 }
 
 void launch_hscale_update(float* state, const int* global_flag, hipStream_t s)
 {
+    set_last_kernel_name("hscale_update_kernel");
     hipLaunchKernelGGL(hscale_update_kernel, dim3(1), dim3(64), 0, s, state, global_flag);
 }
 

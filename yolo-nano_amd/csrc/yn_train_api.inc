@@ -217,6 +217,16 @@ int yn_train_precision(yn_handle* h, int dtype)
 {
     YN_ENTER(h);
     if (dtype != YN_F32 && dtype != YN_F16) return fail(h, "yn_train_precision: unknown dtype %d", dtype);
+    if (dtype == YN_F16) {
+        // the fp16 step's reducing and BatchNorm kernels (hcol_reduce_kernel, hdw_wgrad_kernel, hbn_apply_kernel, hbn_bwd_kernel) combine at most 32
+        // octet lanes and keep 256 channel constants in LDS: a layer above 256 padded channels (bf = 352 / 488 of the 1.5x / 2.0x backbones) is refused
+        // here, not computed wrongly.  A depthwise conv may read a two-plane unit tensor: 2 * roundup8(C / 2) physical channels.
+        for (const Layer& l : h->layers) {
+            if (l.kind == K_STEM || (l.bn.empty() && l.kind != K_DW && !l.has_bias)) continue;
+            const int Cp = l.kind == K_DW ? 2 * r8((l.cout + 1) / 2) : r8(l.cout);
+            if (Cp > 256) return fail(h, "yn_train_precision: the fp16 step serves layers of at most 256 padded channels; %s has %d (the 0.5x and 1.0x backbones fit, 1.5x and 2.0x train in fp32)", l.name.c_str(), l.cout);
+        }
+    }
     h->train_dtype = dtype;
     return 0;
 }
