@@ -728,6 +728,37 @@ const char* yn_jpeg_reason(yn_jpeg* j, int i);
 /* Measurement (synchronises): ms3 = host entropy stage of the last batch (wall clock), upload and kernels of its last chunk (HIP events). */
 int  yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3);
 
+/* ---- baseline JPEG encode: every stage on the device, the finished files come down ------------------------------------------------------
+ * The files cv2.imwrite(path_jpg, frame) / PIL's save write with libjpeg's defaults (JDCT_ISLOW, the Annex K tables, no optimisation, JFIF
+ * 1.01 header), byte for byte: three components, sampling 4:2:0 (jpeg_set_defaults), 4:2:2 or 4:4:4, numbered 2, 1, 0 as PIL numbers them. */
+typedef struct yn_jpeg_enc yn_jpeg_enc;
+/* Host only.  jpeg_set_quality(quality, TRUE): the luma and chroma tables for quality 1..100, [2][64] in natural order.  1 = bad argument. */
+int  yn_jpeg_quant_tables(int quality, uint16_t* qt2x64_natural);
+/* Host only, no handle, no GPU.  The 623 bytes libjpeg writes before the entropy-coded data: SOI, JFIF APP0, two DQT, SOF0, four DHT
+ * (DC0, AC0, DC1, AC1), SOS.  1 = bad argument (a side outside 1..16384, quality outside 1..100, unknown sampling). */
+int  yn_jpeg_header(int w, int h, int quality, int sampling, uint8_t* out623);
+/* An encoder for the handle's device, for up to max_batch (1..1024) frames a call.  stream_bytes (1024..2^32) is the size of the output
+ * buffer that receives the files of one call, and of the unstuffed bit stream beside it; the per-block buffers grow with the frames. */
+int  yn_jpeg_enc_create(yn_handle* h, int max_batch, int64_t stream_bytes, yn_jpeg_enc** out);
+void yn_jpeg_enc_destroy(yn_jpeg_enc* enc);
+/* cv2.imwrite's compression for n frames at once: frames_host[i] is a DEVICE pointer to uint8 [h_i][w_i][3] BGR, geom_host [n][2] = w_i, h_i.
+ * Returns once the work is enqueued on the handle's stream.  Refused (1) before anything is launched, naming the image where there is one:
+ * null pointers, n above max_batch, a side outside 1..16384, a quality outside 1..100, an unknown sampling, a batch of more than 2^24 blocks
+ * (the worst case of its unstuffed stream cannot be staged).  A refused call leaves the previous batch as it was: it can still be
+ * fetched.  n == 0 is no error: it leaves an empty batch. */
+int  yn_jpeg_encode_batch(yn_handle* h, yn_jpeg_enc* enc, int n, const uint8_t* const* frames_host, const int32_t* geom_host, int quality, int sampling);
+/* Synchronises.  offsets_host [n + 1]: file i of the last batch is files_host[offsets[i] .. offsets[i + 1]); one read-back of the offsets, one
+ * copy of offsets[n] bytes.  An image whose file did not fit the encoder's buffers was not written at all: the call fails (1), naming the
+ * image and the bytes the batch needs; so it does when cap is below offsets[n] (offsets_host is filled either way). */
+int  yn_jpeg_encode_fetch(yn_handle* h, yn_jpeg_enc* enc, int64_t* offsets_host, uint8_t* files_host, int64_t cap);
+/* Testing aid (synchronises): the quantised coefficients of image i of the last batch, in exactly yn_jpeg_coefficients' layout. */
+int  yn_jpeg_enc_coefficients(yn_handle* h, yn_jpeg_enc* enc, int i, int16_t* host, int64_t cap);
+/* Testing aid (synchronises): the 64 bytes the encoder keeps behind its output buffer; every one is 0xA5 unless something wrote out of bounds. */
+int  yn_jpeg_enc_guard(yn_handle* h, yn_jpeg_enc* enc, uint8_t* host64);
+/* Measurement (synchronises): ms10 = HIP event times of the last batch: table upload + clearing the stream, fdct, bits, scan tiles, scan sums
+ * + stream layout, emit, 0xFF count, scan tiles, scan sums + file layout, files. */
+int  yn_jpeg_enc_timing(yn_handle* h, yn_jpeg_enc* enc, float* ms10);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every kernel launch of yn_forward_raw / yn_infer is bracketed by a pair of HIP
  * events recorded on the handle's stream (graph replay is bypassed while enabled).  After the

@@ -167,6 +167,15 @@ SIGNATURES = {
     "yn_jpeg_decode_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
     "yn_jpeg_reason": (ctypes.c_char_p, [_vp, _i32]),
     "yn_jpeg_timing": (_i32, [_vp, _vp, _vp]),
+    "yn_jpeg_quant_tables": (_i32, [_i32, _vp]),
+    "yn_jpeg_header": (_i32, [_i32, _i32, _i32, _i32, _vp]),
+    "yn_jpeg_enc_create": (_i32, [_vp, _i32, ctypes.c_int64, ctypes.POINTER(_vp)]),
+    "yn_jpeg_enc_destroy": (None, [_vp]),
+    "yn_jpeg_encode_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32]),
+    "yn_jpeg_encode_fetch": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_int64]),
+    "yn_jpeg_enc_coefficients": (_i32, [_vp, _vp, _i32, _vp, ctypes.c_int64]),
+    "yn_jpeg_enc_guard": (_i32, [_vp, _vp, _vp]),
+    "yn_jpeg_enc_timing": (_i32, [_vp, _vp, _vp]),
     "yn_profile_enable": (_i32, [_vp, _i32]),
     "yn_profile_count": (_i32, [_vp]),
     "yn_profile_get": (_i32, [_vp, _i32, ctypes.c_char_p, _i32, ctypes.c_char_p, _i32, ctypes.POINTER(_f32),

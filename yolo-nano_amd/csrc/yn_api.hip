@@ -69,6 +69,7 @@ struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
 struct yn_jpeg { ynk::JpegState* st; };      // likewise (kernels_jpeg.hip)
+struct yn_jpeg_enc { ynk::JpegEncState* st; };      // likewise (kernels_jpeg_enc.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
 // test-time augmentation for whole batches (kernels_tta.hip): every buffer is allocated once, for max_batch images and the largest scale
 struct yn_tta {
@@ -2645,6 +2646,78 @@ int yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3)
     YN_ENTER(h);
     if (!j || !ms3) return fail(h, "yn_jpeg_timing: null argument");
     YN_EVAL_CALL(ynk::jpeg_timing(j->st, ms3, err));
+}
+
+// ---- baseline JPEG encode: every stage on the device (kernels_jpeg_enc.hip) ------------------------------------------------------------
+int yn_jpeg_quant_tables(int quality, uint16_t* qt2x64_natural)
+{
+    if (!qt2x64_natural || quality < 1 || quality > 100) return 1;
+    ynk::jpeg_quant_tables(quality, qt2x64_natural);
+    return 0;
+}
+
+int yn_jpeg_header(int w, int h, int quality, int sampling, uint8_t* out623)
+{
+    if (!out623 || w < 1 || w > 16384 || h < 1 || h > 16384 || quality < 1 || quality > 100 || sampling < 0 || sampling > 2) return 1;
+    ynk::jpeg_header(w, h, quality, sampling ? 2 : 1, sampling == 2 ? 2 : 1, out623);
+    return 0;
+}
+
+int yn_jpeg_enc_create(yn_handle* h, int max_batch, int64_t stream_bytes, yn_jpeg_enc** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_jpeg_enc_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::JpegEncState* st = nullptr;
+    if (ynk::jpeg_enc_create(h->cfg.device, max_batch, stream_bytes, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_jpeg_enc{st};
+    return 0;
+}
+
+void yn_jpeg_enc_destroy(yn_jpeg_enc* enc)
+{
+    if (!enc) return;
+    ynk::jpeg_enc_destroy(enc->st);
+    delete enc;
+}
+
+#define YN_JPEG_ENC_ENTER(name)                                                                                                           \
+    YN_ENTER(h);                                                                                                                          \
+    if (!enc) return fail(h, name ": null object");                                                                                       \
+    if (ynk::jpeg_enc_device(enc->st) != h->cfg.device)                                                                                   \
+        return fail(h, name ": the object was made for device %d, the handle is on device %d", ynk::jpeg_enc_device(enc->st), h->cfg.device)
+
+int yn_jpeg_encode_batch(yn_handle* h, yn_jpeg_enc* enc, int n, const uint8_t* const* frames_host, const int32_t* geom_host, int quality, int sampling)
+{
+    YN_JPEG_ENC_ENTER("yn_jpeg_encode_batch");
+    YN_EVAL_CALL(ynk::jpeg_encode_batch(enc->st, h->stream, n, frames_host, geom_host, quality, sampling, err));
+}
+
+int yn_jpeg_encode_fetch(yn_handle* h, yn_jpeg_enc* enc, int64_t* offsets_host, uint8_t* files_host, int64_t cap)
+{
+    YN_JPEG_ENC_ENTER("yn_jpeg_encode_fetch");
+    YN_EVAL_CALL(ynk::jpeg_encode_fetch(enc->st, h->stream, offsets_host, files_host, cap, err));
+}
+
+int yn_jpeg_enc_coefficients(yn_handle* h, yn_jpeg_enc* enc, int i, int16_t* host, int64_t cap)
+{
+    YN_JPEG_ENC_ENTER("yn_jpeg_enc_coefficients");
+    YN_EVAL_CALL(ynk::jpeg_enc_coefficients(enc->st, h->stream, i, host, cap, err));
+}
+
+int yn_jpeg_enc_guard(yn_handle* h, yn_jpeg_enc* enc, uint8_t* host64)
+{
+    YN_JPEG_ENC_ENTER("yn_jpeg_enc_guard");
+    if (!host64) return fail(h, "yn_jpeg_enc_guard: null argument");
+    YN_EVAL_CALL(ynk::jpeg_enc_guard(enc->st, h->stream, host64, err));
+}
+
+int yn_jpeg_enc_timing(yn_handle* h, yn_jpeg_enc* enc, float* ms10)
+{
+    YN_JPEG_ENC_ENTER("yn_jpeg_enc_timing");
+    if (!ms10) return fail(h, "yn_jpeg_enc_timing: null argument");
+    YN_EVAL_CALL(ynk::jpeg_enc_timing(enc->st, ms10, err));
 }
 
 }  // extern "C"

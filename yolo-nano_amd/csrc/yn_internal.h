@@ -300,6 +300,19 @@ int  jpeg_timing(JpegState* j, float* ms3, std::string& err);
 int  jpeg_info(const uint8_t* data, int64_t len, int32_t* info8, std::string& reason);
 int  jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef, int64_t cap, uint16_t* qt, int32_t* grid, int64_t* needed, std::string& reason);
 
+// ---- baseline JPEG encode (kernels_jpeg_enc.hip): the state behind yn_jpeg_enc; 0 = ok, 1 = error (text in err) ---------------------------
+struct JpegEncState;
+void jpeg_quant_tables(int quality, uint16_t* qt2x64);                                      // host only; quality 1..100, natural order
+void jpeg_header(int w, int h, int quality, int hs, int vs, uint8_t* out623);               // host only
+int  jpeg_enc_create(int device, int max_batch, int64_t stream_bytes, JpegEncState** out, std::string& err);
+void jpeg_enc_destroy(JpegEncState* j);
+int  jpeg_enc_device(const JpegEncState* j);
+int  jpeg_encode_batch(JpegEncState* j, hipStream_t s, int n, const uint8_t* const* frames, const int32_t* geom, int quality, int sampling, std::string& err);
+int  jpeg_encode_fetch(JpegEncState* j, hipStream_t s, int64_t* offsets, uint8_t* files, int64_t cap, std::string& err);
+int  jpeg_enc_coefficients(JpegEncState* j, hipStream_t s, int i, int16_t* host, int64_t cap, std::string& err);
+int  jpeg_enc_guard(JpegEncState* j, hipStream_t s, uint8_t* host64, std::string& err);
+int  jpeg_enc_timing(JpegEncState* j, float* ms10, std::string& err);
+
 // ---- training loss (kernels_train.hip) --------------------------------------------------------------
 int  loss_num_blocks(const GridInfo& g, int B);
 void launch_loss(const float* conf, const float* cls, const float* t, const float* const head[3], float* const ghead[3],

@@ -6,7 +6,12 @@
 The Huffman stage runs on the host, threaded over the files of a batch; dequantisation, the inverse DCT, chroma upsampling and the colour
 conversion run on the device.  The frames go straight into ValTransforms.batch / TrainTransforms.batch / Mosaic.batch / evaluate /
 Visualizer.batch, which take CUDA uint8 frames as they are.  Files outside the baseline subset (progressive, arithmetic, 12-bit, CMYK,
-unusual sampling factors) are refused with a reason; there is no host decoder to fall back to.  `info` and `coefficients` need no GPU."""
+unusual sampling factors) are refused with a reason; there is no host decoder to fall back to.  `info` and `coefficients` need no GPU.
+
+    imwrite("000001.jpg", frame)                        # the stand-in for cv2.imwrite in test.py / demo.py (yn_jpeg_enc_*)
+    files = JPEGEncoder(max_batch=32).batch(frames)     # bytes objects: the whole encoder runs on the device, the files come down
+
+`quant_tables` and `header` need no GPU."""
 import ctypes
 import os
 
@@ -187,3 +192,188 @@ def imread(path_or_bytes, device=None):
 def imread_batch(paths, device=None, errors="raise"):
     """imread for a list of paths (or bytes objects), decoded together."""
     return _decoder(device).batch([_read(p) for p in paths], errors=errors)
+
+
+# ---- the writer: cv2.imwrite(path_jpg, frame) on the device (yn_jpeg_enc_* / yn_jpeg_encode_*, DESIGN 25) ------------------------------
+SAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+HEADER_BYTES = 623
+
+
+def _sampling(sampling):
+    if sampling in SAMPLINGS:
+        return SAMPLINGS[sampling]
+    if sampling in (0, 1, 2):
+        return int(sampling)
+    raise ValueError("sampling %r is not one of %s" % (sampling, ", ".join(sorted(SAMPLINGS))))
+
+
+def quant_tables(quality):
+    """jpeg_set_quality(quality, TRUE) (yn_jpeg_quant_tables; host only) -> uint16 [2, 64]: luma and chroma, natural order."""
+    qt = np.zeros((2, 64), dtype=np.uint16)
+    if capi.load_library().yn_jpeg_quant_tables(int(quality), qt.ctypes.data):
+        raise ValueError("quality %r outside 1..100" % (quality,))
+    return qt
+
+
+def header(w, h, quality=95, sampling="4:2:0"):
+    """The 623 bytes libjpeg writes before the entropy-coded data (yn_jpeg_header; host only)."""
+    out = np.zeros(HEADER_BYTES, dtype=np.uint8)
+    if capi.load_library().yn_jpeg_header(int(w), int(h), int(quality), _sampling(sampling), out.ctypes.data):
+        raise ValueError("no header for %r x %r at quality %r" % (w, h, quality))
+    return out.tobytes()
+
+
+class JPEGEncoder(object):
+    """A yn_jpeg_enc object: frames (CUDA uint8 [h,w,3] BGR tensors, as imread and Visualizer.batch produce) -> the bytes of the files
+    cv2.imwrite / PIL write from them with libjpeg's defaults.  The whole encoder runs on the device; the finished files are what comes
+    down.  The output buffer grows by itself (the object is recreated and the chunk runs again).
+    Parity with the file cv2 itself writes is unpinned, because cv2 is not in the image: PIL runs the same libjpeg with the same defaults."""
+
+    def __init__(self, max_batch=32, quality=95, sampling="4:2:0", handle=None, device=None, stream_bytes=None):
+        self.lib = capi.load_library()
+        self.max_batch, self.quality, self.sampling = int(max_batch), int(quality), sampling
+        _sampling(sampling)
+        self._handle, self._device = handle, device
+        self.e = None
+        self.stream_bytes = 0
+        self._pinned = None
+        self._n, self._geom, self._samp = 0, [], _sampling(sampling)      # the last encode(): nothing yet, fetch() gives []
+        self._create(int(stream_bytes) if stream_bytes else max(self.max_batch * 640 * 480 * 3 // 4, 1 << 16))      # a quarter of VGA frames to begin with
+
+    _h = JPEGDecoder._h
+
+    def _create(self, stream_bytes, handle=None):
+        h = self._h(handle)                                    # the object belongs to this handle's device
+        keep = self._pinned                                    # the landing buffer outlives a regrow
+        self.close()
+        self._n, self._geom, self._pinned = 0, [], keep
+        e = ctypes.c_void_p()
+        h._ck(self.lib.yn_jpeg_enc_create(h.h, self.max_batch, int(stream_bytes), ctypes.byref(e)), "yn_jpeg_enc_create")
+        self.e, self.stream_bytes = e, int(stream_bytes)
+
+    def close(self):
+        if getattr(self, "e", None):
+            self.lib.yn_jpeg_enc_destroy(self.e)
+            self.e = None
+        self._pinned = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, frames, quality=None, sampling=None, handle=None):
+        """yn_jpeg_encode_batch as it is (at most max_batch frames, asynchronous).  Raises capi.YnError for a refused batch."""
+        h = self._h(handle)
+        n = len(frames)
+        for i, f in enumerate(frames):
+            if not (f.is_cuda and str(f.dtype) == "torch.uint8" and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
+                raise ValueError("frame %d is not a contiguous CUDA uint8 [h,w,3] tensor" % i)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[f.data_ptr() for f in frames])
+        geom = np.array([[f.shape[1], f.shape[0]] for f in frames] + [[0, 0]], dtype=np.int32)
+        h._ck(self.lib.yn_jpeg_encode_batch(h.h, self.e, n, ctypes.cast(ptrs, ctypes.c_void_p), geom.ctypes.data,
+                                            self.quality if quality is None else int(quality), _sampling(self.sampling if sampling is None else sampling)),
+              "yn_jpeg_encode_batch")
+        self._n, self._geom = n, [(int(g[0]), int(g[1])) for g in geom[:n]]
+        self._samp = _sampling(self.sampling if sampling is None else sampling)
+
+    def fetch(self, handle=None):
+        """yn_jpeg_encode_fetch -> the files of the last encode() as a list of bytes.  Raises capi.YnError when an image did not fit.
+        The pinned landing buffer follows the files (a quarter more than the largest batch so far), not the encoder's capacity."""
+        import torch
+        h = self._h(handle)
+        if self._pinned is None:
+            self._pinned = torch.empty(min(self.stream_bytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        offsets = np.zeros(self._n + 1, dtype=np.int64)
+        rc = self.lib.yn_jpeg_encode_fetch(h.h, self.e, offsets.ctypes.data, self._pinned.data_ptr(), self._pinned.numel())
+        if rc == 1 and "the caller's buffer" in self.lib.yn_last_error(h.h).decode():      # offsets are filled: make room, fetch again
+            self._pinned = torch.empty(int(offsets[self._n]) + int(offsets[self._n]) // 4, dtype=torch.uint8, pin_memory=True)
+            rc = self.lib.yn_jpeg_encode_fetch(h.h, self.e, offsets.ctypes.data, self._pinned.data_ptr(), self._pinned.numel())
+        h._ck(rc, "yn_jpeg_encode_fetch")
+        blob = self._pinned.numpy()
+        return [blob[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(self._n)]
+
+    def coefficients(self, i, handle=None):
+        """The quantised coefficients of image i of the last encode() (yn_jpeg_enc_coefficients), as `coefficients` returns a file's:
+        [int16 [bh, bw, 64] per component], natural order, MCU-padded grids."""
+        h = self._h(handle)
+        w, hh = self._geom[i]
+        hs, vs = {0: (1, 1), 1: (2, 1), 2: (2, 2)}[self._samp]
+        mw, mh = -(-w // (8 * hs)), -(-hh // (8 * vs))
+        grids = [(mh * vs, mw * hs), (mh, mw), (mh, mw)]
+        flat = np.zeros(64 * sum(a * b for a, b in grids), dtype=np.int16)
+        h._ck(self.lib.yn_jpeg_enc_coefficients(h.h, self.e, int(i), flat.ctypes.data, flat.size), "yn_jpeg_enc_coefficients")
+        out, off = [], 0
+        for a, b in grids:
+            out.append(flat[off:off + 64 * a * b].reshape(a, b, 64))
+            off += 64 * a * b
+        return out
+
+    def guard_intact(self, handle=None):
+        """True while the 64 bytes behind the output buffer are untouched (yn_jpeg_enc_guard)."""
+        h = self._h(handle)
+        g = np.zeros(64, dtype=np.uint8)
+        h._ck(self.lib.yn_jpeg_enc_guard(h.h, self.e, g.ctypes.data), "yn_jpeg_enc_guard")
+        return bool((g == 0xA5).all())
+
+    def timing(self, handle=None):
+        """Milliseconds of the last encode() per stage (yn_jpeg_enc_timing; synchronises)."""
+        h = self._h(handle)
+        ms = (ctypes.c_float * 10)()
+        h._ck(self.lib.yn_jpeg_enc_timing(h.h, self.e, ctypes.cast(ms, ctypes.c_void_p)), "yn_jpeg_enc_timing")
+        return dict(zip(("upload_clear", "fdct", "bits", "scan_tiles", "scan_sums_layout", "emit", "ff_count", "ff_scan_tiles", "ff_scan_sums_layout", "files"),
+                        [float(v) for v in ms]))
+
+    def batch(self, frames, quality=None, sampling=None, handle=None):
+        """A list of frames -> a list of bytes objects, each a complete JPEG file.  More than max_batch frames are encoded in chunks."""
+        import re
+        h = self._h(handle)
+        h.follow_current_stream()
+        q = self.quality if quality is None else int(quality)
+        s = _sampling(self.sampling if sampling is None else sampling)
+        out = []
+        for c0 in range(0, len(frames), self.max_batch):
+            chunk = list(frames[c0:c0 + self.max_batch])
+            while True:
+                self.encode(chunk, q, s, handle=h)
+                try:
+                    out += self.fetch(handle=h)
+                    break
+                except capi.YnError as err:
+                    m = re.search(r"needs (\d+) output bytes and (\d+) stream bytes", str(err))
+                    if m is None:
+                        raise
+                    self._create(max(2 * self.stream_bytes, int(m.group(1)) + int(m.group(1)) // 64 + 1024, int(m.group(2))), handle=h)
+        return out
+
+
+_default_enc = {}
+
+
+def _encoder(device=None):
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev not in _default_enc:
+        _default_enc[dev] = JPEGEncoder(device=dev)
+    return _default_enc[dev]
+
+
+def imencode(frame, quality=95, sampling="4:2:0"):
+    """cv2.imencode(".jpg", frame) on the device: the bytes of the file."""
+    return _encoder(frame.device).batch([frame], quality=quality, sampling=sampling)[0]
+
+
+def imwrite(path, frame, quality=95, sampling="4:2:0"):
+    """cv2.imwrite(path_jpg, frame) for a CUDA uint8 [h,w,3] BGR frame."""
+    with open(path, "wb") as f:
+        f.write(imencode(frame, quality=quality, sampling=sampling))
+
+
+def imwrite_batch(paths, frames, quality=95, sampling="4:2:0"):
+    """imwrite for a list of paths and frames, encoded together."""
+    assert len(paths) == len(frames)
+    files = _encoder(frames[0].device).batch(list(frames), quality=quality, sampling=sampling) if frames else []
+    for p, b in zip(paths, files):
+        with open(p, "wb") as f:
+            f.write(b)
