@@ -495,7 +495,8 @@ int  yn_loss_heads(yn_handle* h, const float* head_s8_dev, const float* head_s16
  * gradient sum:  g = grads*grad_scale + wd*p ; buf = first_step ? g : momentum*buf + g ; p -= lr*buf.
  * A bucket that holds a NaN or Inf leaves parameters and momentum untouched — the reference skips an iteration whose loss is
  * NaN (train.py:225-226); after the data-parallel all-reduce every rank sees the same non-finite bucket, so all ranks skip
- * together without a host round trip.  yn_train_skipped_steps reads the number of skipped updates (synchronises). */
+ * together without a host round trip (every finite gradient, +-FLT_MAX included, is a step).  n = 0 does nothing.
+ * yn_train_skipped_steps reads the number of skipped updates (synchronises). */
 int  yn_sgd_step(yn_handle* h, float* params_dev, const float* grads_dev, float* momentum_buf_dev, int64_t n,
                  float lr, float momentum, float weight_decay, float grad_scale, int first_step);
 
@@ -641,6 +642,13 @@ int  yn_op_h16_gather(yn_handle* h, const float* src, int src_ld, int src_off, i
  * hscale_update_kernel (update 0: not run; 1: settles from the local flag; 2: from global_flag, as yn_sgd_step passes its
  * bucket-wide one).  state: five 32-bit words on the HOST, in and out: S, 1 / S, clean steps, the overflow flag (an integer), pending. */
 int  yn_op_h16_grad_finish(yn_handle* h, float* g, const float* slots, int64_t n, float* state, int update, int global_flag);
+/* The fp16 step's loss on its own (loss_kernel<true, fp16> + loss_reduce_kernel): the three dense fp32 raw heads [B,S/s,S/s,A(5+C)] are
+ * rounded to fp16 rows of the step's physical width (A(5+C) rounded up to a multiple of 8: 80 for VOC's 75, 256 for COCO's 255), the
+ * gradient rows are zeroed as the step zeroes them, `scale` (> 0) is the loss scale of a state block of this call's own.  losses [4]
+ * (device, fp32); g_* (device, all three or none): the head gradients * scale as the kernel stored them in fp16, dense fp32;
+ * pad_nonzero (host, may be null): how many elements of the gradient rows' pad columns are not +0. */
+int  yn_op_h16_loss(yn_handle* h, const float* head_s8, const float* head_s16, const float* head_s32, const float* target, int B, float scale,
+                    float* losses, float* g_s8, float* g_s16, float* g_s32, int* pad_nonzero);
 /* The column sums the fp16 step takes in its GEMM epilogues instead of separate reduction launches, on their own (kind 0 pointwise,
  * 2 dense 3x3; layouts as yn_op_h16_conv): y = conv(x) with sums_fwd[0][c] = sum y, sums_fwd[1][c] = sum y^2 over the STORED fp16
  * values (the train-mode BatchNorm statistics, utils/modules.py:12-21);  and, when dy is given, dx = the input gradient with

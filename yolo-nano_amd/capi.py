@@ -117,6 +117,7 @@ SIGNATURES = {
     "yn_op_h16_resample": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
     "yn_op_h16_gather": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.c_int64, _i32, _i32]),
     "yn_op_h16_grad_finish": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _i32]),
+    "yn_op_h16_loss": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
     "yn_op_h16_bn2": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_op_h16_bn": (_i32, [_vp, _vp, _vp, ctypes.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "yn_op_h16_gemm_stats": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
@@ -554,23 +555,31 @@ class Handle:
         return res
 
     # ---- training loss
-    def loss(self, conf, cls, txtytwth, target, grads=True):
+    def loss(self, conf, cls, txtytwth, target, grads=True, out=None):
         """tools.loss + iou_score + decode on the reference's split prediction layout.
-        -> (losses [4] device tensor, (g_conf, g_cls, g_txtytwth) or None)"""
+        -> (losses [4] device tensor, (g_conf, g_cls, g_txtytwth) or None); out: the three gradient tensors to write into."""
         B = cls.shape[0]
         conf, cls, t, target = (self._in(v) for v in (conf, cls, txtytwth, target))
         losses = torch.empty((4,), dtype=torch.float32, device=cls.device)
-        g = (torch.empty_like(conf), torch.empty_like(cls), torch.empty_like(t)) if grads else (None, None, None)
+        g = (None, None, None)
+        if grads:
+            g = (torch.empty_like(conf), torch.empty_like(cls), torch.empty_like(t)) if out is None else tuple(out)
+            for v, like in zip(g, (conf, cls, t)):
+                assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.shape == like.shape
         self._ck(self.lib.yn_loss(self.h, conf.data_ptr(), cls.data_ptr(), t.data_ptr(), target.data_ptr(), B, losses.data_ptr(),
                                   _ptr(g[0]), _ptr(g[1]), _ptr(g[2])), "yn_loss")
         return losses, (g if grads else None)
 
-    def loss_heads(self, heads, target, grads=True):
-        """Same, directly on the three raw NHWC head tensors; gradients come back in the head layout."""
+    def loss_heads(self, heads, target, grads=True, out=None):
+        """Same, directly on the three raw NHWC head tensors; gradients come back in the head layout (out: the three tensors to write into)."""
         B = heads[0].shape[0]
         target = self._in(target)
         losses = torch.empty((4,), dtype=torch.float32, device=target.device)
-        g = [torch.empty_like(t) for t in heads] if grads else [None, None, None]
+        g = [None, None, None]
+        if grads:
+            g = [torch.empty_like(t) for t in heads] if out is None else list(out)
+            for v, like in zip(g, heads):
+                assert v.is_cuda and v.is_contiguous() and v.dtype == torch.float32 and v.shape == like.shape
         self._ck(self.lib.yn_loss_heads(self.h, _ptr(heads[0]), _ptr(heads[1]), _ptr(heads[2]), target.data_ptr(), B, losses.data_ptr(),
                                         _ptr(g[0]), _ptr(g[1]), _ptr(g[2])), "yn_loss_heads")
         return losses, (g if grads else None)
@@ -1030,6 +1039,19 @@ class Handle:
         assert st.shape == (5,) and slots.shape == (8, g.numel()) and slots.is_contiguous() and g.is_contiguous()
         self._ck(self.lib.yn_op_h16_grad_finish(self.h, g.data_ptr(), slots.data_ptr(), g.numel(), st.ctypes.data, int(update), int(global_flag)), "yn_op_h16_grad_finish")
         return st
+
+    def op_h16_loss(self, heads, target, scale=1.0, grads=True):
+        """The fp16 step's loss alone (yn_op_h16_loss): dense fp32 raw heads, staged as fp16 rows of the step's width -> (losses [4] device tensor,
+        the three head gradients * scale as dense fp32 or None, the count of pad-column elements of the fp16 gradient rows that are not +0)."""
+        heads = [self._in(t) for t in heads]
+        B = heads[0].shape[0]
+        target = self._in(target)
+        losses = torch.empty((4,), dtype=torch.float32, device=target.device)
+        g = [torch.empty_like(t) for t in heads] if grads else [None, None, None]
+        pad = _i32(-1)
+        self._ck(self.lib.yn_op_h16_loss(self.h, heads[0].data_ptr(), heads[1].data_ptr(), heads[2].data_ptr(), target.data_ptr(), B, float(scale),
+                                         losses.data_ptr(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), ctypes.byref(pad)), "yn_op_h16_loss")
+        return losses, (g if grads else None), int(pad.value)
 
     def op_f32_conv(self, kind, x, w, bias=None, stride=1, dy=None, x_off=0, cin=None, y_ld=None, dx=None, accumulate=False, partial_cap=0,
                     want=("dx", "dw", "dbias")):

@@ -8,6 +8,7 @@
 //                       reference's split layout conf [B,N], cls [B,N,C], txtytwth [B,N,4]; HEADS = true: read
 //                       from / write gradients to the three raw NHWC head tensors directly (no re-layout pass).
 //   loss_reduce_kernel  deterministic final sum of the per-block partials.
+#include <cfloat>
 #include "yn_internal.h"
 #include "yn_h16.h"
 
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256) void grad_finite_kernel(const float* __restric
     bool bad = false;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float v = g[i];
-        bad |= !(fabsf(v) <= 3.0e38f);                      // false for NaN and Inf
+        bad |= !(fabsf(v) <= FLT_MAX);                      // true for a NaN and for +-Inf only: every finite gradient is a step
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }

@@ -1917,7 +1917,8 @@ int yn_sgd_step(yn_handle* h, float* params, const float* grads, float* momentum
                 float lr, float momentum, float weight_decay, float grad_scale, int first_step)
 {
     YN_ENTER(h);
-    if (n < 0 || !params || !grads || !momentum_buf) return fail(h, "yn_sgd_step: bad arguments");
+    if (n < 0 || (n > 0 && (!params || !grads || !momentum_buf))) return fail(h, "yn_sgd_step: bad arguments");
+    if (n == 0) return 0;                                   // an empty bucket: nothing to scan, nothing to step
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) return fail(h, "yn_sgd_step: buffers must be 16-byte aligned");
     if (!h->skip_flag) {
         HIPCHK(h, h->skip_flag.reserve(2));

@@ -566,5 +566,58 @@ int yn_op_h16_grad_finish(yn_handle* h, float* g, const float* slots, int64_t n,
     return 0;
 }
 
+// ---- the fp16 step's loss (loss_kernel<true, h16> + loss_reduce_kernel) on its own: the dense fp32 raw heads [B,S/s,S/s,A(5+C)] are staged as
+//      fp16 rows of the step's physical width (HTrainer::head_ld), the gradient rows are zeroed as the tape zeroes gout_all, the loss scale sits in
+//      a state block of its own.  losses [4] (device); g_* (all or none): the head gradients as dense fp32; pad_nonzero (host, may be null): the
+//      elements of the fp16 gradient rows' pad columns that are not +0 ----
+int yn_op_h16_loss(yn_handle* h, const float* head_s8, const float* head_s16, const float* head_s32, const float* target, int B, float scale,
+                   float* losses, float* g_s8, float* g_s16, float* g_s32, int* pad_nonzero)
+{
+    YN_ENTER(h);
+    if (!head_s8 || !head_s16 || !head_s32 || !target || B <= 0 || !losses || !(scale > 0.0f)) return fail(h, "yn_op_h16_loss: bad arguments");
+    if ((g_s8 != nullptr) != (g_s16 != nullptr) || (g_s8 != nullptr) != (g_s32 != nullptr)) return fail(h, "yn_op_h16_loss: pass all three gradient buffers or none");
+    if (ensure_loss(h, B)) return 1;
+    hipStream_t st = h->stream;
+    h->cur = st;
+    GridInfo g = h->grid;
+    const int HC = g.A * (5 + g.C), HCp = HTrainer::head_ld(HC), pad = HCp - HC;
+    g.head_ld = HCp;
+    const float* const src[3] = {head_s8, head_s16, head_s32};
+    float* const dst[3] = {g_s8, g_s16, g_s32};
+    long M[3], Mall = 0;
+    for (int k = 0; k < 3; ++k) { M[k] = (long)B * g.hw[k]; Mall += M[k]; }
+    Scratch hv((size_t)Mall * HCp * sizeof(h16), st), hg(g_s8 ? (size_t)Mall * HCp * sizeof(h16) : 0, st);      // (zero-filled: the value rows' pads, the gradient rows)
+    Scratch state(5 * sizeof(float), st), padf(g_s8 && pad ? (size_t)Mall * pad * sizeof(float) : 0, st);
+    if (!hv.p || !hg.p || !state.p || !padf.p) return fail(h, "yn_op_h16_loss: out of memory");
+    const float sv[2] = {scale, 1.0f / scale};
+    HIPCHK(h, hipMemcpyAsync(state.p, sv, sizeof(sv), hipMemcpyHostToDevice, st));
+    const h16* heads[3]; h16* gheads[3];
+    long off = 0;
+    for (int k = 0; k < 3; ++k) {
+        heads[k] = hv.as<h16>() + (size_t)off * HCp; gheads[k] = g_s8 ? hg.as<h16>() + (size_t)off * HCp : nullptr;
+        launch_hstage(src[k], HC, hv.as<h16>() + (size_t)off * HCp, HCp, HC, 0, M[k], st);
+        off += M[k];
+    }
+    {
+        Bracket br(h, "op.h16.loss", 0.0, 0.0);
+        launch_loss_h16(heads, g_s8 ? gheads : nullptr, target, g, B, h->loss_partial, losses, state.as<float>(), st);
+    }
+    int bad = 0;
+    if (g_s8) {
+        for (int k = 0; k < 3; ++k) launch_rows_to_f32(gheads[k], 1, HCp, dst[k], HC, M[k], st);
+        if (pad) {                                              // the pad columns of all three levels (one block of rows) as [Mall][pad] floats
+            launch_rows_to_f32(hg.as<h16>() + HC, 1, HCp, padf.as<float>(), pad, Mall, st);
+            std::vector<uint32_t> host((size_t)Mall * pad);
+            HIPCHK(h, hipMemcpyAsync(host.data(), padf.p, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+            for (uint32_t v : host) bad += v != 0u;
+        }
+    }
+    if (pad_nonzero) *pad_nonzero = bad;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(st));
+    return 0;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop
