@@ -105,8 +105,8 @@ int  yn_fuse_decode(yn_handle* h, int enable);
  * a speed switch for A/B runs. */
 int  yn_group_launch(yn_handle* h, int enable);
 /* A stride-2 ShuffleV2 unit (backbone/shufflenetv2.py:30-51, 73-74: branch 2 = pointwise -> depthwise stride 2 -> pointwise, branch 1 =
- * depthwise stride 2 -> pointwise, then concat + channel shuffle) as ONE kernel where its tile fits (input channels <= 32, branch
- * width <= 64: stage 2, whose intermediate is the largest tensor of the network); the wider units (stages 3 / 4, branch width <= 256) as
+ * depthwise stride 2 -> pointwise, then concat + channel shuffle) as ONE kernel for the widths it is built for (24 input channels,
+ * branch width 58 or 24: stage 2 of 1.0x / 0.5x, whose intermediate is the largest tensor of the network); the wider units (stages 3 / 4, branch width <= 256) as
  * their first pointwise conv + ONE kernel for everything behind it.  Default on, split-f16 family only, bit-identical to the five
  * launches. */
 int  yn_down_fuse(yn_handle* h, int enable);
@@ -594,6 +594,10 @@ int  yn_op_maxpool3x3s2(yn_handle* h, const float* x, int B, int H, int W, int C
 /* ShuffleV2Block (backbone/shufflenetv2.py:31-78), weights taken from the handle's loaded params:
  * block = "backbone.stage2.1" etc.  x [B,H,W,Cin] -> y [B,H/stride,W/stride,Cout]. */
 int  yn_op_shuffle_block(yn_handle* h, const char* block, const float* x, int B, int H, int W, float* y);
+/* A stride-2 ShuffleV2Block as the ONE kernel yn_down_fuse selects inside the network (stage 2 of 1.0x / 0.5x), on any even map:
+ * x [B,H,W,Cin] -> y [B,H/2,W/2,Cout].  Split-f16 family; independent of yn_down_fuse and yn_set_pw_config.  An error where that kernel
+ * does not cover the block or the handle is on the exact-f32 family: yn_op_shuffle_block is the five-launch form. */
+int  yn_op_down_unit(yn_handle* h, const char* block, const float* x, int B, int H, int W, float* y);
 /* NCHW <-> NHWC helpers for the tests and the host shim */
 int  yn_op_nchw_to_nhwc(yn_handle* h, const float* x, int B, int C, int H, int W, float* y);
 int  yn_op_nhwc_to_nchw(yn_handle* h, const float* x, int B, int C, int H, int W, float* y);

@@ -106,6 +106,7 @@ SIGNATURES = {
     "yn_op_stem_pool": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_maxpool3x3s2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_shuffle_block": (_i32, [_vp, ctypes.c_char_p, _vp, _i32, _i32, _i32, _vp]),
+    "yn_op_down_unit": (_i32, [_vp, ctypes.c_char_p, _vp, _i32, _i32, _i32, _vp]),
     "yn_op_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_h16_conv": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -866,6 +867,13 @@ class Handle:
         B, H, W, _ = x.shape
         y = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, cout), dtype=torch.float32, device=x.device)
         self._ck(self.lib.yn_op_shuffle_block(self.h, block.encode(), _ptr(self._in(x)), B, H, W, y.data_ptr()), "yn_op_shuffle_block")
+        return y
+
+    def op_down_unit(self, block, x, cout):
+        """A stride-2 block as the one-kernel unit (down_unit_pipe_kernel) on any even map; raises where that kernel does not cover it."""
+        B, H, W, _ = x.shape
+        y = torch.empty((B, H // 2, W // 2, cout), dtype=torch.float32, device=x.device)
+        self._ck(self.lib.yn_op_down_unit(self.h, block.encode(), _ptr(self._in(x)), B, H, W, y.data_ptr()), "yn_op_down_unit")
         return y
 
     def op_h16_conv(self, kind, x, w, bias=None, stride=1, dy=None, gapped=False):

@@ -687,7 +687,7 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
 // anything).  One tile = 8 x 4 OUTPUT pixels of one image: pw1 on the 17 x 9 input pixels the tile's depthwise windows cover (20 %
 // recomputed on tile borders; K = cin <= 32 is one chunk), y1 in an fp32 LDS tile (zero outside the image: the depthwise conv pads its
 // INPUT), depthwise -> split planes, pw2 (K = bf <= 64: two chunks) on wavefronts 0..NP-1 while wavefronts NP..2NP-1 run branch 1's
-// pointwise conv, and the concat + shuffle is the store.  x is read once (x 1.2) and `out` written once: 80 MB per step instead of
+// pointwise conv, the concat + shuffle happens in an LDS tile and all four wavefronts store it in 16-byte row pieces.  x is read once (x 1.2) and `out` written once: 80 MB per step instead of
 // 360 MB in five launches.  Every sum runs in the order of gemm_split_kernel / dwconv3x3_kernel: bit-identical to the five launches
 // (test_down_unit_is_bit_identical).
 // The kernel is a software pipeline (round 4).  With one tile per workgroup the load phase was 10 k of a workgroup's 25 k cycles (one
@@ -702,13 +702,20 @@ static bool unit_chain_dispatch(const ChainArgs& a, hipStream_t s, bool dry)
 //     k-step - down2_kernel's register-direct form) are loaded ONCE per workgroup into 48 registers, like the depthwise taps.  No
 //     weight ever passes through LDS.  LDS 78 KB with the fp32 window: two workgroups per CU.
 // -------------------------------------------------------------------------------------------------
-template <int NP, bool RELU>                                 // RELU: the three pointwise convs end in ReLU, the depthwise convs in nothing (ShuffleNetV2)
+// The widths are template parameters (the model family has two shapes here: (cin, bf) = (24, 58) at 1.0x and (24, 24) at 0.5x; anything else
+// takes the down2 path, down_unit_covers): every item loop has a compile-time trip count and is unrolled - the LDS reads of a wavefront's
+// GEMM-1 items and of a thread's depthwise outputs are issued together, the depthwise fma chains interleave - and the per-tile index
+// arithmetic divides by constants: 48.9 -> 37.4 us at 416 x 416, bs = 32.
+template <int CIN, int BF, bool RELU>                        // RELU: the three pointwise convs end in ReLU, the depthwise convs in nothing (ShuffleNetV2)
 __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int tiles)
 {
+    constexpr int NP = (BF + 31) / 32;
     constexpr int TW = 8, TH = 4, WW = 2 * TW + 1, WH = 2 * TH + 1, NPIX = WW * WH, RT1 = (NPIX + 31) / 32;
-    constexpr int BN = 32 * NP, AST1 = 32 + 8, AST2 = BN + 8, NO = TW * TH, NLD = 5, KS2 = 2 * NP;
+    constexpr int BN = 32 * NP, AST1 = 32 + 8, AST2 = BN + 8, NO = TW * TH, KS2 = 2 * NP;
+    constexpr int bf = BF, CS = bf + 2, cin = CIN, cq = cin >> 2;
+    constexpr int NLD = (WH * WW * cq + 255) / 256;                  // 16-byte window pieces per thread
+    static_assert(CIN >= 16 && CIN <= 32 && !(CIN & 3) && BF <= 64 && !(BF & 1) && BF / 2 <= 256, "down_unit_covers");
     extern __shared__ __attribute__((aligned(16))) float du_smem[];
-    const int bf = a.bf, CS = bf + 2, cin = a.cin, cq = cin >> 2;
     h16* A1h = reinterpret_cast<h16*>(du_smem);                  // [RT1*32][AST1] x 2: pw1's operand planes
     h16* A1l = A1h + RT1 * 32 * AST1;
     h16* A2h = A1h;                                                // behind GEMM 1: [NO][AST2] x 2 (pw2), then [NO][AST1] x 2 (branch 1)
@@ -722,7 +729,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
     const int Ho = a.H >> 1, Wo = a.W >> 1;
     const int tx_n = (Wo + TW - 1) / TW, ty_n = (Ho + TH - 1) / TH, per_img = tx_n * ty_n;
-    const int KQ1 = (cin + 7) >> 3, KQ2 = (bf + 7) >> 3;
+    constexpr int KQ1 = (cin + 7) >> 3, KQ2 = (bf + 7) >> 3;
     // the walk: XCD x = blockIdx & 7 owns tiles [x * TL, (x + 1) * TL)
     const int TL = (tiles + 7) >> 3, GL = (int)(gridDim.x >> 3);
     const int tbase = (int)(blockIdx.x & 7u) * TL;
@@ -738,16 +745,16 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
 #endif
     YN_TS();
     // ---- loop invariants: depthwise taps and biases of both branches, the B fragments of this wavefront's columns --------------------
-    const int cp_n = bf >> 1, ppl = 256 / cp_n;
+    constexpr int cp_n = bf >> 1, ppl = 256 / cp_n, NI2 = (NO + ppl - 1) / ppl;      // channel pairs, pixel lanes, outputs per thread of branch 2's depthwise conv
     const int cp = t % cp_n, dpl = t / cp_n, dc = cp * 2;
     const bool dworker = dpl < ppl;
     float2 wd[9], bd = make_float2(0.0f, 0.0f);
 #pragma unroll
     for (int k = 0; k < 9; ++k) wd[k] = dworker ? *reinterpret_cast<const float2*>(a.wdw + k * bf + dc) : make_float2(0.0f, 0.0f);
     if (dworker) bd = *reinterpret_cast<const float2*>(a.bdw + dc);
-    const int c1_n = cin >> 1, p1_n = 256 / c1_n;
+    constexpr int c1_n = cin >> 1, p1_n = 256 / c1_n;
     const int c1 = (t % c1_n) * 2, p1 = t / c1_n;
-    constexpr int NI1 = 2;                                           // 32 output pixels over >= 16 pixel lanes (cin <= 32)
+    constexpr int NI1 = (NO + p1_n - 1) / p1_n;                      // 32 output pixels over >= 16 pixel lanes (cin <= 32): at most two
     float2 w1d[9], b1d;
 #pragma unroll
     for (int k = 0; k < 9; ++k) w1d[k] = *reinterpret_cast<const float2*>(a.wdw1 + k * cin + c1);
@@ -778,7 +785,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     const float bias23 = (nt2 * 32 + l31 < bf && (pw2_wave || b1_wave)) ? (pw2_wave ? a.b2 : a.b3)[nt2 * 32 + l31] : 0.0f;
     // window pieces of this thread: 16-byte piece e = t + 256 i of the WH runs of WW * cin floats; everything about a piece that does not
     // depend on the tile is computed here
-    const int QR = WW * cq;
+    constexpr int QR = WW * cq;
     int wpos[NLD], wrel[NLD];                                        // wy | wx << 8 | first channel << 16 (or -1); offset from the window's first float
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -809,7 +816,7 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
     request(tbase + tl);
     if (t < RT1 * 32 - NPIX) inside[NPIX + t] = 0;                   // pad rows of the last row tile: never inside
     float amax = 0.0f;                                               // range guard (yn_split.h): largest |value| this thread has split
-    float* PT = T32;                                                 // [32][BN + 1]: branch 1's output tile
+    float* PT = T32;                                                 // [32][2 bf]: the output tile, both branches shuffled together
 
     // ---- 1. the window: fp32 copy + split planes; K tail of the planes (run for the NEXT tile in front of the current tile's stores: the wait
     //      for the prefetch must not stand behind them in the memory counter) --------------------------------------------------------
@@ -830,9 +837,12 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                 if (c4 == 0) inside[p] = (unsigned char)((pok >> i) & 1u);
             }
         }
-        {
-            const int ntail = (32 - cin) >> 2;                       // quads of zero columns up to K = 32
-            for (int i = t; i < RT1 * 32 * ntail; i += 256) {
+        if constexpr (cin < 32) {
+            constexpr int ntail = (32 - cin) >> 2;                   // quads of zero columns up to K = 32
+#pragma unroll
+            for (int i0 = 0; i0 < RT1 * 32 * ntail; i0 += 256) {
+                const int i = i0 + t;
+                if (i0 + 256 > RT1 * 32 * ntail && i >= RT1 * 32 * ntail) break;
                 const int p = i / ntail, c2 = cin + 4 * (i - p * ntail);
                 *reinterpret_cast<uint2*>(A1h + p * AST1 + c2) = make_uint2(0u, 0u);
                 *reinterpret_cast<uint2*>(A1l + p * AST1 + c2) = make_uint2(0u, 0u);
@@ -851,29 +861,48 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
         if (more) request(tbase + tl + GL);                          // the next tile's round trip runs under phases 2-4
 
         // ---- 2. y1 = act(pw1) on the window pixels -> T32 (zero outside the image) ---------------------------------------------------
-        for (int it = it0; it < RT1 * NP; it += 4) {
-            const int rt = it / NP;
-            f32x16 acc0, acc1;
+        // items it0, it0 + 4, ... of this wavefront (three at most), unrolled: the A fragments and `inside` words of ALL of them are read in front
+        // of the first MFMA chain (reads(j + 2) stands in front of chain j).  One accumulator pair: the chain of item j + 1 issued in front of
+        // the epilogue of item j measured equal at 16 more registers, and with all reads first it needs scratch.
+        // The last item exists on some wavefronts only (a wave-uniform guard); its reads come from a clamped row tile.
+        {
+            constexpr int NITEMS = RT1 * NP, NFULL = NITEMS / 4, NIT1 = (NITEMS + 3) / 4;
+            const bool last_ok = it0 + 4 * NFULL < NITEMS;
+            h16x8 fah[NIT1][2], fal[NIT1][2];
+            int inw[NIT1][4];                                        // inside flags of this lane's 16 rows: four bytes per word
+            auto reads = [&](int j) {
+                const int rt = (j < NFULL || last_ok) ? (it0 + 4 * j) / NP : 0;
+                const h16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
+                const h16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
-            const h16* Ahb = A1h + (rt * 32 + l31) * AST1 + h * 8;
-            const h16* Alb = A1l + (rt * 32 + l31) * AST1 + h * 8;
-            int inw[4];                                              // inside flags of this lane's 16 rows: four bytes per word
+                for (int ks = 0; ks < 2; ++ks) {
+                    fah[j][ks] = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
+                    fal[j][ks] = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
+                }
 #pragma unroll
-            for (int g = 0; g < 4; ++g) inw[g] = *reinterpret_cast<const int*>(inside + rt * 32 + 8 * g + 4 * h);
+                for (int g = 0; g < 4; ++g) inw[j][g] = *reinterpret_cast<const int*>(inside + rt * 32 + 8 * g + 4 * h);
+            };
+            reads(0);
+            if (NIT1 > 1) reads(1);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const h16x8 ah = *reinterpret_cast<const h16x8*>(Ahb + ks * 16);
-                const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
-                split_mfma(ah, al, &g1h[ks], &g1l[ks], acc0, acc1);
-            }
-            const int n = nt1 * 32 + l31;
-            if (n < bf) {
-                float* trow = T32 + (rt * 32 + 4 * h) * CS + n;      // row (r & 3) + 8 (r >> 2) of this lane's half: a wave-uniform offset
+            for (int j = 0; j < NIT1; ++j) {
+                if (j + 2 < NIT1) reads(j + 2);
+                if (j < NFULL || last_ok) {
+                    f32x16 acc0, acc1;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = act_pw(split_join(acc0[r], acc1[r]) + bias1, a.act1);
-                    trow[((r & 3) + 8 * (r >> 2)) * CS] = __uint_as_float(__float_as_uint(v) & (unsigned)__builtin_amdgcn_sbfe(inw[r >> 2], 8 * (r & 3), 1));
+                    for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) split_mfma(fah[j][ks], fal[j][ks], &g1h[ks], &g1l[ks], acc0, acc1);
+                    const int rt = (it0 + 4 * j) / NP;
+                    const int n = nt1 * 32 + l31;
+                    if (n < bf) {
+                        float* trow = T32 + (rt * 32 + 4 * h) * CS + n;  // row (r & 3) + 8 (r >> 2) of this lane's half: a wave-uniform offset
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const float v = act_pw(split_join(acc0[r], acc1[r]) + bias1, a.act1);
+                            trow[((r & 3) + 8 * (r >> 2)) * CS] = __uint_as_float(__float_as_uint(v) & (unsigned)__builtin_amdgcn_sbfe(inw[j][r >> 2], 8 * (r & 3), 1));
+                        }
+                    }
                 }
             }
         }
@@ -881,56 +910,81 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
         YN_TS();
 
         // ---- 3. both depthwise convs (stride 2, dwconv3x3_kernel's fma chain) -> the split planes of their branch --------------------
-        if (p1 < p1_n) {
+        {                                                            // the window reads of all of a thread's outputs first, then their fma chains side by side
+            float2 xv[NI1][9], acc[NI1];
+#pragma unroll
+            for (int i = 0; i < NI1; ++i) {
+                const int op = p1 + i * p1_n, opc = op < NO ? op : 0;
+                const int dy = opc / TW, dx = opc - dy * TW;
+                const float* xw = X32 + (2 * dy * WW + 2 * dx) * cin + c1;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) xv[i][k] = *reinterpret_cast<const float2*>(xw + ((k / 3) * WW + k % 3) * cin);
+                acc[i] = b1d;
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+#pragma unroll
+                for (int i = 0; i < NI1; ++i) vfma(acc[i], xv[i][k], w1d[k]);
 #pragma unroll
             for (int i = 0; i < NI1; ++i) {
                 const int op = p1 + i * p1_n;
-                if (op < NO) {
-                    const int dy = op / TW, dx = op - dy * TW;
-                    float2 acc = b1d;
-                    const float* xw = X32 + (2 * dy * WW + 2 * dx) * cin + c1;
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) vfma(acc, *reinterpret_cast<const float2*>(xw + ((k / 3) * WW + k % 3) * cin), w1d[k]);
-                    if (!RELU) acc = vact(acc, a.dw1_act);
-                    amax = range_track(range_track(amax, acc.x), acc.y);
+                if (p1 < p1_n && op < NO) {
+                    if (!RELU) acc[i] = vact(acc[i], a.dw1_act);
+                    amax = range_track(range_track(amax, acc[i].x), acc[i].y);
                     h16x2 hi, lo;
-                    hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
-                    lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
+                    hi[0] = (h16)acc[i].x; hi[1] = (h16)acc[i].y;
+                    lo[0] = split_lo(acc[i].x, hi[0]); lo[1] = split_lo(acc[i].y, hi[1]);
                     *reinterpret_cast<h16x2*>(A3h + op * AST1 + c1) = hi;
                     *reinterpret_cast<h16x2*>(A3l + op * AST1 + c1) = lo;
                 }
             }
         }
         {
-            const int pad1 = (AST1 - cin) >> 2;                      // K tail of branch 1's planes: zero (quads: cin is a multiple of 4)
-            for (int i = t; i < NO * pad1; i += 256) {
+            constexpr int pad1 = (AST1 - cin) >> 2;                    // K tail of branch 1's planes: zero (quads: cin is a multiple of 4)
+#pragma unroll
+            for (int i0 = 0; i0 < NO * pad1; i0 += 256) {
+                const int i = i0 + t;
+                if (i0 + 256 > NO * pad1 && i >= NO * pad1) break;
                 const int r = i / pad1, c2 = cin + 4 * (i - r * pad1);
                 *reinterpret_cast<uint2*>(A3h + r * AST1 + c2) = make_uint2(0u, 0u);
                 *reinterpret_cast<uint2*>(A3l + r * AST1 + c2) = make_uint2(0u, 0u);
             }
         }
-        if (dworker) {
-            for (int op = dpl; op < NO; op += ppl) {
-                const int dy = op / TW, dx = op - dy * TW;
-                float2 acc = bd;
+        {
+            float2 yv[NI2][9], acc[NI2];
+#pragma unroll
+            for (int i = 0; i < NI2; ++i) {
+                const int op = dpl + i * ppl, opc = op < NO ? op : 0;
+                const int dy = opc / TW, dx = opc - dy * TW;
                 const float* yw = T32 + (2 * dy * WW + 2 * dx) * CS + dc;
 #pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
+                for (int k = 0; k < 9; ++k) yv[i][k] = *reinterpret_cast<const float2*>(yw + ((k / 3) * WW + k % 3) * CS);
+                acc[i] = bd;
+            }
 #pragma unroll
-                    for (int kx = 0; kx < 3; ++kx)
-                        vfma(acc, *reinterpret_cast<const float2*>(yw + (ky * WW + kx) * CS), wd[ky * 3 + kx]);
-                if (!RELU) acc = vact(acc, a.dw_act);
-                amax = range_track(range_track(amax, acc.x), acc.y);
-                h16x2 hi, lo;
-                hi[0] = (h16)acc.x; hi[1] = (h16)acc.y;
-                lo[0] = split_lo(acc.x, hi[0]); lo[1] = split_lo(acc.y, hi[1]);
-                *reinterpret_cast<h16x2*>(A2h + op * AST2 + dc) = hi;
-                *reinterpret_cast<h16x2*>(A2l + op * AST2 + dc) = lo;
+            for (int k = 0; k < 9; ++k)
+#pragma unroll
+                for (int i = 0; i < NI2; ++i) vfma(acc[i], yv[i][k], wd[k]);
+#pragma unroll
+            for (int i = 0; i < NI2; ++i) {
+                const int op = dpl + i * ppl;
+                if (dworker && op < NO) {
+                    if (!RELU) acc[i] = vact(acc[i], a.dw_act);
+                    amax = range_track(range_track(amax, acc[i].x), acc[i].y);
+                    h16x2 hi, lo;
+                    hi[0] = (h16)acc[i].x; hi[1] = (h16)acc[i].y;
+                    lo[0] = split_lo(acc[i].x, hi[0]); lo[1] = split_lo(acc[i].y, hi[1]);
+                    *reinterpret_cast<h16x2*>(A2h + op * AST2 + dc) = hi;
+                    *reinterpret_cast<h16x2*>(A2l + op * AST2 + dc) = lo;
+                }
             }
         }
         {
-            const int padn = (AST2 - bf) >> 1;                       // K tail of both planes: zero (pairs: bf is even)
-            for (int i = t; i < NO * padn; i += 256) {
+            constexpr int padn = (AST2 - bf) >> 1;                     // K tail of both planes: zero (pairs: bf is even)
+#pragma unroll
+            for (int i0 = 0; i0 < NO * padn; i0 += 256) {
+                const int i = i0 + t;
+                if (i0 + 256 > NO * padn && i >= NO * padn) break;
                 const int r = i / padn, c2 = bf + 2 * (i - r * padn);
                 *reinterpret_cast<unsigned*>(A2h + r * AST2 + c2) = 0u;
                 *reinterpret_cast<unsigned*>(A2l + r * AST2 + c2) = 0u;
@@ -939,10 +993,11 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
         __syncthreads();
         YN_TS();
 
-        // ---- 4. branch 1's pointwise conv on wavefronts NP..2NP-1 (-> PT, in the free T32 space) while wavefronts 0..NP-1 run pw2 -----
+        // ---- 4. branch 1's pointwise conv on wavefronts NP..2NP-1 while wavefronts 0..NP-1 run pw2; both -> PT, in the free T32 space -----
         f32x16 acc0, acc1;
 #pragma unroll
         for (int k = 0; k < 16; ++k) { acc0[k] = 0.0f; acc1[k] = 0.0f; }
+        constexpr int PS = 2 * bf;                                   // PT: [32 tile pixels][2 bf] in the output's own shuffled order - a tile row is ONE contiguous run of it
         if (b1_wave) {
             const h16* Ahb = A3h + l31 * AST1 + h * 8;
             const h16* Alb = A3l + l31 * AST1 + h * 8;
@@ -952,10 +1007,6 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                 const h16x8 al = *reinterpret_cast<const h16x8*>(Alb + ks * 16);
                 split_mfma(ah, al, &g2h[ks], &g2l[ks], acc0, acc1);
             }
-            float* prow = PT + (4 * h) * (BN + 1) + nt2 * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                prow[((r & 3) + 8 * (r >> 2)) * (BN + 1)] = act_pw(split_join(acc0[r], acc1[r]) + bias23, a.act3);
         }
         if (pw2_wave) {                                              // pw2: one wavefront per 32 output columns, gemm_split_tile's chunks of 32 (whole chunks, zero-padded)
             const h16* Ahb = A2h + l31 * AST2 + h * 8;
@@ -967,28 +1018,34 @@ __global__ __launch_bounds__(256, 2) void down_unit_pipe_kernel(DownArgs a, int 
                 split_mfma(ah, al, &g2h[ks], &g2l[ks], acc0, acc1);
             }
         }
-        __syncthreads();                                             // branch 1's tile is complete; nobody reads the planes, the fp32 window or the flags any more
+        // concat + shuffle in LDS: column 2n = branch 1, 2n + 1 = branch 2.  Row r of the accumulator = tile pixel (r >> 2, (r & 3) + 4 h)
+        if ((pw2_wave || b1_wave) && nt2 * 32 + l31 < bf) {
+            float* prow = PT + (4 * h) * PS + 2 * (nt2 * 32 + l31) + (pw2_wave ? 1 : 0);
+            const int act23 = pw2_wave ? a.act2 : a.act3;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                prow[((r & 3) + 8 * (r >> 2)) * PS] = act_pw(split_join(acc0[r], acc1[r]) + bias23, act23);
+        }
+        __syncthreads();                                             // the output tile is complete; nobody reads the planes, the fp32 window or the flags any more
         if (more) consume();                                         // the next tile's window -> LDS (PT, which the store below reads, lies in T32)
-        // ---- 5. concat + shuffle store: out[2n] = branch 1, out[2n+1] = branch 2.  Row r of the accumulator = tile pixel (r >> 2, (r & 3) + 4 h):
-        //      a wave-uniform base + a 32-bit lane offset per store -----------------------------------------------------------------------
-        if (pw2_wave) {
-            const int n = wave * 32 + l31;
+        // ---- 5. the store, by all four wavefronts: the 16-byte pieces of the tile's rows (8 pixels x 2 bf floats: contiguous in `out` and in PT) ----
+        {
             // byte offsets in 32 bits (down_unit_covers: the output tensor is below 4 GB): ONE 64-bit base, the kernel argument itself
             char* obase = reinterpret_cast<char*>(a.out);
-            const unsigned lane_off = (unsigned)((((b * Ho + oy0) * Wo + ox0) + 4 * h) * 2 * bf + 2 * n) * 4u;
-            const float* prow = PT + (4 * h) * (BN + 1) + n;
-            float pv[16];                                            // branch 1's values first: one LDS wait, not sixteen
+            const unsigned tile_off = (unsigned)(((b * Ho + oy0) * Wo + ox0) * 2 * bf) * 4u;
+            constexpr int PQ = bf / 2, RQ = TW * PQ, NST = (TH * RQ + 255) / 256;      // pieces per pixel, per tile row, per thread
+            float4 ov[NST];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) pv[r] = prow[((r & 3) + 8 * (r >> 2)) * (BN + 1)];
+            for (int i = 0; i < NST; ++i) {
+                const int e = t + 256 * i;
+                ov[i] = *reinterpret_cast<const float4*>(PT + (e < TH * RQ ? e : 0) * 4);
+            }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int dy = r >> 2, dxu = r & 3;
-                if (oy0 + dy < Ho) {
-                    if (n < bf && ox0 + dxu + 4 * h < Wo) {
-                        const float v = act_pw(split_join(acc0[r], acc1[r]) + bias23, a.act2);
-                        *reinterpret_cast<float2*>(obase + (lane_off + (unsigned)((dy * Wo + dxu) * 2 * bf) * 4u)) = make_float2(pv[r], v);
-                    }
-                }
+            for (int i = 0; i < NST; ++i) {
+                const int e = t + 256 * i;
+                const int dy = e / RQ, q = e - dy * RQ, dx = q / PQ;
+                if (e < TH * RQ && oy0 + dy < Ho && ox0 + dx < Wo)
+                    *reinterpret_cast<float4*>(obase + (tile_off + (unsigned)(dy * Wo * 2 * bf) * 4u + (unsigned)q * 16u)) = ov[i];
             }
         }
         YN_TS();
@@ -1009,11 +1066,13 @@ static size_t down_unit_pipe_lds(int bf, int cin)
     return ((size_t)160 * 40 + (size_t)160 * cin + (size_t)160 * (bf + 2)) * sizeof(float) + 160;
 }
 
-// what down_unit_pipe_kernel takes: channel quads (its window pieces are 16 bytes), one K chunk of cin, at most two column tiles, 32-bit byte offsets
+// what down_unit_pipe_kernel takes: exactly the widths it is instantiated for - (cin, bf) = (24, 58) at 1.0x and (24, 24) at 0.5x; wider stages take
+// the down2 path - with one column block per GEMM, even maps and 32-bit byte offsets
 bool down_unit_covers(const DownArgs& a)
 {
-    return a.W1h && a.W1l && a.W2h && a.W2l && a.cin <= 32 && !(a.cin & 3) && a.bf <= 64 && !(a.bf & 1) && a.Npad1 == a.Npad2 && a.Npad1 <= 64 &&
-           !(a.H & 1) && !(a.W & 1) && a.B > 0 && a.cin >= 16 && (size_t)a.B * a.H * a.W * (size_t)(a.cin > a.bf / 2 ? a.cin : a.bf / 2) < ((size_t)1 << 30) &&      // 32-bit byte offsets
+    const bool widths = a.cin == 24 && (a.bf == 58 || a.bf == 24);
+    return widths && a.W1h && a.W1l && a.W2h && a.W2l && a.Npad1 == a.Npad2 && a.Npad1 == 32 * ((a.bf + 31) / 32) &&
+           !(a.H & 1) && !(a.W & 1) && a.B > 0 && (size_t)a.B * a.H * a.W * (size_t)(a.cin > a.bf / 2 ? a.cin : a.bf / 2) < ((size_t)1 << 30) &&      // 32-bit byte offsets
            a.wdw1 && a.bdw1 && a.W3h && a.W3l && a.b3 && a.Npad3 == a.Npad1;
 }
 
@@ -1021,22 +1080,21 @@ void launch_down_unit(const DownArgs& a, hipStream_t s)
 {
     const int Ho = a.H >> 1, Wo = a.W >> 1;
     const unsigned tiles = (unsigned)a.B * ((Ho + 3) / 4) * ((Wo + 7) / 8);
-    const int NP = a.Npad1 / 32;
     static unsigned long long attr = 0;
     if (attr_pending(attr)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<24, 24, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<24, 58, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<24, 24, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(down_unit_pipe_kernel<24, 58, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     constexpr unsigned pipe_g = 1024;   // walking workgroups (a multiple of 8): ~3 tiles each at bs = 32 (512 / 768 / 1024 / 1456 / one per tile measured within 1 % of each other)
     const size_t plds = down_unit_pipe_lds(a.bf, a.cin);
     unsigned g = xcd_grid(tiles);
     if (g > pipe_g) g = pipe_g;
     const bool relu = a.act1 == 1 && a.act2 == 1 && a.act3 == 1 && a.dw_act == 0 && a.dw1_act == 0;
-#define YN_DUP(np, rl) { set_last_kernel_name("down_unit_pipe_kernel<" #np "," #rl ">"); hipLaunchKernelGGL((down_unit_pipe_kernel<np, rl>), dim3(g), dim3(256), plds, s, a, (int)tiles); }
-    if (NP == 1) { if (relu) YN_DUP(1, true) else YN_DUP(1, false) }
-    else         { if (relu) YN_DUP(2, true) else YN_DUP(2, false) }
+#define YN_DUP(ci, bw, rl) { set_last_kernel_name("down_unit_pipe_kernel<" #ci "," #bw "," #rl ">"); hipLaunchKernelGGL((down_unit_pipe_kernel<ci, bw, rl>), dim3(g), dim3(256), plds, s, a, (int)tiles); }
+    if (a.bf == 24) { if (relu) YN_DUP(24, 24, true) else YN_DUP(24, 24, false) }
+    else            { if (relu) YN_DUP(24, 58, true) else YN_DUP(24, 58, false) }
 #undef YN_DUP
 }
 

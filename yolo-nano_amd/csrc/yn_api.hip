@@ -2123,6 +2123,37 @@ int yn_op_shuffle_block(yn_handle* h, const char* block, const float* x, int B, 
     return 0;
 }
 
+// A stride-2 block as down_unit_pipe_kernel on any even map (the network only reaches maps that are multiples of 4 on this kernel: the
+// ragged tile rows are reachable here alone).  An error where the kernel does not cover the block: there is no other path behind this entry.
+int yn_op_down_unit(yn_handle* h, const char* block, const float* x, int B, int H, int W, float* y)
+{
+    YN_ENTER(h);
+    if (!h->folded) return fail(h, "yn_op_down_unit before yn_fold_bn");
+    h->cur = h->stream;
+    const std::string P = block;
+    if (!h->by_name.count(P + ".b2.pw1") || !h->by_name.count(P + ".b1.dw")) return fail(h, "'%s' is not a stride-2 block", block);
+    const Layer &lp1 = L(h, P + ".b2.pw1"), &ldw = L(h, P + ".b2.dw"), &lp2 = L(h, P + ".b2.pw2"), &l1d = L(h, P + ".b1.dw"), &l1p = L(h, P + ".b1.pw");
+    const int bf = lp1.cout, Cin = lp1.cin;
+    DownArgs d{};
+    d.x = x; d.cin = Cin;
+    d.W1h = lp1.ws_hi; d.W1l = lp1.ws_lo; d.b1 = lp1.b_packed; d.act1 = lp1.act; d.Npad1 = lp1.Npad;
+    d.wdw = ldw.w_packed; d.bdw = ldw.b_packed; d.dw_act = ldw.act;
+    d.W2h = lp2.ws_hi; d.W2l = lp2.ws_lo; d.b2 = lp2.b_packed; d.act2 = lp2.act; d.Npad2 = lp2.Npad;
+    d.wdw1 = l1d.w_packed; d.bdw1 = l1d.b_packed; d.dw1_act = l1d.act;
+    d.W3h = l1p.ws_hi; d.W3l = l1p.ws_lo; d.b3 = l1p.b_packed; d.act3 = l1p.act; d.Npad3 = l1p.Npad;
+    d.out = y; d.B = B; d.H = H; d.W = W; d.bf = bf;
+    d.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
+    if (exact(h) || lp2.cin != bf || lp2.cout != bf || ldw.stride != 2 || l1d.stride != 2 || l1d.cout != Cin || l1p.cin != Cin || l1p.cout != bf || !down_unit_covers(d))
+        return fail(h, "yn_op_down_unit: down_unit_pipe_kernel does not cover '%s' at %d x %d x %d (cin %d, branch width %d)", block, B, H, W, Cin, bf);
+    {
+        Bracket br(h, P + ".unit", 0.0, 0.0);
+        launch_down_unit(d, h->cur);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 int yn_op_nchw_to_nhwc(yn_handle* h, const float* x, int B, int C, int H, int W, float* y)
 {
     YN_ENTER(h);
