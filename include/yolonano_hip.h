@@ -598,6 +598,16 @@ int  yn_op_shuffle_block(yn_handle* h, const char* block, const float* x, int B,
  * x [B,H,W,Cin] -> y [B,H/2,W/2,Cout].  Split-f16 family; independent of yn_down_fuse and yn_set_pw_config.  An error where that kernel
  * does not cover the block or the handle is on the exact-f32 family: yn_op_shuffle_block is the five-launch form. */
 int  yn_op_down_unit(yn_handle* h, const char* block, const float* x, int B, int H, int W, float* y);
+/* The candidate decode on its own (models/yolo_nano.py:308-330, 120-156, 362-367, 253-261): dense raw NHWC heads with row stride A(5+C),
+ * as for yn_score_full -> boxes [B,N,4] (normalised, clamped), best score [B,N], class [B,N] int32 (-1 where score < conf_thresh; a
+ * candidate of a wavefront that is below the threshold by objectness alone has score 0).  decode_kernel<false, KMAX>, KMAX by C. */
+int  yn_op_decode_cand(yn_handle* h, const float* head_s8, const float* head_s16, const float* head_s32, int B, float conf_thresh,
+                       float* boxes, float* scores, int32_t* cls);
+/* yn_infer's forward from the output of the heads' layer .1 to the candidate arrays, on caller-provided activations x8 [B,S/8,S/8,96],
+ * x16, x32 (NHWC): layers .2, .3, .4 with the handle's loaded, folded weights and the decode, through the kernels the handle's current
+ * yn_tail_fuse / yn_fuse_decode / yn_group_launch switches and conf_thresh select (the same function yn_infer calls; the profile
+ * records name the kernels).  Outputs as yn_op_decode_cand.  Synchronises the stream. */
+int  yn_op_head_tail(yn_handle* h, const float* x8, const float* x16, const float* x32, int B, float* boxes, float* scores, int32_t* cls);
 /* NCHW <-> NHWC helpers for the tests and the host shim */
 int  yn_op_nchw_to_nhwc(yn_handle* h, const float* x, int B, int C, int H, int W, float* y);
 int  yn_op_nhwc_to_nchw(yn_handle* h, const float* x, int B, int C, int H, int W, float* y);

@@ -107,6 +107,8 @@ SIGNATURES = {
     "yn_op_maxpool3x3s2": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_shuffle_block": (_i32, [_vp, ctypes.c_char_p, _vp, _i32, _i32, _i32, _vp]),
     "yn_op_down_unit": (_i32, [_vp, ctypes.c_char_p, _vp, _i32, _i32, _i32, _vp]),
+    "yn_op_decode_cand": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
+    "yn_op_head_tail": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yn_op_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "yn_op_h16_conv": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -875,6 +877,30 @@ class Handle:
         y = torch.empty((B, H // 2, W // 2, cout), dtype=torch.float32, device=x.device)
         self._ck(self.lib.yn_op_down_unit(self.h, block.encode(), _ptr(self._in(x)), B, H, W, y.data_ptr()), "yn_op_down_unit")
         return y
+
+    def op_decode_cand(self, heads, conf_thresh):
+        """The candidate decode alone on dense raw NHWC heads [B,H,W,A(5+C)] x 3 (decode_kernel<false, KMAX>) ->
+        (boxes [B,N,4], best score [B,N], class [B,N] int32, -1 below conf_thresh)."""
+        heads = [self._in(t) for t in heads]
+        B = heads[0].shape[0]
+        for t, hw in zip(heads, self.head_shapes(B)):
+            assert t.is_cuda and tuple(t.shape) == hw, (tuple(t.shape), hw)
+        boxes, scores, cls, _, _ = self.alloc_outputs(B, device=heads[0].device)
+        self._ck(self.lib.yn_op_decode_cand(self.h, heads[0].data_ptr(), heads[1].data_ptr(), heads[2].data_ptr(), B, float(conf_thresh),
+                                            boxes.data_ptr(), scores.data_ptr(), cls.data_ptr()), "yn_op_decode_cand")
+        return boxes, scores, cls
+
+    def op_head_tail(self, xs):
+        """The heads from the output of their layer .1 (xs: three NHWC [B,S/8 (16, 32),same,96] activations) to the candidate arrays, with
+        the handle's weights, switches and conf_thresh (yn_op_head_tail) -> (boxes [B,N,4], best score [B,N], class [B,N] int32)."""
+        xs = [self._in(t) for t in xs]
+        B = xs[0].shape[0]
+        for t, s in zip(xs, arch.STRIDES):
+            assert t.is_cuda and tuple(t.shape) == (B, self.S // s, self.S // s, arch.NECK_CH), (tuple(t.shape), self.S, s)
+        boxes, scores, cls, _, _ = self.alloc_outputs(B, device=xs[0].device)
+        self._ck(self.lib.yn_op_head_tail(self.h, xs[0].data_ptr(), xs[1].data_ptr(), xs[2].data_ptr(), B,
+                                          boxes.data_ptr(), scores.data_ptr(), cls.data_ptr()), "yn_op_head_tail")
+        return boxes, scores, cls
 
     def op_h16_conv(self, kind, x, w, bias=None, stride=1, dy=None, gapped=False):
         """One conv kernel of the fp16 training step (+ its two gradient kernels when dy is given): x [B,H,W,Cin] fp32 NHWC,

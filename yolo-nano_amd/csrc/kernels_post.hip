@@ -214,13 +214,17 @@ __device__ __forceinline__ void decode_candidate(const GridInfo& g, const float*
     const float tbox = row[g.A * (1 + g.C) + a * 4 + (j & 3)];
     float sum, sc;
     int cbest;
-    if (!FULL && wave_below_conf(obj_raw, conf_skip_logit(conf_thresh))) { sc = 0.0f; cbest = 0; }
+    const float skip_logit = conf_skip_logit(conf_thresh);
+    if (!FULL && wave_below_conf(obj_raw, skip_logit)) { sc = 0.0f; cbest = 0; }
     else if (!cand_class<FULL, KMAX>(g, row, i, a, j, obj_raw, sum, sc, cbest, all_class)) sc = 1.0f / sum * sigmoid_f(obj_raw);
     // lane j evaluates coordinate j & 3 from box values (j & 1) and 2 + (j & 1) of its row (row_newbcast: lane n of the row to all)
     const float tc = (j & 1) ? dpp_f<0x151>(tbox) : dpp_f<0x150>(tbox), ts = (j & 1) ? dpp_f<0x153>(tbox) : dpp_f<0x152>(tbox);
     const float coord = decode_coord(g, s, gx, gy, a, tc, ts, (float)g.S, j & 3);
     if (j < 4) boxes[(size_t)i * 4 + j] = coord;
     if (!FULL && j == 0) {
+        // score 0 for EVERY candidate that is out by its objectness alone, not only where its whole wavefront is: which candidates share a
+        // wavefront differs between this kernel, head_decode_block and head_tail_block, and the candidate arrays must not depend on it
+        if (obj_raw < skip_logit) sc = 0.0f;
         scores[i] = sc;
         cls[i] = (sc >= conf_thresh) ? cbest : -1;
     }
@@ -305,7 +309,8 @@ __device__ __forceinline__ void head_decode_block(const GemmArgs& a, const GridI
         const float* rp = raw + row * LD;
         if (wave_below_conf(rp[an], skip_logit)) { if (j == 0) { st_sum[c] = 0.0f; st_cls[c] = (int)0x80000000; } continue; }
         const bool fin = cand_class<false, KMAX>(g, rp, 0, an, j, rp[an], sum, sc, cbest, nullptr);
-        if (j == 0) { st_sum[c] = fin ? sc : sum; st_cls[c] = fin ? (cbest | (int)0x80000000) : cbest; }
+        const bool out = rp[an] < skip_logit;               // as decode_candidate: out by objectness alone is score 0, whatever the wavefront did
+        if (j == 0) { st_sum[c] = out ? 0.0f : (fin ? sc : sum); st_cls[c] = (fin || out) ? (cbest | (int)0x80000000) : cbest; }
     }
     __syncthreads();
     for (int q = t; q < 5 * ncand; q += 256) {
@@ -356,11 +361,15 @@ static void launch_decode(const float* const heads[3], const GridInfo& g, int B,
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (blocks < 1) blocks = 1;
     const dim3 grid((unsigned)blocks), blk(256);
-    if (g.C <= 16) hipLaunchKernelGGL((decode_kernel<FULL, 1>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class);
-    else if (g.C <= 32) hipLaunchKernelGGL((decode_kernel<FULL, 2>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class);
-    else if (g.C <= 80) hipLaunchKernelGGL((decode_kernel<FULL, 5>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class);
-    else if (g.C <= 256) hipLaunchKernelGGL((decode_kernel<FULL, 16>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class);
-    else hipLaunchKernelGGL((decode_kernel<FULL, 64>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class);
+    // (the symbol the profile records: which KMAX instantiation the class count picked)
+#define YN_DK(kmax) do { set_last_kernel_name(FULL ? "decode_kernel<true," #kmax ">" : "decode_kernel<false," #kmax ">");                                 \
+                      hipLaunchKernelGGL((decode_kernel<FULL, kmax>), grid, blk, 0, s, heads[0], heads[1], heads[2], g, B, conf_thresh, boxes, scores, cls, all_class); } while (0)
+    if (g.C <= 16) YN_DK(1);
+    else if (g.C <= 32) YN_DK(2);
+    else if (g.C <= 80) YN_DK(5);
+    else if (g.C <= 256) YN_DK(16);
+    else YN_DK(64);
+#undef YN_DK
 }
 
 void launch_score_full(const float* const heads[3], const GridInfo& g, int B, float* all_bbox, float* all_class, hipStream_t s)
@@ -384,7 +393,7 @@ void launch_head_decode(const GemmArgs& a, const GridInfo& g, int scale, float c
 {
     const unsigned blocks = (unsigned)(((a.M + 31) / 32 + 7) & ~7);
     const dim3 grid(blocks), blk(256);
-#define YN_HD(nt, kmax) hipLaunchKernelGGL((head_decode_kernel<nt, kmax>), grid, blk, 0, s, a, g, scale, conf_thresh, boxes, scores, cls)
+#define YN_HD(nt, kmax) do { set_last_kernel_name("head_decode_kernel<" #nt "," #kmax ">"); hipLaunchKernelGGL((head_decode_kernel<nt, kmax>), grid, blk, 0, s, a, g, scale, conf_thresh, boxes, scores, cls); } while (0)
     if (a.Npad > 128) YN_HD(2, 5);
     else if (g.C <= 16) YN_HD(1, 1);
     else if (g.C <= 32) YN_HD(1, 2);
@@ -402,7 +411,7 @@ void launch_head_decode_group(const GemmArgs* a, int n, const GridInfo& g, float
     }
     q.first[YN_GROUP_MAX] = tot;
     const dim3 grid(tot), blk(256);
-#define YN_HDG(nt, kmax) hipLaunchKernelGGL((head_decode_group_kernel<nt, kmax>), grid, blk, 0, s, q, g, conf_thresh, boxes, scores, cls)
+#define YN_HDG(nt, kmax) do { set_last_kernel_name("head_decode_group_kernel<" #nt "," #kmax ">"); hipLaunchKernelGGL((head_decode_group_kernel<nt, kmax>), grid, blk, 0, s, q, g, conf_thresh, boxes, scores, cls); } while (0)
     if (a[0].Npad > 128) YN_HDG(2, 5);
     else if (g.C <= 16) YN_HDG(1, 1);
     else if (g.C <= 32) YN_HDG(1, 2);
@@ -671,7 +680,8 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
             float sc;
             int cbest;
             const bool fin = cand_class_finish<false, KMAX>(g, 0, j, obj[u], v[u], sum[u], first[u], general[u], sc, cbest, nullptr);
-            if (j == 0) { st_sum[cnd] = fin ? sc : sum[u]; st_cls[cnd] = fin ? (cbest | (int)0x80000000) : cbest; }
+            const bool out = obj[u] < skip_logit;           // as decode_candidate: out by objectness alone is score 0, whatever the wavefront did
+            if (j == 0) { st_sum[cnd] = out ? 0.0f : (fin ? sc : sum[u]); st_cls[cnd] = (fin || out) ? (cbest | (int)0x80000000) : cbest; }
         }
     }
     __syncthreads();
@@ -737,6 +747,7 @@ void launch_head_tail_group(const HeadTailArgs* a, int n, const GridInfo& g, flo
     const size_t lds = (size_t)HEAD_TAIL_HALVES * 2;
     static unsigned long long attr = 0;
     if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_tail_group_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_last_kernel_name("head_tail_group_kernel<5>");
     hipLaunchKernelGGL((head_tail_group_kernel<5>), dim3(tot), dim3(256), lds, s, q, g, conf_thresh, boxes, scores, cls);
 }
 

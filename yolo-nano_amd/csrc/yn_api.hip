@@ -815,6 +815,177 @@ static GemmArgs head_final_args(yn_handle* h, const Layer& l, const float* in, l
     return a;
 }
 
+// Whether a forward over B images hands the last head conv and the candidate decode to one kernel (head_decode*_kernel / head_tail_group_kernel):
+// the handle's switches, what the layers' packs allow, and the size rule.  want = the caller decodes at all (yn_infer, yn_op_head_tail).
+static bool head_fuse_all(yn_handle* h, int B, bool want)
+{
+    char nm[96];
+    const int S = h->grid.S, W3 = S / 8;
+    bool fuse_all = want && h->fuse_decode && !exact(h);
+    for (int hd = 0; hd < 3 && fuse_all; ++hd) {
+        const int W = S / (8 << hd);
+        snprintf(nm, sizeof nm, "head_det_%d.4", hd + 1);
+        fuse_all = head_decode_supported(head_final_args(h, L(h, nm), nullptr, (long)B * W * W), h->grid);
+    }
+    // small batches: three 16 us fused launches against three 10 us GEMMs + one 7 us decode (bs = 1) - the fusion pays from the
+    // traffic it removes, i.e. when the stride-8 head is large (bs >= 4 at 416x416); yn_fuse_decode(2) forces it (tests)
+    // ... unless the wider fusion applies (head_tail_group_kernel: layers .2-.4 + decode as ONE launch instead of three: bs = 1 0.602 -> 0.593 ms)
+    bool tail_possible = false;
+    if (fuse_all && h->tail_fuse && h->group_launch && h->grid.C > 32) {
+        const GemmArgs gf = head_final_args(h, L(h, "head_det_1.4"), nullptr, (long)B * W3 * W3);
+        tail_possible = gf.Npad > 128 && gf.Npad <= 256;
+    }
+    if (h->fuse_decode_mode != 2 && (long)B * W3 * W3 < 8192 && !tail_possible) fuse_all = false;
+    return fuse_all;
+}
+
+// Layer k of the three heads as ONE grouped launch (hl = the three heads' layers): depthwise, pointwise, or a depthwise + pointwise pair
+// as one kernel (the depthwise output never reaches memory).  src_feat, when given, replaces src_own (layer .0 reads the pyramid levels).
+static bool head_dw_layer(yn_handle* h, const Layer* const hl[3], int B, const float* const src_own[3], const float* const src_feat[3], float* const dst[3], const char* name)
+{
+    DwArgs d[3];
+    for (int hd = 0; hd < 3; ++hd) {
+        const Layer& l = *hl[hd];
+        const int W = h->grid.S / (8 << hd);
+        d[hd] = DwArgs{};
+        d[hd].in = src_feat ? src_feat[hd] : src_own[hd]; d[hd].in_ld = NECK; d[hd].in_off = 0; d[hd].w = l.w_packed; d[hd].bias = l.b_packed;
+        d[hd].out = dst[hd]; d[hd].out_ld = NECK; d[hd].out_off = 0;
+        d[hd].B = B; d[hd].H = W; d[hd].W = W; d[hd].C = l.cout; d[hd].stride = l.stride; d[hd].act = l.act;
+    }
+    if (!dw_group_ok(d, 3)) return false;
+    run_dw_group(h, hl, d, 3, name);
+    return true;
+}
+
+static bool head_pw_layer(yn_handle* h, const Layer* const hl[3], int B, const float* const src[3], float* const dst[3], int dst_ld, int n_store, const char* name)
+{
+    GemmArgs g3[3];
+    for (int hd = 0; hd < 3; ++hd) {
+        const int W = h->grid.S / (8 << hd);
+        g3[hd] = pw_args(h, *hl[hd], src[hd], NECK, 0, (long)B * W * W, dst[hd], dst_ld, 0, nullptr, 0, 0, n_store);
+    }
+    return run_pw_group(h, hl, g3, 3, name);
+}
+
+static bool head_dwpw_layer(yn_handle* h, const Layer* const hld[3], const Layer* const hlp[3], int B, const float* const src_own[3], const float* const src_feat[3],
+                            float* const dst[3], const char* name)
+{
+    DwPwArgs q[3];
+    double fl = 0, by = 0;
+    for (int hd = 0; hd < 3; ++hd) {
+        const Layer &ld = *hld[hd], &lp = *hlp[hd];
+        const int W = h->grid.S / (8 << hd);
+        q[hd] = DwPwArgs{};
+        q[hd].in = src_feat ? src_feat[hd] : src_own[hd];
+        q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
+        q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act; q[hd].Npad = lp.Npad;
+        q[hd].out = dst[hd]; q[hd].B = B; q[hd].H = W; q[hd].W = W; q[hd].C = ld.cout;
+        q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
+        if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK) return false;
+        const double M = (double)B * W * W;
+        fl += 2.0 * M * NECK * (9.0 + NECK);
+        by += 4.0 * (2.0 * M * NECK + (double)NECK * NECK);
+    }
+    if (!dwpw_group_ok(q, 3)) return false;
+    Bracket br(h, name, fl, by);
+    launch_dwpw_group(q, 3, h->cur);
+    return true;
+}
+
+// layers .2 + .3 + .4 + the decode of the three heads as ONE grouped kernel (head_tail_group_kernel): layer .3's output never reaches memory
+static bool head_tail_layer(yn_handle* h, const Layer* const hl2[3], const Layer* const hl3[3], const Layer* const hl4[3], int B, const float* const src[3], bool fuse_all)
+{
+    if (!fuse_all || !h->tail_fuse) return false;
+    HeadTailArgs q[3];
+    double fl = 0, by = 0;
+    for (int hd = 0; hd < 3; ++hd) {
+        const Layer &ld = *hl2[hd], &lp = *hl3[hd], &lf = *hl4[hd];
+        const int W = h->grid.S / (8 << hd);
+        if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK || lp.Npad != NECK || lf.cin != NECK || NECK != 96 || !lf.ws_hi) return false;
+        const GemmArgs gf = head_final_args(h, lf, src[hd], (long)B * W * W);
+        if (gf.act != 0 || gf.pass) return false;
+        q[hd] = HeadTailArgs{};
+        q[hd].in = src[hd]; q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
+        q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act;
+        q[hd].Wfh = gf.Wsh; q[hd].Wfl = gf.Wsl; q[hd].fbias = gf.bias; q[hd].Npad = gf.Npad;
+        q[hd].B = B; q[hd].H = W; q[hd].W = W;
+        q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
+        const double M = (double)B * W * W;
+        fl += 2.0 * M * NECK * (9.0 + NECK) + 2.0 * M * lf.cin * lf.cout;
+        by += 4.0 * (M * NECK + (double)NECK * NECK + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A);
+    }
+    if (!head_tail_ok(q, 3, h->grid)) return false;
+    Bracket br(h, "head_det_*.2+3+4+decode", fl, by);
+    launch_head_tail_group(q, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
+    return true;
+}
+
+// The detection heads from the output of their layer .1 (src) to the end, on h->cur: layers .2 + .3 (scratch hA, output hC), then layer .4
+// into heads[] (row stride head_ld) or, with fuse_all, layer .4 + the candidate decode into h->cand_*.  hd = 0..2: that head with its own
+// launches; hd < 0: the three heads with grouped launches (the split-f16 family: the caller has checked the packs).  yn_infer's forward and
+// yn_op_head_tail both come through here.
+static int run_head_tail(yn_handle* h, int hd, int B, const float* const src[3], float* const hA[3], float* const hC[3], float* const heads[3], int head_ld, bool fuse_all)
+{
+    char nm[96];
+    if (hd >= 0) {
+        const int W = h->grid.S / (8 << hd);
+        const long M = (long)B * W * W;
+        snprintf(nm, sizeof nm, "head_det_%d", hd + 1);
+        const std::string P = nm;
+        run_dwpw(h, L(h, P + ".2"), L(h, P + ".3"), src[hd], NECK, 0, B, W, W, hA[hd], hC[hd], NECK, 0, nullptr, 0, 0);
+        const Layer& lf = L(h, P + ".4");
+        if (fuse_all) {
+            GemmArgs a = head_final_args(h, lf, hC[hd], M);
+            Bracket br(h, lf.name + "+decode", 2.0 * M * lf.cin * lf.cout, 4.0 * (M * (double)lf.cin + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A));
+            launch_head_decode(a, h->grid, hd, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
+        } else {
+            run_pw(h, lf, hC[hd], NECK, 0, M, heads[hd], head_ld, 0, nullptr, 0, 0, head_ld);
+        }
+        return 0;
+    }
+    const Layer* hl[3][3];
+    for (int k = 0; k < 3; ++k)
+        for (int d = 0; d < 3; ++d) {
+            snprintf(nm, sizeof nm, "head_det_%d.%d", d + 1, k + 2);
+            hl[k][d] = &L(h, nm);
+        }
+    if (head_tail_layer(h, hl[0], hl[1], hl[2], B, src, fuse_all)) return 0;
+    bool ok = head_dwpw_layer(h, hl[0], hl[1], B, src, nullptr, hC, "head_det_*.2+3") ||
+              (head_dw_layer(h, hl[0], B, src, nullptr, hA, "head_det_*.2") && head_pw_layer(h, hl[1], B, hA, hC, NECK, 0, "head_det_*.3"));
+    if (ok) {
+        if (fuse_all) {
+            GemmArgs g3[3];
+            double fl = 0, by = 0;
+            for (int d = 0; d < 3; ++d) {
+                const int W = h->grid.S / (8 << d);
+                const long M = (long)B * W * W;
+                g3[d] = head_final_args(h, *hl[2][d], hC[d], M);
+                fl += 2.0 * M * hl[2][d]->cin * hl[2][d]->cout;
+                by += 4.0 * (M * (double)hl[2][d]->cin + (double)hl[2][d]->cin * hl[2][d]->cout + 6.0 * M * h->grid.A);
+            }
+            Bracket br(h, "head_det_*.4+decode", fl, by);
+            launch_head_decode_group(g3, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
+        } else {
+            ok = head_pw_layer(h, hl[2], B, hC, heads, head_ld, head_ld, "head_det_*.4");
+        }
+    }
+    if (!ok) return fail(h, "grouped head launch: unsupported layer layout");
+    return 0;
+}
+
+// true when every GEMM-shaped head layer carries split-f16 packs, which the grouped head launches need
+static bool heads_groupable(yn_handle* h)
+{
+    if (!h->group_launch || exact(h)) return false;
+    char nm[96];
+    for (int k = 0; k < 5; ++k)
+        for (int hd = 0; hd < 3; ++hd) {
+            snprintf(nm, sizeof nm, "head_det_%d.%d", hd + 1, k);
+            if ((k == 1 || k == 3 || k == 4) && !L(h, nm).ws_hi) return false;
+        }
+    return true;
+}
+
 // The network: x NCHW [B,3,S,S] -> three NHWC head tensors.
 // fuse_decode: the last conv of each head runs as head_decode_kernel (candidates written straight into h->cand_*, raw heads not stored);
 // *fused reports whether all three heads took that path (else the caller runs decode_kernel on the raw heads).
@@ -973,20 +1144,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
     // side stream as soon as smooth_1 is enqueued, head 2 after smooth_2, head 3 stays on the main stream.
     const float* feats[3] = {p3a, p4b, p5a};
     const int Ws[3] = {W3, W4, W5};
-    bool fuse_all = fuse_decode && h->fuse_decode && !exact(h);
-    for (int hd = 0; hd < 3 && fuse_all; ++hd) {
-        snprintf(nm, sizeof nm, "head_det_%d.4", hd + 1);
-        fuse_all = head_decode_supported(head_final_args(h, L(h, nm), nullptr, (long)B * Ws[hd] * Ws[hd]), h->grid);
-    }
-    // small batches: three 16 us fused launches against three 10 us GEMMs + one 7 us decode (bs = 1) - the fusion pays from the
-    // traffic it removes, i.e. when the stride-8 head is large (bs >= 4 at 416x416); yn_fuse_decode(2) forces it (tests)
-    // ... unless the wider fusion applies (head_tail_group_kernel: layers .2-.4 + decode as ONE launch instead of three: bs = 1 0.602 -> 0.593 ms)
-    bool tail_possible = false;
-    if (fuse_all && h->tail_fuse && h->group_launch && h->grid.C > 32) {
-        const GemmArgs gf = head_final_args(h, L(h, "head_det_1.4"), nullptr, (long)B * W3 * W3);
-        tail_possible = gf.Npad > 128 && gf.Npad <= 256;
-    }
-    if (h->fuse_decode_mode != 2 && (long)B * W3 * W3 < 8192 && !tail_possible) fuse_all = false;
+    const bool fuse_all = head_fuse_all(h, B, fuse_decode);
     if (fused) *fused = fuse_all;
     auto run_head = [&](int hd) {
         const long M = (long)B * Ws[hd] * Ws[hd];
@@ -997,29 +1155,20 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
         snprintf(nm, sizeof nm, "head_det_%d", hd + 1);
         const std::string P = nm;
         run_dwpw(h, L(h, P + ".0"), L(h, P + ".1"), feats[hd], NECK, 0, B, Ws[hd], Ws[hd], hA, hB, NECK, 0, nullptr, 0, 0);
-        run_dwpw(h, L(h, P + ".2"), L(h, P + ".3"), hB, NECK, 0, B, Ws[hd], Ws[hd], hA, hC, NECK, 0, nullptr, 0, 0);
-        const Layer& lf = L(h, P + ".4");
-        if (fuse_all) {
-            GemmArgs a = head_final_args(h, lf, hC, M);
-            set_last_kernel_name("head_decode_kernel");
-            Bracket br(h, lf.name + "+decode", 2.0 * M * lf.cin * lf.cout, 4.0 * (M * (double)lf.cin + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A));
-            launch_head_decode(a, h->grid, hd, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
-        } else {
-            run_pw(h, lf, hC, NECK, 0, M, heads[hd], head_ld, 0, nullptr, 0, 0, head_ld);
-        }
-        return 0;
+        const float* const src[3] = {hB, hB, hB};           // (only entry hd is read)
+        float* const sA[3] = {hA, hA, hA};
+        float* const sC[3] = {hC, hC, hC};
+        return run_head_tail(h, hd, B, src, sA, sC, heads, head_ld, fuse_all);
     };
     // All three heads layer by layer, each layer ONE grouped launch (5 launches instead of 15): the stride-16 / 32 heads ride along with
     // the stride-8 one instead of paying ten launches of 7-20 us for a few microseconds of work.  Needs the split-f16 family.
-    bool grouped = h->group_launch && !exact(h);
-    const Layer* hl[5][3];
-    for (int k = 0; k < 5 && grouped; ++k)
-        for (int hd = 0; hd < 3; ++hd) {
-            snprintf(nm, sizeof nm, "head_det_%d.%d", hd + 1, k);
-            hl[k][hd] = &L(h, nm);
-            if ((k == 1 || k == 3 || k == 4) && !hl[k][hd]->ws_hi) grouped = false;
-        }
-    if (grouped) {
+    if (heads_groupable(h)) {
+        const Layer* hl[2][3];
+        for (int k = 0; k < 2; ++k)
+            for (int hd = 0; hd < 3; ++hd) {
+                snprintf(nm, sizeof nm, "head_det_%d.%d", hd + 1, k);
+                hl[k][hd] = &L(h, nm);
+            }
         run_c3(h, L(h, "smooth_2"), p4a, p3a, 2, B, W4, W4, p4b);      // p4 + down(p3)
         run_c3(h, L(h, "smooth_3"), p5, p4b, 2, B, W5, W5, p5a);       // p5 + down(p4)
         float *hA[3], *hB[3], *hC[3];
@@ -1028,95 +1177,10 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             hA[hd] = arena_take(h, M * NECK); hB[hd] = arena_take(h, M * NECK); hC[hd] = arena_take(h, M * NECK);
             if (!hA[hd] || !hB[hd] || !hC[hd]) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
         }
-        auto dw_layer = [&](int k, float* const src_own[3], const float* const src_feat[3], float* const dst[3], const char* name) {
-            DwArgs d[3];
-            for (int hd = 0; hd < 3; ++hd) {
-                const Layer& l = *hl[k][hd];
-                d[hd] = DwArgs{};
-                d[hd].in = src_feat ? src_feat[hd] : src_own[hd]; d[hd].in_ld = NECK; d[hd].in_off = 0; d[hd].w = l.w_packed; d[hd].bias = l.b_packed;
-                d[hd].out = dst[hd]; d[hd].out_ld = NECK; d[hd].out_off = 0;
-                d[hd].B = B; d[hd].H = Ws[hd]; d[hd].W = Ws[hd]; d[hd].C = l.cout; d[hd].stride = l.stride; d[hd].act = l.act;
-            }
-            if (!dw_group_ok(d, 3)) return false;
-            run_dw_group(h, hl[k], d, 3, name);
-            return true;
-        };
-        auto pw_layer = [&](int k, float* const src[3], float* const dst[3], int dst_ld, int n_store, const char* name) {
-            GemmArgs g3[3];
-            for (int hd = 0; hd < 3; ++hd)
-                g3[hd] = pw_args(h, *hl[k][hd], src[hd], NECK, 0, (long)B * Ws[hd] * Ws[hd], dst[hd], dst_ld, 0, nullptr, 0, 0, n_store);
-            return run_pw_group(h, hl[k], g3, 3, name);
-        };
-        // depthwise + pointwise pairs as one grouped kernel each (the depthwise output never reaches memory), else two grouped launches each
-        auto dwpw_layer = [&](int kd, float* const src_own[3], const float* const src_feat[3], float* const dst[3], const char* name) {
-            DwPwArgs q[3];
-            double fl = 0, by = 0;
-            for (int hd = 0; hd < 3; ++hd) {
-                const Layer &ld = *hl[kd][hd], &lp = *hl[kd + 1][hd];
-                q[hd] = DwPwArgs{};
-                q[hd].in = src_feat ? src_feat[hd] : src_own[hd];
-                q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
-                q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act; q[hd].Npad = lp.Npad;
-                q[hd].out = dst[hd]; q[hd].B = B; q[hd].H = Ws[hd]; q[hd].W = Ws[hd]; q[hd].C = ld.cout;
-                q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
-                if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK) return false;
-                const double M = (double)B * Ws[hd] * Ws[hd];
-                fl += 2.0 * M * NECK * (9.0 + NECK);
-                by += 4.0 * (2.0 * M * NECK + (double)NECK * NECK);
-            }
-            if (!dwpw_group_ok(q, 3)) return false;
-            Bracket br(h, name, fl, by);
-            launch_dwpw_group(q, 3, h->cur);
-            return true;
-        };
-        // layers .2 + .3 + .4 + the decode as ONE grouped kernel (head_tail_group_kernel): layer .3's output never reaches memory
-        auto tail_layer = [&](float* const src[3]) {
-            if (!fuse_all || !h->tail_fuse) return false;
-            HeadTailArgs q[3];
-            double fl = 0, by = 0;
-            for (int hd = 0; hd < 3; ++hd) {
-                const Layer &ld = *hl[2][hd], &lp = *hl[3][hd], &lf = *hl[4][hd];
-                if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK || lp.Npad != NECK || lf.cin != NECK || NECK != 96 || !lf.ws_hi) return false;
-                const GemmArgs gf = head_final_args(h, lf, src[hd], (long)B * Ws[hd] * Ws[hd]);
-                if (gf.act != 0 || gf.pass) return false;
-                q[hd] = HeadTailArgs{};
-                q[hd].in = src[hd]; q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
-                q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act;
-                q[hd].Wfh = gf.Wsh; q[hd].Wfl = gf.Wsl; q[hd].fbias = gf.bias; q[hd].Npad = gf.Npad;
-                q[hd].B = B; q[hd].H = Ws[hd]; q[hd].W = Ws[hd];
-                q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
-                const double M = (double)B * Ws[hd] * Ws[hd];
-                fl += 2.0 * M * NECK * (9.0 + NECK) + 2.0 * M * lf.cin * lf.cout;
-                by += 4.0 * (M * NECK + (double)NECK * NECK + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A);
-            }
-            if (!head_tail_ok(q, 3, h->grid)) return false;
-            set_last_kernel_name("head_tail_group_kernel");
-            Bracket br(h, "head_det_*.2+3+4+decode", fl, by);
-            launch_head_tail_group(q, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
-            return true;
-        };
-        bool ok = dwpw_layer(0, nullptr, feats, hB, "head_det_*.0+1") || (dw_layer(0, nullptr, feats, hA, "head_det_*.0") && pw_layer(1, hA, hB, NECK, 0, "head_det_*.1"));
-        const bool tailed = ok && tail_layer(hB);
-        if (ok && !tailed) ok = dwpw_layer(2, hB, nullptr, hC, "head_det_*.2+3") || (dw_layer(2, hB, nullptr, hA, "head_det_*.2") && pw_layer(3, hA, hC, NECK, 0, "head_det_*.3"));
-        if (ok && !tailed) {
-            if (fuse_all) {
-                GemmArgs g3[3];
-                double fl = 0, by = 0;
-                for (int hd = 0; hd < 3; ++hd) {
-                    const long M = (long)B * Ws[hd] * Ws[hd];
-                    g3[hd] = head_final_args(h, *hl[4][hd], hC[hd], M);
-                    fl += 2.0 * M * hl[4][hd]->cin * hl[4][hd]->cout;
-                    by += 4.0 * (M * (double)hl[4][hd]->cin + (double)hl[4][hd]->cin * hl[4][hd]->cout + 6.0 * M * h->grid.A);
-                }
-                set_last_kernel_name("head_decode_group_kernel");
-                Bracket br(h, "head_det_*.4+decode", fl, by);
-                launch_head_decode_group(g3, 3, h->grid, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->cur);
-            } else {
-                float* outs[3] = {heads[0], heads[1], heads[2]};
-                ok = pw_layer(4, hC, outs, head_ld, head_ld, "head_det_*.4");
-            }
-        }
+        const bool ok = head_dwpw_layer(h, hl[0], hl[1], B, nullptr, feats, hB, "head_det_*.0+1") ||
+                        (head_dw_layer(h, hl[0], B, nullptr, feats, hA, "head_det_*.0") && head_pw_layer(h, hl[1], B, hA, hB, NECK, 0, "head_det_*.1"));
         if (!ok) return fail(h, "grouped head launch: unsupported layer layout");
+        if (run_head_tail(h, -1, B, hB, hA, hC, heads, head_ld, fuse_all)) return 1;
     } else {
     fork_to(h, 0);
     if (run_head(0)) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
@@ -1632,7 +1696,11 @@ int yn_score_full(yn_handle* h, const float* h8, const float* h16, const float* 
 {
     YN_ENTER(h);
     const float* const heads[3] = {h8, h16, h32};
-    launch_score_full(heads, h->grid, B, all_bbox, all_class, h->stream);
+    h->cur = h->stream;
+    {
+        Bracket br(h, "score_full", 0.0, 0.0);
+        launch_score_full(heads, h->grid, B, all_bbox, all_class, h->stream);
+    }
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1796,6 +1864,14 @@ int yn_nms_merge(yn_handle* h, const float* boxes, const float* scores, const in
     return 0;
 }
 
+// the candidate decode of raw heads that a forward wrote out (no fused front end ran): heads with row stride g.head_ld -> h->cand_*
+static void decode_raw_heads(yn_handle* h, float* const heads[3], const GridInfo& g, int B)
+{
+    const float* const ch[3] = {heads[0], heads[1], heads[2]};
+    Bracket br(h, "decode", 0.0, 4.0 * B * ((double)(g.N / g.A) * h->head_ch + 6.0 * g.N));
+    launch_decode_cand(ch, g, B, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->stream);
+}
+
 int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* out_scores, int32_t* out_cls,
              int32_t* out_index, int32_t* count)
 {
@@ -1811,12 +1887,7 @@ int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* o
         float* const heads[3] = {h->heads_int[0], h->heads_int[1], h->heads_int[2]};
         bool fused = false;
         if (run_network(h, x_dev, B, heads, g.head_ld, true, &fused)) return 1;
-        const float* const ch[3] = {heads[0], heads[1], heads[2]};
-        if (!fused) {
-            set_last_kernel_name("decode_kernel<false>");
-            Bracket br(h, "decode", 0.0, 4.0 * B * ((double)(g.N / g.A) * h->head_ch + 6.0 * g.N));
-            launch_decode_cand(ch, g, B, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->stream);
-        }
+        if (!fused) decode_raw_heads(h, heads, g, B);
         {
             // one profiling bracket per NMS kernel (the hook closes the previous one); bytes: candidate arrays read / written once
             struct Ctx { yn_handle* h; Bracket* cur; double bytes; } ctx{h, nullptr, 4.0 * B * 12.0 * g.N / 5.0};
@@ -2152,6 +2223,61 @@ int yn_op_down_unit(yn_handle* h, const char* block, const float* x, int B, int 
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+// The candidate decode alone (decode_kernel<false, KMAX>): dense raw NHWC heads, row stride A(5+C) as for yn_score_full -> every candidate's
+// box [B,N,4], best score [B,N] and class [B,N] (-1 below conf_thresh).
+int yn_op_decode_cand(yn_handle* h, const float* h8, const float* h16, const float* h32, int B, float conf_thresh,
+                      float* boxes, float* scores, int32_t* cls)
+{
+    YN_ENTER(h);
+    if (B <= 0 || !h8 || !h16 || !h32 || !boxes || !scores || !cls) return fail(h, "yn_op_decode_cand: bad arguments");
+    const float* const heads[3] = {h8, h16, h32};
+    h->cur = h->stream;
+    {
+        Bracket br(h, "op.decode_cand", 0.0, 0.0);
+        launch_decode_cand(heads, h->grid, B, conf_thresh, boxes, scores, cls, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The stretch of yn_infer's forward from the output of the heads' layer .1 to the candidate arrays, on caller-provided activations
+// [B, S/8 (16, 32), same, 96] NHWC: run_head_tail with the handle's weights, switches and conf_thresh, the decode of the raw heads where
+// no fused front end ran, then the handle's candidate arrays copied out.
+int yn_op_head_tail(yn_handle* h, const float* x8, const float* x16, const float* x32, int B, float* boxes, float* scores, int32_t* cls)
+{
+    YN_ENTER(h);
+    if (check_ready(h, B)) return 1;
+    if (!x8 || !x16 || !x32 || !boxes || !scores || !cls) return fail(h, "yn_op_head_tail: null pointer");
+    if (int rp = range_pending(h, "yn_op_head_tail")) return rp;
+    GridInfo g = h->grid;
+    g.head_ld = (h->head_ch + 3) & ~3;
+    if (ensure_post(h, B, g.N, g.C) || ensure_heads(h, B)) return 1;
+    h->cur = h->stream;
+    DevBuf<float> tA, tC;
+    const size_t rows = (size_t)B * (g.hw[0] + g.hw[1] + g.hw[2]);
+    HIPCHK(h, tA.reserve(rows * NECK));
+    HIPCHK(h, tC.reserve(rows * NECK));
+    const float* const src[3] = {x8, x16, x32};
+    float* const hA[3] = {tA, tA + (size_t)B * g.hw[0] * NECK, tA + (size_t)B * (g.hw[0] + g.hw[1]) * NECK};
+    float* const hC[3] = {tC, tC + (size_t)B * g.hw[0] * NECK, tC + (size_t)B * (g.hw[0] + g.hw[1]) * NECK};
+    float* const heads[3] = {h->heads_int[0], h->heads_int[1], h->heads_int[2]};
+    const bool fuse_all = head_fuse_all(h, B, true);
+    int rc = 0;
+    if (heads_groupable(h)) rc = run_head_tail(h, -1, B, src, hA, hC, heads, g.head_ld, fuse_all);
+    else
+        for (int hd = 0; hd < 3 && !rc; ++hd) rc = run_head_tail(h, hd, B, src, hA, hC, heads, g.head_ld, fuse_all);
+    if (!rc && !fuse_all) decode_raw_heads(h, heads, g, B);
+    if (!rc) {
+        const size_t n = (size_t)B * g.N;
+        HIPCHK(h, hipMemcpyAsync(boxes, h->cand_boxes, n * 4 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(scores, h->cand_scores, n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cls, h->cand_cls, n * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));             // the scratch tensors go with this call
+    return rc;
 }
 
 int yn_op_nchw_to_nhwc(yn_handle* h, const float* x, int B, int C, int H, int W, float* y)
