@@ -61,6 +61,23 @@ const char* yn_last_error(yn_handle* h);
  * memory is shared with other processes and cannot show that a destroy gave everything back; this count can. */
 int  yn_live_device_memory(int64_t* blocks, int64_t* bytes);
 int  yn_set_grid(yn_handle* h, int input_size);                 /* YOLONano.set_grid            :115 */
+/* Rectangular inference.  A rectangular grid is a WINDOW OF A LETTERBOXED SQUARE: the canvas is height x width (positive multiples of 32),
+ * its top-left pixel sits at (left, top) of a side x side square, 0 <= left, left + width <= side, 0 <= top, top + height <= side.
+ *   input        x_dev [B][3][height][width]
+ *   raw heads    NHWC [B][height/8][width/8][A(5+C)], then /16, /32;  N = A * sum_s (height/st_s)(width/st_s)
+ *   candidates   scale first, then cell gy * (width/st) + gx, then anchor
+ *   boxes        normalised to the SQUARE, not the canvas: with p the canvas pixel coordinate, v = (p + off) / (float)side clamped to [0, 1],
+ *                off = left for x1 / x2, top for y1 / y2 - one normaliser for both axes.  So every consumer of the packed records
+ *                (yn_pack_detections -> yn_eval_add, yn_coco_add, yn_draw_batch) keeps the ordinary 7-field letterbox geometry of the square.
+ * A 1280x720 frame letterboxed to 640 is 640x360 of picture between two 140-row bands of pad; the 640x384 window at (0, 128) holds it all
+ * in 0.6 of the pixels.  The run differs from the square one only through what the convs see at the cut (zero padding instead of the pad's
+ * activations).  side = 0: side = max(height, width), the window centred (left / top are ignored).  The window that IS the whole square
+ * (height == width == side, left == top == 0) is yn_set_grid(side): the same code path, the same bits.
+ * Follow the grid: yn_forward_raw, yn_forward_taps, yn_score_full, yn_decode_boxes (canvas pixels, no offset), yn_infer, yn_postprocess,
+ * yn_pack_detections, yn_op_decode_cand, yn_op_head_tail.  Refused on a window grid ("... needs a square grid", nothing launched, the grid
+ * unchanged): yn_train_step, yn_train_forward, yn_loss, yn_loss_heads, yn_op_h16_loss, yn_make_targets, yn_tta_infer. */
+int  yn_set_grid_rect(yn_handle* h, int height, int width, int side, int left, int top);
+int  yn_grid_shape(yn_handle* h, int* height, int* width, int* side, int* left, int* top);   /* any pointer may be NULL */
 int  yn_set_stream(yn_handle* h, void* stream);                /* drains the previous stream first  */
 int  yn_set_thresholds(yn_handle* h, float conf_thresh, float nms_thresh, int diou_nms);
 int  yn_num_predictions(yn_handle* h);                          /* N for the current grid            */
@@ -197,6 +214,8 @@ int  yn_decode_boxes(yn_handle* h, const float* txtytwth_dev, int B, float* xyxy
 
 /* YOLONano.create_grid :86-112 — host arrays grid [HWtot,2], stride [HWtot,A,2], anchors [HWtot,A,2]. */
 int  yn_create_grid(yn_handle* h, int input_size, float* grid_host, float* stride_host, float* anchor_host);
+/* the same for a height x width canvas: cells of a scale in row order, gy * (width/st) + gx */
+int  yn_create_grid_rect(yn_handle* h, int height, int width, float* grid_host, float* stride_host, float* anchor_host);
 
 /* ---- post-processing ----------------------------------------------------------------------- */
 /* YOLONano.nms :159-188 / diou_nms :191-242 — one class.  dets [n,4] xyxy, scores [n]; writes the
@@ -222,6 +241,13 @@ int  yn_preprocess(yn_handle* h, const uint8_t* img_dev, int h0, int w0, int rw,
  * top}; x_dev = float32 [n][3][side][side] (the network's input batch). */
 int  yn_preprocess_batch(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, int side,
                          const float* mean_host, const float* std_host, float* x_dev);
+
+/* The win_w x win_h window at (win_left, win_top) of the tensor yn_preprocess_batch would write for the same arguments (the input of a
+ * yn_set_grid_rect grid): x_dev = float32 [n][3][win_h][win_w], the same resize arithmetic, pad value and normalise order, bit for bit.
+ * A window that cuts into any image's resized extent [left_i, left_i + rw_i) x [top_i, top_i + rh_i) is refused: only pad may be cut off. */
+int  yn_preprocess_batch_rect(yn_handle* h, int n, const uint8_t* const* imgs_host, const int32_t* geom_host, int side,
+                              int win_left, int win_top, int win_w, int win_h,
+                              const float* mean_host, const float* std_host, float* x_dev);
 
 /* TrainTransforms / ColorTransforms pixel work (data/transforms.py:402-442; call site data/voc.py:231), n images in one launch per
  * 32: imgs_host[i] = device pointer of frame i, uint8 [h0][w0][3] BGR as cv2.imread gives it -> x_dev float32 [n][3][side][side]

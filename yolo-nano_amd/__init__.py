@@ -11,6 +11,9 @@ def __getattr__(name):
     if name in ("YOLONano", "fuse_conv_bn", "Conv", "ShuffleNetV2", "ShuffleV2Block", "shufflenetv2", "SGD", "multi_gt_creator", "ModelEMA", "TestTimeAugmentation", "ValTransforms", "rescale_boxes", "resize_batch"):
         from . import model
         return getattr(model, name)
+    if name == "rect_window":
+        from . import rect                                    # host arithmetic only
+        return rect.rect_window
     if name in ("TrainTransforms", "ColorTransforms", "AugParams", "Mosaic", "MosaicParams"):
         from . import augment                                 # numpy only: safe to import in DataLoader workers
         return getattr(augment, name)

@@ -37,6 +37,8 @@ SIGNATURES = {
     "yn_last_error": (ctypes.c_char_p, [_vp]),
     "yn_live_device_memory": (_i32, [_i64p, _i64p]),
     "yn_set_grid": (_i32, [_vp, _i32]),
+    "yn_set_grid_rect": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "yn_grid_shape": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_set_stream": (_i32, [_vp, _vp]),
     "yn_set_thresholds": (_i32, [_vp, _f32, _f32, _i32]),
     "yn_num_predictions": (_i32, [_vp]),
@@ -72,6 +74,7 @@ SIGNATURES = {
     "yn_score_full": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "yn_decode_boxes": (_i32, [_vp, _vp, _i32, _vp]),
     "yn_create_grid": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "yn_create_grid_rect": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "yn_nms": (_i32, [_vp, _vp, _vp, _i32, _f32, _i32, _vp, _vp]),
     "yn_postprocess": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "yn_infer": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -93,6 +96,7 @@ SIGNATURES = {
     "yn_make_targets": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "yn_preprocess": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "yn_preprocess_batch": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "yn_preprocess_batch_rect": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "yn_train_transform_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yn_mosaic_transform_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "yn_nms_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -267,6 +271,7 @@ class Handle:
         self.h = h
         self._stream_ptr = cfg.stream
         self.C, self.S = int(num_classes), int(input_size)
+        self.H = self.W = self.S                                # the canvas; S is None on a rectangular grid (set_grid_rect)
         self.max_batch = max(int(max_batch), 1)
         self.backbone = backbone
         self.head_ch = arch.head_channels(self.C, self.A)
@@ -312,7 +317,22 @@ class Handle:
 
     def set_grid(self, S):
         self._ck(self.lib.yn_set_grid(self.h, int(S)), "yn_set_grid")
-        self.S = int(S)
+        self.S = self.H = self.W = int(S)
+
+    def set_grid_rect(self, H, W, side=0, left=0, top=0):
+        """The H x W window at (left, top) of a letterboxed side x side square (yn_set_grid_rect; side = 0: the smallest square, centred).
+        Boxes stay normalised to the square.  The window that is the whole square is set_grid(side)."""
+        self._ck(self.lib.yn_set_grid_rect(self.h, int(H), int(W), int(side), int(left), int(top)), "yn_set_grid_rect")
+        H, W, side, left, top = self.shape
+        self.H, self.W = H, W
+        self.S = side if (H == W == side and left == 0 and top == 0) else None
+
+    @property
+    def shape(self):
+        """(H, W, side, left, top) of the current grid."""
+        v = [ctypes.c_int32() for _ in range(5)]
+        self._ck(self.lib.yn_grid_shape(self.h, *[ctypes.addressof(x) for x in v]), "yn_grid_shape")
+        return tuple(int(x.value) for x in v)
 
     def set_stream(self, stream):
         self._ck(self.lib.yn_set_stream(self.h, stream.cuda_stream), "yn_set_stream")
@@ -450,12 +470,12 @@ class Handle:
 
     # ---- network
     def head_shapes(self, B):
-        return [(B, self.S // s, self.S // s, self.head_ch) for s in arch.STRIDES]
+        return [(B, self.H // s, self.W // s, self.head_ch) for s in arch.STRIDES]
 
     def forward_raw(self, x, out=None):
-        """x: cuda float32 NCHW [B,3,S,S] -> three NHWC head tensors."""
+        """x: cuda float32 NCHW [B,3,H,W] (the grid's canvas) -> three NHWC head tensors."""
         B = x.shape[0]
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape[1:]) == (3, self.S, self.S), (x.shape, self.S)
+        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape[1:]) == (3, self.H, self.W), (x.shape, self.H, self.W)
         x = self._in(x)
         if out is None:
             out = [torch.empty(s, dtype=torch.float32, device=x.device) for s in self.head_shapes(B)]
@@ -464,9 +484,10 @@ class Handle:
 
     def forward_taps(self, x):
         """The backbone taps (c3, c4, c5) of ShuffleNetV2.forward, NHWC."""
-        B, S = x.shape[0], self.S
+        B = x.shape[0]
+        assert tuple(x.shape[1:]) == (3, self.H, self.W), (x.shape, self.H, self.W)
         ch = arch.STAGE_CH[self.backbone]
-        outs = [torch.empty((B, S // st, S // st, c), dtype=torch.float32, device=x.device) for st, c in zip((8, 16, 32), ch)]
+        outs = [torch.empty((B, self.H // st, self.W // st, c), dtype=torch.float32, device=x.device) for st, c in zip((8, 16, 32), ch)]
         self._ck(self.lib.yn_forward_taps(self.h, self._in(x).data_ptr(), B, *[o.data_ptr() for o in outs]), "yn_forward_taps")
         return outs
 
@@ -486,12 +507,17 @@ class Handle:
         return out
 
     def create_grid(self, S):
+        """S: the square input size, or (H, W) of a rectangular canvas (yn_create_grid_rect)."""
         import numpy as np
-        HW = sum((S // s) ** 2 for s in arch.STRIDES)
+        H, W = (int(S[0]), int(S[1])) if isinstance(S, (tuple, list)) else (int(S), int(S))
+        HW = sum((H // s) * (W // s) for s in arch.STRIDES)
         g = np.empty((1, HW, 1, 2), np.float32)
         st = np.empty((1, HW, self.A, 2), np.float32)
         an = np.empty((1, HW, self.A, 2), np.float32)
-        self._ck(self.lib.yn_create_grid(self.h, int(S), g.ctypes.data, st.ctypes.data, an.ctypes.data), "yn_create_grid")
+        if isinstance(S, (tuple, list)):
+            self._ck(self.lib.yn_create_grid_rect(self.h, H, W, g.ctypes.data, st.ctypes.data, an.ctypes.data), "yn_create_grid_rect")
+        else:
+            self._ck(self.lib.yn_create_grid(self.h, H, g.ctypes.data, st.ctypes.data, an.ctypes.data), "yn_create_grid")
         return g, st, an
 
     # ---- post-processing
@@ -522,7 +548,7 @@ class Handle:
 
     def infer(self, x, out=None):
         B = x.shape[0]
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape[1:]) == (3, self.S, self.S), (x.shape, self.S)
+        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape[1:]) == (3, self.H, self.W), (x.shape, self.H, self.W)
         x = self._in(x)
         out = self.alloc_outputs(B, device=x.device) if out is None else out
         self._ck(self.lib.yn_infer(self.h, x.data_ptr(), B, *[o.data_ptr() for o in out]), "yn_infer")
@@ -623,6 +649,26 @@ class Handle:
         sd = (ctypes.c_float * 3)(*[float(v) for v in std])
         self._ck(self.lib.yn_preprocess_batch(self.h, n, ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(geom, ctypes.c_void_p), int(side),
                                               ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p), out.data_ptr()), "yn_preprocess_batch")
+        return out
+
+    def preprocess_batch_rect(self, imgs_u8, geoms, side, window, mean, std, out=None):
+        """The window (left, top, W, H) of what preprocess_batch writes for the same arguments (yn_preprocess_batch_rect) -> float32 [n,3,H,W];
+        a window that cuts into an image's resized extent is refused."""
+        n = len(imgs_u8)
+        wl, wt, ww, wh = (int(v) for v in window)
+        if out is None:
+            out = torch.empty((n, 3, wh, ww), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * 3 * wh * ww
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        geom = (ctypes.c_int32 * (6 * max(n, 1)))()
+        for i, (im, g) in enumerate(zip(imgs_u8, geoms)):
+            assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous() and im.is_cuda
+            ptrs[i] = im.data_ptr()
+            geom[6 * i:6 * i + 6] = [int(im.shape[0]), int(im.shape[1]), int(g[0]), int(g[1]), int(g[2]), int(g[3])]
+        m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self._ck(self.lib.yn_preprocess_batch_rect(self.h, n, ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(geom, ctypes.c_void_p), int(side), wl, wt, ww, wh,
+                                                   ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p), out.data_ptr()), "yn_preprocess_batch_rect")
         return out
 
     def train_transform_batch(self, imgs_u8, geom, photo, side, mean, std, out=None):
@@ -896,7 +942,7 @@ class Handle:
         xs = [self._in(t) for t in xs]
         B = xs[0].shape[0]
         for t, s in zip(xs, arch.STRIDES):
-            assert t.is_cuda and tuple(t.shape) == (B, self.S // s, self.S // s, arch.NECK_CH), (tuple(t.shape), self.S, s)
+            assert t.is_cuda and tuple(t.shape) == (B, self.H // s, self.W // s, arch.NECK_CH), (tuple(t.shape), self.H, self.W, s)
         boxes, scores, cls, _, _ = self.alloc_outputs(B, device=xs[0].device)
         self._ck(self.lib.yn_op_head_tail(self.h, xs[0].data_ptr(), xs[1].data_ptr(), xs[2].data_ptr(), B,
                                           boxes.data_ptr(), scores.data_ptr(), cls.data_ptr()), "yn_op_head_tail")

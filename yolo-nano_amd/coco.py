@@ -190,15 +190,27 @@ class COCOEval:
         return det, seg, matched, ignored
 
 
-def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None):
+def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None, rect=False):
     """COCOAPIEvaluator.evaluate for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3 BGR arrays,
     `image_ids` their COCO ids, `annotations` one float array [G][7] per image (coco_gt_arrays).  Per batch: ValTransforms.batch ->
     yn_infer -> yn_pack_detections -> yn_coco_add; nothing comes back to the host but two 4-byte counts per batch.
     -> (ap50, ap50_95) as the reference returns them; (0, 0) without any detection (cocoapi_evaluator.py:131-132).
     test_aug: a yolo_nano_amd.TestTimeAugmentation - every batch goes through its records() (yn_tta_infer) instead of the single
-    forward."""
+    forward.
+    rect=True: rectangular inference, as voc.evaluate - each batch on its own window of the letterboxed square."""
     from .model import ValTransforms
+    if rect and test_aug is not None:
+        raise ValueError("evaluate_coco: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
     size = int(model.input_size)
+    try:
+        return _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms)
+    finally:
+        if rect:
+            model.set_grid(size)
+
+
+def _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms):
+    from .voc import _rect_batch
     ev = None
     for s in range(0, len(images), batch):
         chunk = images[s:s + batch]
@@ -206,8 +218,12 @@ def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None
         if ev is None:
             ev = COCOEval(model.num_classes, handle=h)
         tf = ValTransforms(size, handle=h)
-        x = tf.batch(chunk)[0]
-        geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
+        if rect:
+            x, geoms = _rect_batch(model, tf, chunk)
+            h = model.handle(len(chunk))
+        else:
+            x = tf.batch(chunk)[0]
+            geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
         ids, gts = image_ids[s:s + batch], annotations[s:s + batch]
         if test_aug is not None:
             rec, off = test_aug.records(x, model)               # (its own range fallback)

@@ -27,6 +27,14 @@ __device__ __forceinline__ void cand_location(const GridInfo& g, int n, int& s, 
     a = local - cell * g.A;
 }
 
+// A window grid (GridInfo::win, yn_set_grid_rect) normalises pixel coordinate p of the H x W canvas to the side x side square the canvas is a
+// window of: x1 / x2 (k even) move by `left`, y1 / y2 by `top` - integers, exact as floats - and BOTH axes divide by side.  g.win is uniform over
+// the launch: a square grid branches past this and divides by S exactly as before.
+__device__ __forceinline__ float grid_window_norm(const GridInfo& g, float p, int k)
+{
+    return (p + (float)((k & 1) ? g.top : g.left)) / (float)g.side;
+}
+
 __device__ __forceinline__ void decode_one(const GridInfo& g, int s, int cell, int a, const float* t, float S, float* box, bool normalise)
 {
     const int gy = cell / g.w[s], gx = cell - gy * g.w[s];
@@ -39,7 +47,7 @@ __device__ __forceinline__ void decode_one(const GridInfo& g, int s, int cell, i
     if (normalise) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float v = box[k] / S;
+            float v = g.win ? grid_window_norm(g, box[k], k) : box[k] / S;
             box[k] = fminf(fmaxf(v, 0.0f), 1.0f);
         }
     }
@@ -98,7 +106,8 @@ __device__ __forceinline__ float decode_coord(const GridInfo& g, int s, int gx, 
     const float stride = (float)(8 << s);
     const float c = (sigmoid_f(tc) + (float)((k & 1) ? gy : gx)) * stride;
     const float e = expf(ts) * g.anchors[(s * g.A + a) * 2 + (k & 1)];
-    const float v = ((k < 2) ? c - e / 2 : c + e / 2) / S;
+    const float p = (k < 2) ? c - e / 2 : c + e / 2;
+    const float v = g.win ? grid_window_norm(g, p, k) : p / S;
     return fminf(fmaxf(v, 0.0f), 1.0f);
 }
 
@@ -2622,11 +2631,9 @@ struct PrepArgs {
     float* out;                                 // [3][side][side], channel 0 = R
 };
 
-__device__ __forceinline__ void preprocess_pixel(const PrepArgs& a, int i)
+// the pixel at (rx, ry) of the resized extent's frame (outside [0, rw) x [0, rh): pad) -> element i of the three output planes
+__device__ __forceinline__ void preprocess_at(const PrepArgs& a, int ry, int rx, size_t plane, int i)
 {
-    if (i >= a.side * a.side) return;
-    const int y = i / a.side, x = i - y * a.side;
-    const int ry = y - a.top, rx = x - a.left;
     float v[3];
     if (ry >= 0 && ry < a.rh && rx >= 0 && rx < a.rw) {
         int u[3];
@@ -2666,7 +2673,6 @@ __device__ __forceinline__ void preprocess_pixel(const PrepArgs& a, int i)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = a.mean[c] * 255.0f;                     // Resize.mean = [v * 255 for v in mean]
     }
-    const size_t plane = (size_t)a.side * a.side;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float t = v[c] / 255.0f;                                                   // Normalize: image /= 255.; -= mean; /= std
@@ -2674,6 +2680,13 @@ __device__ __forceinline__ void preprocess_pixel(const PrepArgs& a, int i)
         t = t / a.std[c];
         a.out[(size_t)(2 - c) * plane + i] = t;                                    // ToTensor: BGR -> RGB, HWC -> CHW
     }
+}
+
+__device__ __forceinline__ void preprocess_pixel(const PrepArgs& a, int i)
+{
+    if (i >= a.side * a.side) return;
+    const int y = i / a.side, x = i - y * a.side;
+    preprocess_at(a, y - a.top, x - a.left, (size_t)a.side * a.side, i);
 }
 
 __global__ __launch_bounds__(256) void preprocess_kernel(PrepArgs a) { preprocess_pixel(a, blockIdx.x * 256 + threadIdx.x); }
@@ -2692,6 +2705,42 @@ __global__ __launch_bounds__(256) void preprocess_batch_kernel(PrepBatchArgs b)
     for (int c = 0; c < 3; ++c) { a.mean[c] = b.mean[c]; a.std[c] = b.std[c]; }
     a.out = b.out + (size_t)blockIdx.y * 3 * b.side * b.side;
     preprocess_pixel(a, blockIdx.x * 256 + threadIdx.x);
+}
+
+// The win_w x win_h window at (win_left, win_top) of the tensor preprocess_batch_kernel writes: pixel (x, y) of the window is pixel
+// (x + win_left, y + win_top) of the square, through the same preprocess_at - the same bits.  out [n][3][win_h][win_w].
+struct PrepRectArgs { PrepImg im[PREP_MAX]; int win_left, win_top, win_w, win_h; float mean[3], std[3]; float* out; };
+__global__ __launch_bounds__(256) void preprocess_batch_rect_kernel(PrepRectArgs b)
+{
+    const PrepImg& d = b.im[blockIdx.y];
+    PrepArgs a;
+    a.img = d.img; a.h0 = d.h0; a.w0 = d.w0; a.rw = d.rw; a.rh = d.rh; a.left = d.left; a.top = d.top; a.side = 0;
+    a.mode = (d.rw == d.w0 && d.rh == d.h0) ? 0 : ((d.w0 == 2 * d.rw && d.h0 == 2 * d.rh) ? 1 : 2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a.mean[c] = b.mean[c]; a.std[c] = b.std[c]; }
+    const size_t plane = (size_t)b.win_w * b.win_h;
+    a.out = b.out + (size_t)blockIdx.y * 3 * plane;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= b.win_w * b.win_h) return;
+    const int y = i / b.win_w, x = i - y * b.win_w;
+    preprocess_at(a, y + b.win_top - a.top, x + b.win_left - a.left, plane, i);
+}
+
+void launch_preprocess_batch_rect(int n, const unsigned char* const* imgs, const int* geom, int win_left, int win_top, int win_w, int win_h,
+                                  const float* mean, const float* stdv, float* out, hipStream_t s)
+{
+    const size_t plane = (size_t)win_w * win_h;
+    for (int i0 = 0; i0 < n; i0 += PREP_MAX) {
+        const int m = n - i0 < PREP_MAX ? n - i0 : PREP_MAX;
+        PrepRectArgs b{};
+        for (int i = 0; i < m; ++i) {
+            const int* g = geom + (size_t)(i0 + i) * 6;
+            b.im[i] = PrepImg{imgs[i0 + i], g[0], g[1], g[2], g[3], g[4], g[5]};
+        }
+        b.win_left = win_left; b.win_top = win_top; b.win_w = win_w; b.win_h = win_h; b.out = out + (size_t)i0 * 3 * plane;
+        for (int c = 0; c < 3; ++c) { b.mean[c] = mean[c]; b.std[c] = stdv[c]; }
+        hipLaunchKernelGGL(preprocess_batch_rect_kernel, dim3((unsigned)((plane + 255) / 256), m), dim3(256), 0, s, b);
+    }
 }
 
 void launch_preprocess_batch(int n, const unsigned char* const* imgs, const int* geom, int side, const float* mean, const float* stdv,

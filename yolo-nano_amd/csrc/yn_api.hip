@@ -269,21 +269,38 @@ void build_layers(yn_handle* h)
     }
 }
 
-int set_grid_info(yn_handle* h, int S)
+// The grid of an H x W canvas that is the window at (left, top) of a letterboxed side x side square (include/yolonano_hip.h, yn_set_grid_rect);
+// the window that is the whole square is the square grid (win = 0, S = side).  The caller has validated the window.
+int set_grid_window(yn_handle* h, int H, int W, int side, int left, int top)
 {
-    if (S <= 0 || (S % 32) != 0) return fail(h, "input_size %d is not a positive multiple of 32", S);
     GridInfo& g = h->grid;
-    g.S = S; g.C = h->cfg.num_classes; g.A = h->cfg.num_anchors;
+    g.win = (H == W && W == side && left == 0 && top == 0) ? 0 : 1;
+    g.S = g.win ? 0 : side; g.C = h->cfg.num_classes; g.A = h->cfg.num_anchors;
+    g.H = H; g.W = W; g.side = side; g.left = left; g.top = top;
     int off = 0;
     for (int s = 0; s < 3; ++s) {
-        const int w = S / (8 << s);
-        g.w[s] = w; g.hw[s] = w * w; g.off[s] = off;
-        off += w * w * g.A;
+        const int w = W / (8 << s), hh = H / (8 << s);
+        g.w[s] = w; g.h[s] = hh; g.hw[s] = hh * w; g.off[s] = off;
+        off += hh * w * g.A;
     }
     g.N = off;
     g.head_ld = g.A * (5 + g.C);
     for (int i = 0; i < 18; ++i) g.anchors[i] = h->cfg.anchors[i];
     return 0;
+}
+
+int set_grid_info(yn_handle* h, int S)
+{
+    if (S <= 0 || (S % 32) != 0) return fail(h, "input_size %d is not a positive multiple of 32", S);
+    return set_grid_window(h, S, S, S, 0, 0);
+}
+
+// the entries that stay square in this library (training, loss, targets, test-time augmentation): refused on a window grid, nothing launched
+int need_square_grid(yn_handle* h, const char* who)
+{
+    if (!h->grid.win) return 0;
+    return fail(h, "%s needs a square grid: the handle holds the %d x %d window at (%d, %d) of a %d square (yn_set_grid_rect)", who, h->grid.H, h->grid.W,
+                h->grid.left, h->grid.top, h->grid.side);
 }
 
 const Param* find_param(yn_handle* h, const std::string& key)
@@ -293,10 +310,10 @@ const Param* find_param(yn_handle* h, const std::string& key)
 }
 
 // ---- arena ------------------------------------------------------------------------------------
-size_t network_arena_bytes(yn_handle* h, int B, int S)
+size_t network_arena_bytes(yn_handle* h, int B, int H, int W)
 {
-    // generous closed form: every buffer of run_network(), no reuse across stages
-    const size_t px2 = (size_t)B * (S / 2) * (S / 2), px4 = px2 / 4;
+    // generous closed form: every buffer of run_network(), no reuse across stages (H and W are multiples of 32: every division is exact)
+    const size_t px2 = (size_t)B * (H / 2) * (W / 2), px4 = px2 / 4;
     size_t fl = px2 * 24 + px4 * 24;
     int cin = 24;
     size_t cur = px4;
@@ -306,11 +323,12 @@ size_t network_arena_bytes(yn_handle* h, int B, int S)
         fl += po * cin + po * bf + cur * bf + po * bf + 2 * po * C;
         cin = C; cur = po;
     }
-    const size_t p3 = (size_t)B * (S / 8) * (S / 8), p4 = p3 / 4, p5 = p4 / 4;
+    const size_t p3 = (size_t)B * (H / 8) * (W / 8), p4 = p3 / 4, p5 = p4 / 4;
     fl += (p3 + p4 + p5) * NECK * 2 + p4 * NECK;      // laterals, smoothed (p4 twice)
     fl += (p3 + p4 + p5) * NECK * 3;                   // head scratch, one set per (concurrent) head
     return fl * sizeof(float) + 192 * 256;           // (rounding + 16 bytes of slack per buffer: arena_take)
 }
+size_t network_arena_bytes(yn_handle* h, int B, int S) { return network_arena_bytes(h, B, S, S); }
 
 // every cached hipGraphExec_t refers to the buffers it was captured with: destroy them whenever those go away
 void drop_train_graphs(yn_handle* h)
@@ -328,14 +346,14 @@ void drop_graphs(yn_handle* h)
     h->graphs.clear();
 }
 
-int ensure_arena(yn_handle* h, int B, int S)
+int ensure_arena(yn_handle* h, int B, int H, int W)
 {
-    const size_t need = network_arena_bytes(h, B, S);
+    const size_t need = network_arena_bytes(h, B, H, W);
     if (need <= h->arena_bytes) return 0;
     if (h->arena) HIPCHK(h, hipStreamSynchronize(h->stream));
-    // behind the activations: the sync words of stage_pipe_kernel (kernels_stage.hip) for the largest stage (stage 2: B (S/8)^2 rows, 32-row tiles,
+    // behind the activations: the sync words of stage_pipe_kernel (kernels_stage.hip) for the largest stage (stage 2: B (H/8)(W/8) rows, 32-row tiles,
     // up to YN_STAGE_MAX units).  Zeroed HERE, once, on the handle's stream; every launch leaves them zero.
-    const size_t sync_bytes = (stage_sync_words((int)((size_t)B * (S / 8) * (S / 8) / 32 + 1), YN_STAGE_MAX) * sizeof(unsigned) + 255) & ~(size_t)255;
+    const size_t sync_bytes = (stage_sync_words((int)((size_t)B * (H / 8) * (W / 8) / 32 + 1), YN_STAGE_MAX) * sizeof(unsigned) + 255) & ~(size_t)255;
     h->arena_bytes = 0; h->stage_sync = nullptr; h->stage_sync_bytes = 0;
     bool moved = false;
     const int rc = h->arena.reserve(need + sync_bytes, 0, &moved);
@@ -820,22 +838,21 @@ static GemmArgs head_final_args(yn_handle* h, const Layer& l, const float* in, l
 static bool head_fuse_all(yn_handle* h, int B, bool want)
 {
     char nm[96];
-    const int S = h->grid.S, W3 = S / 8;
+    const long M3 = (long)B * h->grid.hw[0];
     bool fuse_all = want && h->fuse_decode && !exact(h);
     for (int hd = 0; hd < 3 && fuse_all; ++hd) {
-        const int W = S / (8 << hd);
         snprintf(nm, sizeof nm, "head_det_%d.4", hd + 1);
-        fuse_all = head_decode_supported(head_final_args(h, L(h, nm), nullptr, (long)B * W * W), h->grid);
+        fuse_all = head_decode_supported(head_final_args(h, L(h, nm), nullptr, (long)B * h->grid.hw[hd]), h->grid);
     }
     // small batches: three 16 us fused launches against three 10 us GEMMs + one 7 us decode (bs = 1) - the fusion pays from the
     // traffic it removes, i.e. when the stride-8 head is large (bs >= 4 at 416x416); yn_fuse_decode(2) forces it (tests)
     // ... unless the wider fusion applies (head_tail_group_kernel: layers .2-.4 + decode as ONE launch instead of three: bs = 1 0.602 -> 0.593 ms)
     bool tail_possible = false;
     if (fuse_all && h->tail_fuse && h->group_launch && h->grid.C > 32) {
-        const GemmArgs gf = head_final_args(h, L(h, "head_det_1.4"), nullptr, (long)B * W3 * W3);
+        const GemmArgs gf = head_final_args(h, L(h, "head_det_1.4"), nullptr, M3);
         tail_possible = gf.Npad > 128 && gf.Npad <= 256;
     }
-    if (h->fuse_decode_mode != 2 && (long)B * W3 * W3 < 8192 && !tail_possible) fuse_all = false;
+    if (h->fuse_decode_mode != 2 && M3 < 8192 && !tail_possible) fuse_all = false;
     return fuse_all;
 }
 
@@ -846,11 +863,11 @@ static bool head_dw_layer(yn_handle* h, const Layer* const hl[3], int B, const f
     DwArgs d[3];
     for (int hd = 0; hd < 3; ++hd) {
         const Layer& l = *hl[hd];
-        const int W = h->grid.S / (8 << hd);
+        const int H = h->grid.h[hd], W = h->grid.w[hd];
         d[hd] = DwArgs{};
         d[hd].in = src_feat ? src_feat[hd] : src_own[hd]; d[hd].in_ld = NECK; d[hd].in_off = 0; d[hd].w = l.w_packed; d[hd].bias = l.b_packed;
         d[hd].out = dst[hd]; d[hd].out_ld = NECK; d[hd].out_off = 0;
-        d[hd].B = B; d[hd].H = W; d[hd].W = W; d[hd].C = l.cout; d[hd].stride = l.stride; d[hd].act = l.act;
+        d[hd].B = B; d[hd].H = H; d[hd].W = W; d[hd].C = l.cout; d[hd].stride = l.stride; d[hd].act = l.act;
     }
     if (!dw_group_ok(d, 3)) return false;
     run_dw_group(h, hl, d, 3, name);
@@ -861,8 +878,7 @@ static bool head_pw_layer(yn_handle* h, const Layer* const hl[3], int B, const f
 {
     GemmArgs g3[3];
     for (int hd = 0; hd < 3; ++hd) {
-        const int W = h->grid.S / (8 << hd);
-        g3[hd] = pw_args(h, *hl[hd], src[hd], NECK, 0, (long)B * W * W, dst[hd], dst_ld, 0, nullptr, 0, 0, n_store);
+        g3[hd] = pw_args(h, *hl[hd], src[hd], NECK, 0, (long)B * h->grid.hw[hd], dst[hd], dst_ld, 0, nullptr, 0, 0, n_store);
     }
     return run_pw_group(h, hl, g3, 3, name);
 }
@@ -874,15 +890,15 @@ static bool head_dwpw_layer(yn_handle* h, const Layer* const hld[3], const Layer
     double fl = 0, by = 0;
     for (int hd = 0; hd < 3; ++hd) {
         const Layer &ld = *hld[hd], &lp = *hlp[hd];
-        const int W = h->grid.S / (8 << hd);
+        const int H = h->grid.h[hd], W = h->grid.w[hd];
         q[hd] = DwPwArgs{};
         q[hd].in = src_feat ? src_feat[hd] : src_own[hd];
         q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
         q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act; q[hd].Npad = lp.Npad;
-        q[hd].out = dst[hd]; q[hd].B = B; q[hd].H = W; q[hd].W = W; q[hd].C = ld.cout;
+        q[hd].out = dst[hd]; q[hd].B = B; q[hd].H = H; q[hd].W = W; q[hd].C = ld.cout;
         q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
         if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK) return false;
-        const double M = (double)B * W * W;
+        const double M = (double)B * H * W;
         fl += 2.0 * M * NECK * (9.0 + NECK);
         by += 4.0 * (2.0 * M * NECK + (double)NECK * NECK);
     }
@@ -900,17 +916,17 @@ static bool head_tail_layer(yn_handle* h, const Layer* const hl2[3], const Layer
     double fl = 0, by = 0;
     for (int hd = 0; hd < 3; ++hd) {
         const Layer &ld = *hl2[hd], &lp = *hl3[hd], &lf = *hl4[hd];
-        const int W = h->grid.S / (8 << hd);
+        const int H = h->grid.h[hd], W = h->grid.w[hd];
         if (ld.stride != 1 || ld.cout != NECK || lp.cin != NECK || lp.cout != NECK || lp.Npad != NECK || lf.cin != NECK || NECK != 96 || !lf.ws_hi) return false;
-        const GemmArgs gf = head_final_args(h, lf, src[hd], (long)B * W * W);
+        const GemmArgs gf = head_final_args(h, lf, src[hd], (long)B * H * W);
         if (gf.act != 0 || gf.pass) return false;
         q[hd] = HeadTailArgs{};
         q[hd].in = src[hd]; q[hd].wdw = ld.w_packed; q[hd].bdw = ld.b_packed; q[hd].dw_act = ld.act;
         q[hd].Wh = lp.ws_hi; q[hd].Wl = lp.ws_lo; q[hd].bias = lp.b_packed; q[hd].act = lp.act;
         q[hd].Wfh = gf.Wsh; q[hd].Wfl = gf.Wsl; q[hd].fbias = gf.bias; q[hd].Npad = gf.Npad;
-        q[hd].B = B; q[hd].H = W; q[hd].W = W;
+        q[hd].B = B; q[hd].H = H; q[hd].W = W;
         q[hd].ovf = h->range_flags ? h->range_flags + 1 : nullptr;
-        const double M = (double)B * W * W;
+        const double M = (double)B * H * W;
         fl += 2.0 * M * NECK * (9.0 + NECK) + 2.0 * M * lf.cin * lf.cout;
         by += 4.0 * (M * NECK + (double)NECK * NECK + (double)lf.cin * lf.cout + 6.0 * M * h->grid.A);
     }
@@ -928,11 +944,11 @@ static int run_head_tail(yn_handle* h, int hd, int B, const float* const src[3],
 {
     char nm[96];
     if (hd >= 0) {
-        const int W = h->grid.S / (8 << hd);
-        const long M = (long)B * W * W;
+        const int H = h->grid.h[hd], W = h->grid.w[hd];
+        const long M = (long)B * H * W;
         snprintf(nm, sizeof nm, "head_det_%d", hd + 1);
         const std::string P = nm;
-        run_dwpw(h, L(h, P + ".2"), L(h, P + ".3"), src[hd], NECK, 0, B, W, W, hA[hd], hC[hd], NECK, 0, nullptr, 0, 0);
+        run_dwpw(h, L(h, P + ".2"), L(h, P + ".3"), src[hd], NECK, 0, B, H, W, hA[hd], hC[hd], NECK, 0, nullptr, 0, 0);
         const Layer& lf = L(h, P + ".4");
         if (fuse_all) {
             GemmArgs a = head_final_args(h, lf, hC[hd], M);
@@ -957,8 +973,7 @@ static int run_head_tail(yn_handle* h, int hd, int B, const float* const src[3],
             GemmArgs g3[3];
             double fl = 0, by = 0;
             for (int d = 0; d < 3; ++d) {
-                const int W = h->grid.S / (8 << d);
-                const long M = (long)B * W * W;
+                const long M = (long)B * h->grid.hw[d];
                 g3[d] = head_final_args(h, *hl[2][d], hC[d], M);
                 fl += 2.0 * M * hl[2][d]->cin * hl[2][d]->cout;
                 by += 4.0 * (M * (double)hl[2][d]->cin + (double)hl[2][d]->cin * hl[2][d]->cout + 6.0 * M * h->grid.A);
@@ -986,34 +1001,34 @@ static bool heads_groupable(yn_handle* h)
     return true;
 }
 
-// The network: x NCHW [B,3,S,S] -> three NHWC head tensors.
+// The network: x NCHW [B,3,H,W] (the grid's canvas; H = W = S on a square grid) -> three NHWC head tensors.
 // fuse_decode: the last conv of each head runs as head_decode_kernel (candidates written straight into h->cand_*, raw heads not stored);
 // *fused reports whether all three heads took that path (else the caller runs decode_kernel on the raw heads).
 int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int head_ld, bool fuse_decode = false, bool* fused = nullptr)
 {
-    const int S = h->grid.S;
+    const int GH = h->grid.H, GW = h->grid.W;
     h->arena_used = 0;
     h->cur = h->stream;
 #define TAKE(var, floats)                                                                   \
     float* var = arena_take(h, (size_t)(floats));                                           \
     if (!var) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes)
-    const int H1 = S / 2, H2 = S / 4;
-    TAKE(a0, (size_t)B * H1 * H1 * 24);
-    TAKE(a1, (size_t)B * H2 * H2 * 24);
+    const int H1 = GH / 2, W1 = GW / 2, H2 = GH / 4, W2 = GW / 4;
+    TAKE(a0, (size_t)B * H1 * W1 * 24);
+    TAKE(a1, (size_t)B * H2 * W2 * 24);
     {
-        // stem conv + maxpool in one kernel: the [B,S/2,S/2,24] conv activation stays in LDS (a0 is unused)
+        // stem conv + maxpool in one kernel: the [B,H/2,W/2,24] conv activation stays in LDS (a0 is unused)
         const Layer& l = L(h, "stem");
-        const double Mo = (double)B * H1 * H1;
-        Bracket br(h, "stem+maxpool", 2.0 * Mo * 27 * 24, 4.0 * ((double)B * 3 * S * S + (double)B * H2 * H2 * 24));
-        launch_stem_pool(x, B, S, S, l.w_packed, l.b_packed, l.cout, l.act, a1, h->cur);
+        const double Mo = (double)B * H1 * W1;
+        Bracket br(h, "stem+maxpool", 2.0 * Mo * 27 * 24, 4.0 * ((double)B * 3 * GH * GW + (double)B * H2 * W2 * 24));
+        launch_stem_pool(x, B, GH, GW, l.w_packed, l.b_packed, l.cout, l.act, a1, h->cur);
     }
     const float* cur = a1;
-    int curC = 24, curH = H2;
+    int curC = 24, curH = H2, curW = W2;
     const float* cfeat[3];
     char nm[96];
     for (int si = 0; si < 3; ++si) {
-        const int C = h->stage_ch[si], bf = C / 2, Ho = curH / 2;
-        const long Mi = (long)B * curH * curH, Mo = (long)B * Ho * Ho;
+        const int C = h->stage_ch[si], bf = C / 2, Ho = curH / 2, Wo = curW / 2;
+        const long Mi = (long)B * curH * curW, Mo = (long)B * Ho * Wo;
         TAKE(tdw1, Mo * curC);
         TAKE(tb1, Mo * bf);
         TAKE(t1, Mi * bf);
@@ -1036,7 +1051,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             d.W2h = lp2.ws_hi; d.W2l = lp2.ws_lo; d.b2 = lp2.b_packed; d.act2 = lp2.act; d.Npad2 = lp2.Npad;
             d.wdw1 = l1d.w_packed; d.bdw1 = l1d.b_packed; d.dw1_act = l1d.act;
             d.W3h = l1p.ws_hi; d.W3l = l1p.ws_lo; d.b3 = l1p.b_packed; d.act3 = l1p.act; d.Npad3 = l1p.Npad;
-            d.out = oA; d.B = B; d.H = curH; d.W = curH; d.bf = bf;
+            d.out = oA; d.B = B; d.H = curH; d.W = curW; d.bf = bf;
             d.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
             const bool use_down = h->down_fuse && !exact(h) && lp1.cin == curC && lp1.cout == bf && lp2.cin == bf && lp2.cout == bf && ldw.stride == 2 &&
                                   l1d.stride == 2 && l1d.cout == curC && l1p.cin == curC && l1p.cout == bf && down_unit_covers(d);
@@ -1046,7 +1061,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             d2.W2h = lp2.ws_hi; d2.W2l = lp2.ws_lo; d2.b2 = lp2.b_packed; d2.act2 = lp2.act;
             d2.wdw1 = l1d.w_packed; d2.bdw1 = l1d.b_packed; d2.dw1_act = l1d.act;
             d2.W3h = l1p.ws_hi; d2.W3l = l1p.ws_lo; d2.b3 = l1p.b_packed; d2.act3 = l1p.act;
-            d2.out = oA; d2.B = B; d2.H = curH; d2.W = curH; d2.bf = bf; d2.Npad = lp2.Npad;
+            d2.out = oA; d2.B = B; d2.H = curH; d2.W = curW; d2.bf = bf; d2.Npad = lp2.Npad;
             d2.ovf = h->range_flags ? h->range_flags + 1 : nullptr;
             const bool use_down2 = !use_down && h->down_fuse && !exact(h) && lp1.ws_hi && lp1.cin == curC && lp1.cout == bf && lp2.cin == bf && lp2.cout == bf &&
                                    ldw.stride == 2 && ldw.cout == bf && l1d.stride == 2 && l1d.cout == curC && l1p.cin == curC && l1p.cout == bf && l1p.Npad == lp2.Npad &&
@@ -1056,7 +1071,7 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             // launches).  Beyond that the extra k-steps stream their weights at the CU's L1 rate (each 32-row workgroup pulls the whole
             // matrix): 42 us against 30 + 13 at stage 3 (676 tiles), 58 against 34 + 17 at stage 4 (169 tiles) of a 32-image batch.
             const bool next_pays = Mo <= 32 * 64;
-            if (use_down2 && next_pays && STAGE_REP[si] > 1 && run_unit_chain(h, si + 2, STAGE_REP[si], oA, B, Ho, Ho, C, oB, t2, t1, nullptr, true) == 1) {
+            if (use_down2 && next_pays && STAGE_REP[si] > 1 && run_unit_chain(h, si + 2, STAGE_REP[si], oA, B, Ho, Wo, C, oB, t2, t1, nullptr, true) == 1) {
                 snprintf(nm, sizeof nm, "backbone.stage%d.1.b2.pw1", si + 2);
                 const Layer& l1n = L(h, nm);
                 if (l1n.ws_hi && l1n.cin == bf && l1n.cout == bf && l1n.Npad == lp2.Npad) {
@@ -1079,11 +1094,11 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
             } else {
         fork_to(h, 0);                                      // branch1 and branch2 only meet in the fused cat+shuffle
         {
-            run_dw(h, L(h, P0 + ".b1.dw"), cur, curC, 0, B, curH, curH, tdw1, curC, 0);
+            run_dw(h, L(h, P0 + ".b1.dw"), cur, curC, 0, B, curH, curW, tdw1, curC, 0);
             run_pw(h, L(h, P0 + ".b1.pw"), tdw1, curC, 0, Mo, tb1, bf, 0, nullptr, 0, 0);
             back_to_main(h);
             run_pw(h, L(h, P0 + ".b2.pw1"), cur, curC, 0, Mi, t1, bf, 0, nullptr, 0, 0);
-            run_dw(h, L(h, P0 + ".b2.dw"), t1, bf, 0, B, curH, curH, t2, bf, 0);
+            run_dw(h, L(h, P0 + ".b2.dw"), t1, bf, 0, B, curH, curW, t2, bf, 0);
             join_from(h, 0);
             run_pw(h, L(h, P0 + ".b2.pw2"), t2, bf, 0, Mo, oA, C, 0, tb1, bf, 0);     // cat + shuffle fused
         }
@@ -1094,25 +1109,25 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
         // stride-1 blocks (backbone/shufflenetv2.py:70-72; x1 = ch [0,bf) passes through, x2 = ch [bf,C)): one kernel per
         // unit, cut at the depthwise conv (unit_chain_kernel), after the first unit's pw1; else three kernels per unit
         const int R = STAGE_REP[si];
-        const int chained = R > 1 ? (down_chained ? run_unit_chain(h, si + 2, R, o_cur, B, Ho, Ho, C, o_nxt, t2, t1, &o_cur, false, true)
-                                                  : run_unit_chain(h, si + 2, R, o_cur, B, Ho, Ho, C, o_nxt, t1, t2, &o_cur)) : 0;
+        const int chained = R > 1 ? (down_chained ? run_unit_chain(h, si + 2, R, o_cur, B, Ho, Wo, C, o_nxt, t2, t1, &o_cur, false, true)
+                                                  : run_unit_chain(h, si + 2, R, o_cur, B, Ho, Wo, C, o_nxt, t1, t2, &o_cur)) : 0;
         if (down_chained && chained != 1) return fail(h, "stage %d: the chain the stride-2 unit prepared for did not run", si + 2);
         if (chained < 0) return 1;
         if (!chained) {
             for (int bi = 1; bi < R; ++bi) {
                 snprintf(nm, sizeof nm, "backbone.stage%d.%d", si + 2, bi);
                 const std::string P = nm;
-                run_unit(h, P, o_cur, B, Ho, Ho, o_nxt, t1, t2);
+                run_unit(h, P, o_cur, B, Ho, Wo, o_nxt, t1, t2);
                 float* tmp = o_cur; o_cur = o_nxt; o_nxt = tmp;
             }
         }
         cfeat[si] = o_cur;
         if (h->tap_out[si]) HIPCHK(h, hipMemcpyAsync(h->tap_out[si], o_cur, (size_t)Mo * C * sizeof(float), hipMemcpyDeviceToDevice, h->cur));
-        cur = o_cur; curC = C; curH = Ho;
+        cur = o_cur; curC = C; curH = Ho; curW = Wo;
     }
     // neck: models/yolo_nano.py:286-296
-    const int W3 = S / 8, W4 = S / 16, W5 = S / 32;
-    const long M3 = (long)B * W3 * W3, M4 = (long)B * W4 * W4, M5 = (long)B * W5 * W5;
+    const int H3 = GH / 8, H4 = GH / 16, H5 = GH / 32, W3 = GW / 8, W4 = GW / 16, W5 = GW / 32;
+    const long M3 = (long)B * H3 * W3, M4 = (long)B * H4 * W4, M5 = (long)B * H5 * W5;
     TAKE(p3, M3 * NECK); TAKE(p4, M4 * NECK); TAKE(p5, M5 * NECK);
     // the three laterals are independent (p3 is only needed by smooth_1): one grouped launch, or three launches with the large one
     // forked onto a side stream
@@ -1137,24 +1152,24 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
         run_pw(h, L(h, "conv1x1_2"), cfeat[2], h->stage_ch[2], 0, M5, p5, NECK, 0, nullptr, 0, 0);
     }
     TAKE(p4a, M4 * NECK); TAKE(p3a, M3 * NECK); TAKE(p4b, M4 * NECK); TAKE(p5a, M5 * NECK);
-    run_c3(h, L(h, "smooth_0"), p4, p5, 1, B, W4, W4, p4a);        // p4 + up2(p5)
+    run_c3(h, L(h, "smooth_0"), p4, p5, 1, B, H4, W4, p4a);        // p4 + up2(p5)
     join_from(h, 0);
-    run_c3(h, L(h, "smooth_1"), p3, p4a, 1, B, W3, W3, p3a);       // p3 + up2(p4)
+    run_c3(h, L(h, "smooth_1"), p3, p4a, 1, B, H3, W3, p3a);       // p3 + up2(p4)
     // heads: models/yolo_nano.py:299-301.  head k only needs its own pyramid level, so head 1 (the big one) starts on a
     // side stream as soon as smooth_1 is enqueued, head 2 after smooth_2, head 3 stays on the main stream.
     const float* feats[3] = {p3a, p4b, p5a};
-    const int Ws[3] = {W3, W4, W5};
+    const int Hs[3] = {H3, H4, H5}, Ws[3] = {W3, W4, W5};
     const bool fuse_all = head_fuse_all(h, B, fuse_decode);
     if (fused) *fused = fuse_all;
     auto run_head = [&](int hd) {
-        const long M = (long)B * Ws[hd] * Ws[hd];
+        const long M = (long)B * Hs[hd] * Ws[hd];
         float* hA = arena_take(h, (size_t)M * NECK);
         float* hB = arena_take(h, (size_t)M * NECK);
         float* hC = arena_take(h, (size_t)M * NECK);
         if (!hA || !hB || !hC) return 1;
         snprintf(nm, sizeof nm, "head_det_%d", hd + 1);
         const std::string P = nm;
-        run_dwpw(h, L(h, P + ".0"), L(h, P + ".1"), feats[hd], NECK, 0, B, Ws[hd], Ws[hd], hA, hB, NECK, 0, nullptr, 0, 0);
+        run_dwpw(h, L(h, P + ".0"), L(h, P + ".1"), feats[hd], NECK, 0, B, Hs[hd], Ws[hd], hA, hB, NECK, 0, nullptr, 0, 0);
         const float* const src[3] = {hB, hB, hB};           // (only entry hd is read)
         float* const sA[3] = {hA, hA, hA};
         float* const sC[3] = {hC, hC, hC};
@@ -1169,11 +1184,11 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
                 snprintf(nm, sizeof nm, "head_det_%d.%d", hd + 1, k);
                 hl[k][hd] = &L(h, nm);
             }
-        run_c3(h, L(h, "smooth_2"), p4a, p3a, 2, B, W4, W4, p4b);      // p4 + down(p3)
-        run_c3(h, L(h, "smooth_3"), p5, p4b, 2, B, W5, W5, p5a);       // p5 + down(p4)
+        run_c3(h, L(h, "smooth_2"), p4a, p3a, 2, B, H4, W4, p4b);      // p4 + down(p3)
+        run_c3(h, L(h, "smooth_3"), p5, p4b, 2, B, H5, W5, p5a);       // p5 + down(p4)
         float *hA[3], *hB[3], *hC[3];
         for (int hd = 0; hd < 3; ++hd) {
-            const size_t M = (size_t)B * Ws[hd] * Ws[hd];
+            const size_t M = (size_t)B * Hs[hd] * Ws[hd];
             hA[hd] = arena_take(h, M * NECK); hB[hd] = arena_take(h, M * NECK); hC[hd] = arena_take(h, M * NECK);
             if (!hA[hd] || !hB[hd] || !hC[hd]) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
         }
@@ -1185,11 +1200,11 @@ int run_network(yn_handle* h, const float* x, int B, float* const heads[3], int 
     fork_to(h, 0);
     if (run_head(0)) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
     back_to_main(h);
-    run_c3(h, L(h, "smooth_2"), p4a, p3a, 2, B, W4, W4, p4b);      // p4 + down(p3)
+    run_c3(h, L(h, "smooth_2"), p4a, p3a, 2, B, H4, W4, p4b);      // p4 + down(p3)
     fork_to(h, 1);
     if (run_head(1)) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
     back_to_main(h);
-    run_c3(h, L(h, "smooth_3"), p5, p4b, 2, B, W5, W5, p5a);       // p5 + down(p4)
+    run_c3(h, L(h, "smooth_3"), p5, p4b, 2, B, H5, W5, p5a);       // p5 + down(p4)
     if (run_head(2)) return fail(h, "activation arena exhausted (%zu bytes)", h->arena_bytes);
     join_from(h, 0);
     join_from(h, 1);
@@ -1310,6 +1325,36 @@ int yn_set_grid(yn_handle* h, int input_size)
     YN_ENTER(h);
     if (set_grid_info(h, input_size)) return 1;
     h->cfg.input_size = input_size;
+    return 0;
+}
+
+// A rectangular grid: the H x W window at (left, top) of a letterboxed side x side square (side = 0: the smallest square, the window centred).
+// The window that is the whole square is yn_set_grid(side).
+int yn_set_grid_rect(yn_handle* h, int height, int width, int side, int left, int top)
+{
+    YN_ENTER(h);
+    if (height <= 0 || width <= 0 || (height % 32) != 0 || (width % 32) != 0)
+        return fail(h, "yn_set_grid_rect: the extents %d x %d are not positive multiples of 32", height, width);
+    if (side == 0) {
+        side = height > width ? height : width;
+        left = (side - width) / 2; top = (side - height) / 2;
+    }
+    if (side < 0 || left < 0 || top < 0 || (long)left + width > side || (long)top + height > side)
+        return fail(h, "yn_set_grid_rect: the %d x %d window at (%d, %d) lies outside the %d x %d square", height, width, left, top, side, side);
+    if (set_grid_window(h, height, width, side, left, top)) return 1;
+    if (!h->grid.win) h->cfg.input_size = side;
+    return 0;
+}
+
+int yn_grid_shape(yn_handle* h, int* height, int* width, int* side, int* left, int* top)
+{
+    YN_ENTER(h);
+    const GridInfo& g = h->grid;
+    if (height) *height = g.H;
+    if (width) *width = g.W;
+    if (side) *side = g.side;
+    if (left) *left = g.left;
+    if (top) *top = g.top;
     return 0;
 }
 
@@ -1673,9 +1718,12 @@ int yn_forward_raw(yn_handle* h, const float* x_dev, int B, float* head_s8, floa
 {
     YN_ENTER(h);
     if (check_ready(h, B)) return 1;
-    if (ensure_arena(h, B, h->grid.S)) return 1;
+    const GridInfo& g = h->grid;
+    if (ensure_arena(h, B, g.H, g.W)) return 1;
     float* const heads[3] = {head_s8, head_s16, head_s32};
-    std::vector<uintptr_t> key = {1, (uintptr_t)B, (uintptr_t)h->grid.S, (uintptr_t)x_dev, (uintptr_t)head_s8, (uintptr_t)head_s16, (uintptr_t)head_s32};
+    // (the window is part of the key: a captured graph holds the grid it was captured with, GridInfo travels by value in the kernel arguments)
+    std::vector<uintptr_t> key = {1, (uintptr_t)B, (uintptr_t)g.H, (uintptr_t)g.W, (uintptr_t)g.side, (uintptr_t)g.left, (uintptr_t)g.top, (uintptr_t)x_dev,
+                                  (uintptr_t)head_s8, (uintptr_t)head_s16, (uintptr_t)head_s32};
     return run_maybe_graph(h, key, [&]() { return run_network(h, x_dev, B, heads, h->head_ch); });
 }
 
@@ -1684,7 +1732,7 @@ int yn_forward_taps(yn_handle* h, const float* x_dev, int B, float* c3_dev, floa
     YN_ENTER(h);
     if (check_ready(h, B)) return 1;
     if (!c3_dev || !c4_dev || !c5_dev) return fail(h, "yn_forward_taps: null output");
-    if (ensure_arena(h, B, h->grid.S) || ensure_heads(h, B)) return 1;
+    if (ensure_arena(h, B, h->grid.H, h->grid.W) || ensure_heads(h, B)) return 1;
     float* const heads[3] = {h->heads_int[0], h->heads_int[1], h->heads_int[2]};
     h->tap_out[0] = c3_dev; h->tap_out[1] = c4_dev; h->tap_out[2] = c5_dev;
     const int rc = run_network(h, x_dev, B, heads, (h->head_ch + 3) & ~3);       // eager: the taps are not part of any captured graph
@@ -1717,11 +1765,18 @@ int yn_create_grid(yn_handle* h, int input_size, float* grid, float* stride, flo
 {
     YN_ENTER(h);
     if (input_size <= 0 || input_size % 32) return fail(h, "input_size must be a positive multiple of 32");
+    return yn_create_grid_rect(h, input_size, input_size, grid, stride, anchor);
+}
+
+int yn_create_grid_rect(yn_handle* h, int height, int width, float* grid, float* stride, float* anchor)
+{
+    YN_ENTER(h);
+    if (height <= 0 || width <= 0 || height % 32 || width % 32) return fail(h, "yn_create_grid_rect: the extents %d x %d are not positive multiples of 32", height, width);
     const int A = h->cfg.num_anchors;
     size_t cell = 0;
     for (int s = 0; s < 3; ++s) {
-        const int st = 8 << s, w = input_size / st;
-        for (int y = 0; y < w; ++y)
+        const int st = 8 << s, w = width / st, hh = height / st;
+        for (int y = 0; y < hh; ++y)
             for (int x = 0; x < w; ++x, ++cell) {
                 grid[cell * 2 + 0] = (float)x; grid[cell * 2 + 1] = (float)y;      // (x, y): models/yolo_nano.py:96
                 for (int a = 0; a < A; ++a) {
@@ -1786,6 +1841,31 @@ int yn_preprocess_batch(yn_handle* h, int n, const uint8_t* const* imgs, const i
             return fail(h, "yn_preprocess_batch: bad geometry for image %d", i);
     }
     launch_preprocess_batch(n, imgs, geom, side, mean, stdv, x, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The win_w x win_h window at (win_left, win_top) of the tensor yn_preprocess_batch writes for the same images: x [n][3][win_h][win_w].
+// A window that cuts into an image's resized extent is refused (the picture must survive whole; only pad is cut off).
+int yn_preprocess_batch_rect(yn_handle* h, int n, const uint8_t* const* imgs, const int32_t* geom, int side, int win_left, int win_top, int win_w, int win_h,
+                             const float* mean, const float* stdv, float* x)
+{
+    YN_ENTER(h);
+    if (n == 0) return 0;
+    if (n < 0 || !imgs || !geom || !x || !mean || !stdv || side <= 0) return fail(h, "yn_preprocess_batch_rect: bad arguments");
+    if (win_w <= 0 || win_h <= 0 || win_left < 0 || win_top < 0 || (long)win_left + win_w > side || (long)win_top + win_h > side)
+        return fail(h, "yn_preprocess_batch_rect: the %d x %d window at (%d, %d) lies outside the %d x %d square", win_h, win_w, win_left, win_top, side, side);
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f)) return fail(h, "yn_preprocess_batch_rect: std must be positive");
+    for (int i = 0; i < n; ++i) {
+        const int32_t* g = geom + (size_t)i * 6;
+        if (!imgs[i] || g[0] <= 0 || g[1] <= 0 || g[2] <= 0 || g[3] <= 0 || g[4] < 0 || g[5] < 0 || g[4] + g[2] > side || g[5] + g[3] > side)
+            return fail(h, "yn_preprocess_batch_rect: bad geometry for image %d", i);
+        if (g[4] < win_left || g[5] < win_top || g[4] + g[2] > win_left + win_w || g[5] + g[3] > win_top + win_h)
+            return fail(h, "yn_preprocess_batch_rect: the window [%d, %d) x [%d, %d) cuts image %d, whose resized extent is [%d, %d) x [%d, %d)", win_left,
+                        win_left + win_w, win_top, win_top + win_h, i, g[4], g[4] + g[2], g[5], g[5] + g[3]);
+    }
+    launch_preprocess_batch_rect(n, imgs, geom, win_left, win_top, win_w, win_h, mean, stdv, x, h->stream);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1880,8 +1960,8 @@ int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* o
     if (int rp = range_pending(h, "yn_infer")) return rp;
     GridInfo g = h->grid;
     g.head_ld = (h->head_ch + 3) & ~3;
-    if (ensure_arena(h, B, g.S) || ensure_post(h, B, g.N, g.C) || ensure_heads(h, B)) return 1;
-    std::vector<uintptr_t> key = {2, (uintptr_t)B, (uintptr_t)g.S, (uintptr_t)x_dev, (uintptr_t)out_boxes, (uintptr_t)out_scores,
+    if (ensure_arena(h, B, g.H, g.W) || ensure_post(h, B, g.N, g.C) || ensure_heads(h, B)) return 1;
+    std::vector<uintptr_t> key = {2, (uintptr_t)B, (uintptr_t)g.H, (uintptr_t)g.W, (uintptr_t)g.side, (uintptr_t)g.left, (uintptr_t)g.top, (uintptr_t)x_dev, (uintptr_t)out_boxes, (uintptr_t)out_scores,
                                   (uintptr_t)out_cls, (uintptr_t)out_index, (uintptr_t)count};
     return run_maybe_graph(h, key, [&]() {
         float* const heads[3] = {h->heads_int[0], h->heads_int[1], h->heads_int[2]};
@@ -1936,6 +2016,7 @@ int yn_loss(yn_handle* h, const float* conf, const float* cls, const float* txty
             float* losses, float* g_conf, float* g_cls, float* g_txtytwth)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_loss")) return 1;
     if (B <= 0) return fail(h, "yn_loss: batch must be positive");
     if ((g_conf != nullptr) != (g_cls != nullptr) || (g_conf != nullptr) != (g_txtytwth != nullptr))
         return fail(h, "yn_loss: pass all three gradient buffers or none");
@@ -1950,6 +2031,7 @@ int yn_loss_heads(yn_handle* h, const float* head_s8, const float* head_s16, con
                   float* losses, float* g_s8, float* g_s16, float* g_s32)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_loss_heads")) return 1;
     if (B <= 0) return fail(h, "yn_loss_heads: batch must be positive");
     if ((g_s8 != nullptr) != (g_s16 != nullptr) || (g_s8 != nullptr) != (g_s32 != nullptr))
         return fail(h, "yn_loss_heads: pass all three gradient buffers or none");
@@ -1966,6 +2048,7 @@ int yn_loss_heads(yn_handle* h, const float* head_s8, const float* head_s16, con
 int yn_make_targets(yn_handle* h, const double* labels_dev, const int32_t* offsets_dev, int B, const double* anchors_host, float* target_dev)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_make_targets")) return 1;
     if (B <= 0 || !offsets_dev || !target_dev || !anchors_host) return fail(h, "yn_make_targets: bad arguments");
     if (h->grid.A != 3) return fail(h, "yn_make_targets: the label assigner is defined for 3 anchors per scale (got %d)", h->grid.A);
     HIPCHK(h, hipMemsetAsync(target_dev, 0, (size_t)B * h->grid.N * 11 * sizeof(float), h->stream));
@@ -2243,7 +2326,7 @@ int yn_op_decode_cand(yn_handle* h, const float* h8, const float* h16, const flo
 }
 
 // The stretch of yn_infer's forward from the output of the heads' layer .1 to the candidate arrays, on caller-provided activations
-// [B, S/8 (16, 32), same, 96] NHWC: run_head_tail with the handle's weights, switches and conf_thresh, the decode of the raw heads where
+// [B, H/8 (16, 32), W/8 (16, 32), 96] NHWC: run_head_tail with the handle's weights, switches and conf_thresh, the decode of the raw heads where
 // no fused front end ran, then the handle's candidate arrays copied out.
 int yn_op_head_tail(yn_handle* h, const float* x8, const float* x16, const float* x32, int B, float* boxes, float* scores, int32_t* cls)
 {
@@ -2647,6 +2730,7 @@ int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, flo
 {
     YN_ENTER(h);
     if (!t) return fail(h, "yn_tta_infer: null object");
+    if (need_square_grid(h, "yn_tta_infer")) return 1;      // (before anything of the object's is touched: the grid stays as it was found)
     t->last_B = -1; t->lists_B = -1; t->total = -1;
     if (t->device != h->cfg.device || t->A != h->cfg.num_anchors || t->C != h->cfg.num_classes)
         return fail(h, "yn_tta_infer: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", t->device, t->A, t->C,

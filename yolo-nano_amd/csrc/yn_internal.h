@@ -180,7 +180,14 @@ struct GridInfo {
     int hw[3], w[3], off[3];                    // cells per scale, width per scale, candidate offset
     int head_ld;                                // row stride (floats) of the raw head tensors: A(5+C), or padded to a multiple of 4
     float anchors[18];
+    // Rectangular grids (yn_set_grid_rect): the canvas is H x W, a window whose top-left pixel sits at (left, top) of a letterboxed side x side
+    // square; w[s] = W / stride, h[s] = H / stride, hw[s] = h[s] * w[s].  Boxes are normalised to the SQUARE: (p + left or top) / side.
+    // win = 0: the window is the whole square - the square grid, S = H = W = side, and the decode divides by S as it always has (no offset add:
+    // p + 0.0f would turn a -0 into +0 ahead of the clamp).  win = 1: S = 0.  (Behind the fields the square kernels read: their kernarg offsets stay.)
+    int H, W, h[3];
+    int side, left, top, win;
 };
+inline bool grid_is_square(const GridInfo& g) { return !g.win; }
 
 void launch_score_full(const float* const heads[3], const GridInfo& g, int B, float* all_bbox, float* all_class, hipStream_t s);
 void launch_decode_boxes(const float* txtytwth, const GridInfo& g, int B, float* xyxy, hipStream_t s);
@@ -374,6 +381,8 @@ void launch_preprocess(const unsigned char* img, int h0, int w0, int rw, int rh,
                        const float* mean, const float* stdv, float* out, hipStream_t s);
 void launch_preprocess_batch(int n, const unsigned char* const* imgs, const int* geom, int side, const float* mean, const float* stdv,
                              float* out, hipStream_t s);
+void launch_preprocess_batch_rect(int n, const unsigned char* const* imgs, const int* geom, int win_left, int win_top, int win_w, int win_h,
+                                  const float* mean, const float* stdv, float* out, hipStream_t s);
 // ---- TrainTransforms pixel pass (kernels_aug.hip): the rows of yn_train_transform_batch (include/yolonano_hip.h) ------------------
 constexpr int AUG_GEOM = 12, AUG_PHOTO = 7;    // int32 h0, w0, crop x, y, w, h, mirror, rw, rh, left, top, flags | f32 4 factors + pad[3]
 enum { AUG_BRIGHT = 1, AUG_CONTRAST = 2, AUG_CONTRAST_FIRST = 4, AUG_SAT = 8, AUG_HUE = 16, AUG_FLAGS_ALL = 31, AUG_MIRROR = 32 };

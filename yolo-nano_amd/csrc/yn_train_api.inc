@@ -198,6 +198,7 @@ int yn_train_step(yn_handle* h, const float* x_dev, const float* target_dev, int
                   float grad_scale, int do_update, float* losses_dev)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_train_step")) return 1;
     if (!h->tP) return fail(h, "yn_train_step before yn_train_bind");
     if (B <= 0) return fail(h, "batch must be positive (got %d)", B);
     return (h->train_dtype == YN_F16 ? train_step_h16 : train_step_f32)(h, x_dev, target_dev, B, lr, momentum, weight_decay, grad_scale, do_update, losses_dev);
@@ -206,6 +207,7 @@ int yn_train_step(yn_handle* h, const float* x_dev, const float* target_dev, int
 int yn_train_forward(yn_handle* h, const float* x_dev, int B, float* head_s8, float* head_s16, float* head_s32)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_train_forward")) return 1;
     if (!head_s8 || !head_s16 || !head_s32) return fail(h, "yn_train_forward: null output");
     h->fwd_only[0] = head_s8; h->fwd_only[1] = head_s16; h->fwd_only[2] = head_s32;
     const int rc = yn_train_step(h, x_dev, nullptr, B, 0.0f, 0.0f, 0.0f, 1.0f, 0, nullptr);

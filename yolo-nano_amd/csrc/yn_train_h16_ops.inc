@@ -574,6 +574,7 @@ int yn_op_h16_loss(yn_handle* h, const float* head_s8, const float* head_s16, co
                    float* losses, float* g_s8, float* g_s16, float* g_s32, int* pad_nonzero)
 {
     YN_ENTER(h);
+    if (need_square_grid(h, "yn_op_h16_loss")) return 1;
     if (!head_s8 || !head_s16 || !head_s32 || !target || B <= 0 || !losses || !(scale > 0.0f)) return fail(h, "yn_op_h16_loss: bad arguments");
     if ((g_s8 != nullptr) != (g_s16 != nullptr) || (g_s8 != nullptr) != (g_s32 != nullptr)) return fail(h, "yn_op_h16_loss: pass all three gradient buffers or none");
     if (ensure_loss(h, B)) return 1;

@@ -170,6 +170,7 @@ class YOLONano(nn.Module):
         if self.trainable:
             self.init_bias()
         self._handle = None
+        self._window = None                                   # (side, left, top) of a rectangular grid's window, None: the default
         self._handle_keys = None
         self._sig = None
         self._graph = False
@@ -207,8 +208,9 @@ class YOLONano(nn.Module):
         """models/yolo_nano.py:86-112 -> (grid [1,HW,1,2], stride [1,HW,A,2], anchors [1,HW,A,2])"""
         A = self.num_anchors
         g, st, aw = [], [], []
+        rect = isinstance(input_size, (tuple, list))         # (H, W): a rectangular canvas, cells in row order (yn_create_grid_rect)
         for ind, s in enumerate(self.stride):
-            ws = hs = input_size // s
+            hs, ws = (input_size[0] // s, input_size[1] // s) if rect else (input_size // s, input_size // s)
             gy, gx = torch.meshgrid(torch.arange(hs), torch.arange(ws), indexing="ij")
             g.append(torch.stack([gx, gy], dim=-1).float().view(1, hs * ws, 1, 2))
             st.append(torch.ones([1, hs * ws, A, 2]) * s)
@@ -217,11 +219,47 @@ class YOLONano(nn.Module):
         return (torch.cat(g, dim=1).to(dev), torch.cat(st, dim=1).to(dev), torch.cat(aw, dim=0).to(dev).unsqueeze(0))
 
     def set_grid(self, input_size):
-        """models/yolo_nano.py:115-117"""
+        """models/yolo_nano.py:115-117; input_size = S, or (H, W) for rectangular inference: the H x W window, centred, of the smallest
+        letterboxed square (set_window places it elsewhere).  Eval mode only: training stays square."""
+        if isinstance(input_size, (tuple, list)):
+            input_size = (int(input_size[0]), int(input_size[1]))
         self.input_size = input_size
+        self._window = None
         self.grid_cell, self.stride_tensor, self.all_anchors_wh = self.create_grid(input_size)
         if self._handle is not None:
-            self._handle.set_grid(input_size)
+            self._sync_grid(self._handle)
+
+    def set_window(self, side, left, top):
+        """Where the (H, W) canvas of set_grid((H, W)) sits in the letterboxed side x side square (yn_set_grid_rect); boxes come out
+        normalised to that square.  side = 0: the smallest square, centred."""
+        if not isinstance(self.input_size, tuple):
+            raise YnError("set_window: the grid is square (input_size %r); call set_grid((H, W)) first" % (self.input_size,))
+        self._window = (int(side), int(left), int(top))
+        if self._handle is not None:
+            self._sync_grid(self._handle)
+
+    def _grid_target(self):
+        """(H, W, side, left, top) the handle should hold, or None for the square grid of input_size."""
+        if not isinstance(self.input_size, tuple):
+            return None
+        H, W = self.input_size
+        side, left, top = self._window if getattr(self, "_window", None) else (0, 0, 0)
+        if side == 0:
+            side = max(H, W)
+            left, top = (side - W) // 2, (side - H) // 2
+        return (H, W, side, left, top)
+
+    def _sync_grid(self, h, square_only=None):
+        want = self._grid_target()
+        if want is None:
+            if h.S != self.input_size:
+                h.set_grid(self.input_size)
+            return
+        if square_only:
+            raise YnError("%s needs a square grid: the model holds the %d x %d window of a %d square (rectangular inference is eval-mode only)"
+                          % (square_only, want[0], want[1], want[2]))
+        if h.shape != want:
+            h.set_grid_rect(*want)
 
     # ---- native handle ------------------------------------------------------------------------------
     def use_graph(self, on=True):
@@ -245,7 +283,7 @@ class YOLONano(nn.Module):
         if self._handle is None or self._handle_keys != keys or self._handle.device != first.device:
             if self._handle is not None:
                 self._handle.close()
-            self._handle = Handle(self.input_size, self.num_classes, self.anchor_list, self.bk, self.conf_thresh, self.nms_thresh,
+            self._handle = Handle(self.input_size if not isinstance(self.input_size, tuple) else max(self.input_size), self.num_classes, self.anchor_list, self.bk, self.conf_thresh, self.nms_thresh,
                                   self.use_diou_nms, max_batch=batch, device=first.device)
             self._handle_keys = keys
             self._handle.use_graph(self._graph)
@@ -254,8 +292,7 @@ class YOLONano(nn.Module):
             self._sig = None
         h = self._handle
         h.follow_current_stream()
-        if h.S != self.input_size:
-            h.set_grid(self.input_size)
+        self._sync_grid(h)
         h.set_thresholds(self.conf_thresh, self.nms_thresh, self.use_diou_nms)
         if sig != self._sig:
             for k, v in sd.items():
@@ -363,6 +400,8 @@ class YOLONano(nn.Module):
         """The handle with this module's parameters living INSIDE its flat training buffers: every nn.Parameter becomes a
         view of `flat_params` (named_parameters() order == the C ABI's flat order), so the HIP step, torch.optim.SGD,
         `yolo_nano_amd.SGD`, load_state_dict and ModelEMA all see the same storage and nothing is copied per step."""
+        if self._grid_target() is not None:
+            self._sync_grid(None, "the training step")
         h = self._handle
         if h is None or self._bound is not h:
             h = self.handle(batch)                           # loads the current weights + BN statistics
@@ -381,8 +420,7 @@ class YOLONano(nn.Module):
             self._stats_stale = False
             h.train_precision(self._train_dtype)
         h.follow_current_stream()
-        if h.S != self.input_size:                           # multi-scale training: train.py:202-208
-            h.set_grid(self.input_size)
+        self._sync_grid(h, "the training step")             # multi-scale training: train.py:202-208
         if self._stats_stale:                                # load_state_dict after binding: push the BN statistics down
             for k, v in self.state_dict().items():
                 if k.endswith(("running_mean", "running_var")):
@@ -402,9 +440,10 @@ class YOLONano(nn.Module):
 
     def make_targets(self, label_lists):
         """tools.multi_gt_creator for this model's input size / anchors, on the model's device -> [B, N, 11] CUDA tensor."""
+        if self._grid_target() is not None:
+            self._sync_grid(None, "make_targets")
         h = self._handle if self._handle is not None else self.handle(len(label_lists))
-        if h.S != self.input_size:
-            h.set_grid(self.input_size)
+        self._sync_grid(h, "make_targets")
         return h.make_targets(label_lists, self.anchor_list)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -435,6 +474,8 @@ class YOLONano(nn.Module):
 
     def forward(self, x, target=None):
         if self.trainable:
+            if self._grid_target() is not None:
+                self._sync_grid(None, "the trainable forward")
             if target is None:
                 raise YnError("trainable forward needs target [B, N, 11] (tools.multi_gt_creator layout)")
             return _TrainStep.apply(self, x, target, *list(self.parameters()))
@@ -590,11 +631,28 @@ class ValTransforms(object):
         return x, boxes, labels, scale, offset
 
 
-    def batch(self, images, out=None):
+    def batch(self, images, out=None, rect=False):
         """A list of uint8 HxWx3 BGR frames (any sizes; numpy arrays, or CUDA uint8 tensors such as jpeg.imread's, which skip the
         upload) -> (x float32 [n,3,size,size] on the device, scales, offsets): the loop of benchmark.py:58 / vocapi_evaluator.py:64
-        over a batch, one kernel launch per 32 images."""
+        over a batch, one kernel launch per 32 images.
+        rect=True (rectangular inference): -> (x [n,3,H,W], geoms, window) - only the window (left, top, W, H) = rect_window(geoms, size)
+        of that tensor is written, the smallest one that holds every frame's picture; geoms are the unchanged rows (w0, h0, rw, rh, left,
+        top, side) the evaluators and the painter take.  The model runs it after set_grid((H, W)) + set_window(size, left, top)."""
         hd = self._h()
+        if rect:
+            from .rect import rect_window
+            dev_imgs, geoms = [], []
+            for im in images:
+                rw, rh, left, top = self.geometry(im.shape[0], im.shape[1])[:4]
+                if isinstance(im, torch.Tensor):
+                    assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "frames are uint8 [h,w,3]"
+                    dev_imgs.append(im.to(hd.device, non_blocking=True).contiguous())
+                else:
+                    dev_imgs.append(torch.as_tensor(np.ascontiguousarray(im, dtype=np.uint8)).to(hd.device, non_blocking=True))
+                geoms.append((int(im.shape[1]), int(im.shape[0]), int(rw), int(rh), int(left), int(top), int(self.size)))
+            window = rect_window(geoms, self.size)
+            x = hd.preprocess_batch_rect(dev_imgs, [g[2:6] for g in geoms], self.size, window, self.mean, self.std, out=out)
+            return x, geoms, window
         dev_imgs, geoms, scales, offsets = [], [], [], []
         for im in images:
             rw, rh, left, top, scale, offset = self.geometry(im.shape[0], im.shape[1])

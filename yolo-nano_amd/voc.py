@@ -165,15 +165,37 @@ class VOCEval:
         return out
 
 
-def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None):
+def _rect_batch(model, tf, chunk):
+    """One batch of rectangular inference: the frames' window of the letterboxed square (ValTransforms.batch(rect=True)), the model's grid
+    set to it - only when it differs from the one it holds - -> (x [B,3,H,W], geoms).  The records keep the square's normalisation."""
+    x, geoms, (left, top, W, H) = tf.batch(chunk, rect=True)
+    if model._grid_target() != (H, W, tf.size, left, top):
+        model.set_grid((H, W))
+        model.set_window(tf.size, left, top)
+    return x, geoms
+
+
+def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None, rect=False):
     """VOCAPIEvaluator.evaluate + do_python_eval for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3
     BGR arrays, `annotations` one int array [G][6] per image (gt_array).  Per batch: ValTransforms.batch -> yn_infer ->
     yn_pack_detections -> yn_eval_add; nothing comes back to the host but each batch's 4-byte record count.  -> (aps, mAP).
     test_aug: a yolo_nano_amd.TestTimeAugmentation - every batch goes through its records() (yn_tta_infer: all scales x flip, merged
     per image on the device) instead of the single forward: the mAP eval.py's -tta flag promises (eval.py:132 builds the object,
-    the evaluator never calls it)."""
+    the evaluator never calls it).
+    rect=True: rectangular inference - each batch runs on its own window of the letterboxed square (rect_window: the smallest one that
+    holds every frame's picture), the grid is set only when the window changes, and the model's square grid is back afterwards."""
     from .model import ValTransforms
+    if rect and test_aug is not None:
+        raise ValueError("evaluate: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
     size = int(model.input_size)
+    try:
+        return _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms)
+    finally:
+        if rect:
+            model.set_grid(size)
+
+
+def _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms):
     ev = None
     for s in range(0, len(images), batch):
         chunk = images[s:s + batch]
@@ -181,8 +203,12 @@ def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=
         if ev is None:
             ev = VOCEval(model.num_classes, ovthresh, handle=h)
         tf = ValTransforms(size, handle=h)
-        x = tf.batch(chunk)[0]
-        geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
+        if rect:
+            x, geoms = _rect_batch(model, tf, chunk)
+            h = model.handle(len(chunk))
+        else:
+            x = tf.batch(chunk)[0]
+            geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
         gts = annotations[s:s + batch]
         if test_aug is not None:
             rec, off = test_aug.records(x, model)               # (its own range fallback)
