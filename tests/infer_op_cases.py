@@ -62,7 +62,22 @@ DW_CASES = {
     "dw58-s1-long": (58, 1, (2, 70, 513)),
     "dw464-s2-long": (464, 2, (2, 67, 265)),
     "dw58-s2-long": (58, 2, (2, 135, 529)),
+    # the branch widths of the 1.5x / 2.0x backbones (88 / 176 / 352 and 122 / 244 / 488): each at both strides, Wo on the same marks around R,
+    # odd H and W at stride 2.  C = 122 is the wide backbones' only channel count that is no multiple of 4: the 2-channel variants
+    "dw88-s1-w3": (88, 1, (2, 4, 3)),                        # <1,4,2>, Wo = R + 1
+    "dw88-s2-w5": (88, 2, (2, 5, 5)),                        # <2,4,2>, Wo = 3
+    "dw122-s1-w5": (122, 1, (2, 3, 5)),                      # <1,2,4>, Wo = R + 1
+    "dw122-s1-w9": (122, 1, (3, 5, 9)),                      # <1,2,4>, Wo = 2R + 1
+    "dw122-s2-w5": (122, 2, (2, 5, 5)),                      # <2,2,2>, Wo = 3
+    "dw122-s2-w9": (122, 2, (3, 7, 9)),                      # <2,2,2>, Wo = 5
+    "dw244-s1-w5": (244, 1, (2, 3, 5)),                      # <1,4,2>, Wo = 2R + 1
+    "dw244-s2-w7": (244, 2, (2, 7, 7)),                      # <2,4,2>, Wo = 4
+    "dw352-s1-w2": (352, 1, (2, 3, 2)),                      # <1,4,2>, Wo = R
+    "dw352-s2-w3": (352, 2, (2, 5, 3)),                      # <2,4,2>, Wo = R
+    "dw488-s1-w3": (488, 1, (2, 5, 3)),                      # <1,4,2>, Wo = R + 1
+    "dw488-s2-w9": (488, 2, (3, 9, 9)),                      # <2,4,2>, Wo = 2R + 1
 }
+DW_WIDE_C = (88, 122, 244, 352, 488)
 
 
 def dw_last_run_partial(C, stride, B, H, W):
@@ -215,4 +230,12 @@ def maxpool_threads(B, H, W, C):
 # pointwise: the shape list of test_op_pointwise_shapes_vs_oracle (M, Cin, Cout, act), first configuration of each family
 # =====================================================================================================================================
 PW_CASES = [(1, 58, 58, 1), (127, 116, 116, 1), (129, 232, 232, 1), (1000, 464, 96, 2), (333, 24, 58, 1), (4096, 96, 255, 0), (77, 48, 24, 1), (5000, 96, 96, 2)]
+# the 1.5x (176 / 352 / 704, bf 88 / 176 / 352) and 2.0x (244 / 488 / 976, bf 122 / 244 / 488) networks: the unit GEMMs (K = N = bf), the GEMMs that enter a
+# stage (cin != cout: stage 2's pw1 and branch 1's pw read the stem's 24 channels; stages 3 / 4 enter with K = N = the unit list's 176 ... 488, the halved
+# N here are the same K against a narrower last tile) and the laterals of all three stages.  Ragged M throughout; N = 88 leaves 8, N = 122 six, N = 244 twelve and
+# N = 488 twenty-four masked columns of the last 32-column tile, K = 122 / 244 / 488 end inside an octet pair of the split operands
+PW_WIDE_UNIT = [(129, 88, 88, 1), (127, 122, 122, 1), (65, 176, 176, 1), (129, 244, 244, 1), (33, 352, 352, 1), (130, 488, 488, 1)]
+PW_WIDE_ENTRY = [(333, 24, 88, 1), (333, 24, 122, 1), (77, 176, 88, 1), (77, 244, 122, 1), (66, 352, 176, 1), (66, 488, 244, 1)]
+PW_WIDE_LATERAL = [(200, 704, 96, 2), (200, 976, 96, 2), (100, 176, 96, 2), (100, 352, 96, 2), (100, 244, 96, 2), (100, 488, 96, 2)]
+PW_WIDE_CASES = PW_WIDE_UNIT + PW_WIDE_ENTRY + PW_WIDE_LATERAL
 PW_FIRST_KERNEL = ("gemm_conv_kernel<4,1,1,0,16,2>", "gemm_split_kernel<4,1,1,32>")      # f32-MFMA family, split-f16 family

@@ -16,6 +16,8 @@ Which case reaches which kernel (template arguments in brackets):
   dwconv3x3_kernel      [1,4,2] dw24-s1-w1 / -w2 / -w3-h1, dw116-s1-w5     [1,2,4] dw58-s1-w1 / -w3 / -w4 / -w5-h1 / -w9     [2,4,2] dw116-s2-w1 / -w4 / -w10,
                         dw24-s2-w5-h1, dw232-s2-w9     [2,2,2] dw58-s2-w1 / -w3 / -w6-h1 / -w9: Wo = R - 1, R, R + 1, 2R + 1, one-row and one-column strips
                         [1,4,4] dw232-s1-long  [1,2,8] dw58-s1-long  [2,4,4] dw464-s2-long  [2,2,4] dw58-s2-long: the smallest tensors with >= 1024 blocks
+                        the branch widths of 1.5x / 2.0x: [1,4,2] dw88- / dw244- / dw352- / dw488-s1-*   [2,4,2] the same widths' -s2-* (odd H and W)
+                        [1,2,4] dw122-s1-w5 / -w9   [2,2,2] dw122-s2-w5 / -w9 (122 is the one wide width that is no multiple of 4)
   conv3x3_split_kernel  [1,1,9] c3s-1tile(-rs), c3s-3tiles(-rs), c3s-w65, c3s-n80   [1,1,3] c3s-w66 / -w70 / -w109   [1,1,1] c3s-w110 / -w112 / -w124
                         [1,2,1] c3s-86tiles   [3,2] c3s-257tiles
   conv3x3_halo_tap_kernel (exact_f32)  [1,96,1] c3t-1tile, c3t-3tiles-rs, c3t-w23 / -w32 / -w96, c3t-n192, c3t-n80   [1,96,2] c3t-w24, c3t-26x26, c3t-w31
@@ -26,7 +28,8 @@ Which case reaches which kernel (template arguments in brackets):
   stem_pool_kernel      sp-*: pooled extents below, at and above the 8 x 7 tile, odd conv extents (the -inf padding of the last window), B = 2 and 3
   maxpool_kernel        mp-*; mp-2nd-pass: the grid-stride loop's second turn
   gemm_conv_kernel<4,1,1,0,16,2> / gemm_split_kernel<4,1,1,32>   the pointwise shape list, plain and with the concat+shuffle epilogue (the other
-                        configurations of each family are pinned bit-identical to these by test_gpu_parity.py)
+                        configurations of each family are pinned bit-identical to these by test_gpu_parity.py); PW_WIDE_CASES: every K / N of the 1.5x and
+                        2.0x networks - unit GEMMs (K = N = 88 ... 488), stage entries (24 -> 88 / 122, 176 -> 88, ... 488 -> 244), laterals (K = 704 / 976)
 
 Measured on an MI355X: the worst (kernel error) / (4 * e32 + 4 ulp) over the random cases of each family, with that case's kernel error and e32.
 Every exact case matched bit for bit.
@@ -36,6 +39,8 @@ Every exact case matched bit for bit.
   conv3x3_halo        0.25  c3h-96-96-w97 act 1        8.5e-05 / 7.7e-05        pointwise split-f16 0.14  77x48->24 act 1         3.5e-06 / 4.4e-06
   gemm_conv (3x3)     0.27  c3g-256-96 act 1           3.6e-04 / 3.2e-04        (the shuffle form gives the same figures as the plain one: same bits)
 The split-f16 kernels stay below half of the f32-MFMA kernels' error on the same problems (c3s-* against c3t-*, pointwise split against f32).
+With the 1.5x / 2.0x widths added the worst cases moved to them: depthwise 0.23 dw122-s1-w9 act 1 (2.0e-06 / 1.1e-06), pointwise f32-MFMA 0.47 33x352->352 act 0
+(6.2e-05 / 2.6e-05), pointwise split-f16 0.15 on the same problem (1.9e-05); every exact case, K = 976 included, matched bit for bit.
 The cases notice what the whole-network tests cannot.  Tried once with a deliberately wrong library, three mask changes (no address, bound or loop limit
 touched): (1) dwconv3x3_block's column mask left on for the column just past the right edge (the clamped load then brings the last column in) failed every
 depthwise case, exact and random, whose last window reaches past the edge - all stride-1 cases, the four long-run ones included, and the stride-2 cases of
@@ -305,7 +310,7 @@ def _pw_each(hop, fam, M, cin, cout, x, w, b, passthrough, acts):
 
 
 @pytest.mark.parametrize("fam", [0, 1], ids=["f32", "split"])
-@pytest.mark.parametrize("M,cin,cout,act", ioc.PW_CASES)
+@pytest.mark.parametrize("M,cin,cout,act", ioc.PW_CASES + ioc.PW_WIDE_CASES)
 def test_pw_exact(hop, M, cin, cout, act, fam):
     x, w, b, passthrough = _pw_data(M, cin, cout, ints, 91)
     pre = _pw_ref(x, w, b, torch.float64)
@@ -315,7 +320,7 @@ def test_pw_exact(hop, M, cin, cout, act, fam):
 
 
 @pytest.mark.parametrize("fam", [0, 1], ids=["f32", "split"])
-@pytest.mark.parametrize("M,cin,cout,act", ioc.PW_CASES)
+@pytest.mark.parametrize("M,cin,cout,act", ioc.PW_CASES + ioc.PW_WIDE_CASES)
 def test_pw_random(hop, M, cin, cout, act, fam):
     x, w, b, passthrough = _pw_data(M, cin, cout, normal, 92)
     p64, p32 = _pw_ref(x, w, b, torch.float64), _pw_ref(x, w, b, torch.float32)

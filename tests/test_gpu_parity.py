@@ -106,7 +106,8 @@ def test_op_maxpool_and_layout(golden, hvoc):
 @pytest.mark.parametrize("M,cin,cout,act", [(1, 58, 58, 1), (127, 116, 116, 1), (129, 232, 232, 1), (1000, 464, 96, 2),
                                            (333, 24, 58, 1), (4096, 96, 255, 0), (77, 48, 24, 1), (5000, 96, 96, 2)])
 def test_op_pointwise_shapes_vs_oracle(hvoc, M, cin, cout, act):
-    """ragged M (tile tails), every K/N of the 1.0x and 0.5x networks, fused activations."""
+    """ragged M (tile tails), every K/N of the 1.0x and 0.5x networks, fused activations.  The K/N of the 1.5x and 2.0x networks (up to K = 976,
+    N = 488) are infer_op_cases.PW_WIDE_CASES, run against float64 by tests/test_gpu_infer_ops.py."""
     rs = np.random.RandomState(M + cin)
     x = rs.standard_normal((1, cin, 1, M)).astype(np.float32)
     w = (rs.standard_normal((cout, cin, 1, 1)) / np.sqrt(cin)).astype(np.float32)
@@ -116,7 +117,8 @@ def test_op_pointwise_shapes_vs_oracle(hvoc, M, cin, cout, act):
 
 
 @pytest.mark.parametrize("M,cin,cout,act", [(127, 116, 116, 1), (1000, 232, 232, 1), (333, 24, 58, 1), (4096, 96, 255, 0),
-                                           (700, 464, 96, 2), (77, 48, 24, 1)])
+                                           (700, 464, 96, 2), (77, 48, 24, 1),
+                                           (200, 976, 96, 2), (130, 488, 488, 1), (127, 122, 122, 1), (333, 24, 88, 1)])     # K / N of the 1.5x and 2.0x networks
 def test_op_pointwise_every_tile_configuration_bit_identical(hvoc, M, cin, cout, act):
     """All instantiated GEMM configurations (LDS-tiled, register-direct) sum k in the same order: pinning any of
     them must give bit-identical output (the autotuner's choice is a pure speed matter), and a shuffle unit with its

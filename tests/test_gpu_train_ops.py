@@ -19,8 +19,11 @@ Which exact case reaches which kernel of csrc/kernels_bwd.hip (template variant 
                         [3,3 pw] pw464-96, pw96-255-head                       [2,2 dense] c3-6-14, c3-6-14-strip   [2,4 dense] c3-8-16, c3-8-16-m1
                         [3,3 dense] c3-96-96 (one slice), c3-96-96-m297 (two slices, the cut inside an image), c3-96-96-b3
                         wgrad_reduce_kernel in all of them; ragged last slice: m257 (136 + 121 rows), m999 (3 x 256 + 231), m297 (152 + 145)
+                        the 1.5x / 2.0x widths (no tile beyond these three): [2,4 pw] pw122-122-off-acc (one slice, a channel slice of the unit tensor),
+                        pw244-244-m297, pw488-488-m297 (two slices)   [3,3 pw] pw352-352-m297 (two slices), pw976-96, pw704-96 (31 / 22 k-tiles for 33 / 24)
   dw_wgrad_kernel       [1,vec] dw*-s1 (W = 7, 8, 9, 13: below, at and above one run of 8)     [2,vec] dw*-s2 (W = 6, 10, 12: Wo = 3, 5, 6 around the run of 4;
-                        odd H / W in dw232-s2-odd, dw58-s2-odd), rows_sum_kernel; dw232-s1-cap clips the block count (14 -> 8).  The non-vector variants [*,false] need an
+                        odd H / W in dw232-s2-odd, dw58-s2-odd, dw488-s2-odd), rows_sum_kernel; dw122- / dw244- / dw352- / dw488-*: the wide branch widths on 64,
+                        128 and 256 channel-pair lanes (at 256 a block holds ONE row-lane: the LDS combine adds nothing); dw232-s1-cap clips the block count (14 -> 8).  The non-vector variants [*,false] need an
                         odd channel offset or count: no tensor of the network has one, the forward kernel cannot read one, the entry refuses it (asserted).
   dw_dgrad_s2_kernel    dw*-s2, accumulate 0 and 1        stem_wgrad_kernel  stem-* (Wo = 15, 16, 17, 24: a ragged and a full last 16-pixel step; stem-cap: more rows than 4 x blocks)
   col_reduce_kernel     [3: plain column sum] dbias of every conv case (pw96-255-head: odd C on a padded row, 10 blocks over the 8 slots)
@@ -29,7 +32,8 @@ Which exact case reaches which kernel of csrc/kernels_bwd.hip (template variant 
   strided_copy_kernel   the accumulate route of every stride-1 dx (tmp, then += into the view) and the unit form's even channels (test_bn, exact part)
   pack_bwd_kernel       [0] pw dx  [1] depthwise stride-1 dx  [2] dense dx          grad_combine_kernel  dw / dbias of every conv case
   bn_apply_kernel       [1 dense] plain   [2 shuffle] unit form          bn_bwd_kernel / col_reduce_kernel<2>  [vec] plain dense dz
-                        [non-vec] the unit form (dz_cs = 2), bn-dzoff (odd dz_off).  bn_apply_kernel<0> (scalar stores) and the odd-C lanes of these kernels
+                        [non-vec] the unit form (dz_cs = 2), bn-dzoff (odd dz_off).  bn-*x122 / x176 / x244 / x352 / x488: the wide widths, plain and unit form;
+                        col_reduce_kernel's LDS combine with 4, 2, 2, 1 and 1 row-lanes per block (1.0x: 2 at C = 232).  bn_apply_kernel<0> (scalar stores) and the odd-C lanes of these kernels
                         serve no layer of the network; they read the pair (c, c + 1) of a dense row, one float past an odd-C tensor's end, so the entry refuses odd C.
 Not reached at these sizes: launch_dw's long-run variants (R = 4 / 8) need more than 261888 threads, i.e. tensors of millions of elements; they are forward
 kernels of kernels_conv.hip, and tests/test_gpu_infer_ops.py checks each of them on its own against float64 (the inference parity tests run them only inside
@@ -44,6 +48,9 @@ Every exact case matched bit for bit.
   bn dy       0.19  bn-64x24-relu    4.9e-07 / 3.9e-07        bn dgamma   0.16  bn-333x116-unit  3.6e-06 / 3.6e-06
   bn dbeta    0.07  bn-64x24-relu    4.1e-07 / 4.3e-07        resample    0.13  mode 2, 4<->2    5.4e-07 / 5.4e-07
   undecided activation signs: at most 2.6e-05 of a case's elements (bn-333x116), none in six of the ten cases.
+  With the 1.5x / 2.0x widths added, five of the worst cases moved to them, none above 0.20: conv dbias 0.17 dw244-s1-w7 (2.8e-06 / 2.3e-06), bn mean 0.08, bn z 0.17 and
+  bn dy 0.20 bn-65x352-leaky (1.5e-08 / 1.7e-08, 4.0e-07 / 3.7e-07, 7.6e-07 / 4.7e-07), bn dbeta 0.08 bn-65x352-unit (9.4e-07 / 9.7e-07); undecided signs at most 4.4e-05
+  (bn-65x352).  Every exact case at the wide widths matched bit for bit.
 The cases notice what the whole-step tests cannot.  Tried once with deliberately wrong libraries: the last row pair of an M slice masked off in
 wgrad_kernel together with a bottom-border tap of the dense im2col reading the next image failed every pointwise and dense case, exact and random; the last
 pixel of a partial run dropped in dw_wgrad_kernel failed every depthwise case that has a partial run (W = 8 has none and rightly passed); one row counted
@@ -84,6 +91,14 @@ CONV_CASES = {
     "pw96-255-head": (PW, 96, 255, 1, (3, 5, 5), {"y_ld": 256}),
     "pw58-58-off-acc": (PW, 58, 58, 1, (2, 9, 7), {"x_ld": 116, "x_off": 58, "acc": (0, 1)}),      # pw1 of a stride-1 unit: the second half of the unit tensor
     "pw116-116-cap": (PW, 116, 116, 1, (3, 9, 37), {"cap": 2}),
+    # the 1.5x / 2.0x networks: pw1 of a 2.0x stage-2 unit (bf 122: no multiple of 4) on the second half of its unit tensor; the unit GEMMs of the
+    # wider stages at M = 297 (two slices of 152 + 145 rows, the cut inside an image); the two widest laterals
+    "pw122-122-off-acc": (PW, 122, 122, 1, (2, 9, 7), {"x_ld": 244, "x_off": 122, "acc": (0, 1)}),
+    "pw244-244-m297": (PW, 244, 244, 1, (3, 9, 11), {}),
+    "pw352-352-m297": (PW, 352, 352, 1, (3, 9, 11), {}),
+    "pw488-488-m297": (PW, 488, 488, 1, (3, 9, 11), {}),
+    "pw976-96": (PW, 976, 96, 1, (2, 9, 7), {}),
+    "pw704-96": (PW, 704, 96, 1, (2, 9, 7), {}),
     # dense 3x3: the network's 96 -> 96, and the two small shapes that select the other tiles
     "c3-96-96": (C3, 96, 96, 1, (2, 9, 7), {"acc": (0, 1)}),
     "c3-96-96-b3": (C3, 96, 96, 1, (3, 5, 5), {}),
@@ -105,6 +120,15 @@ CONV_CASES = {
     "dw116-s2-w12": (DW, 116, 116, 2, (3, 4, 12), {"acc": (0, 1)}),
     "dw232-s2-odd": (DW, 232, 232, 2, (2, 7, 9), {"acc": (0, 1)}),
     "dw58-s2-odd": (DW, 58, 58, 2, (1, 5, 5), {"acc": (0, 1)}),
+    # the branch widths of 2.0x and 1.5x stage 4: 122 (61 channel pairs on 64 lanes), 244 (122 on 128), 352 and 488 (176 / 244 on 256 lanes: one row-lane per block)
+    "dw122-s1-w9": (DW, 122, 122, 1, (2, 5, 9), {"acc": (0, 1)}),
+    "dw244-s1-w7": (DW, 244, 244, 1, (2, 5, 7), {"acc": (0, 1)}),
+    "dw352-s1-w8": (DW, 352, 352, 1, (2, 4, 8), {"acc": (0, 1)}),
+    "dw488-s1-w13": (DW, 488, 488, 1, (2, 4, 13), {"acc": (0, 1)}),
+    "dw122-s2-w6": (DW, 122, 122, 2, (2, 8, 6), {"acc": (0, 1)}),
+    "dw244-s2-w10": (DW, 244, 244, 2, (2, 6, 10), {"acc": (0, 1)}),
+    "dw352-s2-w12": (DW, 352, 352, 2, (3, 4, 12), {"acc": (0, 1)}),
+    "dw488-s2-odd": (DW, 488, 488, 2, (2, 7, 9), {"acc": (0, 1)}),
     # stem: Wo = 16, 15, 24, 17; B = 1 and 3
     "stem-32x32-b1": (STEM, 3, 24, 2, (1, 32, 32), {}),
     "stem-32x32-b3": (STEM, 3, 24, 2, (3, 32, 32), {}),
@@ -246,6 +270,16 @@ BN_CASES = {
     "bn-333x116-unit": (333, 116, 1, True, (0, 0)),
     "bn-64x24-unit-leaky": (64, 24, 2, True, (0, 0)),
     "bn-dzoff": (129, 58, 2, False, (6, 3)),
+    # the BatchNorm widths of 1.5x / 2.0x: 122 only occurs as a unit's last layer (2.0x stage 2); 176 ... 488 as pw1 (plain) and pw2 (unit form)
+    "bn-77x122-unit": (77, 122, 1, True, (0, 0)),
+    "bn-129x176-relu": (129, 176, 1, False, (0, 0)),
+    "bn-129x176-unit": (129, 176, 1, True, (0, 0)),
+    "bn-300x244": (300, 244, 0, False, (0, 0)),
+    "bn-300x244-unit": (300, 244, 1, True, (0, 0)),
+    "bn-65x352-leaky": (65, 352, 2, False, (0, 0)),
+    "bn-65x352-unit": (65, 352, 1, True, (0, 0)),
+    "bn-200x488-relu": (200, 488, 1, False, (0, 0)),
+    "bn-200x488-unit-leaky": (200, 488, 2, True, (0, 0)),
 }
 AMBIGUOUS = 1e-5
 

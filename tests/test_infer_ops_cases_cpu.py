@@ -34,6 +34,51 @@ def test_depthwise_cases_reach_all_eight_variants():
         assert ioc.DW_LONG_BLOCKS <= blocks < ioc.DW_LONG_BLOCKS + 32 and B * H * W * C <= 17 * 2 ** 20, (n, blocks)
 
 
+def test_depthwise_cases_cover_the_wide_branch_widths():
+    """C = 88 / 176 / 352 (1.5x) and 122 / 244 / 488 (2.0x): each wide width the table names runs at both strides with B >= 2 and odd H and W at stride 2;
+    122 - no multiple of 4 - is what brings the 2-channel variants to a wide backbone."""
+    assert ioc.DW_WIDE_C == (88, 122, 244, 352, 488)
+    for C in ioc.DW_WIDE_C:
+        mine = [c for c in ioc.DW_CASES.values() if c[0] == C]
+        assert {c[1] for c in mine} == {1, 2}, C
+        assert all(c[2][0] >= 2 for c in mine), C
+        assert any(c[1] == 2 and c[2][1] % 2 and c[2][2] % 2 and c[2][1] > 1 for c in mine), C
+        vecs = {ioc.dw_variant(c[0], c[1], *c[2])[1] for c in mine}
+        assert vecs == ({2} if C % 4 else {4}), C
+    two = {ioc.dw_variant(c[0], c[1], *c[2]) for c in ioc.DW_CASES.values() if c[0] == 122}
+    assert two == {(1, 2, 4), (2, 2, 2)}
+    R = {1: 4, 2: 2}
+    for stride in (1, 2):                                    # and the 2-channel cases of 122 sit past one run: a partial last run
+        assert any(dw_wo(c) > R[stride] and dw_wo(c) % R[stride] for c in ioc.DW_CASES.values() if c[0] == 122 and c[1] == stride)
+
+
+def dw_wo(case):
+    C, stride, (B, H, W) = case
+    return (W - 1) // stride + 1
+
+
+def test_pointwise_wide_cases_hold_every_width_of_the_wide_networks():
+    from yolo_nano_amd import arch
+    have = set(ioc.PW_WIDE_CASES)
+    assert len(have) == len(ioc.PW_WIDE_CASES) and not have & set(ioc.PW_CASES)
+    need = set()                                             # every (K, N) a pointwise layer of the two backbones and their laterals has
+    for bb in ("1.5x", "2.0x"):
+        cin = 24
+        for C in arch.STAGE_CH[bb]:
+            need |= {(C // 2, C // 2), (cin, C // 2), (C, 96)}
+            cin = C
+    assert need <= {(k, n) for _, k, n, _ in ioc.PW_WIDE_CASES}, need - {(k, n) for _, k, n, _ in ioc.PW_WIDE_CASES}
+    assert set(ioc.PW_WIDE_CASES) >= {(129, 88, 88, 1), (127, 122, 122, 1), (65, 176, 176, 1), (129, 244, 244, 1), (33, 352, 352, 1), (130, 488, 488, 1),
+                                      (333, 24, 88, 1), (333, 24, 122, 1), (77, 176, 88, 1), (77, 244, 122, 1), (66, 352, 176, 1), (66, 488, 244, 1),
+                                      (200, 704, 96, 2), (200, 976, 96, 2)}
+    for M, k, n, act in ioc.PW_WIDE_CASES:
+        assert M % 32 and k % 2 == 0 and n % 2 == 0, (M, k, n)           # ragged M; an even N: the shuffle entry runs too
+        assert 9 * k + 3 < 2 ** 24                                       # integers in {-3..3}: exact in fp32 in any order
+    assert all(M >= 64 and act == 2 for M, _, _, act in ioc.PW_WIDE_LATERAL)
+    assert all(k == n for _, k, n, _ in ioc.PW_WIDE_UNIT) and all(k != n for _, k, n, _ in ioc.PW_WIDE_ENTRY)
+    assert max(k for _, k, _, _ in ioc.PW_WIDE_CASES) == 976 and max(n for _, _, n, _ in ioc.PW_WIDE_CASES) == 488
+
+
 C3_EXPECT = {
     "c3s-1tile": "conv3x3_split_kernel<1,1,9>", "c3s-1tile-rs": "conv3x3_split_kernel<1,1,9>", "c3s-3tiles": "conv3x3_split_kernel<1,1,9>",
     "c3s-3tiles-rs": "conv3x3_split_kernel<1,1,9>", "c3s-w65": "conv3x3_split_kernel<1,1,9>", "c3s-w66": "conv3x3_split_kernel<1,1,3>",
