@@ -3,6 +3,7 @@
 #include "yn_device.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace ynk {
 
@@ -1370,34 +1371,99 @@ void launch_down2(const Down2Args& a, hipStream_t s)
 // Depthwise 3x3 + pointwise conv of a detection head (models/yolo_nano.py:60-82: Conv(96, 96, k=3, g=96) -> Conv(96, 96, k=1)) as one
 // kernel, for up to three pyramid levels per launch (Group<>).  The depthwise output of the stride-8 head is 33 MB per 32-image step,
 // written by one launch and read back by the next; here it goes from registers into the GEMM's LDS operand planes.  One tile = 8 x 4
-// pixels of one image: thread = (4 channels, a run of 4 pixels along x) with its 3 x 6 window in ONE batch of clamped loads, masked where
-// they are consumed (dwconv3x3_kernel's thread, the same fma chain); 192 threads = three wavefronts = the three 32-column tiles of the
-// GEMM, 16-byte stores through the in-quad transpose.  The 96 x 96 split weights are register-resident (a lane's B fragments of its
-// wavefront's 32 columns: 48 registers, loaded once per workgroup - nothing of them in LDS: 13 KB), a workgroup walks ~3 tiles
-// (XCD-contiguous, after down_unit_pipe_kernel) and requests the next tile's depthwise windows right behind the barrier that ends the
-// depthwise phase - the round trip runs under the GEMM and the stores.  Bit-identical to dwconv3x3_kernel + gemm_split_kernel
-// (test_grouped_launches_are_bit_identical).
+// pixels of one image; 192 threads = three wavefronts = the three 32-column tiles of the GEMM, 16-byte stores through the in-quad
+// transpose.  The 96 x 96 split weights are register-resident (a lane's B fragments of its wavefront's 32 columns: 48 registers, loaded
+// once per workgroup - nothing of them in LDS).
+//
+// A PERSISTENT, software-pipelined walk after unit_pipe_kernel (kernels_pipe.hip):
+//   * a tile's depthwise window - six row runs of ten pixels x 96 channels, 3 840 contiguous bytes of the NHWC input each - arrives in LDS
+//     by LDS-DMA (dma16: no registers, no staging instructions): a row run is four pieces of 1 KB (240 granules of a pixel's channel quad +
+//     16 of padding, which fetch the last granule again), wavefront w brings rows 2 w and 2 w + 1 - eight pieces per wavefront and tile,
+//     each at a wave-uniform LDS base AND from a wave-uniform global row: the row's clamped start is scalar arithmetic, a lane's place in
+//     the row is the same in both rows - four lane offsets per tile, no vector instruction per piece.  Rows and pixels outside the image
+//     are fetched from the clamped address (LDS-DMA cannot write zeros) and zeroed where they are consumed (`wok` / vmask, as the register
+//     form did);
+//   * ONE window buffer, 168 registers, 37 KB of LDS: FOUR workgroups per CU, three wavefronts on every SIMD (the register form: 222 registers,
+//     two workgroups, six wavefronts on four SIMDs).  The window of tile n + 1 is requested right behind the barrier that ends tile n's
+//     depthwise phase - the buffer's last reader - and flies under the GEMM and the epilogue's arithmetic; each wavefront waits for its own
+//     pieces in front of its stores (nothing else is in flight there but the previous tile's stores, a whole tile old), and the barrier
+//     that ends the tile orders every wavefront's pieces before the reads (wait, barrier, read: MI355X orders an LDS read behind a DMA
+//     piece by nothing else).  What covers the rest of the round trip is the other three workgroups of the CU.  The form with two window
+//     buffers, requested two tiles ahead behind a counted s_waitcnt vmcnt(8), fits two workgroups per CU and measured slower;
+//   * the depthwise conv reads its 3 x 6 window row by row with 16-byte LDS reads (consecutive lanes = consecutive channel quads), thread =
+//     (channel quad, run of four pixels along x), the fma chain of dwconv3x3_kernel per output: bias, then ky, kx in order; a tile whose
+//     window lies inside the image runs it without the masks;
+//   * the grid is what is resident (launch_dwpw_group): the weight panel and the taps are loaded once per slot.
+// Bit-identical to dwconv3x3_kernel + gemm_split_kernel (test_grouped_launches_are_bit_identical, tests/test_gpu_dwpw_pipe.py).
 // -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, unsigned bid, unsigned nblocks)
+constexpr int DWPW_PLANES = 2 * 32 * 104 * 2;               // the two operand planes [32][96 + 8] of f16
+constexpr int DWPW_WIN = 24 * 1024;                         // one window buffer: 6 row runs of four 1 KB pieces (10 pixels x 384 bytes + 256 of padding)
+constexpr int DWPW_LDS = DWPW_PLANES + DWPW_WIN;            // 37 888 bytes: four workgroups per CU
+constexpr unsigned DWPW_SLOTS = 1024;                       // resident workgroups: 256 CUs x 4 (168 registers: tests/test_isa_dwpw_cpu.py)
+
+__device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, unsigned char* smem, unsigned bid, unsigned nblocks)
 {
     constexpr int TW = 8, TH = 4, NO = TW * TH, C = 96, KQ = C / 8, KS = KQ / 2, AST = C + 8, R = 4;
-    h16* Ah = smem;                                       // [NO][AST]
+    constexpr int WW = TW + 2, WR = TH + 2, CQ = C / 4, NP = 8;         // window: WR row runs of WW pixels of CQ quads; pieces per wavefront and tile
+    constexpr unsigned WROW = 4096;                                     // a row run in LDS: four pieces (3 840 bytes + 256 of padding)
+    static_assert(2 * NO * AST * 2 == DWPW_PLANES && WR * WROW == DWPW_WIN && WW * CQ * 16 <= WROW && 3 * NP == 4 * WR, "LDS carve; three wavefronts x two rows");
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    h16* Ah = reinterpret_cast<h16*>(smem);               // [NO][AST]
     h16* Al = Ah + NO * AST;
+    const unsigned char* win = smem + DWPW_PLANES;          // [WR rows of WROW bytes]: [WW pixels][CQ] x 16 bytes of fp32
+    const unsigned lds_win = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem + (unsigned)DWPW_PLANES;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
     const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH, per_img = tx_n * ty_n;
     const int tiles = a.B * per_img;
+    // XCD-contiguous walk: XCD x (= bid % 8) owns tiles [x TL, (x + 1) TL), its workgroups take them round-robin
     const int TL = (tiles + 7) >> 3, GL = (int)(nblocks >> 3);
-    const int tbase = (int)(bid & 7u) * TL;
-    int tl = (int)(bid >> 3);
-    if (tl >= TL || tbase + tl >= tiles) return;
+    const int tend = ((int)(bid & 7u) + 1) * TL < tiles ? ((int)(bid & 7u) + 1) * TL : tiles;
+    const int tile0 = (int)(bid & 7u) * TL + (int)(bid >> 3);
+    if (tile0 >= tend) return;                              // no tile: nothing requested
+
+    const int cq = t % CQ, run = t / CQ;                    // 24 channel quads x 8 runs of 4 pixels (2 per tile row) = 192 workers
+    const int c = cq * 4, ry = run >> 1, rx = (run & 1) * R;
+    // a tile index -> (image, first row, first column), once per tile and wave-uniform
+    struct Pos { int b, oy0, ox0; };
+    auto decode = [&](int tile) {
+        const int b = tile / per_img, trem = tile - b * per_img, ty = trem / tx_n;
+        return Pos{__builtin_amdgcn_readfirstlane(b), __builtin_amdgcn_readfirstlane(ty * TH), __builtin_amdgcn_readfirstlane((trem - ty * tx_n) * TW)};
+    };
+    // the window of one tile -> LDS: eight pieces per wavefront.  Wavefront w brings window rows 2 w and 2 w + 1, four pieces each: the row is
+    // wave-uniform - its clamped start goes into the piece's scalar base - and a lane's place in the row, (pixel, quad) of granule
+    // 64 k + lane, is the same in both rows: four lane offsets per tile, no vector work per piece
+    auto issue = [&](const Pos& p) {
+        int tt = t;                                         // (opaque: as loop invariants the four granule decodes are held in registers across the GEMM)
+        asm volatile("" : "+v"(tt));
+        const int ln = tt & 63;
+        unsigned xo[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q = ln + 64 * k;                            // the row's padding granules fetch its last one again
+            if (k == 3) q = q < WW * CQ - 1 ? q : WW * CQ - 1;
+            const int px = q / CQ, qq = q - px * CQ;
+            int ix = p.ox0 - 1 + px;
+            ix = ix < 0 ? 0 : (ix < a.W ? ix : a.W - 1);
+            xo[k] = (unsigned)(ix * C + qq * 4) * 4u;
+        }
+        const unsigned dst = lds_win + (unsigned)wave * (2u * WROW);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            int iy = p.oy0 - 1 + 2 * wave + (i >> 2);
+            iy = iy < 0 ? 0 : (iy < a.H ? iy : a.H - 1);
+            const unsigned row = (unsigned)((p.b * a.H + iy) * a.W) * (unsigned)(C * 4);
+            dma16(reinterpret_cast<const char*>(a.in) + row, xo[i & 3], dst + (unsigned)(i >> 2) * WROW + (unsigned)(i & 3) * 1024u);
+        }
+    };
+    int t1 = tile0 + GL < tend ? tile0 + GL : -1;           // the next tile of the walk
+    Pos cur = decode(tile0), nxt = cur;
+    issue(cur);
 
     // ---- loop invariants: the thread's depthwise taps and bias, the B fragments and bias of its GEMM columns --------------------------
-    const int cq = t % (C / 4), run = t / (C / 4);          // 24 channel quads x 8 runs of 4 pixels (2 per tile row) = 192 workers
-    const int c = cq * 4, ry = run >> 1, rx = (run & 1) * R;
-    float4 wd[9];
+    f32x4 wd[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) wd[k] = *reinterpret_cast<const float4*>(a.wdw + k * C + c);
-    const float4 bd = *reinterpret_cast<const float4*>(a.bdw + c);
+    for (int k = 0; k < 9; ++k) wd[k] = *reinterpret_cast<const f32x4*>(a.wdw + k * C + c);
+    f32x4 bd = *reinterpret_cast<const f32x4*>(a.bdw + c);
     h16x8 gh[KS], gl[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -1405,61 +1471,74 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, un
         gh[ks] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(a.Wh) + off);
         gl[ks] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const h16*>(a.Wl) + off);
     }
-    const float gbias = a.bias[wave * 32 + l31];
-    float4 win[3][R + 2];
-    unsigned wok = 0;                                       // validity of the 18 window positions of the pending request
-    const char* xbase = reinterpret_cast<const char*>(a.in);
-    auto request = [&](int tile) {
-        const int b = tile / per_img, trem = tile - b * per_img;
-        const int oy = (trem / tx_n) * TH + ry, ox = (trem % tx_n) * TW + rx;
-        wok = 0;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = oy - 1 + ky;
-            const bool yok = oy < a.H && iy >= 0 && iy < a.H;
-#pragma unroll
-            for (int j = 0; j < R + 2; ++j) {
-                const int ix = ox - 1 + j;
-                const bool ok = yok && ix >= 0 && ix < a.W;
-                // raw value from a clamped address, zeroed where it is consumed (a mask applied here would wait for the load here)
-                win[ky][j] = *reinterpret_cast<const float4*>(xbase + (unsigned)(ok ? ((b * a.H + iy) * a.W + ix) * C + c : c) * 4u);
-                wok |= (ok ? 1u : 0u) << (ky * (R + 2) + j);
-            }
-        }
-    };
-    request(tbase + tl);
+    float gbias = a.bias[wave * 32 + l31];
+    // The first window and the invariants have landed, and hipcc is TOLD so (an asm that reads and writes their registers: its own waits for these
+    // loads go HERE, ahead of the loop, not in front of their first use inside it, where a vmcnt(0) would retire the pieces in flight)
+    static_assert(KS == 6, "23 asm operands");
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(wd[0]), "+v"(wd[1]), "+v"(wd[2]), "+v"(wd[3]), "+v"(wd[4]), "+v"(wd[5]), "+v"(wd[6]), "+v"(wd[7]), "+v"(wd[8]), "+v"(bd), "+v"(gbias),
+                   "+v"(gh[0]), "+v"(gh[1]), "+v"(gh[2]), "+v"(gh[3]), "+v"(gh[4]), "+v"(gh[5]), "+v"(gl[0]), "+v"(gl[1]), "+v"(gl[2]), "+v"(gl[3]), "+v"(gl[4]), "+v"(gl[5])
+                 :: "memory");
     float amax = 0.0f;                                      // range guard (yn_split.h)
     const int j4 = lane & 3;
     const int nq = wave * 32 + (l31 & ~3);
-
-    for (;;) {
-        const int tile = tbase + tl;
-        const int b = tile / per_img, trem = tile - b * per_img;
-        const int oy0 = (trem / tx_n) * TH, ox0 = (trem % tx_n) * TW;
-        // ---- 1. depthwise (dwconv3x3_kernel's chain) -> split planes ---------------------------------------------------------------
+    const unsigned wbase = (unsigned)ry * WROW + (unsigned)((rx * CQ + cq) * 16);     // the thread's top-left window granule
+    // thread = (channel quad, run of four pixels along x): its 3 x 6 window row by row (18 sixteen-byte LDS reads), four independent fma chains in
+    // dwconv3x3_kernel's order - bias, then ky, kx.  MASKED: zero padding and idle rows (nothing valid) as per-thread validity bits (`wok`),
+    // applied where the values are consumed (the clamped fetches brought real pixels there)
+    auto depthwise = [&](auto masked) {
+        constexpr bool MASKED = decltype(masked)::value;
+        unsigned wok = 0;                                   // validity of the 18 window positions, bit ky * 6 + j: valid rows x valid columns are ranges
+        if constexpr (MASKED) {
+            int tt = t;                                     // (opaque: one register for the thread's place instead of three held across the tile)
+            asm volatile("" : "+v"(tt));
+            const int rn = tt / CQ, oy = cur.oy0 + (rn >> 1), ox = cur.ox0 + (rn & 1) * R;
+            const int jlo = ox < 1 ? 1 - ox : 0, jhi = min(max(a.W + 1 - ox, 0), R + 2);        // columns [jlo, jhi) lie inside the image
+            const int klo = oy < 1 ? 1 - oy : 0, khi = oy < a.H ? min(a.H + 1 - oy, 3) : 0;     // rows [klo, khi); an idle run has none
+            const unsigned xb = jhi > jlo ? (1u << jhi) - (1u << jlo) : 0u, yb = khi > klo ? (1u << khi) - (1u << klo) : 0u;
+            wok = ((yb & 1u) ? xb : 0u) | ((yb & 2u) ? xb << (R + 2) : 0u) | ((yb & 4u) ? xb << (2 * (R + 2)) : 0u);
+        }
+        const unsigned char* wp = win + wbase;
+        float4 acc[R];
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
+        for (int o = 0; o < R; ++o) acc[o] = make_float4(bd.x, bd.y, bd.z, bd.w);
 #pragma unroll
-            for (int j = 0; j < R + 2; ++j) win[ky][j] = vmask(win[ky][j], 0u - ((wok >> (ky * (R + 2) + j)) & 1u));
+        for (int ky = 0; ky < 3; ++ky) {
+            float4 row[R + 2];
+#pragma unroll
+            for (int j = 0; j < R + 2; ++j) {
+                row[j] = *reinterpret_cast<const float4*>(wp + ky * WROW + j * (CQ * 16));
+                if constexpr (MASKED) row[j] = vmask(row[j], 0u - ((wok >> (ky * (R + 2) + j)) & 1u));
+            }
+#pragma unroll
+            for (int o = 0; o < R; ++o)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const f32x4 w = wd[ky * 3 + kx];
+                    vfma(acc[o], row[o + kx], make_float4(w.x, w.y, w.z, w.w));
+                }
+        }
 #pragma unroll
         for (int o = 0; o < R; ++o) {
-            float4 acc = bd;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) vfma(acc, win[ky][o + kx], wd[ky * 3 + kx]);
-            acc = vact(acc, a.dw_act);
+            const float4 v = vact(acc[o], a.dw_act);
             const int op = ry * TW + rx + o;
-            const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
+            const float x4[4] = {v.x, v.y, v.z, v.w};
             h16x4 hi, lo;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { amax = range_track(amax, x4[j]); hi[j] = (h16)x4[j]; lo[j] = split_lo(x4[j], hi[j]); }
             *reinterpret_cast<h16x4*>(Ah + op * AST + c) = hi;
             *reinterpret_cast<h16x4*>(Al + op * AST + c) = lo;
         }
-        __syncthreads();
-        const bool more = tl + GL < TL && tbase + tl + GL < tiles;
-        if (more) request(tbase + tl + GL);                 // the next tile's windows fly under the GEMM and the stores
+    };
+    lds_barrier();                                          // every wavefront's pieces of the first window
+
+    for (;;) {
+        // ---- 1. depthwise (dwconv3x3_kernel's chain) from the LDS window -> split planes.  A tile whose window lies inside the image (a
+        //      wave-uniform test: most tiles of a large map) has nothing to zero and runs without the masks - the same values, the same bits ----
+        if (cur.oy0 >= 1 && cur.oy0 + TH < a.H && cur.ox0 >= 1 && cur.ox0 + TW < a.W) depthwise(std::false_type{});
+        else depthwise(std::true_type{});
+        lds_barrier();                                      // planes complete; every window read has returned: the window buffer is free
+        if (t1 >= 0) { nxt = decode(t1); issue(nxt); }      // the next tile's window flies under the GEMM and the epilogue's arithmetic
 
         // ---- 2. pointwise conv: 32 x 32 per wavefront, K = 96 in gemm_split_tile's order; bias, activation, 16-byte stores -------------
         f32x16 acc0, acc1;
@@ -1475,8 +1554,9 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, un
         }
         // tile pixel of accumulator group g, lane (h, j4): row g, column 4 h + j4 - a wave-uniform row offset + one lane offset, 32-bit
         char* obase = reinterpret_cast<char*>(a.out);
-        const unsigned lane_off = (unsigned)(((b * a.H + oy0) * a.W + ox0 + 4 * h + j4) * C + nq) * 4u;
-        const bool xin = ox0 + 4 * h + j4 < a.W;
+        const unsigned lane_off = (unsigned)(((cur.b * a.H + cur.oy0) * a.W + cur.ox0 + 4 * h + j4) * C + nq) * 4u;
+        const bool xin = cur.ox0 + 4 * h + j4 < a.W;
+        float4 ov[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v0 = apply_act(split_join(acc0[4 * g + 0], acc1[4 * g + 0]) + gbias, a.act);
@@ -1493,22 +1573,29 @@ __device__ __forceinline__ void dwpw_pipe_block(const DwPwArgs& a, h16* smem, un
                 const float r0 = quad_xor2(s0), r1 = quad_xor2(s1);
                 if (j4 & 2) { v0 = r0; v1 = r1; } else { v2 = r0; v3 = r1; }
             }
-            if (oy0 + g < a.H && xin)
-                *reinterpret_cast<float4*>(obase + (lane_off + (unsigned)(g * a.W * C) * 4u)) = make_float4(v0, v1, v2, v3);
+            ov[g] = make_float4(v0, v1, v2, v3);
         }
-        if (!more) break;
-        tl += GL;
-        __syncthreads();                                    // every wavefront is done with the planes
+        // this wavefront's pieces of the next window, in front of the stores (which share the counter and need not be waited for: what is in
+        // flight here is the eight pieces and the previous tile's stores, issued a whole tile ago)
+        if (t1 >= 0) vm_drain();
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (cur.oy0 + g < a.H && xin) *reinterpret_cast<float4*>(obase + (lane_off + (unsigned)(g * a.W * C) * 4u)) = ov[g];
+        if (t1 < 0) break;
+        cur = nxt;
+        t1 = t1 + GL < tend ? t1 + GL : -1;
+        lds_barrier();                                      // every wavefront is done with the planes, and has waited for its pieces of the next window
     }
     range_report(a.ovf, amax);
 }
 
-__global__ __launch_bounds__(192, 2) void dwpw_pipe_group_kernel(Group<DwPwArgs> g)
+// three wavefronts per SIMD (168 registers): four workgroups of three wavefronts per CU
+__global__ __attribute__((amdgpu_flat_work_group_size(192, 192), amdgpu_waves_per_eu(3, 3))) void dwpw_pipe_group_kernel(Group<DwPwArgs> g)
 {
-    extern __shared__ __attribute__((aligned(16))) float dwpw_smem[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char dwpw_smem[];
     unsigned local, nb;
     const int p = group_problem(g.first, blockIdx.x, local, nb);
-    dwpw_pipe_block(g.a[p], reinterpret_cast<h16*>(dwpw_smem), local, nb);
+    dwpw_pipe_block(g.a[p], dwpw_smem, local, nb);
 }
 
 bool dwpw_group_ok(const DwPwArgs* a, int n)
@@ -1521,18 +1608,44 @@ bool dwpw_group_ok(const DwPwArgs* a, int n)
     return true;
 }
 
+// Walking workgroups of every problem: ceil(tiles / 3) rounded up to a multiple of 8 (XCD-contiguous ranges: GL = grid / 8 tiles per step), or -
+// where that is more than the chip holds at four workgroups per CU - the fewest steps S with which all levels fit the resident slots
+// together, every level's workgroups walking at most S tiles (416 x 416, 32 images: 728 + 224 + 64 workgroups, 4 steps).
+static void dwpw_group_grid(const DwPwArgs* a, int n, unsigned (&wgs)[YN_GROUP_MAX])
+{
+    constexpr unsigned per = 3;                             // at least this many tiles per walking workgroup
+    unsigned TL[YN_GROUP_MAX] = {}, all = 0, tot = 0;       // TL: tiles per XCD range
+    for (int p = 0; p < YN_GROUP_MAX; ++p) {
+        wgs[p] = 0;
+        if (p >= n) continue;
+        const unsigned tiles = (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8);
+        TL[p] = (tiles + 7u) >> 3;
+        wgs[p] = xcd_grid((tiles + per - 1) / per);
+        all += tiles;
+        tot += wgs[p];
+    }
+    if (tot <= DWPW_SLOTS) return;
+    for (unsigned S = (all + DWPW_SLOTS - 1) / DWPW_SLOTS > per ? (all + DWPW_SLOTS - 1) / DWPW_SLOTS : per;; ++S) {
+        unsigned used = 0;
+        for (int p = 0; p < n; ++p) used += 8u * ((TL[p] + S - 1) / S);
+        if (used > DWPW_SLOTS) continue;                    // (ends: 8 n workgroups at the latest)
+        for (int p = 0; p < n; ++p) { const unsigned w = 8u * ((TL[p] + S - 1) / S); if (w < wgs[p]) wgs[p] = w; }
+        return;
+    }
+}
+
 void launch_dwpw_group(const DwPwArgs* a, int n, hipStream_t s)
 {
     Group<DwPwArgs> g{};
-    unsigned tot = 0;
-    constexpr unsigned per = 3;                             // tiles per walking workgroup
+    unsigned tot = 0, wgs[YN_GROUP_MAX];
+    dwpw_group_grid(a, n, wgs);
     for (int p = 0; p < YN_GROUP_MAX; ++p) {
         g.first[p] = tot;
-        if (p < n) { g.a[p] = a[p]; const unsigned tiles = (unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8); tot += xcd_grid((tiles + per - 1) / per); }
+        if (p < n) { g.a[p] = a[p]; tot += wgs[p]; }
     }
     g.first[YN_GROUP_MAX] = tot;
     set_last_kernel_name("dwpw_pipe_group_kernel");
-    hipLaunchKernelGGL(dwpw_pipe_group_kernel, dim3(tot), dim3(192), (size_t)2 * 32 * 104 * 2, s, g);
+    hipLaunchKernelGGL(dwpw_pipe_group_kernel, dim3(tot), dim3(192), (size_t)DWPW_LDS, s, g);
 }
 
 bool launch_unit_chain(const ChainArgs& a, hipStream_t s) { return unit_chain_dispatch(a, s, false); }
