@@ -15,10 +15,14 @@ from yolo_nano_amd import arch
 
 
 class TorchNet:
-    def __init__(self, state_dict, backbone="1.0x", num_classes=20, num_anchors=3, dtype=torch.float32):
+    def __init__(self, state_dict, backbone="1.0x", num_classes=20, num_anchors=3, dtype=torch.float32, peaks=None):
         """dtype=torch.float64: folding and every layer in double precision - the exact reference of the same network, of which the
-        float32 instance measures the fp32 round-off (tests/test_gpu_wide.py)."""
+        float32 instance measures the fp32 round-off (tests/test_gpu_wide.py).
+        peaks: an optional dict the forward fills, per conv name, with max |y| per image of the layer's activated output ([B] float64 numpy), and under
+        name + ":in" with max |x| per image of what the layer reads (the FPN / PAN sums for the smooth convs) - what the split-f16 range guard of the
+        HIP kernels watches (tests/range_cases.py).  None (default): nothing is recorded."""
         self.C, self.A, self.backbone, self.dt = num_classes, num_anchors, backbone, dtype
+        self.peaks = peaks
         sd = {k: torch.as_tensor(np.asarray(v)) for k, v in state_dict.items()}
         sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
         self.specs = {s.name: s for s in arch.conv_specs(backbone, num_classes, num_anchors)}
@@ -38,9 +42,12 @@ class TorchNet:
         w, b = self.wb[name]
         y = F.conv2d(x, w, b, stride=s.stride, padding=0 if s.kind == "pw" else 1, groups=s.cout if s.kind == "dw3" else 1)
         if s.act == arch.ACT_RELU:
-            return F.relu_(y)
-        if s.act == arch.ACT_LEAKY:
-            return F.leaky_relu_(y, 0.1)
+            y = F.relu_(y)
+        elif s.act == arch.ACT_LEAKY:
+            y = F.leaky_relu_(y, 0.1)
+        if self.peaks is not None:
+            self.peaks[name] = y.abs().amax(dim=(1, 2, 3)).double().numpy()
+            self.peaks[name + ":in"] = x.abs().amax(dim=(1, 2, 3)).double().numpy()
         return y
 
     def block(self, p, x, stride):

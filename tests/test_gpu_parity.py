@@ -1429,6 +1429,114 @@ def test_split_f16_range_guard(hvoc, kind):
     assert hvoc.range_status() == (False, False)
 
 
+def _guarded(h, fn):
+    """fn() under the handle's profile -> (its result, range_status() behind it, the kernel symbols its launches recorded)"""
+    h.profile_enable(True)
+    try:
+        y = fn()
+        st = h.range_status()
+        names = [r[1] for r in h.profile_records()]
+    finally:
+        h.profile_enable(False)
+    return y, st, names
+
+
+def _inside_1e30(t):
+    """the same tensor as a view inside a larger buffer filled with a FINITE 1e30: whatever a kernel reads past the tensor's rows or behind its last one
+    would raise the range flag if it were tracked (a NaN there never would: test_pw_k_tail_never_reads_a_neighbours_nan cannot see this)"""
+    pad = 4096
+    buf = torch.full((t.numel() + 2 * pad,), 1.0e30, dtype=torch.float32, device=t.device)
+    v = buf[pad:pad + t.numel()].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+@pytest.mark.parametrize("cfg", list(range(15)))
+def test_split_f16_range_guard_places_pw(hvoc, cfg):
+    """test_split_f16_range_guard's flag under EVERY index of the split family (the fourteen gemm_split_kernel tiles and pw_pipe_kernel), the kernel that
+    ran asserted.  FALSE ALARMS: an in-range tensor (|x| <= 3e4) in a plain allocation and as a view inside a buffer of finite 1e30 - flag silent both
+    times, results bit-identical (a kernel that tracked a clamped row, an unzeroed K tail or a prefetch behind the tensor would demote the host shim to
+    the f32-MFMA family for good).  PLACES of the single 7e4: row 0; the last row of the ragged last tile; the last channel of K = 58 (K % 16 != 0);
+    and, for the persistent kernel, row 0 of 1025 tiles on 1024 workgroups - a tile that is not the last of its workgroup's walk."""
+    import range_cases as rc
+    assert rc.N_SPLIT_CONFIGS + 1 == 15
+    K, N = (rc.PW_K, rc.PW_N) if cfg < rc.N_SPLIT_CONFIGS else (rc.PW_PIPE_K, rc.PW_PIPE_K)
+    rs = np.random.RandomState(100 + cfg)
+    w = dev((rs.standard_normal((N, K, 1, 1)) / np.sqrt(K)).astype(np.float32))
+    b = dev(rs.standard_normal((N,)).astype(np.float32))
+    _, fam = hvoc.pw_families()
+    assert len(fam) == rc.N_SPLIT_CONFIGS + 1
+    kern = rc.split_kernel(cfg, K, N)
+    hvoc.exact_f32(False)
+    hvoc.range_status()
+    try:
+        hvoc.set_pw_config(fam[cfg])
+        for M in [rc.PW_M] + ([rc.PW_WALK_M] if cfg == rc.N_SPLIT_CONFIGS else []):
+            x = dev(rs.uniform(-3.0e4, 3.0e4, (1, 1, M, K)).astype(np.float32))
+            y0, st, names = _guarded(hvoc, lambda: hvoc.op_pwconv(x, w, b, 1))
+            assert st == (False, False) and names == [kern], (st, names, kern)
+            xv = _inside_1e30(x)
+            y1, st, names = _guarded(hvoc, lambda: hvoc.op_pwconv(xv, w, b, 1))
+            assert st == (False, False), "%s M %d: a false alarm from what lies around the tensor" % (kern, M)
+            assert names == [kern] and torch.equal(y0, y1) and bool(torch.isfinite(y0).all())
+            for r, c in ((0, 0), (M - 1, 5), (M // 2, K - 1)):
+                xp = _inside_1e30(x)
+                xp[0, 0, r, c] = 7.0e4
+                _, st, names = _guarded(hvoc, lambda: hvoc.op_pwconv(xp, w, b, 1))
+                assert st == (False, True), "%s M %d: 7e4 at row %d, channel %d did not raise the flag" % (kern, M, r, c)
+                assert names == [kern] and hvoc.range_status() == (False, False)
+    finally:
+        hvoc.set_pw_config(-1)
+
+
+@pytest.mark.parametrize("case", ["c3s-257tiles", "c3s-86tiles", "c3s-3tiles", "c3s-3tiles-rs", "c3s-w70", "c3s-w112"])
+def test_split_f16_range_guard_places_c3(hvoc, case):
+    """The same for one shape of every conv3x3_split_kernel variant (<3,2>, <1,2>, <1,1,9>, <1,1,3>, <1,1,1>; infer_op_cases.C3_CASES, all with a ragged last
+    tile), and for both resample modes of <1,1,9>.  Plain: a single 7e4 at the first pixel, at the last pixel of the last tile, and in the last channel.
+    Resample: what is split is the SUM, so two addends of 4e4 - each in range - must raise the flag at the same places, and either alone must not."""
+    import infer_op_cases as ioc
+    import range_cases as rc
+    assert case in rc.C3_PLACES
+    cin, cout, (B, H, W), exact, modes = ioc.C3_CASES[case]
+    kern = ioc.c3_kernel(cin, cout, B, H, W, exact)
+    rs = np.random.RandomState(len(case) + H)
+    w = dev((rs.standard_normal((cout, cin, 3, 3)) / np.sqrt(9 * cin)).astype(np.float32))
+    b = dev(rs.standard_normal((cout,)).astype(np.float32))
+    hvoc.exact_f32(False)
+    hvoc.range_status()
+    for mode in modes:
+        x = dev(rs.uniform(-3.0e4, 3.0e4, (B, H, W, cin)).astype(np.float32))
+        x2 = None if mode == 0 else dev(rs.uniform(-3.0e4, 3.0e4, (B, H // 2, W // 2, cin) if mode == 1 else (B, 2 * H, 2 * W, cin)).astype(np.float32))
+        run = lambda a, a2: _guarded(hvoc, lambda: hvoc.op_conv3x3(a, w, b, 2, x2=a2, resample=mode))
+        y0, st, names = run(x, x2)
+        assert st == (False, False) and names == [kern], (st, names, kern)
+        y1, st, names = run(_inside_1e30(x), None if x2 is None else _inside_1e30(x2))
+        assert st == (False, False), "%s mode %d: a false alarm from what lies around the tensors" % (kern, mode)
+        assert names == [kern] and torch.equal(y0, y1) and bool(torch.isfinite(y0).all())
+        for bi, yy, xx, c in ((0, 0, 0, 0), (B - 1, H - 1, W - 1, 7), (B // 2, H // 2, W // 2, cin - 1)):
+            xp = _inside_1e30(x)
+            if mode == 0:
+                xp[bi, yy, xx, c] = 7.0e4
+                x2p = None
+            else:
+                src = (bi, yy // 2, xx // 2, c) if mode == 1 else (bi, 2 * yy, 2 * xx, c)      # a + up2(b): b[y // 2, x // 2];  a + down(b): b[2y, 2x]
+                if mode == 1:                                              # (the pixels that share the source element stay out of it)
+                    xp[bi, yy // 2 * 2:yy // 2 * 2 + 2, xx // 2 * 2:xx // 2 * 2 + 2, c] = 0.0
+                xp[bi, yy, xx, c] = 4.0e4
+                x2p = _inside_1e30(x2)
+                x2p[src] = 4.0e4
+                x2c = x2.clone()
+                x2c[src] = 0.0
+                xc = xp.clone()
+                xc[bi, yy, xx, c] = 0.0
+                for a, a2 in ((xp, x2c), (xc, x2p)):                       # either addend alone is no alarm
+                    _, st, _ = run(a, a2)
+                    assert st == (False, False), "%s mode %d: one addend of 4e4 raised the flag" % (kern, mode)
+            _, st, names = run(xp, x2p)
+            assert st == (False, True), "%s mode %d: pixel (%d, %d, %d) channel %d did not raise the flag" % (kern, mode, bi, yy, xx, c)
+            assert names == [kern] and hvoc.range_status() == (False, False)
+
+
 def test_range_guard_whole_network_and_shim(capi):
     """The guard end to end.  (a) BatchNorm gains that make a folded weight >= 65504: yn_fold_bn reports it (weights_exceed_f16) and
     the handle runs on the f32-MFMA family; (b) a stem gain of 3e5 makes the activations of stage 2 overflow the split: the C ABI
