@@ -773,8 +773,39 @@ int  yn_jpeg_decode_batch(yn_handle* h, yn_jpeg* j, int n, const uint8_t* const*
 /* Why image i of the last batch was refused ("" if it was not).  j == NULL: the reason of the calling thread's last yn_jpeg_info /
  * yn_jpeg_coefficients. */
 const char* yn_jpeg_reason(yn_jpeg* j, int i);
-/* Measurement (synchronises): ms3 = host entropy stage of the last batch (wall clock), upload and kernels of its last chunk (HIP events). */
+/* Measurement (synchronises): ms3 = host entropy stage of the last batch (wall clock), upload and kernels of its last chunk (HIP events).
+ * In entropy mode 1 the host time is the copy pass plus any files the host decoded after all, and the upload time runs from the first
+ * upload to the last, the entropy kernels in between included (yn_jpeg_entropy_timing splits them). */
 int  yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3);
+/* ---- the entropy mode of a decoder: the Huffman stage on the host (default) or on the device (opt-in) ---------------------------------------
+ * mode 0: the host decodes, as described above.  mode 1: the host only parses the markers and copies each scan once (byte stuffing and
+ * restart markers go); the device decodes it in subsequences of subseq_bits (a multiple of 32; 0 = the default, 1024) that synchronise in
+ * at most max_rounds rounds (0 = the default, 64), and hands the same coefficients to the same kernels.  A file the device cannot vouch for
+ * (no fixed point within max_rounds, anything entropy_decode would refuse, block counts that disagree with the header, restart markers
+ * out of order) is decoded by the host after all, so frames, statuses and reasons are those of mode 0 in every case.  In mode 1
+ * yn_jpeg_decode_batch waits, per chunk, for one result word per file before it enqueues the pixel kernels; the scans are staged in a
+ * further slot pair of staging_bytes (a chunk whose scans exceed it fails the call like one whose coefficients do).  Setting a mode
+ * synchronises the device and resets the statistics.  Returns 1 for values out of range; the reason is yn_jpeg_reason(NULL, 0). */
+int  yn_jpeg_entropy(yn_jpeg* j, int mode, int subseq_bits, int max_rounds);
+/* Since the mode was set: files whose coefficients the device decoded, files that took the host decoder in mode 1; of the last chunk: the
+ * largest number of rounds a file used and the number of subsequences.  All 0 in mode 0. */
+int  yn_jpeg_entropy_stats(yn_jpeg* j, int64_t* device_files, int64_t* host_files, int32_t* rounds_last, int32_t* subseqs_last);
+/* Testing aid (synchronises): the coefficients of file i of the last chunk as the device's entropy stage left them, in exactly
+ * yn_jpeg_coefficients' layout.  Fails for a file that took the host decoder: the device wrote none for it. */
+int  yn_jpeg_device_coefficients(yn_handle* h, yn_jpeg* j, int i, int16_t* host, int64_t cap);
+/* Testing aid (synchronises): per subsequence of file i of the last chunk the state its decode started from at the fixed point and the
+ * blocks finished before it: host [subsequences][4] = bit position in the unstuffed scan, unit in the MCU, zigzag index, blocks before.
+ * cap counts int32 elements; the error names the number needed. */
+int  yn_jpeg_entropy_states(yn_handle* h, yn_jpeg* j, int i, int32_t* host, int64_t cap);
+/* Host only, no handle, no GPU: the copy pass of mode 1 for one file.  unstuffed_host [cap] receives the scan without byte stuffing and
+ * restart markers (cap >= len always suffices), segments_host [seg_cap][2] = first byte in it and first MCU of every restart segment,
+ * info4 = unstuffed bytes, segments found, 1 if the file must take the host decoder (markers damaged or misnumbered, a segment count that
+ * disagrees with the header), segments the header asks for.  Returns the parser's status, YN_JPEG_TOO_LARGE when a buffer is too small. */
+int  yn_jpeg_scan_prepare(const uint8_t* data, int64_t len, uint8_t* unstuffed_host, int64_t cap, int32_t* segments_host, int64_t seg_cap, int32_t* info4);
+/* Measurement (synchronises): of the last chunk decoded in mode 1, HIP event times in ms: upload of scans and tables, clearing the
+ * coefficients, jpeg_huff_first_kernel, jpeg_huff_sync_kernel, jpeg_huff_write_kernel, jpeg_huff_dc_kernel; ms7[6] is no time: subsequence
+ * decodes of the synchronisation per subsequence (1 = a serial decoder's work). */
+int  yn_jpeg_entropy_timing(yn_handle* h, yn_jpeg* j, float* ms7);
 
 /* ---- baseline JPEG encode: every stage on the device, the finished files come down ------------------------------------------------------
  * The files cv2.imwrite(path_jpg, frame) / PIL's save write with libjpeg's defaults (JDCT_ISLOW, the Annex K tables, no optimisation, JFIF

@@ -175,6 +175,12 @@ SIGNATURES = {
     "yn_jpeg_decode_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
     "yn_jpeg_reason": (ctypes.c_char_p, [_vp, _i32]),
     "yn_jpeg_timing": (_i32, [_vp, _vp, _vp]),
+    "yn_jpeg_entropy": (_i32, [_vp, _i32, _i32, _i32]),
+    "yn_jpeg_entropy_stats": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "yn_jpeg_device_coefficients": (_i32, [_vp, _vp, _i32, _vp, ctypes.c_int64]),
+    "yn_jpeg_entropy_states": (_i32, [_vp, _vp, _i32, _vp, ctypes.c_int64]),
+    "yn_jpeg_scan_prepare": (_i32, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp]),
+    "yn_jpeg_entropy_timing": (_i32, [_vp, _vp, _vp]),
     "yn_jpeg_quant_tables": (_i32, [_i32, _vp]),
     "yn_jpeg_header": (_i32, [_i32, _i32, _i32, _i32, _vp]),
     "yn_jpeg_enc_create": (_i32, [_vp, _i32, ctypes.c_int64, ctypes.POINTER(_vp)]),

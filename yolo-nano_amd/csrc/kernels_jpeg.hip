@@ -6,9 +6,13 @@
 //   jpeg_color_kernel   libjpeg's "fancy" (triangle) chroma upsampling for 2x1 / 2x2 + YCbCr -> BGR, written as uint8 [h][w][3] frames
 // Every step is the integer arithmetic of libjpeg's default decode (JDCT_ISLOW, do_fancy_upsampling), so the frames equal cv2.imread's and
 // PIL's byte for byte (tests/jpeg_oracle.py restates the rules).  Nothing is addressed by data: garbage coefficients give garbage pixels, no fault.
+// Opt-in (yn_jpeg_entropy): the Huffman stage runs on the device too (kernels_jpeg_huff.hip) and leaves the same coefficient
+// buffer to the same two kernels; jpeg_entropy_device() below stages the scans, reads one result word per file back and lets the host decode
+// whatever the device could not vouch for.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -207,9 +211,52 @@ struct JpegSlot {
     bool used = false;
 };
 
+// ---- the device entropy mode: what exists only after yn_jpeg_entropy(j, 1, ..) -------------------------------------------------
+struct JpegHuffSlot {
+    PinnedBuf<uint8_t> scan;       // the chunk's unstuffed scans, each file on a 16-byte boundary and zeroed up to the next one
+    PinnedBuf<char> meta;          // FileDesc [max_batch], int32 [max_batch + 1] workgroup starts, Segment [seg_cap], Table [6 * max_batch]
+    PinnedBuf<ynhuff::FileResult> result;
+};
+
+struct JpegHuffLast {              // a file of the last chunk, for the test entries
+    int64_t off = 0, total = 0;
+    int dev = -1;                  // its FileDesc, -1: the device never saw it
+    int flag = 0;
+};
+
+struct JpegHuff {
+    int sb = 0, max_rounds = 0, max_batch = 0;
+    int64_t scan_cap = 0, seg_cap = 0;
+    JpegHuffSlot slot[2];
+    DevBuf<uint8_t> scan;
+    DevBuf<char> meta;
+    DevBuf<uint64_t> start, end;
+    DevBuf<int32_t> nblk, base;
+    DevBuf<ynhuff::FileResult> result;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};       // around: upload, clear, first round, sync, write, dc
+    bool timed = false;
+    int64_t device_files = 0, host_files = 0, decodes_last = 0;
+    int32_t rounds_last = 0, subseqs_last = 0;
+    std::vector<JpegHuffLast> last;
+    std::vector<ynhuff::FileDesc> last_desc;
+    std::vector<ynjpeg::ScanSegment> segs;
+    std::vector<ynjpeg::ScanInfo> info;
+    std::vector<int64_t> scan_off, seg_off;
+    size_t files_bytes() const { return ((size_t)max_batch * sizeof(ynhuff::FileDesc) + ((size_t)max_batch + 1) * sizeof(int32_t) + 15) / 16 * 16; }
+    size_t segs_at() const { return files_bytes(); }
+    size_t tables_at() const { return segs_at() + (size_t)seg_cap * sizeof(ynhuff::Segment); }
+    size_t meta_bytes() const { return tables_at() + 6 * (size_t)max_batch * sizeof(ynhuff::Table); }
+    ~JpegHuff()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace
 
 struct JpegState {
+    std::unique_ptr<JpegHuff> huff;                          // null: the host decodes the Huffman stage
     int device = 0, max_batch = 0, threads = 1;
     int64_t staging_bytes = 0;
     JpegSlot slot[2];
@@ -275,6 +322,160 @@ const char* jpeg_reason(const JpegState* j, int i)
     return j->reasons[(size_t)i].c_str();
 }
 
+static int64_t scan_reserve(int64_t stuffed) { return stuffed > 0 ? (stuffed + 15) / 16 * 16 : 16; }      // what a file's unstuffed scan may take of the slot
+
+#define YN_JPEG_HIP(call)                                                                              \
+    do {                                                                                               \
+        const hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess) { err = std::string("yn_jpeg_decode_batch: ") + hipGetErrorString(e_); return 1; } \
+    } while (0)
+
+// The Huffman stage of one chunk on the device.  On return the coefficients of every file that is still JPEG_OK are in (or on
+// their way to) coef_dev at off[i]; a file the device could not vouch for went through entropy_decode on the worker pool, which decided its
+// status and reason and whose coefficients were uploaded over the device's.  Synchronous: it waits for the chunk's result words.
+static int jpeg_entropy_device(JpegState* j, JpegSlot& s, hipStream_t st, int c0, int m, const uint8_t* const* data, const int64_t* len, int32_t* status,
+                               const std::vector<int64_t>& off, int64_t total, std::string& err)
+{
+    using namespace ynhuff;
+    JpegHuff& F = *j->huff;
+    JpegHuffSlot& hs = F.slot[j->next];
+    const auto t0 = std::chrono::steady_clock::now();
+    F.scan_off.assign((size_t)m, 0); F.seg_off.assign((size_t)m, 0);
+    F.info.assign((size_t)m, ynjpeg::ScanInfo());
+    F.last.assign((size_t)m, JpegHuffLast());
+    F.last_desc.clear();
+    F.rounds_last = 0; F.subseqs_last = 0; F.decodes_last = 0; F.timed = false;
+    int64_t sbytes = 0, nsegs = 0;
+    for (int i = 0; i < m; ++i) {
+        if (status[c0 + i] != ynjpeg::JPEG_OK) continue;
+        const ynjpeg::Header& H = j->hdr[(size_t)(c0 + i)];
+        F.scan_off[(size_t)i] = sbytes; sbytes += scan_reserve(len[c0 + i] - H.scan_pos);
+        F.seg_off[(size_t)i] = nsegs; nsegs += ynjpeg::scan_segments(H);
+        F.last[(size_t)i].off = off[(size_t)i]; F.last[(size_t)i].total = H.coef_total;
+    }
+    if (sbytes > F.scan_cap || nsegs > F.seg_cap) { err = "yn_jpeg_decode_batch: the scans of a chunk outgrew their staging slot"; return 1; }
+    F.segs.resize((size_t)nsegs);
+    const int copiers = (int)(1 + (sbytes >> 21)) < j->threads ? (int)(1 + (sbytes >> 21)) : j->threads;      // a worker per 2 MiB: starting one costs what copying 1 MiB does
+    ynjpeg::parallel_for(m, copiers, [&](int i) {
+        const int g = c0 + i;
+        if (status[g] != ynjpeg::JPEG_OK) return;
+        const ynjpeg::Header& H = j->hdr[(size_t)g];
+        uint8_t* out = hs.scan.get() + F.scan_off[(size_t)i];
+        ynjpeg::ScanInfo& I = F.info[(size_t)i];
+        ynjpeg::scan_prepare(data[g], len[g], H, out, len[g] - H.scan_pos, F.segs.data() + F.seg_off[(size_t)i], ynjpeg::scan_segments(H), I);
+        memset(out + I.bytes, 0, (size_t)((I.bytes + 15) / 16 * 16 - I.bytes));
+    });
+    FileDesc* fd = reinterpret_cast<FileDesc*>(hs.meta.get());
+    int32_t* wg_start = reinterpret_cast<int32_t*>(hs.meta.get() + (size_t)F.max_batch * sizeof(FileDesc));
+    Segment* dseg = reinterpret_cast<Segment*>(hs.meta.get() + F.segs_at());
+    Table* dtab = reinterpret_cast<Table*>(hs.meta.get() + F.tables_at());
+    const int per_wg = jpeg_huff_write_threads();
+    int nf = 0, ntab = 0;
+    int64_t nsub = 0, wgs = 0, ndseg = 0;
+    Table fresh;
+    for (int i = 0; i < m; ++i) {
+        if (status[c0 + i] != ynjpeg::JPEG_OK || F.info[(size_t)i].host) continue;
+        const ynjpeg::Header& H = j->hdr[(size_t)(c0 + i)];
+        const ynjpeg::ScanInfo& I = F.info[(size_t)i];
+        FileDesc& D = fd[nf];
+        memset(&D, 0, sizeof D);
+        ynjpeg::huff_geometry(H, off[(size_t)i], D.G);
+        D.scan_off = F.scan_off[(size_t)i]; D.scan_bytes = I.bytes;
+        D.seg0 = (int32_t)ndseg; D.nseg = I.segments; D.sub0 = (int32_t)nsub; D.nc = H.nc;
+        int64_t fsub = 0;
+        for (int k = 0; k < I.segments; ++k) {
+            const ynjpeg::ScanSegment& a = F.segs[(size_t)(F.seg_off[(size_t)i] + k)];
+            const int64_t end = k + 1 < I.segments ? F.segs[(size_t)(F.seg_off[(size_t)i] + k + 1)].start : I.bytes;
+            const int64_t bits = (end - a.start) * 8;
+            Segment& g = dseg[ndseg++];
+            g.start = a.start; g.first_mcu = a.first_mcu; g.sub0 = (int32_t)fsub; g.pad = 0;
+            fsub += bits > F.sb ? (bits + F.sb - 1) / F.sb : 1;
+        }
+        D.nsub = (int32_t)fsub;
+        for (int c = 0; c < H.nc; ++c)
+            for (int ac = 0; ac < 2; ++ac) {                 // identical tables of a chunk are stored once
+                ynjpeg::huff_table(ac ? H.ac[H.ta[c]] : H.dc[H.td[c]], fresh);
+                int at = 0;
+                while (at < ntab && memcmp(&dtab[at], &fresh, sizeof fresh) != 0) ++at;
+                if (at == ntab) dtab[ntab++] = fresh;
+                D.tab[2 * c + ac] = at;
+            }
+        wg_start[nf] = (int32_t)wgs;
+        wgs += (fsub + per_wg - 1) / per_wg;
+        nsub += fsub;
+        F.last[(size_t)i].dev = nf;
+        F.last_desc.push_back(D);
+        ++nf;
+    }
+    wg_start[nf] = (int32_t)wgs;
+    j->host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    YN_JPEG_HIP(hipEventRecord(s.e0, st));
+    if (nf) {
+        if (nsub > 0x7fffffff || wgs > 0x7fffffff) { err = "yn_jpeg_decode_batch: more than 2^31 subsequences in a chunk; raise subseq_bits"; return 1; }
+        int r = F.start.reserve((size_t)nsub, 4096);
+        if (!r) r = F.end.reserve((size_t)nsub, 4096);
+        if (!r) r = F.nblk.reserve((size_t)nsub, 4096);
+        if (!r) r = F.base.reserve((size_t)nsub, 4096);
+        if (r) { (void)hipGetLastError(); err = std::string("yn_jpeg_decode_batch: ") + hipGetErrorString((hipError_t)r) + " (" + std::to_string(nsub) + " subsequences)"; return 1; }
+        YN_JPEG_HIP(hipEventRecord(F.ev[0], st));
+        YN_JPEG_HIP(hipMemcpyAsync(F.scan.get(), hs.scan.get(), (size_t)sbytes, hipMemcpyHostToDevice, st));
+        YN_JPEG_HIP(hipMemcpyAsync(F.meta.get(), hs.meta.get(), F.files_bytes(), hipMemcpyHostToDevice, st));
+        YN_JPEG_HIP(hipMemcpyAsync(F.meta.get() + F.segs_at(), dseg, (size_t)ndseg * sizeof(Segment), hipMemcpyHostToDevice, st));
+        YN_JPEG_HIP(hipMemcpyAsync(F.meta.get() + F.tables_at(), dtab, (size_t)ntab * sizeof(Table), hipMemcpyHostToDevice, st));
+        YN_JPEG_HIP(hipEventRecord(F.ev[1], st));
+        YN_JPEG_HIP(hipMemsetAsync(j->coef_dev.get(), 0, (size_t)total * sizeof(int16_t), st));
+        YN_JPEG_HIP(hipEventRecord(F.ev[2], st));
+        j->launched = true;
+        s.used = true;
+        JpegHuffArgs a;
+        a.files = F.meta.get();
+        a.wg_start = reinterpret_cast<const int32_t*>(F.meta.get() + (size_t)F.max_batch * sizeof(FileDesc));
+        a.segs = F.meta.get() + F.segs_at();
+        a.tables = F.meta.get() + F.tables_at();
+        a.scan = F.scan.get();
+        a.start = F.start.get(); a.end = F.end.get(); a.nblk = F.nblk.get(); a.base = F.base.get();
+        a.result = F.result.get();
+        a.coef = j->coef_dev.get();
+        a.nfiles = nf; a.write_wgs = (int)wgs; a.sb = F.sb; a.max_rounds = F.max_rounds;
+        jpeg_huff_launch(a, st, F.ev[3], F.ev[4], F.ev[5]);
+        YN_JPEG_HIP(hipGetLastError());
+        YN_JPEG_HIP(hipEventRecord(F.ev[6], st));
+        YN_JPEG_HIP(hipMemcpyAsync(hs.result.get(), F.result.get(), (size_t)nf * sizeof(FileResult), hipMemcpyDeviceToHost, st));
+        YN_JPEG_HIP(hipEventRecord(s.e1, st));               // the slot's pinned memory is free again once this has passed
+        YN_JPEG_HIP(hipStreamSynchronize(st));               // the one synchronisation of the mode: the per-file result words
+        F.timed = true;
+    }
+    // what the device could not vouch for takes the host decoder, which knows the status and the reason
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<int> redo;
+    for (int i = 0; i < m; ++i) {
+        if (status[c0 + i] != ynjpeg::JPEG_OK) continue;
+        JpegHuffLast& L = F.last[(size_t)i];
+        if (L.dev >= 0) {
+            const FileResult& R = hs.result.get()[L.dev];
+            L.flag = R.flag;
+            F.subseqs_last += R.nsub; F.decodes_last += R.decodes;
+            if (R.rounds > F.rounds_last) F.rounds_last = R.rounds;
+        }
+        if (L.dev < 0 || L.flag) redo.push_back(i); else F.device_files += 1;
+    }
+    F.host_files += (int64_t)redo.size();
+    ynjpeg::parallel_for((int)redo.size(), j->threads, [&](int r) {
+        const int i = redo[(size_t)r], g = c0 + i;
+        status[g] = ynjpeg::entropy_decode(data[g], len[g], j->hdr[(size_t)g], s.coef.get() + off[(size_t)i], j->reasons[(size_t)g]);
+    });
+    j->host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    for (int i : redo) {
+        if (status[c0 + i] != ynjpeg::JPEG_OK) continue;
+        YN_JPEG_HIP(hipMemcpyAsync(j->coef_dev.get() + off[(size_t)i], s.coef.get() + off[(size_t)i], (size_t)j->hdr[(size_t)(c0 + i)].coef_total * sizeof(int16_t),
+                                   hipMemcpyHostToDevice, st));
+        j->launched = true;
+        s.used = true;
+    }
+    return 0;
+}
+#undef YN_JPEG_HIP
+
 int jpeg_decode_batch(JpegState* j, hipStream_t st, int n, const uint8_t* const* data, const int64_t* len, uint8_t* const* frames, int32_t* status,
                       int32_t* failed, std::string& err)
 {
@@ -288,18 +489,28 @@ int jpeg_decode_batch(JpegState* j, hipStream_t st, int n, const uint8_t* const*
     // headers of the whole batch first: a batch that does not fit fails before anything is written or launched
     j->hdr.assign((size_t)n, ynjpeg::Header());
     const auto t0 = std::chrono::steady_clock::now();
-    ynjpeg::parallel_for(n, j->threads, [&](int i) {
+    const int parsers = !j->huff ? j->threads : 1 + n / 64 < j->threads ? 1 + n / 64 : j->threads;      // device entropy mode: the host's work is small, a worker per 64 headers
+    ynjpeg::parallel_for(n, parsers, [&](int i) {
         status[i] = (!data[i] || len[i] < 0) ? ynjpeg::refuse_null(j->reasons[(size_t)i]) : ynjpeg::parse(data[i], len[i], j->hdr[(size_t)i], j->reasons[(size_t)i]);
     });
-    int64_t need = 0;
+    int64_t need = 0, need_scan = 0;
     for (int c0 = 0; c0 < n; c0 += j->max_batch) {
-        int64_t bytes = 0;
+        int64_t bytes = 0, scan = 0;
         for (int i = c0; i < n && i < c0 + j->max_batch; ++i) {
             if (status[i] != ynjpeg::JPEG_OK) continue;
             if (!frames[i]) { err = "yn_jpeg_decode_batch: image " + std::to_string(i) + " has no frame"; return 1; }
             bytes += j->hdr[(size_t)i].coef_total * (int64_t)sizeof(int16_t);
+            scan += scan_reserve(len[i] - j->hdr[(size_t)i].scan_pos);
         }
         if (bytes > need) need = bytes;
+        if (scan > need_scan) need_scan = scan;
+    }
+    // device entropy mode: the unstuffed scans of a chunk are staged too, in a slot of their own of the same size.  The segment table holds
+    // a segment per 128 coefficient bytes and the table store six tables per image: whatever fits above fits those.
+    if (j->huff && need_scan > j->huff->scan_cap) {
+        err = "yn_jpeg_decode_batch: the scans of " + std::to_string(n < j->max_batch ? n : j->max_batch) + " images need " + std::to_string(need_scan) +
+              " staging bytes, the decoder has " + std::to_string(j->huff->scan_cap);
+        return 1;
     }
     if (need > j->staging_bytes) {
         err = "yn_jpeg_decode_batch: the coefficients of " + std::to_string(n < j->max_batch ? n : j->max_batch) + " images need " + std::to_string(need) +
@@ -320,12 +531,16 @@ int jpeg_decode_batch(JpegState* j, hipStream_t st, int n, const uint8_t* const*
             off[(size_t)i] = total;
             if (status[c0 + i] == ynjpeg::JPEG_OK) total += j->hdr[(size_t)(c0 + i)].coef_total;
         }
-        const auto t1 = std::chrono::steady_clock::now();
-        ynjpeg::parallel_for(m, j->threads, [&](int i) {
-            const int g = c0 + i;
-            if (status[g] == ynjpeg::JPEG_OK) status[g] = ynjpeg::entropy_decode(data[g], len[g], j->hdr[(size_t)g], s.coef.get() + off[(size_t)i], j->reasons[(size_t)g]);
-        });
-        j->host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (j->huff) {
+            if (jpeg_entropy_device(j, s, st, c0, m, data, len, status, off, total, err)) return 1;
+        } else {
+            const auto t1 = std::chrono::steady_clock::now();
+            ynjpeg::parallel_for(m, j->threads, [&](int i) {
+                const int g = c0 + i;
+                if (status[g] == ynjpeg::JPEG_OK) status[g] = ynjpeg::entropy_decode(data[g], len[g], j->hdr[(size_t)g], s.coef.get() + off[(size_t)i], j->reasons[(size_t)g]);
+            });
+            j->host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        }
         JpegDesc* desc = reinterpret_cast<JpegDesc*>(s.table.get());
         int32_t* group_start = reinterpret_cast<int32_t*>(s.table.get() + (size_t)j->max_batch * sizeof(JpegDesc));
         int32_t* tile_start = group_start + j->max_batch + 1;
@@ -357,8 +572,8 @@ int jpeg_decode_batch(JpegState* j, hipStream_t st, int n, const uint8_t* const*
         group_start[k] = (int32_t)groups;
         tile_start[k] = (int32_t)tiles;
         if (k == 0) continue;                                // nothing of this chunk can be decoded: the slot stays free
-        hipError_t e = hipEventRecord(s.e0, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(j->coef_dev.get(), s.coef.get(), (size_t)total * sizeof(int16_t), hipMemcpyHostToDevice, st);
+        hipError_t e = j->huff ? hipSuccess : hipEventRecord(s.e0, st);      // device entropy mode: e0 went in front of its uploads
+        if (e == hipSuccess && !j->huff) e = hipMemcpyAsync(j->coef_dev.get(), s.coef.get(), (size_t)total * sizeof(int16_t), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(j->table_dev.get(), s.table.get(), j->table_bytes(), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipEventRecord(s.e1, st);
         if (e != hipSuccess) { err = std::string("yn_jpeg_decode_batch: ") + hipGetErrorString(e); return 1; }
@@ -420,6 +635,129 @@ int jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef, int64_t c
         return ynjpeg::JPEG_TOO_LARGE;
     }
     return ynjpeg::entropy_decode(data, len, H, coef, reason);
+}
+
+int jpeg_scan_prepare(const uint8_t* data, int64_t len, uint8_t* unstuffed, int64_t cap, int32_t* segments, int64_t seg_cap, int32_t* info4, std::string& reason)
+{
+    static thread_local ynjpeg::Header H;
+    H = ynjpeg::Header();
+    info4[0] = info4[1] = info4[2] = info4[3] = 0;
+    const int st = (!data || len < 0) ? ynjpeg::refuse_null(reason) : ynjpeg::parse(data, len, H, reason);
+    if (st != ynjpeg::JPEG_OK) return st;
+    const int64_t want = ynjpeg::scan_segments(H);
+    info4[3] = (int32_t)want;
+    if (!unstuffed || cap < len - H.scan_pos || !segments || seg_cap < want) {
+        reason = "the scan needs " + std::to_string(len - H.scan_pos) + " bytes and " + std::to_string(want) + " segments";
+        return ynjpeg::JPEG_TOO_LARGE;
+    }
+    std::vector<ynjpeg::ScanSegment> segs((size_t)want);
+    ynjpeg::ScanInfo I;
+    ynjpeg::scan_prepare(data, len, H, unstuffed, cap, segs.data(), want, I);
+    for (int k = 0; k < I.segments; ++k) { segments[2 * k] = (int32_t)segs[(size_t)k].start; segments[2 * k + 1] = segs[(size_t)k].first_mcu; }
+    info4[0] = (int32_t)I.bytes; info4[1] = I.segments; info4[2] = I.host ? 1 : 0;
+    return ynjpeg::JPEG_OK;
+}
+
+// ---- the entropy mode --------------------------------------------------------------------------------------------------------------------
+enum { HUFF_DEFAULT_BITS = 1024, HUFF_DEFAULT_ROUNDS = 64 };
+
+int jpeg_entropy(JpegState* j, int mode, int subseq_bits, int max_rounds, std::string& err)
+{
+    if (mode != 0 && mode != 1) { err = "yn_jpeg_entropy: mode " + std::to_string(mode) + " is neither 0 (host) nor 1 (device)"; return 1; }
+    if (subseq_bits < 0 || subseq_bits % 32 || subseq_bits > (1 << 20)) { err = "yn_jpeg_entropy: subseq_bits " + std::to_string(subseq_bits) + " is no multiple of 32 in 32..2^20 (0: the default)"; return 1; }
+    if (max_rounds < 0 || max_rounds > (1 << 24)) { err = "yn_jpeg_entropy: max_rounds " + std::to_string(max_rounds) + " outside 1..2^24 (0: the default)"; return 1; }
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(j->device);
+    if (j->launched) (void)hipDeviceSynchronize();           // nothing in flight reads what is released or replaced below
+    j->huff.reset();
+    int r = 0;
+    if (mode == 1) {
+        std::unique_ptr<JpegHuff> F(new JpegHuff);
+        F->sb = subseq_bits ? subseq_bits : HUFF_DEFAULT_BITS;
+        F->max_rounds = max_rounds ? max_rounds : HUFF_DEFAULT_ROUNDS;
+        F->max_batch = j->max_batch;
+        F->scan_cap = j->staging_bytes + 16 * (int64_t)j->max_batch;
+        F->seg_cap = j->staging_bytes / 128 + j->max_batch;
+        r = F->scan.reserve((size_t)F->scan_cap);
+        if (!r) r = F->meta.reserve(F->meta_bytes());
+        if (!r) r = F->result.reserve((size_t)j->max_batch);
+        for (JpegHuffSlot& s : F->slot) {
+            if (!r) r = s.scan.reserve((size_t)F->scan_cap);
+            if (!r) r = s.meta.reserve(F->meta_bytes());
+            if (!r) r = s.result.reserve((size_t)j->max_batch);
+        }
+        for (hipEvent_t& e : F->ev)
+            if (!r) r = (int)hipEventCreate(&e);
+        if (r) {
+            (void)hipGetLastError();
+            err = std::string("yn_jpeg_entropy: ") + hipGetErrorString((hipError_t)r) + " (the device mode stages the scans: " + std::to_string(F->scan_cap) + " bytes twice pinned, once on the device)";
+        } else {
+            j->huff = std::move(F);
+        }
+    }
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return r ? 1 : 0;
+}
+
+void jpeg_entropy_stats(const JpegState* j, int64_t* device_files, int64_t* host_files, int32_t* rounds_last, int32_t* subseqs_last)
+{
+    const JpegHuff* F = j->huff.get();
+    if (device_files) *device_files = F ? F->device_files : 0;
+    if (host_files) *host_files = F ? F->host_files : 0;
+    if (rounds_last) *rounds_last = F ? F->rounds_last : 0;
+    if (subseqs_last) *subseqs_last = F ? F->subseqs_last : 0;
+}
+
+static const JpegHuffLast* huff_last(JpegState* j, int i, const char* who, std::string& err)
+{
+    if (!j->huff) { err = std::string(who) + ": the decoder is in host entropy mode"; return nullptr; }
+    if (i < 0 || (size_t)i >= j->huff->last.size()) { err = std::string(who) + ": file " + std::to_string(i) + " outside the last chunk of " + std::to_string(j->huff->last.size()); return nullptr; }
+    const JpegHuffLast& L = j->huff->last[(size_t)i];
+    if (L.dev < 0 || L.flag) { err = std::string(who) + ": file " + std::to_string(i) + " of the last chunk took the host decoder (flag " + std::to_string(L.dev < 0 ? -1 : L.flag) + ")"; return nullptr; }
+    return &L;
+}
+
+int jpeg_device_coefficients(JpegState* j, hipStream_t s, int i, int16_t* host, int64_t cap, std::string& err)
+{
+    const JpegHuffLast* L = huff_last(j, i, "yn_jpeg_device_coefficients", err);
+    if (!L) return 1;
+    if (!host || cap < L->total) { err = "yn_jpeg_device_coefficients: the file has " + std::to_string(L->total) + " coefficients, the buffer " + std::to_string(cap); return 1; }
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(host, j->coef_dev.get() + L->off, (size_t)L->total * sizeof(int16_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = std::string("yn_jpeg_device_coefficients: ") + hipGetErrorString(e); return 1; }
+    return 0;
+}
+
+int jpeg_entropy_states(JpegState* j, hipStream_t s, int i, int32_t* host, int64_t cap, std::string& err)
+{
+    const JpegHuffLast* L = huff_last(j, i, "yn_jpeg_entropy_states", err);
+    if (!L) return 1;
+    const ynhuff::FileDesc& D = j->huff->last_desc[(size_t)L->dev];
+    if (!host || cap < 4 * (int64_t)D.nsub) { err = "yn_jpeg_entropy_states: the file has " + std::to_string(D.nsub) + " subsequences of 4 numbers, the buffer holds " + std::to_string(cap); return 1; }
+    std::vector<uint64_t> st((size_t)D.nsub);
+    std::vector<int32_t> before((size_t)D.nsub);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(st.data(), j->huff->start.get() + D.sub0, st.size() * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(before.data(), j->huff->base.get() + D.sub0, before.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { err = std::string("yn_jpeg_entropy_states: ") + hipGetErrorString(e); return 1; }
+    for (int32_t k = 0; k < D.nsub; ++k) {
+        host[4 * k] = (int32_t)ynhuff::state_bit(st[(size_t)k]); host[4 * k + 1] = ynhuff::state_u(st[(size_t)k]);
+        host[4 * k + 2] = ynhuff::state_k(st[(size_t)k]); host[4 * k + 3] = before[(size_t)k];
+    }
+    return 0;
+}
+
+int jpeg_entropy_timing(JpegState* j, float* ms7, std::string& err)
+{
+    for (int k = 0; k < 7; ++k) ms7[k] = 0.0f;
+    JpegHuff* F = j->huff.get();
+    if (!F || !F->timed) return 0;
+    hipError_t e = hipEventSynchronize(F->ev[6]);
+    for (int k = 0; k < 6 && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms7[k], F->ev[k], F->ev[k + 1]);
+    if (e != hipSuccess) { err = std::string("yn_jpeg_entropy_timing: ") + hipGetErrorString(e); return 1; }
+    ms7[6] = F->subseqs_last ? (float)((double)F->decodes_last / F->subseqs_last) : 0.0f;
+    return 0;
 }
 
 }  // namespace ynk

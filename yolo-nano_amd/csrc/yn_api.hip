@@ -2890,6 +2890,52 @@ int yn_jpeg_timing(yn_handle* h, yn_jpeg* j, float* ms3)
     YN_EVAL_CALL(ynk::jpeg_timing(j->st, ms3, err));
 }
 
+int yn_jpeg_scan_prepare(const uint8_t* data, int64_t len, uint8_t* unstuffed_host, int64_t cap, int32_t* segments_host, int64_t seg_cap, int32_t* info4)
+{
+    int32_t scratch[4];
+    g_jpeg_reason.clear();
+    return ynk::jpeg_scan_prepare(data, len, unstuffed_host, cap, segments_host, seg_cap, info4 ? info4 : scratch, g_jpeg_reason);
+}
+
+int yn_jpeg_entropy(yn_jpeg* j, int mode, int subseq_bits, int max_rounds)
+{
+    g_jpeg_reason.clear();
+    if (!j) { g_jpeg_reason = "yn_jpeg_entropy: null object"; return 1; }
+    return ynk::jpeg_entropy(j->st, mode, subseq_bits, max_rounds, g_jpeg_reason);
+}
+
+int yn_jpeg_entropy_stats(yn_jpeg* j, int64_t* device_files, int64_t* host_files, int32_t* rounds_last, int32_t* subseqs_last)
+{
+    if (!j) return 1;
+    ynk::jpeg_entropy_stats(j->st, device_files, host_files, rounds_last, subseqs_last);
+    return 0;
+}
+
+#define YN_JPEG_ENTER(name)                                                                                                               \
+    YN_ENTER(h);                                                                                                                          \
+    if (!j) return fail(h, name ": null object");                                                                                         \
+    if (ynk::jpeg_device(j->st) != h->cfg.device)                                                                                         \
+        return fail(h, name ": the object was made for device %d, the handle is on device %d", ynk::jpeg_device(j->st), h->cfg.device)
+
+int yn_jpeg_device_coefficients(yn_handle* h, yn_jpeg* j, int i, int16_t* host, int64_t cap)
+{
+    YN_JPEG_ENTER("yn_jpeg_device_coefficients");
+    YN_EVAL_CALL(ynk::jpeg_device_coefficients(j->st, h->stream, i, host, cap, err));
+}
+
+int yn_jpeg_entropy_states(yn_handle* h, yn_jpeg* j, int i, int32_t* host, int64_t cap)
+{
+    YN_JPEG_ENTER("yn_jpeg_entropy_states");
+    YN_EVAL_CALL(ynk::jpeg_entropy_states(j->st, h->stream, i, host, cap, err));
+}
+
+int yn_jpeg_entropy_timing(yn_handle* h, yn_jpeg* j, float* ms7)
+{
+    YN_JPEG_ENTER("yn_jpeg_entropy_timing");
+    if (!ms7) return fail(h, "yn_jpeg_entropy_timing: null argument");
+    YN_EVAL_CALL(ynk::jpeg_entropy_timing(j->st, ms7, err));
+}
+
 // ---- baseline JPEG encode: every stage on the device (kernels_jpeg_enc.hip) ------------------------------------------------------------
 int yn_jpeg_quant_tables(int quality, uint16_t* qt2x64_natural)
 {

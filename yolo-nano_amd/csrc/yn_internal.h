@@ -306,6 +306,30 @@ int  jpeg_timing(JpegState* j, float* ms3, std::string& err);
 // host only; they return the YN_JPEG_ status and the reason of a refusal
 int  jpeg_info(const uint8_t* data, int64_t len, int32_t* info8, std::string& reason);
 int  jpeg_coefficients(const uint8_t* data, int64_t len, int16_t* coef, int64_t cap, uint16_t* qt, int32_t* grid, int64_t* needed, std::string& reason);
+int  jpeg_scan_prepare(const uint8_t* data, int64_t len, uint8_t* unstuffed, int64_t cap, int32_t* segments, int64_t seg_cap, int32_t* info4, std::string& reason);
+// the entropy mode: 0 = the host decodes the Huffman stage (default), 1 = the device does (kernels_jpeg_huff.hip)
+int  jpeg_entropy(JpegState* j, int mode, int subseq_bits, int max_rounds, std::string& err);
+void jpeg_entropy_stats(const JpegState* j, int64_t* device_files, int64_t* host_files, int32_t* rounds_last, int32_t* subseqs_last);
+int  jpeg_device_coefficients(JpegState* j, hipStream_t s, int i, int16_t* host, int64_t cap, std::string& err);
+int  jpeg_entropy_states(JpegState* j, hipStream_t s, int i, int32_t* host, int64_t cap, std::string& err);
+int  jpeg_entropy_timing(JpegState* j, float* ms7, std::string& err);
+// the four entropy kernels of one chunk, enqueued on s (kernels_jpeg_huff.hip); the pointers are device memory laid out by jpeg_decode_batch
+struct JpegHuffArgs {
+    const void* files;             // ynhuff::FileDesc [nfiles]
+    const void* segs;              // ynhuff::Segment
+    const void* tables;            // ynhuff::Table
+    const uint8_t* scan;
+    uint64_t* start;               // per subsequence of the chunk
+    uint64_t* end;
+    int32_t* nblk;
+    int32_t* base;
+    void* result;                  // ynhuff::FileResult [nfiles]
+    const int32_t* wg_start;       // [nfiles + 1] first workgroup of a file in the first-round and write kernels
+    int16_t* coef;
+    int nfiles, write_wgs, sb, max_rounds;
+};
+void jpeg_huff_launch(const JpegHuffArgs& a, hipStream_t s, hipEvent_t after_first, hipEvent_t after_sync, hipEvent_t after_write);
+int  jpeg_huff_write_threads();
 
 // ---- baseline JPEG encode (kernels_jpeg_enc.hip): the state behind yn_jpeg_enc; 0 = ok, 1 = error (text in err) ---------------------------
 struct JpegEncState;

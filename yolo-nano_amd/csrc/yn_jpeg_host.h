@@ -13,6 +13,8 @@
 #include <thread>
 #include <vector>
 
+#include "yn_jpeg_huff.h"
+
 namespace ynjpeg {
 
 enum { JPEG_OK = 0, JPEG_UNSUPPORTED = 1, JPEG_CORRUPT = 2, JPEG_TOO_LARGE = 3 };
@@ -339,6 +341,82 @@ inline int entropy_decode(const uint8_t* d, int64_t n, const Header& H, int16_t*
         }
     }
     return JPEG_OK;
+}
+
+// ---- the host's share of the device entropy mode --------------------------------------------------------------------------
+struct ScanSegment {
+    uint32_t start;                // first byte of the restart segment in the unstuffed scan
+    int32_t first_mcu;
+};
+
+struct ScanInfo {
+    int64_t bytes = 0;             // unstuffed bytes written
+    int32_t segments = 0;
+    bool host = false;             // scan_prepare cannot vouch for the file: it takes entropy_decode, which knows the status and the reason
+};
+
+enum { SCAN_MAX_BYTES = 1 << 28 };                // beyond that a bit position or a block count could leave 31 bits: the host decodes the file
+
+inline int64_t scan_segments(const Header& H)     // the restart segments a whole scan has
+{
+    const int64_t mcus = (int64_t)H.mcus_w * H.mcus_h;
+    return H.restart ? (mcus + H.restart - 1) / H.restart : 1;
+}
+
+// One pass over the entropy-coded data of a parsed file, the copy into the staging slot: byte stuffing goes (FF 00 -> FF), the restart
+// markers go and leave the segment table, the copy stops at the first other marker or at the end of the data.  A restart marker counts
+// when it is the next one of RST0..7 in order, after any number of FF fill bytes (the rules of BitReader::restart), and a segment is still
+// missing.  out[cap] with cap >= n - H.scan_pos always suffices; segs[seg_cap] with seg_cap >= scan_segments(H) likewise.
+inline void scan_prepare(const uint8_t* d, int64_t n, const Header& H, uint8_t* out, int64_t cap, ScanSegment* segs, int64_t seg_cap, ScanInfo& I)
+{
+    I = ScanInfo();
+    const int64_t expect = scan_segments(H);
+    if (seg_cap < 1 || H.scan_pos > n) { I.host = true; return; }
+    int64_t p = H.scan_pos, o = 0, nseg = 1;
+    int next_rst = 0;
+    segs[0].start = 0; segs[0].first_mcu = 0;
+    for (;;) {
+        const uint8_t* ff = p < n ? (const uint8_t*)memchr(d + p, 0xFF, (size_t)(n - p)) : nullptr;
+        const int64_t run = ff ? ff - (d + p) : n - p;
+        if (o + run > cap || o + run >= SCAN_MAX_BYTES) { I.host = true; break; }
+        if (run) memcpy(out + o, d + p, (size_t)run);
+        o += run; p += run;
+        if (p >= n) break;
+        if (p + 1 < n && d[p + 1] == 0x00) {                                   // a stuffed FF
+            if (o + 1 > cap) { I.host = true; break; }
+            out[o++] = 0xFF; p += 2;
+            continue;
+        }
+        int64_t q = p;
+        while (q + 1 < n && d[q] == 0xFF && d[q + 1] == 0xFF) q += 1;          // fill bytes
+        if (H.restart && nseg < expect && nseg < seg_cap && q + 1 < n && d[q] == 0xFF && d[q + 1] == 0xD0 + next_rst) {
+            segs[nseg].start = (uint32_t)o; segs[nseg].first_mcu = (int32_t)(nseg * H.restart);
+            ++nseg;
+            next_rst = (next_rst + 1) & 7;
+            p = q + 2;
+            continue;
+        }
+        break;                                                                 // any other marker ends the scan
+    }
+    I.bytes = o; I.segments = (int32_t)nseg;
+    if (nseg != expect) I.host = true;
+}
+
+inline void huff_table(const HuffTable& t, ynhuff::Table& o)
+{
+    memset(&o, 0, sizeof o);
+    for (int i = 0; i < (1 << LOOK_BITS); ++i) o.look[i] = (uint16_t)(t.look_len[i] << 8 | t.look_sym[i]);
+    memcpy(o.maxcode, t.maxcode, sizeof o.maxcode);
+    memcpy(o.valoff, t.valoff, sizeof o.valoff);
+    memcpy(o.vals, t.vals, sizeof o.vals);
+}
+
+inline void huff_geometry(const Header& H, const int64_t base, ynhuff::Geometry& G)
+{
+    G.L = H.hs[0] * H.vs[0]; G.U = G.L + (H.nc == 3 ? 2 : 0);
+    G.hs = H.hs[0]; G.vs = H.vs[0]; G.mcus_w = H.mcus_w; G.restart = H.restart;
+    G.blocks = (int32_t)((int64_t)H.mcus_w * H.mcus_h * G.U);
+    for (int c = 0; c < 3; ++c) { G.bw[c] = H.bw[c]; G.coef_off[c] = base + H.coef_off[c]; }
 }
 
 // fn(i) for i in [0, n) on up to `threads` workers (the caller is one of them), one item at a time each

@@ -8,6 +8,12 @@ conversion run on the device.  The frames go straight into ValTransforms.batch /
 Visualizer.batch, which take CUDA uint8 frames as they are.  Files outside the baseline subset (progressive, arithmetic, 12-bit, CMYK,
 unusual sampling factors) are refused with a reason; there is no host decoder to fall back to.  `info` and `coefficients` need no GPU.
 
+    JPEGDecoder(max_batch=32, entropy="device")        # opt-in (yn_jpeg_entropy): the device decodes the Huffman stage too
+
+With entropy="device" the host only parses the markers and copies each scan once; frames, statuses and reasons stay those of the default
+in every case (a file the device cannot vouch for is decoded by the host after all), and a batch() call waits for one result word per file.
+`scan_prepare` (that copy pass alone) needs no GPU.
+
     imwrite("000001.jpg", frame)                        # the stand-in for cv2.imwrite in test.py / demo.py (yn_jpeg_enc_*)
     files = JPEGEncoder(max_batch=32).batch(frames)     # bytes objects: the whole encoder runs on the device, the files come down
 
@@ -69,11 +75,36 @@ def coefficients(blob):
     return dict(status=int(st.value), reason=lib.yn_jpeg_reason(None, 0).decode() if st.value else "", coef=coef, qt=qt, grid=grid)
 
 
+def scan_prepare(blob):
+    """The copy pass of the device entropy mode alone (yn_jpeg_scan_prepare; host only) -> dict(status, reason, scan = the entropy-coded
+    data without byte stuffing and restart markers (bytes), segments int32 [n, 2] = first byte and first MCU of every restart segment,
+    host = True when the file must take the host decoder, expected = the segments its header asks for)."""
+    lib = capi.load_library()
+    keep, ptr, n = _buffer(blob)
+    info4 = np.zeros(4, dtype=np.int32)
+    st = lib.yn_jpeg_scan_prepare(ptr, n, None, 0, None, 0, info4.ctypes.data)                # asks for the segment count
+    if st != TOO_LARGE:
+        return dict(status=int(st), reason=lib.yn_jpeg_reason(None, 0).decode() if st else "", scan=b"", segments=np.zeros((0, 2), np.int32), host=True, expected=0)
+    out = np.zeros(max(n, 1), dtype=np.uint8)
+    segs = np.zeros((max(int(info4[3]), 1), 2), dtype=np.int32)
+    st = lib.yn_jpeg_scan_prepare(ptr, n, out.ctypes.data, out.size, segs.ctypes.data, segs.shape[0], info4.ctypes.data)
+    return dict(status=int(st), reason=lib.yn_jpeg_reason(None, 0).decode() if st else "", scan=out[:int(info4[0])].tobytes(),
+                segments=segs[:int(info4[1])].copy(), host=bool(info4[2]), expected=int(info4[3]))
+
+
+ENTROPY_MODES = {"host": 0, "device": 1}
+
+
 class JPEGDecoder(object):
     """A yn_jpeg object: two pinned staging slots, so the host decodes one chunk while the previous one uploads and runs.
-    threads=None: min(16, $OMP_NUM_THREADS or 8) host workers.  Staging grows by itself (the object is recreated)."""
+    threads=None: min(16, $OMP_NUM_THREADS or 8) host workers.  Staging grows by itself (the object is recreated).
+    entropy="device": the Huffman stage runs on the device in subsequences of subseq_bits (a multiple of 32) that synchronise in at most
+    max_rounds rounds (None: the library's defaults); the results are those of entropy="host", the default, in every case."""
 
-    def __init__(self, max_batch=32, threads=None, handle=None, device=None, staging_bytes=None):
+    def __init__(self, max_batch=32, threads=None, handle=None, device=None, staging_bytes=None, entropy="host", subseq_bits=None, max_rounds=None):
+        if entropy not in ENTROPY_MODES:
+            raise ValueError("entropy %r is not one of %s" % (entropy, ", ".join(sorted(ENTROPY_MODES))))
+        self.entropy, self.subseq_bits, self.max_rounds = entropy, subseq_bits, max_rounds
         self.lib = capi.load_library()
         self.max_batch = int(max_batch)
         self.threads = int(threads) if threads is not None else min(16, int(os.environ.get("OMP_NUM_THREADS", 8)))
@@ -98,6 +129,48 @@ class JPEGDecoder(object):
         j = ctypes.c_void_p()
         h._ck(self.lib.yn_jpeg_create(h.h, self.max_batch, int(staging_bytes), self.threads, ctypes.byref(j)), "yn_jpeg_create")
         self.j, self.staging_bytes = j, int(staging_bytes)
+        if self.entropy != "host" or self.subseq_bits is not None or self.max_rounds is not None:
+            if self.lib.yn_jpeg_entropy(j, ENTROPY_MODES[self.entropy], int(self.subseq_bits or 0), int(self.max_rounds or 0)):
+                reason = self.lib.yn_jpeg_reason(None, 0).decode()
+                self.close()
+                raise ValueError(reason)
+
+    def entropy_stats(self):
+        """{'device_files', 'host_files'} since the object was (re)created, {'rounds_last', 'subseqs_last'} of the last chunk
+        (yn_jpeg_entropy_stats); all 0 with entropy="host"."""
+        d, hf = ctypes.c_int64(), ctypes.c_int64()
+        r, n = ctypes.c_int32(), ctypes.c_int32()
+        self.lib.yn_jpeg_entropy_stats(self.j, ctypes.byref(d), ctypes.byref(hf), ctypes.byref(r), ctypes.byref(n))
+        return {"device_files": int(d.value), "host_files": int(hf.value), "rounds_last": int(r.value), "subseqs_last": int(n.value)}
+
+    def entropy_timing(self, handle=None):
+        """Of the last chunk decoded with entropy="device" (yn_jpeg_entropy_timing; synchronises): milliseconds of the upload of scans and
+        tables, the clearing, and the four entropy kernels, and 'decodes_per_subseq' of the synchronisation (1 = a serial decoder's work)."""
+        h = self._h(handle)
+        ms = (ctypes.c_float * 7)()
+        h._ck(self.lib.yn_jpeg_entropy_timing(h.h, self.j, ctypes.cast(ms, ctypes.c_void_p)), "yn_jpeg_entropy_timing")
+        return dict(zip(("upload_ms", "clear_ms", "first_ms", "sync_ms", "write_ms", "dc_ms", "decodes_per_subseq"), [float(v) for v in ms]))
+
+    def device_coefficients(self, i, meta, handle=None):
+        """The coefficients of file i of the last chunk as the device's entropy stage left them (yn_jpeg_device_coefficients), as
+        `coefficients` returns a file's; meta = info(file)."""
+        h = self._h(handle)
+        flat = np.zeros(coefficient_count(meta), dtype=np.int16)
+        h._ck(self.lib.yn_jpeg_device_coefficients(h.h, self.j, int(i), flat.ctypes.data, flat.size), "yn_jpeg_device_coefficients")
+        mw, mh = -(-meta["w"] // (8 * meta["h_samp"])), -(-meta["h"] // (8 * meta["v_samp"]))
+        grids = [(mh * meta["v_samp"], mw * meta["h_samp"])] + [(mh, mw)] * (meta["components"] - 1)
+        out, off = [], 0
+        for a, b in grids:
+            out.append(flat[off:off + 64 * a * b].reshape(a, b, 64))
+            off += 64 * a * b
+        return out
+
+    def entropy_states(self, i, handle=None):
+        """int32 [subsequences, 4] of file i of the last chunk (yn_jpeg_entropy_states): bit, unit in the MCU, zigzag index, blocks before."""
+        h = self._h(handle)
+        out = np.full((max(self.entropy_stats()["subseqs_last"], 1), 4), -1, dtype=np.int32)
+        h._ck(self.lib.yn_jpeg_entropy_states(h.h, self.j, int(i), out.ctypes.data, out.size), "yn_jpeg_entropy_states")
+        return out[out[:, 0] >= 0].copy()
 
     def close(self):
         if getattr(self, "j", None):
@@ -140,7 +213,8 @@ class JPEGDecoder(object):
 
     def batch(self, blobs, errors="raise", handle=None):
         """A list of JPEG files (bytes-like) -> a list of CUDA uint8 [h,w,3] BGR tensors.  A refused file raises ValueError naming its
-        index and the reason; with errors="none" its entry is None and the others are decoded.  Asynchronous on the handle's stream."""
+        index and the reason; with errors="none" its entry is None and the others are decoded.  Asynchronous on the handle's stream with
+        entropy="host"; with entropy="device" it waits, per chunk, for the entropy kernels' result words."""
         import torch
         assert errors in ("raise", "none")
         h = self._h(handle)
@@ -153,6 +227,8 @@ class JPEGDecoder(object):
         need = 0
         for c0 in range(0, len(blobs), self.max_batch):
             need = max(need, sum(2 * coefficient_count(m) for m in metas[c0:c0 + self.max_batch] if not m["status"]))
+            if self.entropy == "device":                       # the scans are staged too: never more than the files themselves
+                need = max(need, sum(-(-len(b) // 16) * 16 for b, m in zip(blobs[c0:c0 + self.max_batch], metas[c0:c0 + self.max_batch]) if not m["status"]))
         if need > self.staging_bytes:
             self._create(max(need, 2 * self.staging_bytes))
         frames = [None if m["status"] else torch.empty((m["h"], m["w"], 3), dtype=torch.uint8, device=h.device) for m in metas]
