@@ -75,7 +75,8 @@ int  yn_set_grid(yn_handle* h, int input_size);                 /* YOLONano.set_
  * (height == width == side, left == top == 0) is yn_set_grid(side): the same code path, the same bits.
  * Follow the grid: yn_forward_raw, yn_forward_taps, yn_score_full, yn_decode_boxes (canvas pixels, no offset), yn_infer, yn_postprocess,
  * yn_pack_detections, yn_op_decode_cand, yn_op_head_tail.  Refused on a window grid ("... needs a square grid", nothing launched, the grid
- * unchanged): yn_train_step, yn_train_forward, yn_loss, yn_loss_heads, yn_op_h16_loss, yn_make_targets, yn_tta_infer. */
+ * unchanged): yn_train_step, yn_train_forward, yn_loss, yn_loss_heads, yn_op_h16_loss, yn_make_targets, yn_tta_infer, yn_slice_append,
+ * yn_slice_infer. */
 int  yn_set_grid_rect(yn_handle* h, int height, int width, int side, int left, int top);
 int  yn_grid_shape(yn_handle* h, int* height, int* width, int* side, int* left, int* top);   /* any pointer may be NULL */
 int  yn_set_stream(yn_handle* h, void* stream);                /* drains the previous stream first  */
@@ -463,6 +464,75 @@ int  yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev
  * order: where forward f's rows start in image b's list.  Any pointer may be NULL.  Synchronises the stream. */
 int  yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host,
                      int32_t* forward_start_host);
+
+/* ---- sliced inference: a frame larger than the network input runs as overlapping tiles at native resolution, plus the whole frame once;
+ * every tile's boxes go back into the frame and are merged per frame with per-class NMS (DESIGN.md 28 is the specification;
+ * yolo_nano_amd.slicing.slice_grid / tile_table build the table).  Frames are uint8 [h0][w0][3] BGR on the device, rows contiguous, sides
+ * 1..16384: frames_host[f] = device pointer of frame f, shapes_host[f] = {h0, w0}.  The tile table tiles_host [T][9] is int32 rows
+ * frame, x, y, tw, th, rw, rh, left, top: the rectangle frame[y:y+th, x:x+tw], and Resize's integer geometry of that rectangle taken as an
+ * image (what yn_preprocess_batch takes as rw, rh, left, top).  Every entry checks the rows it reads before anything is launched and
+ * refuses, naming the tile: a frame index outside the frames, a rectangle outside its frame, non-positive extents, a letterbox geometry
+ * outside the side x side square.  The object stands on its own, as yn_tta does, and launches on the stream of the handle passed. */
+typedef struct yn_slice yn_slice;
+/* max_frames: frames per call (1..4096); list_capacity: rows of one frame's merge list, 1..131072 - the sum over the frame's tiles of what
+ * yn_infer keeps (after the edge filter).  The lists and the result are allocated here; the tile batch of yn_slice_infer follows the
+ * handle's grid and max_batch at its first call.  The handle gives the device, the anchors per cell and the class count. */
+int  yn_slice_create(yn_handle* h, int max_frames, int list_capacity, yn_slice** out);
+void yn_slice_destroy(yn_slice* s);
+/* The tile kernel on its own: x_dev float32 [T][3][side][side]; tile t holds, bit for bit, what yn_preprocess_batch writes for a
+ * contiguous copy of frame[y:y+th, x:x+tw] with geometry {th, tw, rw, rh, left, top} - the same cv2 8-bit INTER_LINEAR (a copy when the
+ * extent is the tile's, the area path for an exact 2:1), the same pad and normalise order.  The frame is read in place by its row pitch
+ * 3 * w0; no crop is made.  One launch per 64 tiles.  mean / std: 3 host floats each, BGR order.  Also refused: null pointers (a frame's
+ * included), non-positive std.  The table's frame indices must lie inside frames_host / shapes_host (this entry has no frame count to
+ * check them against; only negative ones are refused).  T == 0 does nothing.  Asynchronous.
+ * On a tile with tw == th == rw == rh == side (side % 4 == 0, x_dev 16-byte aligned) the kernel loads the source as whole 4-byte-aligned
+ * words: it may READ up to 3 bytes in front of the frame's first byte and up to 3 behind its last.  Such a word always holds a byte of
+ * the frame, so it lies in the frame's page and the read cannot fault; nothing outside the frame is used or written.  A tool that
+ * checks object bounds byte by byte would report it. */
+int  yn_slice_preprocess(yn_handle* h, int T, const uint8_t* const* frames_host, const int32_t* shapes_host, const int32_t* tiles_host, int side,
+                         const float* mean_host, const float* std_host, float* x_dev);
+/* The kept rows of ONE yn_infer over tiles t0 .. t0 + n - 1 of the table (out_* and count_dev in yn_infer's layout, image j = tile t0 + j,
+ * N = capacity per image) go to the end of their frames' merge lists.  A frame's list is in table order of its tiles, ascending candidate
+ * order inside a tile, whatever the chunking: chunks must arrive in table order, t0 == 0 opens a new table (empties the F lists), any other
+ * t0 must continue where the last chunk ended.  `side` of the geometry is the handle's current grid, which must be square.
+ * A box b in [0,1] of the tile's square becomes
+ *   p = bboxes -= offset; /= scale; *= size of the evaluators with the geometry {tw, th, rw, rh, left, top, side} (float64 operands, every
+ *       step rounded to float32)
+ *   q = p + (float)x for x1 / x2, p + (float)y for y1 / y2                                       one float32 add each
+ *   edge filter, only when edge_margin m >= 0 (float32, every sum rounded once): the row is dropped if
+ *       x > 0 && q.x1 < (float)x + m,  or  x + tw < w0 && q.x2 > (float)(x + tw) - m,  or the same two tests in y
+ *     (a side that lies on the frame's edge never drops a box, so a full-frame tile is never filtered; strict compares: a box at
+ *     exactly the margin stays)
+ *   q clamped to [0, w0] (x) / [0, h0] (y):  q < 0 ? 0 : (q > hi ? hi : q)
+ *   v = q / (float)max(h0, w0)                                                                     one float32 divide
+ * Score and class are copied.  With the identity geometry row (w0, h0, w0, h0, 0, 0, max(h0, w0)) v is what yn_eval_add, yn_coco_add and
+ * yn_draw_batch take.  A negative count (the split-f16 range mark) sets the object's range mark and appends none of that tile's rows.
+ * Rows past list_capacity are counted, not written; the next yn_slice_merge fails on them.  out_boxes_dev must be 16-byte aligned (a
+ * box is loaded as one float4; refused otherwise), as any buffer yn_infer's boxes come from is.  Asynchronous. */
+int  yn_slice_append(yn_handle* h, yn_slice* s, int F, const int32_t* shapes_host, int T, const int32_t* tiles_host, int t0, int n,
+                     const float* out_boxes_dev, const float* out_scores_dev, const int32_t* out_cls_dev, const int32_t* count_dev, int N,
+                     float edge_margin);
+/* ONE read-back (list sizes, overflow flag, range mark), per-class NMS of the F lists in yn_nms_merge's arithmetic (never DIoU; kept rows
+ * stay in ascending list order) and yn_pack_detections into the object's record buffer.  A range mark returns YN_STATUS_RANGE; a list
+ * that would have passed list_capacity fails, naming the first such frame and the rows it needed.  Nothing is delivered then. */
+int  yn_slice_merge(yn_handle* h, yn_slice* s, int F, float nms_thresh);
+/* The composition: per chunk of at most the handle's max_batch tiles, in table order, yn_slice_preprocess into the object's input buffer,
+ * ONE yn_infer at the handle's current grid and thresholds, one yn_slice_append; then yn_slice_merge.  The grid must be square (its side
+ * is the table's `side`); a window grid is refused and nothing is launched.  The result does not depend on where the chunk boundaries
+ * fall.  A range mark returns YN_STATUS_RANGE and delivers nothing (acknowledge with yn_range_status, yn_exact_f32(h, 1), run again).
+ * F == 0 or T == 0 is an empty result, not an error. */
+int  yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frames_host, const int32_t* shapes_host, int T,
+                    const int32_t* tiles_host, const float* mean_host, const float* std_host, float nms_thresh, float edge_margin);
+/* the last successful yn_slice_merge's result, with the contract of yn_tta_result: rec_dev [total][6] + offsets_dev [F+1], owned by the
+ * object and valid until its next call.  Any pointer may be NULL; `total` costs one 4-byte read-back (once per result).  Returns 1 when
+ * there is no result. */
+int  yn_slice_result(yn_slice* s, const float** rec_dev, const int32_t** offsets_dev, int32_t* total);
+/* testing aid: the merge lists of the current table (also after a merge that failed on list_capacity), to the host: boxes_host
+ * [F][list_capacity][4], scores_host / cls_host [F][list_capacity] (rows >= count: class -1), count_host [F] (the rows the list needed,
+ * which may exceed list_capacity) and tile_start_host [T]: where tile t's rows start in its frame's list.  Any pointer may be NULL.
+ * Synchronises the stream. */
+int  yn_slice_lists(yn_handle* h, yn_slice* s, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host,
+                    int32_t* tile_start_host);
 
 /* ---- detections painted onto frames in list order: test.py:50-92 / demo.py:48-71 (visualize, plot_bbox_labels) for B frames at once,
  * straight from the rec_dev / offsets_dev pair of yn_pack_detections or yn_tta_result: no read-back, no per-detection host work

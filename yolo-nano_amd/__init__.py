@@ -14,6 +14,9 @@ def __getattr__(name):
     if name == "rect_window":
         from . import rect                                    # host arithmetic only
         return rect.rect_window
+    if name in ("SlicedInference", "slice_grid", "tile_table"):
+        from . import slicing                                 # host arithmetic until SlicedInference touches a model
+        return getattr(slicing, name)
     if name in ("TrainTransforms", "ColorTransforms", "AugParams", "Mosaic", "MosaicParams"):
         from . import augment                                 # numpy only: safe to import in DataLoader workers
         return getattr(augment, name)

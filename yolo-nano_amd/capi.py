@@ -163,6 +163,14 @@ SIGNATURES = {
     "yn_tta_infer": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32]),
     "yn_tta_result": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
     "yn_tta_forwards": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_slice_create": (_i32, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
+    "yn_slice_destroy": (None, [_vp]),
+    "yn_slice_preprocess": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "yn_slice_append": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32]),
+    "yn_slice_merge": (_i32, [_vp, _vp, _i32, _f32]),
+    "yn_slice_infer": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _f32]),
+    "yn_slice_result": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
+    "yn_slice_lists": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_draw_create": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "yn_draw_destroy": (None, [_vp]),
     "yn_draw_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, ctypes.c_int64, _f32]),
@@ -1291,3 +1299,126 @@ class Tta:
         h._ck(self.lib.yn_tta_forwards(h.h, self.t, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
               "yn_tta_forwards")
         return boxes, scores, cls, count, start
+
+
+class Slice:
+    """One yn_slice: sliced inference - tiles of large frames, merged per frame.  Thin, 1:1 with the C ABI; `handle` gives the device, the
+    anchors per cell and the class count, and is the default handle of every call.  Frames are uint8 [h0,w0,3] CUDA tensors, `tiles` an
+    int32 [T,9] table (slicing.tile_table)."""
+
+    def __init__(self, handle, max_frames=1, list_capacity=8192):
+        self.lib = handle.lib
+        self.handle = handle
+        self.max_frames, self.list_capacity = int(max_frames), int(list_capacity)
+        s = _vp()
+        handle._ck(self.lib.yn_slice_create(handle.h, self.max_frames, self.list_capacity, ctypes.byref(s)), "yn_slice_create")
+        self.s = s
+        self.F = None                                           # frames of the result
+        self.lists = None                                       # (F, T) of the table being appended
+
+    def close(self):
+        if getattr(self, "s", None):
+            self.lib.yn_slice_destroy(self.s)
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _frames(frames):
+        n = len(frames)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        shapes = np.zeros((max(n, 1), 2), np.int32)
+        for f, im in enumerate(frames):
+            assert im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous(), "frames are contiguous uint8 [h,w,3] on the device"
+            ptrs[f] = im.data_ptr()
+            shapes[f] = (int(im.shape[0]), int(im.shape[1]))
+        return ptrs, shapes
+
+    @staticmethod
+    def _table(tiles):
+        return np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 9))
+
+    def preprocess(self, frames, tiles, side, mean, std, out=None, handle=None):
+        """The tile kernel on its own (yn_slice_preprocess) -> float32 [T,3,side,side]."""
+        h = self.handle if handle is None else handle
+        tiles = self._table(tiles)
+        T = len(tiles)
+        if out is None:
+            out = torch.empty((T, 3, side, side), dtype=torch.float32, device=h.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == T * 3 * side * side
+        ptrs, shapes = self._frames(frames)
+        m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+        h._ck(self.lib.yn_slice_preprocess(h.h, T, ctypes.cast(ptrs, _vp), shapes.ctypes.data, tiles.ctypes.data, int(side), ctypes.cast(m, _vp),
+                                           ctypes.cast(sd, _vp), out.data_ptr()), "yn_slice_preprocess")
+        return out
+
+    def append(self, shapes, tiles, t0, out, edge_margin=-1.0, handle=None):
+        """The kept rows of one infer() over tiles t0 .. t0 + n - 1 (`out` = its five outputs, n = their batch) go to their frames' lists
+        (yn_slice_append).  shapes: F rows (h0, w0).  t0 == 0 opens a new table."""
+        h = self.handle if handle is None else handle
+        boxes, scores, cls, _, count = out
+        n, N = int(scores.shape[0]), int(scores.shape[1])
+        shapes = np.ascontiguousarray(np.asarray(shapes, dtype=np.int32).reshape(-1, 2))
+        tiles = self._table(tiles)
+        assert boxes.is_contiguous() and scores.is_contiguous() and cls.is_contiguous() and count.is_contiguous()
+        assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and cls.dtype == torch.int32 and count.dtype == torch.int32
+        self.F = None
+        h._ck(self.lib.yn_slice_append(h.h, self.s, len(shapes), shapes.ctypes.data, len(tiles), tiles.ctypes.data, int(t0), n, boxes.data_ptr(),
+                                       scores.data_ptr(), cls.data_ptr(), count.data_ptr(), N, float(edge_margin)), "yn_slice_append")
+        self.lists = (len(shapes), len(tiles))
+
+    def merge(self, F, nms_thresh=0.5, handle=None):
+        """Per-class NMS of the F lists + pack (yn_slice_merge).  Raises YnRangeError on the range mark, YnError naming the frame when a
+        list would have passed list_capacity."""
+        h = self.handle if handle is None else handle
+        self.F = None
+        h._ck(self.lib.yn_slice_merge(h.h, self.s, int(F), float(nms_thresh)), "yn_slice_merge")
+        self.F = int(F)
+
+    def infer(self, frames, tiles, mean, std, nms_thresh=0.5, edge_margin=-1.0, handle=None):
+        """Every tile through the handle's yn_infer in chunks of its max_batch, the per-frame merge and the pack (yn_slice_infer)."""
+        h = self.handle if handle is None else handle
+        tiles = self._table(tiles)
+        ptrs, shapes = self._frames(frames)
+        m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+        self.F = None
+        self.lists = (len(frames), len(tiles))
+        h._ck(self.lib.yn_slice_infer(h.h, self.s, len(frames), ctypes.cast(ptrs, _vp), shapes.ctypes.data, len(tiles), tiles.ctypes.data,
+                                      ctypes.cast(m, _vp), ctypes.cast(sd, _vp), float(nms_thresh), float(edge_margin)), "yn_slice_infer")
+        self.F = len(frames)
+
+    def result(self, total=False):
+        """(rec [max_frames * list_capacity, 6] float32, offsets [F+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
+        object's buffers, valid until its next call (yn_slice_result).  total=True: also offsets[F] as an int (one read-back)."""
+        if self.F is None:
+            raise YnError("yn_slice_result: no result (infer() or merge() first)")
+        rec, off, n = _vp(), _vp(), _i32(0)
+        if self.lib.yn_slice_result(self.s, ctypes.byref(rec), ctypes.byref(off), ctypes.byref(n) if total else None):
+            raise YnError("yn_slice_result: no result")
+        dev = self.handle.device
+        r = torch.as_tensor(_DeviceView(rec.value, (self.max_frames * self.list_capacity, 6), "<f4", self), device=dev)
+        o = torch.as_tensor(_DeviceView(off.value, (self.F + 1,), "<i4", self), device=dev)
+        return (r, o, int(n.value)) if total else (r, o)
+
+    def lists_to_host(self, handle=None):
+        """Testing aid (yn_slice_lists): the merge lists before the NMS -> (boxes [F,cap,4], scores [F,cap], cls [F,cap] int32,
+        count [F] int32, tile_start [T] int32) numpy arrays."""
+        h = self.handle if handle is None else handle
+        if self.lists is None:
+            raise YnError("yn_slice_lists: no table (append() or infer() first)")
+        F, T = self.lists
+        cap = self.list_capacity
+        boxes = np.zeros((F, cap, 4), np.float32)
+        scores = np.zeros((F, cap), np.float32)
+        cls = np.zeros((F, cap), np.int32)
+        count = np.zeros((max(F, 1),), np.int32)
+        start = np.zeros((max(T, 1),), np.int32)
+        h._ck(self.lib.yn_slice_lists(h.h, self.s, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
+              "yn_slice_lists")
+        return boxes, scores, cls, count[:F], start[:T]

@@ -190,30 +190,40 @@ class COCOEval:
         return det, seg, matched, ignored
 
 
-def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None, rect=False):
+def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None, rect=False, sliced=None):
     """COCOAPIEvaluator.evaluate for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3 BGR arrays,
     `image_ids` their COCO ids, `annotations` one float array [G][7] per image (coco_gt_arrays).  Per batch: ValTransforms.batch ->
     yn_infer -> yn_pack_detections -> yn_coco_add; nothing comes back to the host but two 4-byte counts per batch.
     -> (ap50, ap50_95) as the reference returns them; (0, 0) without any detection (cocoapi_evaluator.py:131-132).
     test_aug: a yolo_nano_amd.TestTimeAugmentation - every batch goes through its records() (yn_tta_infer) instead of the single
     forward.
-    rect=True: rectangular inference, as voc.evaluate - each batch on its own window of the letterboxed square."""
+    rect=True: rectangular inference, as voc.evaluate - each batch on its own window of the letterboxed square.
+    sliced: a yolo_nano_amd.SlicedInference, as voc.evaluate - every batch of frames goes through its records() (yn_slice_infer)."""
     from .model import ValTransforms
     if rect and test_aug is not None:
         raise ValueError("evaluate_coco: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
+    if sliced is not None and (rect or test_aug is not None):
+        raise ValueError("evaluate_coco: sliced inference runs its own tiles on square grids; sliced and %s exclude each other" % ("rect=True" if rect else "test_aug"))
     size = int(model.input_size)
     try:
-        return _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms)
+        return _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms, sliced)
     finally:
         if rect:
             model.set_grid(size)
 
 
-def _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms):
+def _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms, sliced=None):
     from .voc import _rect_batch
     ev = None
     for s in range(0, len(images), batch):
         chunk = images[s:s + batch]
+        if sliced is not None:
+            h = sliced.device_handle(model, len(chunk))
+            if ev is None:
+                ev = COCOEval(model.num_classes, handle=h)
+            rec, off, geoms = sliced.records(chunk, model)      # (its own range fallback; boxes in the frame, identity geometry)
+            ev.add(rec, off, geoms, image_ids[s:s + batch], annotations[s:s + batch], handle=h)
+            continue
         h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
         if ev is None:
             ev = COCOEval(model.num_classes, handle=h)

@@ -9,6 +9,7 @@
 //   argmax_cand_kernel   :253-261 from caller-provided (all_local, all_conf)
 //   bucket / sort / matrix / resolve / compact : exact per-class greedy NMS (see the block comment below)
 #include "yn_device.h"
+#include "yn_prep.h"
 
 namespace ynk {
 
@@ -2624,64 +2625,7 @@ void launch_nms_single(const float* dets, const float* scores, int n, float thre
 // into one image slot of the network input.  Thread = one output pixel (three channels); HBM-bound: 3 bytes read per resized
 // pixel (4 taps from L1/L2), 12 bytes written.  mode: 0 copy, 1 exact 2:1 reduction (2x2 box), 2 linear.
 // -------------------------------------------------------------------------------------------------
-struct PrepArgs {
-    const unsigned char* img; int h0, w0;       // source
-    int rw, rh, left, top, side, mode;          // resized extent, placement inside the side x side square
-    float mean[3], std[3];                      // BGR order, as the reference passes them
-    float* out;                                 // [3][side][side], channel 0 = R
-};
-
-// the pixel at (rx, ry) of the resized extent's frame (outside [0, rw) x [0, rh): pad) -> element i of the three output planes
-__device__ __forceinline__ void preprocess_at(const PrepArgs& a, int ry, int rx, size_t plane, int i)
-{
-    float v[3];
-    if (ry >= 0 && ry < a.rh && rx >= 0 && rx < a.rw) {
-        int u[3];
-        if (a.mode == 0) {
-            const unsigned char* p = a.img + ((size_t)ry * a.w0 + rx) * 3;
-            u[0] = p[0]; u[1] = p[1]; u[2] = p[2];
-        } else if (a.mode == 1) {
-            const unsigned char* p = a.img + ((size_t)(2 * ry) * a.w0 + 2 * rx) * 3;
-            const unsigned char* q = p + (size_t)a.w0 * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = (p[c] + p[3 + c] + q[c] + q[3 + c] + 2) >> 2;
-        } else {
-            // resizeGeneric_ (ksize 2): fx = (float)((dx + 0.5) * scale - 0.5), scale = 1 / (dsize / ssize) in double
-            const double scx = 1.0 / ((double)a.rw / (double)a.w0), scy = 1.0 / ((double)a.rh / (double)a.h0);
-            float fx = (float)(((double)rx + 0.5) * scx - 0.5), fy = (float)(((double)ry + 0.5) * scy - 0.5);
-            int sx = (int)floorf(fx), sy = (int)floorf(fy);
-            fx -= (float)sx; fy -= (float)sy;
-            if (sx < 0) { fx = 0.0f; sx = 0; }
-            if (sx >= a.w0 - 1) { fx = 0.0f; sx = a.w0 - 1; }
-            const int a0 = __float2int_rn((1.0f - fx) * 2048.0f), a1 = __float2int_rn(fx * 2048.0f);   // cvRound -> short
-            const int b0 = __float2int_rn((1.0f - fy) * 2048.0f), b1 = __float2int_rn(fy * 2048.0f);
-            const int sx1 = min(sx + 1, a.w0 - 1);
-            const int r0 = min(max(sy, 0), a.h0 - 1), r1 = min(max(sy + 1, 0), a.h0 - 1);
-            const unsigned char* p0 = a.img + (size_t)r0 * a.w0 * 3;
-            const unsigned char* p1 = a.img + (size_t)r1 * a.w0 * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int s0 = p0[sx * 3 + c] * a0 + p0[sx1 * 3 + c] * a1;          // HResizeLinear (scale 2048)
-                const int s1 = p1[sx * 3 + c] * a0 + p1[sx1 * 3 + c] * a1;
-                const int r = (((b0 * (s0 >> 4)) >> 16) + ((b1 * (s1 >> 4)) >> 16) + 2) >> 2;   // VResizeLinear 8u
-                u[c] = min(max(r, 0), 255);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = (float)u[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = a.mean[c] * 255.0f;                     // Resize.mean = [v * 255 for v in mean]
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float t = v[c] / 255.0f;                                                   // Normalize: image /= 255.; -= mean; /= std
-        t = t - a.mean[c];
-        t = t / a.std[c];
-        a.out[(size_t)(2 - c) * plane + i] = t;                                    // ToTensor: BGR -> RGB, HWC -> CHW
-    }
-}
-
+// PrepArgs, preprocess_at: yn_prep.h (shared with kernels_slice.hip)
 __device__ __forceinline__ void preprocess_pixel(const PrepArgs& a, int i)
 {
     if (i >= a.side * a.side) return;
@@ -2699,8 +2643,8 @@ __global__ __launch_bounds__(256) void preprocess_batch_kernel(PrepBatchArgs b)
 {
     const PrepImg& d = b.im[blockIdx.y];
     PrepArgs a;
-    a.img = d.img; a.h0 = d.h0; a.w0 = d.w0; a.rw = d.rw; a.rh = d.rh; a.left = d.left; a.top = d.top; a.side = b.side;
-    a.mode = (d.rw == d.w0 && d.rh == d.h0) ? 0 : ((d.w0 == 2 * d.rw && d.h0 == 2 * d.rh) ? 1 : 2);
+    a.img = d.img; a.h0 = d.h0; a.w0 = d.w0; a.pitch = d.w0; a.rw = d.rw; a.rh = d.rh; a.left = d.left; a.top = d.top; a.side = b.side;
+    a.mode = prep_mode(d.h0, d.w0, d.rw, d.rh);
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.mean[c] = b.mean[c]; a.std[c] = b.std[c]; }
     a.out = b.out + (size_t)blockIdx.y * 3 * b.side * b.side;
@@ -2714,8 +2658,8 @@ __global__ __launch_bounds__(256) void preprocess_batch_rect_kernel(PrepRectArgs
 {
     const PrepImg& d = b.im[blockIdx.y];
     PrepArgs a;
-    a.img = d.img; a.h0 = d.h0; a.w0 = d.w0; a.rw = d.rw; a.rh = d.rh; a.left = d.left; a.top = d.top; a.side = 0;
-    a.mode = (d.rw == d.w0 && d.rh == d.h0) ? 0 : ((d.w0 == 2 * d.rw && d.h0 == 2 * d.rh) ? 1 : 2);
+    a.img = d.img; a.h0 = d.h0; a.w0 = d.w0; a.pitch = d.w0; a.rw = d.rw; a.rh = d.rh; a.left = d.left; a.top = d.top; a.side = 0;
+    a.mode = prep_mode(d.h0, d.w0, d.rw, d.rh);
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.mean[c] = b.mean[c]; a.std[c] = b.std[c]; }
     const size_t plane = (size_t)b.win_w * b.win_h;
@@ -2763,9 +2707,9 @@ void launch_preprocess(const unsigned char* img, int h0, int w0, int rw, int rh,
                        const float* mean, const float* stdv, float* out, hipStream_t s)
 {
     PrepArgs a;
-    a.img = img; a.h0 = h0; a.w0 = w0; a.rw = rw; a.rh = rh; a.left = left; a.top = top; a.side = side; a.out = out;
+    a.img = img; a.h0 = h0; a.w0 = w0; a.pitch = w0; a.rw = rw; a.rh = rh; a.left = left; a.top = top; a.side = side; a.out = out;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = stdv[c]; }
-    a.mode = (rw == w0 && rh == h0) ? 0 : ((w0 == 2 * rw && h0 == 2 * rh) ? 1 : 2);
+    a.mode = prep_mode(h0, w0, rw, rh);
     const int n = side * side;
     hipLaunchKernelGGL(preprocess_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
 }

@@ -89,6 +89,24 @@ struct yn_tta {
     hipStream_t last_stream = nullptr;
 };
 
+// sliced inference (kernels_slice.hip): the merge lists and the result are allocated once, for max_frames frames; the tile batch and yn_infer's
+// outputs of one chunk follow the handle's grid and max_batch on the first yn_slice_infer that needs them
+struct yn_slice {
+    int device = 0, max_frames = 0, cap = 0, A = 0, C = 0;
+    ynk::DevBuf<float> x;                                            // one chunk of tiles [max_batch][3][side][side] (yn_slice_infer)
+    ynk::DevBuf<float> fb, fs; ynk::DevBuf<int32_t> fc, fcount;      // yn_infer's outputs for it: [max_batch][N]
+    ynk::DevBuf<float> lb, ls; ynk::DevBuf<int32_t> lc;              // the merge lists [max_frames][cap]
+    ynk::DevBuf<int32_t> state;                                      // [SLICE_STATE + max_frames]: flags + cursors (slice_append_kernel)
+    ynk::DevBuf<int32_t> tstart;                                     // [T] of the current table
+    ynk::DevBuf<float> mb, ms; ynk::DevBuf<int32_t> mc, mcount;      // the merge's kept rows [max_frames][cap]
+    ynk::DevBuf<float> rec; ynk::DevBuf<int32_t> offsets;            // yn_pack_detections layout: [max_frames * cap][6], [max_frames + 1]
+    std::vector<int32_t> state_host;                                 // the one read-back of yn_slice_merge
+    int lists_F = -1, lists_T = 0, next_t = 0;                       // the table being appended: its frames (-1: none), tiles, the tile the next chunk starts at
+    int last_F = -1;                                                 // frames of the last successful yn_slice_merge, -1: none
+    int total = -1;                                                  // offsets[last_F], read on the first yn_slice_result that asks for it
+    hipStream_t last_stream = nullptr;
+};
+
 struct yn_handle {
     yn_config cfg;
     hipStream_t stream = nullptr;
@@ -2656,6 +2674,41 @@ int yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap)
     YN_EVAL_CALL(ynk::draw_prims(d->st, h->stream, host, cap, err));
 }
 
+// The tail yn_tta_infer and yn_slice_merge share: B merge lists [B][cap] of an object (members state / state_host, lb ls lc, mb ms mc mcount, rec,
+// offsets, cap, C; state = MERGE_STATE flag words, then the B list sizes) -> ONE read-back (sizes, overflow flag, range mark), per-class NMS in
+// yn_nms_merge's arithmetic (never DIoU), yn_pack_detections into rec / offsets.  `unit` names a list's owner in the overflow message;
+// *lists_valid (when given) is set to B once the lists have been read, before any refusal.
+static_assert(TTA_STATE == SLICE_STATE, "merge_lists reads both objects' state words");
+constexpr int MERGE_STATE = TTA_STATE;
+extern "C++" {      // (a template cannot have C linkage)
+template <class Obj>
+static int merge_lists(yn_handle* h, Obj* o, const char* who, const char* unit, int B, float nms_thresh, int* lists_valid)
+{
+    int32_t* st = o->state_host.data();
+    HIPCHK(h, hipMemcpyAsync(st, o->state, (MERGE_STATE + B) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (lists_valid) *lists_valid = B;
+    if (st[2] || range_pending(h, who)) {
+        fail(h, "%s: a forward split an activation >= 65504 (split-f16 range): nothing is delivered - call yn_range_status to acknowledge, "
+                "then yn_exact_f32(h, 1) and run again", who);
+        return YN_STATUS_RANGE;
+    }
+    if (st[0]) {
+        int worst = 0;
+        for (int b = 0; b < B; ++b) if (st[MERGE_STATE + b] > o->cap) { worst = b; break; }
+        return fail(h, "%s: the merge list of %s %d needs %d rows, list_capacity is %d (the largest list of the batch needs %d)", who, unit, worst,
+                    st[MERGE_STATE + worst], o->cap, st[1]);
+    }
+    if (ensure_post(h, B, o->cap, o->C)) return 1;
+    NmsWork wk = h->nms;
+    wk.ovf = nullptr; wk.ovf_host = nullptr;
+    launch_nms_pipeline(o->lb, o->ls, o->lc, B, o->cap, o->C, nms_thresh, 0, wk, o->mb, o->ms, o->mc, nullptr, o->mcount, h->stream);
+    launch_pack(o->mb, o->ms, o->mc, o->mcount, B, o->cap, o->rec, o->offsets, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+
 // ---- test-time augmentation for whole batches (kernels_tta.hip; utils/misc.py:90-148) ----------------------------------------------
 int yn_resize_batch(yn_handle* h, const float* x_dev, int B, int S0, int s, int flip_pairs, float* out_dev)
 {
@@ -2766,28 +2819,7 @@ int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, flo
                           t->fstart, h->stream);
         HIPCHK(h, hipGetLastError());
     }
-    // the one read-back: flags + list sizes
-    int32_t* st = t->state_host.data();
-    HIPCHK(h, hipMemcpyAsync(st, t->state, (TTA_STATE + B) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    t->lists_B = B;
-    if (st[2] || range_pending(h, "yn_tta_infer")) {
-        fail(h, "yn_tta_infer: a forward split an activation >= 65504 (split-f16 range): nothing is delivered - call yn_range_status to acknowledge, "
-                "then yn_exact_f32(h, 1) and run again");
-        return YN_STATUS_RANGE;
-    }
-    if (st[0]) {
-        int worst = 0;
-        for (int b = 0; b < B; ++b) if (st[TTA_STATE + b] > t->cap) { worst = b; break; }
-        return fail(h, "yn_tta_infer: the merge list of image %d needs %d rows, list_capacity is %d (the largest list of the batch needs %d)", worst,
-                    st[TTA_STATE + worst], t->cap, st[1]);
-    }
-    if (ensure_post(h, B, t->cap, t->C)) return 1;
-    NmsWork wk = h->nms;
-    wk.ovf = nullptr; wk.ovf_host = nullptr;
-    launch_nms_pipeline(t->lb, t->ls, t->lc, B, t->cap, t->C, nms_thresh, 0, wk, t->mb, t->ms, t->mc, nullptr, t->mcount, h->stream);
-    launch_pack(t->mb, t->ms, t->mc, t->mcount, B, t->cap, t->rec, t->offsets, h->stream);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = merge_lists(h, t, "yn_tta_infer", "image", B, nms_thresh, &t->lists_B)) return rc;
     t->last_B = B;
     return 0;
 }
@@ -2828,6 +2860,231 @@ int yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_ho
     if (forward_start_host)
         for (size_t f = 0; f < forwards; ++f)
             HIPCHK(h, hipMemcpyAsync(forward_start_host + f * B, t->fstart + f * t->max_batch, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- sliced inference: tiles of large frames on the device, merged per frame (kernels_slice.hip) ------------------------------
+namespace {
+
+// the checks every entry makes on rows t0 .. t0 + n - 1 of a tile table before anything is launched; F < 0: the caller holds no frame count
+int slice_check(yn_handle* h, const char* who, int F, const uint8_t* const* frames, const int32_t* shapes, const int32_t* tiles, int t0, int n, int side)
+{
+    for (int t = t0; t < t0 + n; ++t) {
+        const int32_t* r = tiles + (size_t)t * SLICE_ROW;
+        if (r[0] < 0 || (F >= 0 && r[0] >= F)) return fail(h, "%s: tile %d names frame %d of %d", who, t, r[0], F < 0 ? 0 : F);
+        const int h0 = shapes[2 * r[0]], w0 = shapes[2 * r[0] + 1];
+        if (h0 < 1 || w0 < 1 || h0 > 16384 || w0 > 16384) return fail(h, "%s: tile %d: frame %d is %d x %d (sides 1..16384)", who, t, r[0], h0, w0);
+        if (frames && !frames[r[0]]) return fail(h, "%s: tile %d: frame %d is a null pointer", who, t, r[0]);
+        if (r[3] <= 0 || r[4] <= 0) return fail(h, "%s: tile %d has the non-positive extent %d x %d", who, t, r[4], r[3]);
+        if (r[1] < 0 || r[2] < 0 || r[1] > w0 - r[3] || r[2] > h0 - r[4])
+            return fail(h, "%s: tile %d, %d x %d at (%d, %d), lies outside its %d x %d frame", who, t, r[4], r[3], r[1], r[2], h0, w0);
+        if (r[5] <= 0 || r[6] <= 0 || r[7] < 0 || r[8] < 0 || r[7] > side - r[5] || r[8] > side - r[6])
+            return fail(h, "%s: tile %d has a bad letterbox geometry (%d x %d at (%d, %d) in %d)", who, t, r[6], r[5], r[7], r[8], side);
+    }
+    return 0;
+}
+
+int slice_object(yn_handle* h, const yn_slice* s, const char* who, int F)
+{
+    if (!s) return fail(h, "%s: null object", who);
+    if (s->device != h->cfg.device || s->A != h->cfg.num_anchors || s->C != h->cfg.num_classes)
+        return fail(h, "%s: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", who, s->device, s->A, s->C, h->cfg.device,
+                    h->cfg.num_anchors, h->cfg.num_classes);
+    if (F < 0 || F > s->max_frames) return fail(h, "%s: %d frames, the object's max_frames is %d", who, F, s->max_frames);
+    return 0;
+}
+
+// a new table of T tiles over F frames: empty lists
+int slice_clear(yn_handle* h, yn_slice* s, int F, int T)
+{
+    s->last_F = -1; s->lists_F = -1; s->total = -1; s->last_stream = h->stream;
+    HIPCHK(h, s->tstart.reserve((size_t)(T > 0 ? T : 1), 256));
+    HIPCHK(h, hipMemsetAsync(s->state, 0, (SLICE_STATE + F) * sizeof(int32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(s->tstart, 0, (size_t)(T > 0 ? T : 1) * sizeof(int32_t), h->stream));
+    if (F > 0) HIPCHK(h, hipMemsetAsync(s->lc, 0xFF, (size_t)F * s->cap * sizeof(int32_t), h->stream));      // class -1: not a candidate (bucket_kernel)
+    s->lists_F = F; s->lists_T = T; s->next_t = 0;
+    return 0;
+}
+
+}  // namespace
+
+void yn_slice_destroy(yn_slice* s)
+{
+    if (!s) return;
+    int prev = -1;
+    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != s->device && hipSetDevice(s->device) == hipSuccess;
+    (void)hipDeviceSynchronize();
+    delete s;
+    if (moved) (void)hipSetDevice(prev);
+}
+
+int yn_slice_create(yn_handle* h, int max_frames, int list_capacity, yn_slice** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_slice_create: null argument");
+    *out = nullptr;
+    if (max_frames < 1 || max_frames > 4096) return fail(h, "yn_slice_create: max_frames %d outside 1..4096", max_frames);
+    if (list_capacity < 1 || list_capacity > nms_max_segment())
+        return fail(h, "yn_slice_create: list_capacity %d outside 1..%d (the largest list the merge's NMS takes)", list_capacity, nms_max_segment());
+    yn_slice* s = new yn_slice();
+    s->device = h->cfg.device; s->max_frames = max_frames; s->cap = list_capacity;
+    s->A = h->cfg.num_anchors; s->C = h->cfg.num_classes;
+    s->state_host.resize(SLICE_STATE + max_frames);
+    const size_t lN = (size_t)max_frames * s->cap;
+    size_t failed = 0;                                  // bytes of the first allocation that failed
+    auto take = [&](auto& buf, size_t n) { if (!failed && buf.reserve(n)) failed = n * sizeof(buf[0]); };
+    take(s->lb, lN * 4); take(s->ls, lN); take(s->lc, lN);
+    take(s->state, (size_t)SLICE_STATE + max_frames);
+    take(s->mb, lN * 4); take(s->ms, lN); take(s->mc, lN); take(s->mcount, (size_t)max_frames);
+    take(s->rec, lN * 6); take(s->offsets, (size_t)max_frames + 1);
+    if (failed) {
+        (void)hipGetLastError();
+        yn_slice_destroy(s);
+        return fail(h, "yn_slice_create: out of device memory (%zu bytes for %d frames, %d rows per list)", failed, max_frames, list_capacity);
+    }
+    // the lists' unused rows are never candidates (class -1, set per table), but the NMS kernels may load them: finite values once
+    if (hipMemsetAsync(s->lb, 0, lN * 4 * sizeof(float), h->stream) != hipSuccess || hipMemsetAsync(s->ls, 0, lN * sizeof(float), h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+        yn_slice_destroy(s);
+        return fail(h, "yn_slice_create: clearing the merge lists failed");
+    }
+    *out = s;
+    return 0;
+}
+
+int yn_slice_preprocess(yn_handle* h, int T, const uint8_t* const* frames, const int32_t* shapes, const int32_t* tiles, int side, const float* mean,
+                        const float* stdv, float* x)
+{
+    YN_ENTER(h);
+    if (T == 0) return 0;                                   // no tiles is not an error
+    if (T < 0 || !frames || !shapes || !tiles || !x || !mean || !stdv) return fail(h, "yn_slice_preprocess: null pointer or negative tile count");
+    if (side <= 0 || side > 16384) return fail(h, "yn_slice_preprocess: side %d outside 1..16384", side);
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f)) return fail(h, "yn_slice_preprocess: std must be positive");
+    if (slice_check(h, "yn_slice_preprocess", -1, frames, shapes, tiles, 0, T, side)) return 1;
+    launch_slice_tiles(T, frames, shapes, tiles, side, mean, stdv, x, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int yn_slice_append(yn_handle* h, yn_slice* s, int F, const int32_t* shapes, int T, const int32_t* tiles, int t0, int n, const float* out_boxes,
+                    const float* out_scores, const int32_t* out_cls, const int32_t* count, int N, float edge_margin)
+{
+    YN_ENTER(h);
+    if (slice_object(h, s, "yn_slice_append", F)) return 1;
+    if (need_square_grid(h, "yn_slice_append")) return 1;
+    if (T < 0 || t0 < 0 || n < 0 || t0 > T - n) return fail(h, "yn_slice_append: tiles %d .. %d of a table of %d", t0, t0 + n - 1, T);
+    if (n > 0 && (!shapes || !tiles || !out_boxes || !out_scores || !out_cls || !count)) return fail(h, "yn_slice_append: null pointer");
+    if (n > 0 && N < 1) return fail(h, "yn_slice_append: capacity %d per tile", N);
+    if (n > 0 && ((uintptr_t)out_boxes & 15)) return fail(h, "yn_slice_append: out_boxes_dev must be 16-byte aligned (a box is loaded as one float4)");
+    if (edge_margin != edge_margin) return fail(h, "yn_slice_append: edge_margin is not a number");
+    if (t0 != 0 && (s->lists_F != F || s->lists_T != T || s->next_t != t0))
+        return fail(h, "yn_slice_append: chunks go in table order - tile %d of %d over %d frames was expected next, got tile %d of %d over %d", s->next_t,
+                    s->lists_T, s->lists_F, t0, T, F);
+    if (slice_check(h, "yn_slice_append", F, nullptr, shapes, tiles, t0, n, h->grid.S)) return 1;
+    if (t0 == 0 && slice_clear(h, s, F, T)) return 1;       // the first chunk opens the table
+    s->last_F = -1; s->total = -1; s->last_stream = h->stream;
+    if (n > 0 && F > 0) {
+        launch_slice_append(F, shapes, tiles, t0, n, h->grid.S, out_boxes, out_scores, out_cls, count, N, s->cap, edge_margin, s->lb, s->ls, s->lc, s->state,
+                            s->tstart, h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
+    s->next_t = t0 + n;
+    return 0;
+}
+
+int yn_slice_merge(yn_handle* h, yn_slice* s, int F, float nms_thresh)
+{
+    YN_ENTER(h);
+    if (slice_object(h, s, "yn_slice_merge", F)) return 1;
+    s->last_F = -1; s->total = -1;
+    if (s->lists_F != F) return fail(h, "yn_slice_merge: the lists hold %d frames, not %d (yn_slice_append from tile 0 first)", s->lists_F, F);
+    s->last_stream = h->stream;
+    if (F == 0) {
+        HIPCHK(h, hipMemsetAsync(s->offsets, 0, sizeof(int32_t), h->stream));
+        s->last_F = 0; s->total = 0;
+        return 0;
+    }
+    if (int rc = merge_lists(h, s, "yn_slice_merge", "frame", F, nms_thresh, nullptr)) return rc;
+    s->last_F = F;
+    return 0;
+}
+
+int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frames, const int32_t* shapes, int T, const int32_t* tiles, const float* mean,
+                   const float* stdv, float nms_thresh, float edge_margin)
+{
+    YN_ENTER(h);
+    if (slice_object(h, s, "yn_slice_infer", F)) return 1;
+    if (need_square_grid(h, "yn_slice_infer")) return 1;    // (before anything of the object's is touched)
+    s->last_F = -1; s->total = -1;
+    if (T < 0) return fail(h, "yn_slice_infer: %d tiles", T);
+    if (F == 0 || T == 0) {                                 // nothing to run: empty lists, F empty results
+        if (slice_clear(h, s, F, 0)) return 1;
+        HIPCHK(h, hipMemsetAsync(s->offsets, 0, (size_t)(F + 1) * sizeof(int32_t), h->stream));
+        s->last_F = F; s->total = 0;
+        return 0;
+    }
+    if (!frames || !shapes || !tiles || !mean || !stdv) return fail(h, "yn_slice_infer: null pointer");
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] > 0.0f)) return fail(h, "yn_slice_infer: std must be positive");
+    if (edge_margin != edge_margin) return fail(h, "yn_slice_infer: edge_margin is not a number");
+    if (check_ready(h, 1)) return 1;
+    if (int rp = range_pending(h, "yn_slice_infer")) return rp;
+    const int side = h->grid.S, N = h->grid.N, mb = h->cfg.max_batch;
+    for (int f = 0; f < F; ++f)
+        if (!frames[f]) return fail(h, "yn_slice_infer: frame %d is a null pointer", f);
+    if (slice_check(h, "yn_slice_infer", F, frames, shapes, tiles, 0, T, side)) return 1;
+    const size_t fN = (size_t)mb * N;
+    if (s->x.cap() < (size_t)mb * 3 * side * side || s->fb.cap() < fN * 4) HIPCHK(h, hipStreamSynchronize(h->stream));      // a block in use goes
+    HIPCHK(h, s->x.reserve((size_t)mb * 3 * side * side));
+    HIPCHK(h, s->fb.reserve(fN * 4)); HIPCHK(h, s->fs.reserve(fN)); HIPCHK(h, s->fc.reserve(fN)); HIPCHK(h, s->fcount.reserve((size_t)mb));
+    for (int t0 = 0; t0 < T; t0 += mb) {
+        const int n = T - t0 < mb ? T - t0 : mb;
+        launch_slice_tiles(n, frames, shapes, tiles + (size_t)t0 * SLICE_ROW, side, mean, stdv, s->x, h->stream);
+        HIPCHK(h, hipGetLastError());
+        if (int rc = yn_infer(h, s->x, n, s->fb, s->fs, s->fc, nullptr, s->fcount)) return rc;
+        if (int rc = yn_slice_append(h, s, F, shapes, T, tiles, t0, n, s->fb, s->fs, s->fc, s->fcount, N, edge_margin)) return rc;
+    }
+    return yn_slice_merge(h, s, F, nms_thresh);
+}
+
+int yn_slice_result(yn_slice* s, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
+{
+    if (!s || s->last_F < 0) return 1;
+    if (rec_dev) *rec_dev = s->rec;
+    if (offsets_dev) *offsets_dev = s->offsets;
+    if (total) {
+        if (s->total < 0) {
+            int prev = -1;
+            const bool moved = hipGetDevice(&prev) == hipSuccess && prev != s->device && hipSetDevice(s->device) == hipSuccess;
+            int32_t v = 0;
+            const bool ok = hipMemcpyAsync(&v, s->offsets + s->last_F, sizeof(int32_t), hipMemcpyDeviceToHost, s->last_stream) == hipSuccess &&
+                            hipStreamSynchronize(s->last_stream) == hipSuccess;
+            if (moved) (void)hipSetDevice(prev);
+            if (!ok) return 1;
+            s->total = v;
+        }
+        *total = s->total;
+    }
+    return 0;
+}
+
+int yn_slice_lists(yn_handle* h, yn_slice* s, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host, int32_t* tile_start_host)
+{
+    YN_ENTER(h);
+    if (!s) return fail(h, "yn_slice_lists: null object");
+    if (s->lists_F < 0) return fail(h, "yn_slice_lists: no yn_slice_append has filled the lists");
+    const int F = s->lists_F;
+    const size_t lN = (size_t)F * s->cap;
+    if (F > 0) {
+        if (boxes_host) HIPCHK(h, hipMemcpyAsync(boxes_host, s->lb, lN * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (scores_host) HIPCHK(h, hipMemcpyAsync(scores_host, s->ls, lN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (cls_host) HIPCHK(h, hipMemcpyAsync(cls_host, s->lc, lN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        if (count_host) HIPCHK(h, hipMemcpyAsync(count_host, s->state + SLICE_STATE, F * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (tile_start_host && s->lists_T > 0)
+        HIPCHK(h, hipMemcpyAsync(tile_start_host, s->tstart, (size_t)s->lists_T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

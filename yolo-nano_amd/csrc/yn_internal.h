@@ -283,6 +283,18 @@ void launch_tta_resize(const float* x, int B, int S0, int s, int flip, float* ou
 void launch_tta_append(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, int flip, int cap,
                        int bstride, int fwd, float* lboxes, float* lscores, int32_t* lcls, int32_t* state, int32_t* fstart, hipStream_t st);
 
+// ---- sliced inference (kernels_slice.hip): the kernels behind yn_slice ----------------------------------------------------------------
+constexpr int SLICE_STATE = 4;                  // as TTA_STATE: overflow flag, needed size, range mark, pad, then the per-frame cursors
+constexpr int SLICE_ROW = 9;                    // int32 per row of the tile table: frame, x, y, tw, th, rw, rh, left, top
+constexpr int SLICE_CHUNK = 64;                 // tiles per launch (their descriptors travel by value in the kernel arguments)
+// tiles [T][SLICE_ROW] of frames[f] (uint8 [h0][w0][3], shapes[f] = {h0, w0}), read in place -> out [T][3][side][side]; all host arrays, checked by the caller
+void launch_slice_tiles(int T, const unsigned char* const* frames, const int* shapes, const int* tiles, int side, const float* mean,
+                        const float* stdv, float* out, hipStream_t st);
+// the kept rows of one yn_infer over tiles t0 .. t0 + n - 1, mapped into their frames and appended to the F merge lists [F][cap]
+void launch_slice_append(int F, const int* shapes, const int* tiles, int t0, int n, int side, const float* boxes, const float* scores, const int32_t* cls,
+                         const int32_t* count, int N, int cap, float margin, float* lboxes, float* lscores, int32_t* lcls, int32_t* state,
+                         int32_t* tstart, hipStream_t st);
+
 // ---- detections painted onto frames (kernels_draw.hip): the state behind yn_draw; 0 = ok, 1 = error (text in err) ---------------------
 struct DrawState;
 int  draw_create(int device, int C, const uint8_t* colors, const char* const* labels, const uint8_t* atlas, int gw, int gh, int thickness,

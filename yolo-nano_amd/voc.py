@@ -175,7 +175,7 @@ def _rect_batch(model, tf, chunk):
     return x, geoms
 
 
-def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None, rect=False):
+def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None, rect=False, sliced=None):
     """VOCAPIEvaluator.evaluate + do_python_eval for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3
     BGR arrays, `annotations` one int array [G][6] per image (gt_array).  Per batch: ValTransforms.batch -> yn_infer ->
     yn_pack_detections -> yn_eval_add; nothing comes back to the host but each batch's 4-byte record count.  -> (aps, mAP).
@@ -183,22 +183,33 @@ def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=
     per image on the device) instead of the single forward: the mAP eval.py's -tta flag promises (eval.py:132 builds the object,
     the evaluator never calls it).
     rect=True: rectangular inference - each batch runs on its own window of the letterboxed square (rect_window: the smallest one that
-    holds every frame's picture), the grid is set only when the window changes, and the model's square grid is back afterwards."""
+    holds every frame's picture), the grid is set only when the window changes, and the model's square grid is back afterwards.
+    sliced: a yolo_nano_amd.SlicedInference - every batch of frames goes through its records() (yn_slice_infer: overlapping tiles at native
+    resolution plus the whole frame, merged per frame on the device); the model's grid must be the tile (model.set_grid(tile))."""
     from .model import ValTransforms
     if rect and test_aug is not None:
         raise ValueError("evaluate: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
+    if sliced is not None and (rect or test_aug is not None):
+        raise ValueError("evaluate: sliced inference runs its own tiles on square grids; sliced and %s exclude each other" % ("rect=True" if rect else "test_aug"))
     size = int(model.input_size)
     try:
-        return _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms)
+        return _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms, sliced)
     finally:
         if rect:
             model.set_grid(size)
 
 
-def _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms):
+def _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms, sliced=None):
     ev = None
     for s in range(0, len(images), batch):
         chunk = images[s:s + batch]
+        if sliced is not None:
+            h = sliced.device_handle(model, len(chunk))
+            if ev is None:
+                ev = VOCEval(model.num_classes, ovthresh, handle=h)
+            rec, off, geoms = sliced.records(chunk, model)      # (its own range fallback; boxes in the frame, identity geometry)
+            ev.add(rec, off, geoms, annotations[s:s + batch], handle=h)
+            continue
         h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
         if ev is None:
             ev = VOCEval(model.num_classes, ovthresh, handle=h)
