@@ -1238,8 +1238,18 @@ void launch_conv3x3(const GemmArgs& a, hipStream_t s)
         if (tiles >= 256) {                                // N in one block column; channel halves, two workgroups per CU
             g_last_kernel = "conv3x3_split_kernel<3,2>";
             hipLaunchKernelGGL((conv3x3_split_kernel<3, 2>), dim3(xcd_grid(tiles), 1), dim3(256), conv3x3_split_lds(a.W, 3, 2), s, a);
-        } else if (tiles * 3 >= 256) {                     // N over three block columns (more, shorter workgroups).  (Three taps per step here: 38-41 us
-            g_last_kernel = "conv3x3_split_kernel<1,2>";    //  against 31 - the 12 KB of weight space cost the third workgroup per CU)
+        } else if (tiles * 3 >= 256) {                     // N over three block columns (more, shorter workgroups)
+            if (tiles * 2 >= 256) {
+                // A tile for at least every second CU (26x26 at bs 32: 169): one block column all the same.  The three columns stage every halo three times - alone
+                // they are 1.4 us ahead (27.8 against 29.3), but the chip is shared by four streams, and there a third of the workgroups and of the bytes
+                // through the L2 is worth +1.5 % of the default run (profiles/r09_ab_c3_tile96.txt).  Same K order as every form: same bits.
+                g_last_kernel = "conv3x3_split_kernel<3,2>";
+                hipLaunchKernelGGL((conv3x3_split_kernel<3, 2>), dim3(xcd_grid(tiles), 1), dim3(256), conv3x3_split_lds(a.W, 3, 2), s, a);
+                return;
+            }
+            // (Three taps per step here: 38-41 us against 31 - the 12 KB of weight space cost the third workgroup per CU.  On 96-pixel tiles, where three
+            //  still fit: 27.7 us against 28.6 alone, but 0.8 % LESS under four streams - DESIGN 14, r09)
+            g_last_kernel = "conv3x3_split_kernel<1,2>";
             hipLaunchKernelGGL((conv3x3_split_kernel<1, 2, 1>), dim3(xcd_grid(tiles), 3), dim3(256), conv3x3_split_lds(a.W, 1, 2, 1), s, a);
         } else if (conv3x3_split_lds(a.W, 1, 1, 9) <= 160 * 1024) {   // less than one workgroup per CU: latency-bound, all channels staged at once, nine taps per step
             g_last_kernel = "conv3x3_split_kernel<1,1,9>";
