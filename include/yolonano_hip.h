@@ -145,6 +145,38 @@ int  yn_nms_sweep(yn_handle* h, int enable);
 /* Testing aid: how many (image, class) segments of the LAST yn_infer / yn_postprocess call (B images, C classes) the sweep handled
  * (synchronises the handle's stream); -1 on a failed copy. */
 int  yn_nms_sweep_segments(yn_handle* h, int B, int C);
+/* Testing aid: the state the per-class NMS chain of the LAST yn_postprocess / yn_infer / yn_nms_merge call (B images, N candidates, C
+ * classes: they must be that call's, else an error) left in the handle's scratch, copied to HOST buffers (synchronises the handle's
+ * stream; any pointer may be NULL).  A normal call pays nothing for it: the plan is a host-side record of the decisions the launch function
+ * took anyway, everything else already sits in the scratch.  (A yn_infer that replays a captured graph launches nothing on the host: the
+ * plan is then the one recorded at the last capture or eager call - turn yn_use_graph off to inspect a yn_infer.)
+ *   plan[YN_NMS_PLAN_INTS]  the launch plan, indexed by YN_NMS_PLAN_*: which kernels ran (few-segments route, fused bucket + sort, chunked
+ *                           sort, merge, prefilter with its sliced ranks, sweep with its LDS form / slots / workgroups per segment, resolve
+ *                           as one launch or split, DIoU)
+ *   seg_count, seg_off [B][C]   boxes per class and the class's first position
+ *   bucket [B][N], sbox [B][N][4]   per class at seg_off: candidate ids by (score descending, id descending) and their boxes
+ *   seg_count2 [B][C], bucket2 [B][N], sbox2 [B][N][4], seg_sparse [B][C]   only where plan[YN_NMS_PLAN_PREFILTER] is set (else left
+ *                           untouched): the prefilter's survivors per class at seg_off, and 1 for the classes handed to the sweep
+ *   keep [B][N]             the kept flags by candidate id (what compact_kernel read) */
+#define YN_NMS_PLAN_B             0
+#define YN_NMS_PLAN_N             1
+#define YN_NMS_PLAN_C             2
+#define YN_NMS_PLAN_FEW           3
+#define YN_NMS_PLAN_FUSED         4
+#define YN_NMS_PLAN_CHUNKS        5
+#define YN_NMS_PLAN_MERGE         6
+#define YN_NMS_PLAN_PREFILTER     7
+#define YN_NMS_PLAN_PRE_RANKS     8
+#define YN_NMS_PLAN_SWEEP         9
+#define YN_NMS_PLAN_SWEEP_MAXN    10
+#define YN_NMS_PLAN_SWEEP_SLOTS   11
+#define YN_NMS_PLAN_SWEEP_SPLIT   12
+#define YN_NMS_PLAN_RESOLVE_ONE   13
+#define YN_NMS_PLAN_RESOLVE_SPLIT 14
+#define YN_NMS_PLAN_DIOU          15
+#define YN_NMS_PLAN_INTS          16
+int  yn_nms_stages(yn_handle* h, int B, int N, int C, int32_t* plan, int32_t* seg_count, int32_t* seg_off, int32_t* bucket, float* sbox,
+                   int32_t* seg_count2, int32_t* bucket2, float* sbox2, int32_t* seg_sparse, int32_t* keep);
 /* Per-layer tile autotuning of the pointwise-conv GEMM (default on): the first eager execution of a layer
  * shape times every instantiated tile configuration of the layer's family (split-f16 by default, f32-MFMA under yn_exact_f32) on
  * the handle's stream and caches the fastest.  All configurations of a family produce bit-identical results; disabling falls back

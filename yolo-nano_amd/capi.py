@@ -65,6 +65,7 @@ SIGNATURES = {
     "yn_nms_prefilter": (_i32, [_vp, _i32]),
     "yn_nms_sweep": (_i32, [_vp, _i32]),
     "yn_nms_sweep_segments": (_i32, [_vp, _i32, _i32]),
+    "yn_nms_stages": (_i32, [_vp, _i32, _i32, _i32] + [_vp] * 10),
     "yn_load_param": (_i32, [_vp, ctypes.c_char_p, _vp, _i64p, _i32]),
     "yn_load_param_dev": (_i32, [_vp, ctypes.c_char_p, _vp, _i64p, _i32]),
     "yn_fold_bn": (_i32, [_vp]),
@@ -423,6 +424,27 @@ class Handle:
     def nms_sweep_segments(self, B, C):
         """Testing aid: segments of the last NMS call (B images, C classes) that nms_sweep_kernel handled."""
         return int(self.lib.yn_nms_sweep_segments(self.h, int(B), int(C)))
+
+    # yn_nms_stages: plan[i] by name (YN_NMS_PLAN_* of the header, in order)
+    NMS_PLAN_FIELDS = ("B", "N", "C", "few", "fused", "chunks", "merge", "prefilter", "pre_ranks", "sweep", "sweep_maxn", "sweep_slots",
+                       "sweep_split", "resolve_one", "resolve_split", "diou")
+
+    def nms_stages(self, B, N, C):
+        """Testing aid: what the NMS chain of the last postprocess / infer / nms_merge call (B, N, C: that call's) left behind, as host
+        numpy arrays (yn_nms_stages; synchronises the stream) -> dict: plan (dict of ints by NMS_PLAN_FIELDS), seg_count / seg_off [B, C],
+        bucket [B, N] (sorted candidate ids per class at seg_off), sbox [B, N, 4], keep [B, N]; where plan["prefilter"] is set also
+        seg_count2 [B, C], bucket2 [B, N], sbox2 [B, N, 4], seg_sparse [B, C] (None otherwise)."""
+        B, N, C = int(B), int(N), int(C)
+        plan = np.zeros(len(self.NMS_PLAN_FIELDS), np.int32)
+        a = {"seg_count": np.zeros((B, C), np.int32), "seg_off": np.zeros((B, C), np.int32), "bucket": np.zeros((B, N), np.int32),
+             "sbox": np.zeros((B, N, 4), np.float32), "seg_count2": np.zeros((B, C), np.int32), "bucket2": np.zeros((B, N), np.int32),
+             "sbox2": np.zeros((B, N, 4), np.float32), "seg_sparse": np.zeros((B, C), np.int32), "keep": np.zeros((B, N), np.int32)}
+        self._ck(self.lib.yn_nms_stages(self.h, B, N, C, plan.ctypes.data, *[v.ctypes.data for v in a.values()]), "yn_nms_stages")
+        a["plan"] = dict(zip(self.NMS_PLAN_FIELDS, (int(v) for v in plan)))
+        if not a["plan"]["prefilter"]:
+            for k in ("seg_count2", "bucket2", "sbox2", "seg_sparse"):
+                a[k] = None
+        return a
 
     def down_fuse(self, on=True):
         """Main branch of the stride-2 unit of stage 2 as one kernel (default on; bit-identical outputs either way)."""

@@ -2482,9 +2482,11 @@ static void set_sort_attr()
 void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C,
                          float nms_thresh, int diou, const NmsWork& wk,
                          float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
-                         hipStream_t s, const NmsHook* hook)
+                         hipStream_t s, const NmsHook* hook, NmsPlan* plan)
 {
     set_sort_attr();
+    NmsPlan rec{};                                          // the decisions below, as they are taken (host ints only; copied out at the end)
+    rec.B = B; rec.N = N; rec.C = C; rec.diou = diou != 0;
     const int large_cap = wk.large_cap;
     auto mark = [&](const char* k) { if (hook && hook->fn) hook->fn(hook->ctx, k); };
     float4* sbox = reinterpret_cast<float4*>(wk.sbox);
@@ -2495,8 +2497,10 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     constexpr int few_n = 16384;
     const bool few = (long)B * C <= 256 && N <= few_n;
     const int32_t* seg_order = wk.seg_order;                // bucket_kernel's size ranking; the fused kernel does not produce one (few segments: nothing to order)
+    rec.few = few;
     if (few && wk.ctr) {
         seg_order = nullptr;
+        rec.fused = 1;
         static unsigned long long attr_bs = 0;
         if (attr_pending(attr_bs)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, YN_SORT_LARGE * 8);
         mark("bucket_sort_kernel");
@@ -2507,6 +2511,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
         hipLaunchKernelGGL(bucket_kernel, dim3(B), dim3(1024), 2 * C * sizeof(int32_t), s, cls, N, C, wk.seg_count, wk.seg_off, wk.tile_off, wk.bucket, wk.keep,
                            wk.large_list, large_cap, YN_SORT_SMALL, wk.seg_order);
         const bool chunks = !few && wk.large_list && (size_t)N <= wk.matrix_stride;
+        rec.chunks = chunks;
         mark(chunks ? "sort_chunk_kernel" : "sort_kernel");
         if (few) {
             // few segments (bs <= 3 at 80 classes): every one gets a 1024-thread / 128 KB-LDS workgroup, all resident at once - one launch
@@ -2520,6 +2525,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
                                N, C, (const int32_t*)wk.seg_order, (const int32_t*)wk.large_list, large_cap, M, wk.matrix_stride);
             if (N > YN_SORT_SMALL) {
                 mark("sort_merge_kernel");
+                rec.merge = 1;
                 hipLaunchKernelGGL(sort_merge_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, boxes, wk.seg_count, wk.seg_off, wk.bucket, sbox,
                                    N, C, (const int32_t*)wk.large_list, large_cap, (const u64*)M, wk.matrix_stride);
             }
@@ -2556,6 +2562,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
         hipLaunchKernelGGL(nms_prefilter_kernel, dim3(B, C + pre_ranks * YN_PRE_Z), dim3(64 * YN_PRE_W), 0, s, sbox, wk.seg_count, wk.seg_off, wk.bucket, N, C, nms_thresh, wk.keep,
                            reinterpret_cast<float4*>(wk.sbox2), wk.bucket2, wk.seg_count2, seg_order, wk.seg_sparse, reinterpret_cast<u64*>(wk.pre_sync), pre_ranks,
                            (const int32_t*)wk.large_list, large_cap, sweep ? sweep_slots : 0, sweep_maxn);
+        rec.prefilter = 1; rec.pre_ranks = pre_ranks;
         m_count = wk.seg_count2; m_toff = wk.tile_off2; m_ids = wk.bucket2; m_box = reinterpret_cast<const float4*>(wk.sbox2);
         mark("nms_tile_off_kernel");
         hipLaunchKernelGGL(nms_tile_off_kernel, dim3(B), dim3(64), 0, s, wk.seg_count2, C, wk.tile_off2, (const int32_t*)(sweep ? wk.seg_sparse : nullptr), sweep ? wk.work_off : nullptr);
@@ -2575,6 +2582,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
         // 8 -> 28.0 / 97.2 / 46.2 / 15.7 (every workgroup repeats the binning, ~13 k cycles)
         int sweep_split = (sweep_maxn * 20 <= 64 * 1024 ? 256 : 128) / (B > 0 ? B : 1);
         sweep_split = sweep_split < 2 ? 2 : (sweep_split > 8 ? 8 : sweep_split);
+        rec.sweep = 1; rec.sweep_maxn = sweep_maxn; rec.sweep_slots = sweep_slots; rec.sweep_split = sweep_split;
         static unsigned long long attr_sw = 0;
         if (attr_pending(attr_sw)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, YN_SWEEP_MAXN * 20);
         hipLaunchKernelGGL(nms_sweep_kernel, dim3(B, sweep_split, sweep_slots), dim3(1024), (size_t)sweep_maxn * 20, s, m_box, m_count, wk.seg_off, m_toff, N, C, nms_thresh,
@@ -2582,6 +2590,8 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     }
     mark("resolve_kernel");
     const bool split = N > YN_SORT_SMALL && wk.large_list && large_cap > 0;
+    rec.resolve_one = (long)B * C <= 256;
+    rec.resolve_split = !rec.resolve_one && split;
     if ((long)B * C <= 256) {
         // few segments (bs <= 3 at 80 classes): all of them on the 512-thread kernel in ONE launch — the short walks ride along with the long
         // ones instead of preceding them (one image: -20 us)
@@ -2595,6 +2605,7 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
     }
     mark("compact_kernel");
     hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(1024), 0, s, boxes, scores, cls, wk.keep, N, out_boxes, out_scores, out_cls, out_index, count, wk.ovf, wk.ovf_host);
+    if (plan) *plan = rec;
 }
 
 // scratch: ids[n] int32, sbox[n] float4, M[nms_matrix_words_per_image(n,1)] u64 — all provided by the handle

@@ -134,6 +134,7 @@ struct yn_handle {
     DevBuf<int32_t> nms_seg[10];          // seg_count, seg_off, tile_off, large_list, seg_count2, tile_off2, seg_order, seg_sparse, work_off, ctr
     DevBuf<unsigned long long> nms_matrix, nms_pre_sync;
     NmsWork nms{};                        // the view of that scratch launch_nms_pipeline takes, filled by ensure_post
+    NmsPlan nms_plan{};                   // launch_nms_pipeline's decisions in the last yn_postprocess / yn_infer / yn_nms_merge (yn_nms_stages; B = 0: none yet)
     DevBuf<float> heads_buf;              // the three raw head tensors, one block
     float* heads_int[3] = {nullptr, nullptr, nullptr};    // its split for the current grid (ensure_heads)
     float* fwd_only[3] = {nullptr, nullptr, nullptr};     // yn_train_forward: the training executors stop after the forward pass and copy the raw heads here
@@ -1484,6 +1485,33 @@ int yn_nms_sweep_segments(yn_handle* h, int B, int C)
     for (int32_t x : v) k += x == 1;
     return k;
 }
+int yn_nms_stages(yn_handle* h, int B, int N, int C, int32_t* plan, int32_t* seg_count, int32_t* seg_off, int32_t* bucket, float* sbox,
+                  int32_t* seg_count2, int32_t* bucket2, float* sbox2, int32_t* seg_sparse, int32_t* keep)
+{
+    YN_ENTER(h);
+    const NmsPlan& p = h->nms_plan;
+    if (B <= 0 || N <= 0 || C <= 0 || p.B != B || p.N != N || p.C != C)
+        return fail(h, "yn_nms_stages: (B, N, C) = (%d, %d, %d), the last NMS call had (%d, %d, %d)", B, N, C, p.B, p.N, p.C);
+    const size_t cand = (size_t)B * N, seg = (size_t)B * C;
+    if (cand > h->nms_bucket.cap() || cand > h->nms_keep.cap() || cand * 4 > h->nms_sbox.cap() || cand > h->nms_bucket2.cap() || cand * 4 > h->nms_sbox2.cap() ||
+        seg > h->nms_seg[0].cap() || !h->nms.seg_count)
+        return fail(h, "yn_nms_stages: the handle holds no NMS scratch of that size");
+    if (plan) {
+        const int32_t v[YN_NMS_PLAN_INTS] = {p.B, p.N, p.C, p.few, p.fused, p.chunks, p.merge, p.prefilter, p.pre_ranks, p.sweep, p.sweep_maxn, p.sweep_slots,
+                                             p.sweep_split, p.resolve_one, p.resolve_split, p.diou};
+        for (int i = 0; i < YN_NMS_PLAN_INTS; ++i) plan[i] = v[i];
+    }
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        if (dst) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    };
+    if (get(seg_count, h->nms.seg_count, seg * 4) || get(seg_off, h->nms.seg_off, seg * 4) || get(bucket, h->nms.bucket, cand * 4) ||
+        get(sbox, h->nms.sbox, cand * 16) || get(keep, h->nms.keep, cand * 4)) return 1;
+    if (p.prefilter && (get(seg_count2, h->nms.seg_count2, seg * 4) || get(bucket2, h->nms.bucket2, cand * 4) || get(sbox2, h->nms.sbox2, cand * 16) ||
+                        get(seg_sparse, h->nms.seg_sparse, seg * 4))) return 1;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
 int yn_nms_sweep(yn_handle* h, int enable)
 {
     if (!h) return 1;
@@ -1827,7 +1855,7 @@ int yn_postprocess(yn_handle* h, const float* all_local, const float* all_conf, 
     if (ensure_post(h, B, N, C)) return 1;
     launch_argmax_cand(all_local, all_conf, B, N, C, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->stream);
     launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, N, C, h->cfg.nms_thresh, h->cfg.diou_nms, h->nms,
-                        out_boxes, out_scores, out_cls, out_index, count, h->stream);
+                        out_boxes, out_scores, out_cls, out_index, count, h->stream, nullptr, &h->nms_plan);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1957,7 +1985,7 @@ int yn_nms_merge(yn_handle* h, const float* boxes, const float* scores, const in
     if (n < 0 || num_classes <= 0 || !count) return fail(h, "yn_nms_merge: bad arguments");
     if (n == 0) { HIPCHK(h, hipMemsetAsync(count, 0, sizeof(int32_t), h->stream)); return 0; }
     if (ensure_post(h, 1, n, num_classes)) return 1;
-    launch_nms_pipeline(boxes, scores, cls, 1, n, num_classes, nms_thresh, diou, h->nms, out_boxes, out_scores, out_cls, out_index, count, h->stream);
+    launch_nms_pipeline(boxes, scores, cls, 1, n, num_classes, nms_thresh, diou, h->nms, out_boxes, out_scores, out_cls, out_index, count, h->stream, nullptr, &h->nms_plan);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1999,7 +2027,7 @@ int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* o
             wk.ovf = exact(h) ? nullptr : h->range_flags + 1;         // the network's range flag rides out with the counts (compact_kernel)
             wk.ovf_host = exact(h) ? nullptr : h->range_host_dev;     // ... and into the handle's pinned word (range_pending)
             launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, g.N, g.C, h->cfg.nms_thresh, h->cfg.diou_nms, wk,
-                                out_boxes, out_scores, out_cls, out_index, count, h->stream, h->profiling ? &hook : nullptr);
+                                out_boxes, out_scores, out_cls, out_index, count, h->stream, h->profiling ? &hook : nullptr, &h->nms_plan);
             delete ctx.cur;
         }
         HIPCHK(h, hipGetLastError());

@@ -230,10 +230,26 @@ size_t nms_pre_sync_words(int B, int N);
 int nms_max_segment();                      // largest per-class segment resolve_segment() can hold (its removed-mask lives in LDS)
 // optional per-kernel hook of launch_nms_pipeline: called with the kernel's name right before each launch (profiling brackets)
 struct NmsHook { void (*fn)(void* ctx, const char* kernel); void* ctx; };
+// optional host-side record of launch_nms_pipeline's decisions (plain ints, filled as they are taken: no device work, no launch) - the testing
+// aid behind yn_nms_stages.  Order = YN_NMS_PLAN_* of the C header.
+struct NmsPlan {
+    int B, N, C;
+    int few;                                    // B * C <= 256 and N <= 16 384
+    int fused;                                  // bucket_sort_kernel (bucket + sort in one launch)
+    int chunks;                                 // sort_chunk_kernel
+    int merge;                                  // sort_merge_kernel launched
+    int prefilter;                              // nms_prefilter_kernel + nms_tile_off_kernel launched
+    int pre_ranks;                              // sliced ranks per image (0 without the prefilter)
+    int sweep;                                  // nms_sweep_kernel launched; the next three are 0 without it
+    int sweep_maxn, sweep_slots, sweep_split;
+    int resolve_one;                            // every segment on resolve_large_kernel, one launch
+    int resolve_split;                          // resolve_kernel + resolve_large_kernel on the large list
+    int diou;
+};
 void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C,
                          float nms_thresh, int diou, const NmsWork& wk,
                          float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
-                         hipStream_t s, const NmsHook* hook = nullptr);
+                         hipStream_t s, const NmsHook* hook = nullptr, NmsPlan* plan = nullptr);
 void launch_pack(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, float* rec, int32_t* offsets, hipStream_t s);
 
 // ---- VOC mAP (kernels_eval.hip): the state behind yn_eval; 0 = ok, 1 = error (text in err), 2 = range mark (eval_add only) --------
