@@ -478,9 +478,9 @@ void yn_tta_destroy(yn_tta* t);
 /* x_dev float32 [B][3][S0][S0].  Per scale s, ascending: one resize (+ mirror) launch, yn_set_grid(s), ONE yn_infer over the 2B (B
  * without flip) images on the handle's own path and thresholds, one append of every image's kept rows to its merge list - plain rows
  * copied, mirrored rows with x1' = 1.0f - x2, x2' = 1.0f - x1 (:126).  List order is the reference's concatenation order: scale by
- * scale, plain before mirrored, ascending candidate order inside a forward.  Then ONE read-back (list sizes, overflow flag, range
- * mark), per-class NMS of the B lists (nms_thresh; the reference uses 0.4; never DIoU) and yn_pack_detections into the object's
- * record buffer.  The grid that was set before the call is restored, also on failure.
+ * scale, plain before mirrored, ascending candidate order inside a forward.  Then the merge of the B lists, the one yn_slice_merge
+ * documents below (nms_thresh; the reference uses 0.4): yn_tta and yn_slice hold the same merge lists, state words and result
+ * (DESIGN.md 28 describes them once).  The grid that was set before the call is restored, also on failure.
  * Needs a handle created with max_batch >= 2B (B without flip), refused by name otherwise.  A forward that left the split-f16 range
  * returns YN_STATUS_RANGE and delivers nothing (acknowledge with yn_range_status, yn_exact_f32(h, 1), run again).  A list that would
  * pass list_capacity fails, naming the first such image and the rows it needed; nothing is written past a list.  B == 0 is an empty

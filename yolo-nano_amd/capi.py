@@ -217,6 +217,18 @@ class YnRangeError(YnError):
     valid.  Call range_status() (clears the flag), switch the handle to exact_f32(True) and run again - YOLONano does this by itself."""
 
 
+def records_to_host(rec, offsets):
+    """(rec [>= total, 6], offsets [B+1]) in yn_pack_detections' layout (device tensors; offsets may already be a host array) -> list of B
+    (bboxes [K,4] f32, scores [K] f32, cls_inds [K] i64) numpy triples, fresh and writable: two device-to-host copies."""
+    off = offsets if isinstance(offsets, np.ndarray) else offsets.cpu().numpy()
+    host = rec[: int(off[-1])].cpu().numpy()
+    res = []
+    for b in range(len(off) - 1):
+        r = host[off[b]:off[b + 1]]
+        res.append((r[:, :4].copy(), r[:, 4].copy(), r[:, 5].astype(np.int64)))
+    return res
+
+
 def load_library():
     """dlopen the in-tree HIP library and type every entry point.  Raises if it is not built."""
     global _lib
@@ -612,12 +624,7 @@ class Handle:
         except YnRangeError:
             self.range_status()                                 # the exception IS the report: acknowledge, so that the flag does not poison later calls
             raise
-        host = rec[: int(off[-1])].cpu().numpy()
-        res = []
-        for b in range(len(off) - 1):
-            r = host[off[b]:off[b + 1]]
-            res.append((r[:, :4].copy(), r[:, 4].copy(), r[:, 5].astype(np.int64)))
-        return res
+        return records_to_host(rec, off)
 
     # ---- training loss
     def loss(self, conf, cls, txtytwth, target, grads=True, out=None):
@@ -1257,33 +1264,57 @@ class _DeviceView:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
-class Tta:
-    """One yn_tta: test-time augmentation for whole batches.  Thin, 1:1 with the C ABI; `handle` gives the device, the anchors per cell
-    and the class count, and is the default handle of infer()."""
-
-    def __init__(self, handle, scales, flip=True, max_batch=1, list_capacity=8192):
-        self.lib = handle.lib
-        self.handle = handle
-        self.scales = [int(s) for s in scales]
-        self.flip, self.max_batch, self.list_capacity = bool(flip), int(max_batch), int(list_capacity)
-        self.forwards = len(self.scales) * (2 if self.flip else 1)
-        arr = (ctypes.c_int32 * max(len(self.scales), 1))(*self.scales)
-        t = _vp()
-        handle._ck(self.lib.yn_tta_create(handle.h, ctypes.cast(arr, _vp), len(self.scales), int(self.flip), self.max_batch, self.list_capacity,
-                                          ctypes.byref(t)), "yn_tta_create")
-        self.t = t
-        self.B = None
+class _MergeObject:
+    """What Tta and Slice share: the object's lifetime, the (rec, offsets) views of its result and the host arrays of its merge lists.  A subclass
+    names its C functions (_destroy, _result) and sets .obj, .units (its max_batch / max_frames) and .n (the units of the result, None: no
+    result)."""
 
     def close(self):
-        if getattr(self, "t", None):
-            self.lib.yn_tta_destroy(self.t)
-            self.t = None
+        if getattr(self, "obj", None):
+            getattr(self.lib, self._destroy)(self.obj)
+            self.obj = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    def _result_views(self, total, hint):
+        if self.n is None:
+            raise YnError("%s: no result (%s first)" % (self._result, hint))
+        rec, off, n = _vp(), _vp(), _i32(0)
+        if getattr(self.lib, self._result)(self.obj, ctypes.byref(rec), ctypes.byref(off), ctypes.byref(n) if total else None):
+            raise YnError("%s: no result" % self._result)
+        dev = self.handle.device
+        r = torch.as_tensor(_DeviceView(rec.value, (self.units * self.list_capacity, 6), "<f4", self), device=dev)
+        o = torch.as_tensor(_DeviceView(off.value, (self.n + 1,), "<i4", self), device=dev)
+        return (r, o, int(n.value)) if total else (r, o)
+
+    def _list_arrays(self, n):
+        """boxes [n,cap,4], scores [n,cap], cls [n,cap] int32, count [max(n,1)] int32: zeroed host arrays for the lists' read-back"""
+        cap = self.list_capacity
+        return np.zeros((n, cap, 4), np.float32), np.zeros((n, cap), np.float32), np.zeros((n, cap), np.int32), np.zeros((max(n, 1),), np.int32)
+
+
+class Tta(_MergeObject):
+    """One yn_tta: test-time augmentation for whole batches.  Thin, 1:1 with the C ABI; `handle` gives the device, the anchors per cell
+    and the class count, and is the default handle of infer()."""
+    _destroy, _result = "yn_tta_destroy", "yn_tta_result"
+
+    def __init__(self, handle, scales, flip=True, max_batch=1, list_capacity=8192):
+        self.lib = handle.lib
+        self.handle = handle
+        self.scales = [int(s) for s in scales]
+        self.flip, self.max_batch, self.list_capacity = bool(flip), int(max_batch), int(list_capacity)
+        self.units = self.max_batch
+        self.forwards = len(self.scales) * (2 if self.flip else 1)
+        arr = (ctypes.c_int32 * max(len(self.scales), 1))(*self.scales)
+        t = _vp()
+        handle._ck(self.lib.yn_tta_create(handle.h, ctypes.cast(arr, _vp), len(self.scales), int(self.flip), self.max_batch, self.list_capacity,
+                                          ctypes.byref(t)), "yn_tta_create")
+        self.obj = t
+        self.n = None                                           # images of the result
 
     def infer(self, x, nms_thresh=0.4, handle=None):
         """x float32 [B,3,S0,S0] on the device: every scale (x flip) forward, the per-image merge and the pack (yn_tta_infer).  Raises
@@ -1291,63 +1322,42 @@ class Tta:
         h = self.handle if handle is None else handle
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3], tuple(x.shape)
         x = h._in(x)
-        self.B = None
-        h._ck(self.lib.yn_tta_infer(h.h, self.t, x.data_ptr(), int(x.shape[0]), int(x.shape[2]), float(nms_thresh)), "yn_tta_infer")
-        self.B = int(x.shape[0])
+        self.n = None
+        h._ck(self.lib.yn_tta_infer(h.h, self.obj, x.data_ptr(), int(x.shape[0]), int(x.shape[2]), float(nms_thresh)), "yn_tta_infer")
+        self.n = int(x.shape[0])
 
     def result(self, total=False):
         """(rec [max_batch * list_capacity, 6] float32, offsets [B+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
         object's buffers, valid until its next infer() (yn_tta_result).  total=True: also offsets[B] as an int (one read-back)."""
-        if self.B is None:
-            raise YnError("yn_tta_result: no result (infer() first)")
-        rec, off, n = _vp(), _vp(), _i32(0)
-        if self.lib.yn_tta_result(self.t, ctypes.byref(rec), ctypes.byref(off), ctypes.byref(n) if total else None):
-            raise YnError("yn_tta_result: no result")
-        dev = self.handle.device
-        r = torch.as_tensor(_DeviceView(rec.value, (self.max_batch * self.list_capacity, 6), "<f4", self), device=dev)
-        o = torch.as_tensor(_DeviceView(off.value, (self.B + 1,), "<i4", self), device=dev)
-        return (r, o, int(n.value)) if total else (r, o)
+        return self._result_views(total, "infer()")
 
     def forwards_to_host(self, B, handle=None):
         """Testing aid (yn_tta_forwards): the merge lists before the NMS -> (boxes [B,cap,4], scores [B,cap], cls [B,cap] int32,
         count [B] int32, forward_start [forwards,B] int32) numpy arrays."""
         h = self.handle if handle is None else handle
-        cap = self.list_capacity
-        boxes = np.zeros((B, cap, 4), np.float32)
-        scores = np.zeros((B, cap), np.float32)
-        cls = np.zeros((B, cap), np.int32)
-        count = np.zeros((B,), np.int32)
+        boxes, scores, cls, count = self._list_arrays(B)
         start = np.zeros((self.forwards, B), np.int32)
-        h._ck(self.lib.yn_tta_forwards(h.h, self.t, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
+        h._ck(self.lib.yn_tta_forwards(h.h, self.obj, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
               "yn_tta_forwards")
-        return boxes, scores, cls, count, start
+        return boxes, scores, cls, count[:B], start
 
 
-class Slice:
+class Slice(_MergeObject):
     """One yn_slice: sliced inference - tiles of large frames, merged per frame.  Thin, 1:1 with the C ABI; `handle` gives the device, the
     anchors per cell and the class count, and is the default handle of every call.  Frames are uint8 [h0,w0,3] CUDA tensors, `tiles` an
     int32 [T,9] table (slicing.tile_table)."""
+    _destroy, _result = "yn_slice_destroy", "yn_slice_result"
 
     def __init__(self, handle, max_frames=1, list_capacity=8192):
         self.lib = handle.lib
         self.handle = handle
         self.max_frames, self.list_capacity = int(max_frames), int(list_capacity)
+        self.units = self.max_frames
         s = _vp()
         handle._ck(self.lib.yn_slice_create(handle.h, self.max_frames, self.list_capacity, ctypes.byref(s)), "yn_slice_create")
-        self.s = s
-        self.F = None                                           # frames of the result
+        self.obj = s
+        self.n = None                                           # frames of the result
         self.lists = None                                       # (F, T) of the table being appended
-
-    def close(self):
-        if getattr(self, "s", None):
-            self.lib.yn_slice_destroy(self.s)
-            self.s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _frames(frames):
@@ -1389,8 +1399,8 @@ class Slice:
         tiles = self._table(tiles)
         assert boxes.is_contiguous() and scores.is_contiguous() and cls.is_contiguous() and count.is_contiguous()
         assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and cls.dtype == torch.int32 and count.dtype == torch.int32
-        self.F = None
-        h._ck(self.lib.yn_slice_append(h.h, self.s, len(shapes), shapes.ctypes.data, len(tiles), tiles.ctypes.data, int(t0), n, boxes.data_ptr(),
+        self.n = None
+        h._ck(self.lib.yn_slice_append(h.h, self.obj, len(shapes), shapes.ctypes.data, len(tiles), tiles.ctypes.data, int(t0), n, boxes.data_ptr(),
                                        scores.data_ptr(), cls.data_ptr(), count.data_ptr(), N, float(edge_margin)), "yn_slice_append")
         self.lists = (len(shapes), len(tiles))
 
@@ -1398,9 +1408,9 @@ class Slice:
         """Per-class NMS of the F lists + pack (yn_slice_merge).  Raises YnRangeError on the range mark, YnError naming the frame when a
         list would have passed list_capacity."""
         h = self.handle if handle is None else handle
-        self.F = None
-        h._ck(self.lib.yn_slice_merge(h.h, self.s, int(F), float(nms_thresh)), "yn_slice_merge")
-        self.F = int(F)
+        self.n = None
+        h._ck(self.lib.yn_slice_merge(h.h, self.obj, int(F), float(nms_thresh)), "yn_slice_merge")
+        self.n = int(F)
 
     def infer(self, frames, tiles, mean, std, nms_thresh=0.5, edge_margin=-1.0, handle=None):
         """Every tile through the handle's yn_infer in chunks of its max_batch, the per-frame merge and the pack (yn_slice_infer)."""
@@ -1409,24 +1419,16 @@ class Slice:
         ptrs, shapes = self._frames(frames)
         m = (ctypes.c_float * 3)(*[float(v) for v in mean])
         sd = (ctypes.c_float * 3)(*[float(v) for v in std])
-        self.F = None
+        self.n = None
         self.lists = (len(frames), len(tiles))
-        h._ck(self.lib.yn_slice_infer(h.h, self.s, len(frames), ctypes.cast(ptrs, _vp), shapes.ctypes.data, len(tiles), tiles.ctypes.data,
+        h._ck(self.lib.yn_slice_infer(h.h, self.obj, len(frames), ctypes.cast(ptrs, _vp), shapes.ctypes.data, len(tiles), tiles.ctypes.data,
                                       ctypes.cast(m, _vp), ctypes.cast(sd, _vp), float(nms_thresh), float(edge_margin)), "yn_slice_infer")
-        self.F = len(frames)
+        self.n = len(frames)
 
     def result(self, total=False):
         """(rec [max_frames * list_capacity, 6] float32, offsets [F+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
         object's buffers, valid until its next call (yn_slice_result).  total=True: also offsets[F] as an int (one read-back)."""
-        if self.F is None:
-            raise YnError("yn_slice_result: no result (infer() or merge() first)")
-        rec, off, n = _vp(), _vp(), _i32(0)
-        if self.lib.yn_slice_result(self.s, ctypes.byref(rec), ctypes.byref(off), ctypes.byref(n) if total else None):
-            raise YnError("yn_slice_result: no result")
-        dev = self.handle.device
-        r = torch.as_tensor(_DeviceView(rec.value, (self.max_frames * self.list_capacity, 6), "<f4", self), device=dev)
-        o = torch.as_tensor(_DeviceView(off.value, (self.F + 1,), "<i4", self), device=dev)
-        return (r, o, int(n.value)) if total else (r, o)
+        return self._result_views(total, "infer() or merge()")
 
     def lists_to_host(self, handle=None):
         """Testing aid (yn_slice_lists): the merge lists before the NMS -> (boxes [F,cap,4], scores [F,cap], cls [F,cap] int32,
@@ -1435,12 +1437,8 @@ class Slice:
         if self.lists is None:
             raise YnError("yn_slice_lists: no table (append() or infer() first)")
         F, T = self.lists
-        cap = self.list_capacity
-        boxes = np.zeros((F, cap, 4), np.float32)
-        scores = np.zeros((F, cap), np.float32)
-        cls = np.zeros((F, cap), np.int32)
-        count = np.zeros((max(F, 1),), np.int32)
+        boxes, scores, cls, count = self._list_arrays(F)
         start = np.zeros((max(T, 1),), np.int32)
-        h._ck(self.lib.yn_slice_lists(h.h, self.s, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
+        h._ck(self.lib.yn_slice_lists(h.h, self.obj, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
               "yn_slice_lists")
         return boxes, scores, cls, count[:F], start[:T]

@@ -199,52 +199,16 @@ def evaluate_coco(model, images, image_ids, annotations, batch=32, test_aug=None
     forward.
     rect=True: rectangular inference, as voc.evaluate - each batch on its own window of the letterboxed square.
     sliced: a yolo_nano_amd.SlicedInference, as voc.evaluate - every batch of frames goes through its records() (yn_slice_infer)."""
-    from .model import ValTransforms
-    if rect and test_aug is not None:
-        raise ValueError("evaluate_coco: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
-    if sliced is not None and (rect or test_aug is not None):
-        raise ValueError("evaluate_coco: sliced inference runs its own tiles on square grids; sliced and %s exclude each other" % ("rect=True" if rect else "test_aug"))
-    size = int(model.input_size)
-    try:
-        return _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms, sliced)
-    finally:
-        if rect:
-            model.set_grid(size)
+    from .voc import _run_batches
+    ev = None                                                   # made on the first chunk, on the handle its route has settled on
 
-
-def _evaluate_coco(model, images, image_ids, annotations, batch, test_aug, rect, size, ValTransforms, sliced=None):
-    from .voc import _rect_batch
-    ev = None
-    for s in range(0, len(images), batch):
-        chunk = images[s:s + batch]
-        if sliced is not None:
-            h = sliced.device_handle(model, len(chunk))
-            if ev is None:
-                ev = COCOEval(model.num_classes, handle=h)
-            rec, off, geoms = sliced.records(chunk, model)      # (its own range fallback; boxes in the frame, identity geometry)
-            ev.add(rec, off, geoms, image_ids[s:s + batch], annotations[s:s + batch], handle=h)
-            continue
-        h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
+    def consume(h, rec, off, geoms, lo, hi):
+        nonlocal ev
         if ev is None:
             ev = COCOEval(model.num_classes, handle=h)
-        tf = ValTransforms(size, handle=h)
-        if rect:
-            x, geoms = _rect_batch(model, tf, chunk)
-            h = model.handle(len(chunk))
-        else:
-            x = tf.batch(chunk)[0]
-            geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
-        ids, gts = image_ids[s:s + batch], annotations[s:s + batch]
-        if test_aug is not None:
-            rec, off = test_aug.records(x, model)               # (its own range fallback)
-            ev.add(rec, off, geoms, ids, gts, handle=h)
-            continue
+        ev.add(rec, off, geoms, image_ids[lo:hi], annotations[lo:hi], handle=h)
 
-        def finish(out, geoms=geoms, ids=ids, gts=gts, h=h):
-            rec, off = h.pack_detections(out)
-            ev.add(rec, off, geoms, ids, gts, handle=h)
-
-        model._infer_guarded(h, x, finish)                      # the split-f16 range mark: re-run under exact f32, nothing added
+    _run_batches("evaluate_coco", model, images, batch, test_aug, rect, sliced, consume)
     if ev is None:
         raise ValueError("evaluate_coco: no images")
     if ev.size()[0] == 0:

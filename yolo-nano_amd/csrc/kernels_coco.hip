@@ -408,11 +408,8 @@ int coco_create(int device, int C, int max_det, CocoState** out, std::string& er
 void coco_destroy(CocoState* e)
 {
     if (!e) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(e->device);
+    DeviceScope on(e->device);
     delete e;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int coco_reset(CocoState* e, hipStream_t s, std::string& err)

@@ -275,11 +275,8 @@ int draw_device(const DrawState* d) { return d->device; }
 void draw_destroy(DrawState* d)
 {
     if (!d) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(d->device);
+    DeviceScope on(d->device);
     delete d;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int draw_create(int device, int C, const uint8_t* colors, const char* const* labels, const uint8_t* atlas, int gw, int gh, int thickness,

@@ -362,11 +362,8 @@ int eval_create(int device, int C, double ovthresh, EvalState** out, std::string
 void eval_destroy(EvalState* e)
 {
     if (!e) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(e->device);
+    DeviceScope on(e->device);
     delete e;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int eval_reset(EvalState* e, hipStream_t s, std::string& err)

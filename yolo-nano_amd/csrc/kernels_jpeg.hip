@@ -276,15 +276,12 @@ int jpeg_device(const JpegState* j) { return j->device; }
 void jpeg_destroy(JpegState* j)
 {
     if (!j) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(j->device);
+    DeviceScope on(j->device);
     if (j->launched) (void)hipDeviceSynchronize();           // the kernels read the buffers below, the copies read the pinned slots
     for (JpegSlot& s : j->slot)
         for (hipEvent_t e : {s.e0, s.e1, s.e2})
             if (e) (void)hipEventDestroy(e);
     delete j;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int jpeg_create(int device, int max_batch, int64_t staging_bytes, int threads, JpegState** out, std::string& err)
@@ -666,9 +663,7 @@ int jpeg_entropy(JpegState* j, int mode, int subseq_bits, int max_rounds, std::s
     if (mode != 0 && mode != 1) { err = "yn_jpeg_entropy: mode " + std::to_string(mode) + " is neither 0 (host) nor 1 (device)"; return 1; }
     if (subseq_bits < 0 || subseq_bits % 32 || subseq_bits > (1 << 20)) { err = "yn_jpeg_entropy: subseq_bits " + std::to_string(subseq_bits) + " is no multiple of 32 in 32..2^20 (0: the default)"; return 1; }
     if (max_rounds < 0 || max_rounds > (1 << 24)) { err = "yn_jpeg_entropy: max_rounds " + std::to_string(max_rounds) + " outside 1..2^24 (0: the default)"; return 1; }
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(j->device);
+    DeviceScope on(j->device);
     if (j->launched) (void)hipDeviceSynchronize();           // nothing in flight reads what is released or replaced below
     j->huff.reset();
     int r = 0;
@@ -696,7 +691,6 @@ int jpeg_entropy(JpegState* j, int mode, int subseq_bits, int max_rounds, std::s
             j->huff = std::move(F);
         }
     }
-    if (prev >= 0) (void)hipSetDevice(prev);
     return r ? 1 : 0;
 }
 

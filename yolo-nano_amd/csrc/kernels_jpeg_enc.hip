@@ -591,15 +591,12 @@ int jpeg_enc_device(const JpegEncState* j) { return j->device; }
 void jpeg_enc_destroy(JpegEncState* j)
 {
     if (!j) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(j->device);
+    DeviceScope on(j->device);
     if (j->launched) (void)hipDeviceSynchronize();
     if (j->uploaded) (void)hipEventDestroy(j->uploaded);
     for (hipEvent_t e : j->ev)
         if (e) (void)hipEventDestroy(e);
     delete j;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int jpeg_enc_create(int device, int max_batch, int64_t stream_bytes, JpegEncState** out, std::string& err)

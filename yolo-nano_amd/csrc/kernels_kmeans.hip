@@ -461,11 +461,8 @@ int kmeans_create(int device, int64_t capacity, int max_k, KmeansState** out, st
 void kmeans_destroy(KmeansState* e)
 {
     if (!e) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(e->device);
+    DeviceScope on(e->device);
     delete e;
-    if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int kmeans_set_boxes(KmeansState* e, hipStream_t s, const double* wh_dev, int64_t n, std::string& err)

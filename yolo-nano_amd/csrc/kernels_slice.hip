@@ -78,9 +78,9 @@ struct SliceAppendArgs { SliceRow row[SLICE_CHUNK]; int n, t0, side; };
 
 // One workgroup per frame f: the tiles of the launch that belong to f, in table order; a tile's surviving rows keep their candidate order (a
 // block-wide ordered compaction per 256 candidates).  The forward's outputs are yn_infer's: boxes [n][N][4], scores / cls [n][N], count [n]
-// (negative: the range mark - none of that tile's rows is appended).  state = int32 [SLICE_STATE + max_frames]: [0] a list overflowed, [1] the
-// largest size a list would have needed, [2] a count carried the range mark, [SLICE_STATE + f] = the cursor of frame f.  tstart [T]: where
-// each tile's rows start in its frame's list.  Rows past `cap` are counted and not written.
+// (negative: the range mark - none of that tile's rows is appended).  state = int32 [MERGE_STATE + max_frames]: the merge lists' flag words and
+// the cursor of each frame (yn_internal.h).  tstart [T]: where each tile's rows start in its frame's list.  Rows past `cap` are counted and
+// not written.
 __global__ __launch_bounds__(256) void slice_append_kernel(SliceAppendArgs a, const float* __restrict__ boxes, const float* __restrict__ scores,
                                                            const int32_t* __restrict__ cls, const int32_t* __restrict__ count, int N, int cap, float margin,
                                                            float* __restrict__ lboxes, float* __restrict__ lscores, int32_t* __restrict__ lcls,
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void slice_append_kernel(SliceAppendArgs a, co
     __shared__ int wave_kept[4];
     const int f = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int cursor = state[SLICE_STATE + f];
+    int cursor = state[MERGE_STATE + f];
     bool bad = false;
     for (int j = 0; j < a.n; ++j) {
         const SliceRow& r = a.row[j];
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void slice_append_kernel(SliceAppendArgs a, co
         }
     }
     if (threadIdx.x == 0) {
-        state[SLICE_STATE + f] = cursor;
+        state[MERGE_STATE + f] = cursor;
         if (cursor > cap) { atomicOr(&state[0], 1); atomicMax(&state[1], cursor); }
         if (bad) atomicOr(&state[2], 1);
     }

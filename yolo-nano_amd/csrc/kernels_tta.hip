@@ -99,10 +99,9 @@ __global__ __launch_bounds__(256) void tta_resize_flip_kernel(const float* __res
 }
 
 // One workgroup per image b.  The forward's outputs are yn_infer's: boxes [nb][N][4], scores / cls [nb][N], count [nb] (negative: the
-// range mark, -1 - kept); with flip, image 2b is the plain and 2b + 1 the mirrored forward of b.  state = int32 [TTA_STATE + max_batch]:
-// [0] a list overflowed, [1] the largest size a list would have needed, [2] a count carried the range mark, [TTA_STATE + b] = the
-// cursor of image b.  fstart [forwards][bstride]: where each forward's rows start in each image's list.  Rows past `cap` are counted
-// and not written.
+// range mark, -1 - kept); with flip, image 2b is the plain and 2b + 1 the mirrored forward of b.  state = int32 [MERGE_STATE + max_batch]:
+// the merge lists' flag words and the cursor of each image (yn_internal.h).  fstart [forwards][bstride]: where each forward's rows start
+// in each image's list.  Rows past `cap` are counted and not written.
 __global__ __launch_bounds__(256) void tta_append_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const int32_t* __restrict__ cls,
                                                          const int32_t* __restrict__ count, int N, int flip, int cap, int bstride, int fwd,
                                                          float* __restrict__ lboxes, float* __restrict__ lscores, int32_t* __restrict__ lcls,
@@ -116,11 +115,11 @@ __global__ __launch_bounds__(256) void tta_append_kernel(const float* __restrict
     int n0 = c0 < 0 ? -1 - c0 : c0, n1 = c1 < 0 ? -1 - c1 : c1;
     n0 = n0 < N ? n0 : N;
     n1 = n1 < N ? n1 : N;
-    const int base = state[TTA_STATE + b];
+    const int base = state[MERGE_STATE + b];
     __syncthreads();                                        // every thread holds the cursor before thread 0 moves it
     if (threadIdx.x == 0) {
         const int end = base + n0 + n1;
-        state[TTA_STATE + b] = end;
+        state[MERGE_STATE + b] = end;
         fstart[(size_t)fwd * bstride + b] = base;
         if (flip) fstart[(size_t)(fwd + 1) * bstride + b] = base + n0;
         if (end > cap) { atomicOr(&state[0], 1); atomicMax(&state[1], end); }

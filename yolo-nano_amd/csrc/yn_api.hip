@@ -71,40 +71,66 @@ struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
 struct yn_jpeg { ynk::JpegState* st; };      // likewise (kernels_jpeg.hip)
 struct yn_jpeg_enc { ynk::JpegEncState* st; };      // likewise (kernels_jpeg_enc.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
+namespace {
+
+// DevBuf::reserve for the members of an object that is allocated in one go: after the first failure nothing more is tried
+struct Reserve {
+    int rc = 0;                                                      // the first failure's code (a hipError_t), 0: none
+    size_t failed = 0;                                               // its bytes
+    template <class Buf> void operator()(Buf& buf, size_t n) { if (!rc && (rc = buf.reserve(n)) != 0) failed = n * sizeof(buf[0]); }
+};
+
+// yn_infer's outputs for one forward of yn_tta / yn_slice
+struct InferOut {
+    ynk::DevBuf<float> fb, fs; ynk::DevBuf<int32_t> fc, fcount;      // [images][N] ([4] per box), [images]
+    void reserve(Reserve& take, size_t images, size_t N) { take(fb, images * N * 4); take(fs, images * N); take(fc, images * N); take(fcount, images); }
+};
+
+// What yn_tta and yn_slice end in ("The merge lists and the merge"): one merge list per unit (an image / a frame) that the object's append kernel fills, ONE read-back of
+// the state words (MERGE_STATE, yn_internal.h), per-class NMS, yn_pack_detections into rec / offsets.  Allocated once, for `units` lists of `cap` rows.
+struct MergeLists {
+    int device = 0, cap = 0, A = 0, C = 0, units = 0;                // units: the object's max_batch / max_frames
+    ynk::DevBuf<float> lb, ls; ynk::DevBuf<int32_t> lc;              // the merge lists [units][cap]
+    ynk::DevBuf<int32_t> state;                                      // [MERGE_STATE + units]: flags + cursors (the append kernels)
+    ynk::DevBuf<float> mb, ms; ynk::DevBuf<int32_t> mc, mcount;      // the merge's kept rows [units][cap]
+    ynk::DevBuf<float> rec; ynk::DevBuf<int32_t> offsets;            // yn_pack_detections layout: [units * cap][6], [units + 1]
+    std::vector<int32_t> state_host;                                 // the one read-back of merge()
+    int lists_n = -1;                                                // units whose merge lists are valid (copy_lists), -1: none
+    int last_n = -1;                                                 // units of the last successful merge() / empty_result(), -1: none
+    int total = -1;                                                  // offsets[last_n], read on the first result() that asks for it
+    hipStream_t last_stream = nullptr;
+
+    void reserve(Reserve& take, const yn_config& cfg, int units, int cap);
+    bool clear_once(hipStream_t s);
+    int belongs(yn_handle* h, const char* who) const;
+    void drop_result() { last_n = -1; total = -1; }
+    int open(yn_handle* h, int n);
+    int merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh);
+    int empty_result(yn_handle* h, int n);
+    int result(const float** rec_dev, const int32_t** offsets_dev, int32_t* total_out);
+    int copy_lists(yn_handle* h, int n, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host) const;
+};
+
+}  // namespace
+
 // test-time augmentation for whole batches (kernels_tta.hip): every buffer is allocated once, for max_batch images and the largest scale
 struct yn_tta {
-    int device = 0, flip = 1, max_batch = 0, cap = 0, A = 0, C = 0, Nmax = 0, smax = 0;
+    int flip = 1, max_batch = 0, Nmax = 0, smax = 0;
     std::vector<int> scales;
     ynk::DevBuf<float> xr;                                           // the resized (+ mirrored) batch [nb][3][smax][smax], nb = flip ? 2 max_batch : max_batch
-    ynk::DevBuf<float> fb, fs; ynk::DevBuf<int32_t> fc, fcount;      // yn_infer's outputs for one scale: [nb][Nmax]
-    ynk::DevBuf<float> lb, ls; ynk::DevBuf<int32_t> lc;              // the merge lists [max_batch][cap]
-    ynk::DevBuf<int32_t> state;                                      // [TTA_STATE + max_batch]: flags + cursors (tta_append_kernel)
+    InferOut f;                                                      // yn_infer's outputs for one scale: [nb][Nmax]
     ynk::DevBuf<int32_t> fstart;                                     // [forwards][max_batch]
-    ynk::DevBuf<float> mb, ms; ynk::DevBuf<int32_t> mc, mcount;      // the merge's kept rows [max_batch][cap]
-    ynk::DevBuf<float> rec; ynk::DevBuf<int32_t> offsets;            // yn_pack_detections layout: [max_batch * cap][6], [max_batch + 1]
-    std::vector<int32_t> state_host;                                 // the one read-back of yn_tta_infer
-    int last_B = -1;                                                 // images of the last successful yn_tta_infer, -1: none
-    int lists_B = -1;                                                // images whose merge lists are valid (yn_tta_forwards), -1: none
-    int total = -1;                                                  // offsets[last_B], read on the first yn_tta_result that asks for it
-    hipStream_t last_stream = nullptr;
+    MergeLists m;                                                    // one list per image
 };
 
 // sliced inference (kernels_slice.hip): the merge lists and the result are allocated once, for max_frames frames; the tile batch and yn_infer's
 // outputs of one chunk follow the handle's grid and max_batch on the first yn_slice_infer that needs them
 struct yn_slice {
-    int device = 0, max_frames = 0, cap = 0, A = 0, C = 0;
     ynk::DevBuf<float> x;                                            // one chunk of tiles [max_batch][3][side][side] (yn_slice_infer)
-    ynk::DevBuf<float> fb, fs; ynk::DevBuf<int32_t> fc, fcount;      // yn_infer's outputs for it: [max_batch][N]
-    ynk::DevBuf<float> lb, ls; ynk::DevBuf<int32_t> lc;              // the merge lists [max_frames][cap]
-    ynk::DevBuf<int32_t> state;                                      // [SLICE_STATE + max_frames]: flags + cursors (slice_append_kernel)
+    InferOut f;                                                      // yn_infer's outputs for it: [max_batch][N]
     ynk::DevBuf<int32_t> tstart;                                     // [T] of the current table
-    ynk::DevBuf<float> mb, ms; ynk::DevBuf<int32_t> mc, mcount;      // the merge's kept rows [max_frames][cap]
-    ynk::DevBuf<float> rec; ynk::DevBuf<int32_t> offsets;            // yn_pack_detections layout: [max_frames * cap][6], [max_frames + 1]
-    std::vector<int32_t> state_host;                                 // the one read-back of yn_slice_merge
-    int lists_F = -1, lists_T = 0, next_t = 0;                       // the table being appended: its frames (-1: none), tiles, the tile the next chunk starts at
-    int last_F = -1;                                                 // frames of the last successful yn_slice_merge, -1: none
-    int total = -1;                                                  // offsets[last_F], read on the first yn_slice_result that asks for it
-    hipStream_t last_stream = nullptr;
+    MergeLists m;                                                    // one list per frame; lists_n = the frames of the table being appended
+    int lists_T = 0, next_t = 0;                                     // that table's tiles, the tile the next chunk starts at
 };
 
 struct yn_handle {
@@ -207,10 +233,8 @@ int fail(yn_handle* h, const char* fmt, ...)
 
 // Every entry point runs with the handle's device current and restores the caller's afterwards (a handle created on
 // cuda:1 may be called while cuda:0 is current: its allocations, launches and hipFuncSetAttributes must not land there).
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(const yn_handle* h);
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+struct DevGuard : DeviceScope {
+    explicit DevGuard(const yn_handle* h) : DeviceScope(h->cfg.device) {}
 };
 #define YN_ENTER(h) if (!(h)) return 1; DevGuard dev_guard_(h)
 
@@ -219,12 +243,6 @@ struct DevGuard {
         hipError_t e_ = (hipError_t)(expr);                                                                 \
         if (e_ != hipSuccess) return fail((h), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-DevGuard::DevGuard(const yn_handle* h)
-{
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != h->cfg.device && hipSetDevice(h->cfg.device) == hipSuccess) prev = cur;
-}
 
 // the f32-MFMA family runs every GEMM-shaped conv when the caller asked for it or when the folded weights do not fit the split
 inline bool exact(const yn_handle* h) { return h->exact_f32 || h->range_fallback; }
@@ -2702,20 +2720,50 @@ int yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap)
     YN_EVAL_CALL(ynk::draw_prims(d->st, h->stream, host, cap, err));
 }
 
-// The tail yn_tta_infer and yn_slice_merge share: B merge lists [B][cap] of an object (members state / state_host, lb ls lc, mb ms mc mcount, rec,
-// offsets, cap, C; state = MERGE_STATE flag words, then the B list sizes) -> ONE read-back (sizes, overflow flag, range mark), per-class NMS in
-// yn_nms_merge's arithmetic (never DIoU), yn_pack_detections into rec / offsets.  `unit` names a list's owner in the overflow message;
-// *lists_valid (when given) is set to B once the lists have been read, before any refusal.
-static_assert(TTA_STATE == SLICE_STATE, "merge_lists reads both objects' state words");
-constexpr int MERGE_STATE = TTA_STATE;
-extern "C++" {      // (a template cannot have C linkage)
-template <class Obj>
-static int merge_lists(yn_handle* h, Obj* o, const char* who, const char* unit, int B, float nms_thresh, int* lists_valid)
+// ---- the merge lists of yn_tta and yn_slice (struct MergeLists above) ------------------------------------------------------------
+void MergeLists::reserve(Reserve& take, const yn_config& cfg, int units_, int cap_)
 {
-    int32_t* st = o->state_host.data();
-    HIPCHK(h, hipMemcpyAsync(st, o->state, (MERGE_STATE + B) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    device = cfg.device; A = cfg.num_anchors; C = cfg.num_classes; units = units_; cap = cap_;
+    state_host.resize(MERGE_STATE + units);
+    const size_t lN = (size_t)units * cap;
+    take(lb, lN * 4); take(ls, lN); take(lc, lN);
+    take(state, (size_t)MERGE_STATE + units);
+    take(mb, lN * 4); take(ms, lN); take(mc, lN); take(mcount, (size_t)units);
+    take(rec, lN * 6); take(offsets, (size_t)units + 1);
+}
+
+// the lists' unused rows are never candidates (class -1, set by open()), but the NMS kernels may load them: finite values once
+bool MergeLists::clear_once(hipStream_t s)
+{
+    const size_t lN = (size_t)units * cap;
+    return hipMemsetAsync(lb, 0, lN * 4 * sizeof(float), s) == hipSuccess && hipMemsetAsync(ls, 0, lN * sizeof(float), s) == hipSuccess &&
+           hipStreamSynchronize(s) == hipSuccess;
+}
+
+int MergeLists::belongs(yn_handle* h, const char* who) const
+{
+    if (device != h->cfg.device || A != h->cfg.num_anchors || C != h->cfg.num_classes)
+        return fail(h, "%s: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", who, device, A, C, h->cfg.device,
+                    h->cfg.num_anchors, h->cfg.num_classes);
+    return 0;
+}
+
+// n empty lists (lists_n is the caller's: the lists count as valid once they have been appended to)
+int MergeLists::open(yn_handle* h, int n)
+{
+    HIPCHK(h, hipMemsetAsync(state, 0, (MERGE_STATE + n) * sizeof(int32_t), h->stream));
+    if (n > 0) HIPCHK(h, hipMemsetAsync(lc, 0xFF, (size_t)n * cap * sizeof(int32_t), h->stream));      // class -1: not a candidate (bucket_kernel)
+    return 0;
+}
+
+// n filled lists -> ONE read-back (sizes, overflow flag, range mark), per-class NMS in yn_nms_merge's arithmetic (never DIoU), yn_pack_detections into
+// rec / offsets.  `unit` names a list's owner in the overflow message; lists_n is n once the lists have been read, before any refusal.
+int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh)
+{
+    int32_t* st = state_host.data();
+    HIPCHK(h, hipMemcpyAsync(st, state, (MERGE_STATE + n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (lists_valid) *lists_valid = B;
+    lists_n = n;
     if (st[2] || range_pending(h, who)) {
         fail(h, "%s: a forward split an activation >= 65504 (split-f16 range): nothing is delivered - call yn_range_status to acknowledge, "
                 "then yn_exact_f32(h, 1) and run again", who);
@@ -2723,19 +2771,57 @@ static int merge_lists(yn_handle* h, Obj* o, const char* who, const char* unit, 
     }
     if (st[0]) {
         int worst = 0;
-        for (int b = 0; b < B; ++b) if (st[MERGE_STATE + b] > o->cap) { worst = b; break; }
+        for (int b = 0; b < n; ++b) if (st[MERGE_STATE + b] > cap) { worst = b; break; }
         return fail(h, "%s: the merge list of %s %d needs %d rows, list_capacity is %d (the largest list of the batch needs %d)", who, unit, worst,
-                    st[MERGE_STATE + worst], o->cap, st[1]);
+                    st[MERGE_STATE + worst], cap, st[1]);
     }
-    if (ensure_post(h, B, o->cap, o->C)) return 1;
+    if (ensure_post(h, n, cap, C)) return 1;
     NmsWork wk = h->nms;
     wk.ovf = nullptr; wk.ovf_host = nullptr;
-    launch_nms_pipeline(o->lb, o->ls, o->lc, B, o->cap, o->C, nms_thresh, 0, wk, o->mb, o->ms, o->mc, nullptr, o->mcount, h->stream);
-    launch_pack(o->mb, o->ms, o->mc, o->mcount, B, o->cap, o->rec, o->offsets, h->stream);
+    launch_nms_pipeline(lb, ls, lc, n, cap, C, nms_thresh, 0, wk, mb, ms, mc, nullptr, mcount, h->stream);
+    launch_pack(mb, ms, mc, mcount, n, cap, rec, offsets, h->stream);
     HIPCHK(h, hipGetLastError());
+    last_n = n;
     return 0;
 }
-}  // extern "C++"
+
+// nothing to merge: n empty results (offsets[0 .. n] = 0)
+int MergeLists::empty_result(yn_handle* h, int n)
+{
+    HIPCHK(h, hipMemsetAsync(offsets, 0, (size_t)(n + 1) * sizeof(int32_t), h->stream));
+    last_n = n; lists_n = n; total = 0;
+    return 0;
+}
+
+int MergeLists::result(const float** rec_dev, const int32_t** offsets_dev, int32_t* total_out)
+{
+    if (last_n < 0) return 1;
+    if (rec_dev) *rec_dev = rec;
+    if (offsets_dev) *offsets_dev = offsets;
+    if (total_out) {
+        if (total < 0) {
+            DeviceScope on(device);
+            int32_t v = 0;
+            if (hipMemcpyAsync(&v, offsets + last_n, sizeof(int32_t), hipMemcpyDeviceToHost, last_stream) != hipSuccess ||
+                hipStreamSynchronize(last_stream) != hipSuccess)
+                return 1;
+            total = v;
+        }
+        *total_out = total;
+    }
+    return 0;
+}
+
+// the first n lists and their sizes to host arrays (null: skipped), enqueued on the handle's stream: the caller synchronises
+int MergeLists::copy_lists(yn_handle* h, int n, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host) const
+{
+    const size_t lN = (size_t)n * cap;
+    if (boxes_host) HIPCHK(h, hipMemcpyAsync(boxes_host, lb, lN * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) HIPCHK(h, hipMemcpyAsync(scores_host, ls, lN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (cls_host) HIPCHK(h, hipMemcpyAsync(cls_host, lc, lN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (count_host) HIPCHK(h, hipMemcpyAsync(count_host, state + MERGE_STATE, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
 
 // ---- test-time augmentation for whole batches (kernels_tta.hip; utils/misc.py:90-148) ----------------------------------------------
 int yn_resize_batch(yn_handle* h, const float* x_dev, int B, int S0, int s, int flip_pairs, float* out_dev)
@@ -2753,11 +2839,9 @@ int yn_resize_batch(yn_handle* h, const float* x_dev, int B, int S0, int s, int 
 void yn_tta_destroy(yn_tta* t)
 {
     if (!t) return;
-    int prev = -1;
-    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != t->device && hipSetDevice(t->device) == hipSuccess;
-    if (t->last_stream || t->lists_B >= 0) (void)hipDeviceSynchronize();
+    DeviceScope on(t->m.device);
+    if (t->m.last_stream || t->m.lists_n >= 0) (void)hipDeviceSynchronize();      // (an object no call has launched on has nothing in flight)
     delete t;
-    if (moved) (void)hipSetDevice(prev);
 }
 
 int yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip, int max_batch, int list_capacity, yn_tta** out)
@@ -2774,32 +2858,24 @@ int yn_tta_create(yn_handle* h, const int32_t* scales, int num_scales, int flip,
     if (list_capacity < 1 || list_capacity > nms_max_segment())
         return fail(h, "yn_tta_create: list_capacity %d outside 1..%d (the largest list the merge's NMS takes)", list_capacity, nms_max_segment());
     yn_tta* t = new yn_tta();
-    t->device = h->cfg.device; t->flip = flip != 0; t->max_batch = max_batch; t->cap = list_capacity;
-    t->A = h->cfg.num_anchors; t->C = h->cfg.num_classes;
+    t->flip = flip != 0; t->max_batch = max_batch;
     t->scales.assign(scales, scales + num_scales);
     t->smax = scales[num_scales - 1];
-    t->Nmax = t->A * ((t->smax / 8) * (t->smax / 8) + (t->smax / 16) * (t->smax / 16) + (t->smax / 32) * (t->smax / 32));
-    const size_t nb = (size_t)(t->flip ? 2 : 1) * max_batch, fN = nb * t->Nmax, lN = (size_t)max_batch * t->cap;
-    const size_t forwards = (size_t)(t->flip ? 2 : 1) * num_scales;
-    t->state_host.resize(TTA_STATE + max_batch);
-    size_t failed = 0;                                  // bytes of the first allocation that failed
-    auto take = [&](auto& buf, size_t n) { if (!failed && buf.reserve(n)) failed = n * sizeof(buf[0]); };
+    t->Nmax = h->cfg.num_anchors * ((t->smax / 8) * (t->smax / 8) + (t->smax / 16) * (t->smax / 16) + (t->smax / 32) * (t->smax / 32));
+    const size_t nb = (size_t)(t->flip ? 2 : 1) * max_batch, forwards = (size_t)(t->flip ? 2 : 1) * num_scales;
+    Reserve take;
     take(t->xr, nb * 3 * t->smax * t->smax);
-    take(t->fb, fN * 4); take(t->fs, fN); take(t->fc, fN); take(t->fcount, nb);
-    take(t->lb, lN * 4); take(t->ls, lN); take(t->lc, lN);
-    take(t->state, (size_t)TTA_STATE + max_batch); take(t->fstart, forwards * max_batch);
-    take(t->mb, lN * 4); take(t->ms, lN); take(t->mc, lN); take(t->mcount, (size_t)max_batch);
-    take(t->rec, lN * 6); take(t->offsets, (size_t)max_batch + 1);
-    if (failed) {
+    t->f.reserve(take, nb, (size_t)t->Nmax);
+    take(t->fstart, forwards * max_batch);
+    t->m.reserve(take, h->cfg, max_batch, list_capacity);
+    if (take.rc) {
         (void)hipGetLastError();
         const int smax = t->smax;
         yn_tta_destroy(t);
-        return fail(h, "yn_tta_create: out of device memory (%zu bytes for %d images, %d scales up to %d, %d rows per list)", failed, max_batch, num_scales,
-                    smax, list_capacity);
+        return fail(h, "yn_tta_create: out of device memory (%zu bytes for %d images, %d scales up to %d, %d rows per list)", take.failed, max_batch,
+                    num_scales, smax, list_capacity);
     }
-    // the lists' unused rows are never candidates (class -1, set per call), but the NMS kernels may load them: finite values once
-    if (hipMemsetAsync(t->lb, 0, lN * 4 * sizeof(float), h->stream) != hipSuccess || hipMemsetAsync(t->ls, 0, lN * sizeof(float), h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) {
+    if (!t->m.clear_once(h->stream)) {
         yn_tta_destroy(t);
         return fail(h, "yn_tta_create: clearing the merge lists failed");
     }
@@ -2812,29 +2888,22 @@ int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, flo
     YN_ENTER(h);
     if (!t) return fail(h, "yn_tta_infer: null object");
     if (need_square_grid(h, "yn_tta_infer")) return 1;      // (before anything of the object's is touched: the grid stays as it was found)
-    t->last_B = -1; t->lists_B = -1; t->total = -1;
-    if (t->device != h->cfg.device || t->A != h->cfg.num_anchors || t->C != h->cfg.num_classes)
-        return fail(h, "yn_tta_infer: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", t->device, t->A, t->C,
-                    h->cfg.device, h->cfg.num_anchors, h->cfg.num_classes);
+    MergeLists& m = t->m;
+    m.drop_result(); m.lists_n = -1;
+    if (m.belongs(h, "yn_tta_infer")) return 1;
     if (B < 0 || B > t->max_batch) return fail(h, "yn_tta_infer: %d images, the object's max_batch is %d", B, t->max_batch);
     const int nb = t->flip ? 2 * B : B;
     if (nb > h->cfg.max_batch)
         return fail(h, "yn_tta_infer: %d images%s need a handle with max_batch >= %d, this one has max_batch %d", B, t->flip ? " with their mirrors" : "", nb,
                     h->cfg.max_batch);
-    t->last_stream = h->stream;
-    if (B == 0) {
-        HIPCHK(h, hipMemsetAsync(t->offsets, 0, sizeof(int32_t), h->stream));
-        t->last_B = 0; t->lists_B = 0; t->total = 0;
-        return 0;
-    }
+    m.last_stream = h->stream;
+    if (B == 0) return m.empty_result(h, 0);
     if (!x_dev || S0 < 1 || S0 > 16384) return fail(h, "yn_tta_infer: bad input (side %d)", S0);
     if (check_ready(h, B)) return 1;
     if (int rp = range_pending(h, "yn_tta_infer")) return rp;
     const int S_prev = h->grid.S;
     struct Restore { yn_handle* h; int S; ~Restore() { if (h->grid.S != S) (void)yn_set_grid(h, S); } } restore{h, S_prev};      // the grid that was set before the call
-    const size_t lN = (size_t)B * t->cap;
-    HIPCHK(h, hipMemsetAsync(t->state, 0, (TTA_STATE + B) * sizeof(int32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(t->lc, 0xFF, lN * sizeof(int32_t), h->stream));      // class -1: not a candidate (bucket_kernel)
+    if (m.open(h, B)) return 1;
     for (size_t si = 0; si < t->scales.size(); ++si) {
         const int s = t->scales[si];
         launch_tta_resize(x_dev, B, S0, s, t->flip, t->xr, h->stream);
@@ -2842,49 +2911,28 @@ int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, flo
         if (yn_set_grid(h, s)) return 1;
         const int N = h->grid.N;
         if (N > t->Nmax) return fail(h, "yn_tta_infer: %d predictions at %d exceed the object's %d", N, s, t->Nmax);
-        if (int rc = yn_infer(h, t->xr, nb, t->fb, t->fs, t->fc, nullptr, t->fcount)) return rc;
-        launch_tta_append(t->fb, t->fs, t->fc, t->fcount, B, N, t->flip, t->cap, t->max_batch, (int)si * (t->flip ? 2 : 1), t->lb, t->ls, t->lc, t->state,
+        if (int rc = yn_infer(h, t->xr, nb, t->f.fb, t->f.fs, t->f.fc, nullptr, t->f.fcount)) return rc;
+        launch_tta_append(t->f.fb, t->f.fs, t->f.fc, t->f.fcount, B, N, t->flip, m.cap, t->max_batch, (int)si * (t->flip ? 2 : 1), m.lb, m.ls, m.lc, m.state,
                           t->fstart, h->stream);
         HIPCHK(h, hipGetLastError());
     }
-    if (int rc = merge_lists(h, t, "yn_tta_infer", "image", B, nms_thresh, &t->lists_B)) return rc;
-    t->last_B = B;
-    return 0;
+    return m.merge(h, "yn_tta_infer", "image", B, nms_thresh);
 }
 
 int yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
 {
-    if (!t || t->last_B < 0) return 1;
-    if (rec_dev) *rec_dev = t->rec;
-    if (offsets_dev) *offsets_dev = t->offsets;
-    if (total) {
-        if (t->total < 0) {
-            int prev = -1;
-            const bool moved = hipGetDevice(&prev) == hipSuccess && prev != t->device && hipSetDevice(t->device) == hipSuccess;
-            int32_t v = 0;
-            const bool ok = hipMemcpyAsync(&v, t->offsets + t->last_B, sizeof(int32_t), hipMemcpyDeviceToHost, t->last_stream) == hipSuccess &&
-                            hipStreamSynchronize(t->last_stream) == hipSuccess;
-            if (moved) (void)hipSetDevice(prev);
-            if (!ok) return 1;
-            t->total = v;
-        }
-        *total = t->total;
-    }
-    return 0;
+    return t ? t->m.result(rec_dev, offsets_dev, total) : 1;
 }
 
 int yn_tta_forwards(yn_handle* h, yn_tta* t, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host, int32_t* forward_start_host)
 {
     YN_ENTER(h);
     if (!t) return fail(h, "yn_tta_forwards: null object");
-    if (t->lists_B < 0) return fail(h, "yn_tta_forwards: no yn_tta_infer has filled the lists");
-    const int B = t->lists_B;
+    if (t->m.lists_n < 0) return fail(h, "yn_tta_forwards: no yn_tta_infer has filled the lists");
+    const int B = t->m.lists_n;
     if (B == 0) return 0;
-    const size_t lN = (size_t)B * t->cap, forwards = t->scales.size() * (t->flip ? 2 : 1);
-    if (boxes_host) HIPCHK(h, hipMemcpyAsync(boxes_host, t->lb, lN * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (scores_host) HIPCHK(h, hipMemcpyAsync(scores_host, t->ls, lN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (cls_host) HIPCHK(h, hipMemcpyAsync(cls_host, t->lc, lN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (count_host) HIPCHK(h, hipMemcpyAsync(count_host, t->state + TTA_STATE, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    const size_t forwards = t->scales.size() * (t->flip ? 2 : 1);
+    if (t->m.copy_lists(h, B, boxes_host, scores_host, cls_host, count_host)) return 1;
     if (forward_start_host)
         for (size_t f = 0; f < forwards; ++f)
             HIPCHK(h, hipMemcpyAsync(forward_start_host + f * B, t->fstart + f * t->max_batch, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -2916,22 +2964,20 @@ int slice_check(yn_handle* h, const char* who, int F, const uint8_t* const* fram
 int slice_object(yn_handle* h, const yn_slice* s, const char* who, int F)
 {
     if (!s) return fail(h, "%s: null object", who);
-    if (s->device != h->cfg.device || s->A != h->cfg.num_anchors || s->C != h->cfg.num_classes)
-        return fail(h, "%s: the object was made for device %d, %d anchors, %d classes; the handle has %d, %d, %d", who, s->device, s->A, s->C, h->cfg.device,
-                    h->cfg.num_anchors, h->cfg.num_classes);
-    if (F < 0 || F > s->max_frames) return fail(h, "%s: %d frames, the object's max_frames is %d", who, F, s->max_frames);
+    if (s->m.belongs(h, who)) return 1;
+    if (F < 0 || F > s->m.units) return fail(h, "%s: %d frames, the object's max_frames is %d", who, F, s->m.units);
     return 0;
 }
 
 // a new table of T tiles over F frames: empty lists
 int slice_clear(yn_handle* h, yn_slice* s, int F, int T)
 {
-    s->last_F = -1; s->lists_F = -1; s->total = -1; s->last_stream = h->stream;
+    MergeLists& m = s->m;
+    m.drop_result(); m.lists_n = -1; m.last_stream = h->stream;
     HIPCHK(h, s->tstart.reserve((size_t)(T > 0 ? T : 1), 256));
-    HIPCHK(h, hipMemsetAsync(s->state, 0, (SLICE_STATE + F) * sizeof(int32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(s->tstart, 0, (size_t)(T > 0 ? T : 1) * sizeof(int32_t), h->stream));
-    if (F > 0) HIPCHK(h, hipMemsetAsync(s->lc, 0xFF, (size_t)F * s->cap * sizeof(int32_t), h->stream));      // class -1: not a candidate (bucket_kernel)
-    s->lists_F = F; s->lists_T = T; s->next_t = 0;
+    if (m.open(h, F)) return 1;
+    m.lists_n = F; s->lists_T = T; s->next_t = 0;
     return 0;
 }
 
@@ -2940,11 +2986,9 @@ int slice_clear(yn_handle* h, yn_slice* s, int F, int T)
 void yn_slice_destroy(yn_slice* s)
 {
     if (!s) return;
-    int prev = -1;
-    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != s->device && hipSetDevice(s->device) == hipSuccess;
-    (void)hipDeviceSynchronize();
+    DeviceScope on(s->m.device);
+    (void)hipDeviceSynchronize();      // always: a yn_slice_infer that failed in its first forward has launched on x / f without leaving a mark in m
     delete s;
-    if (moved) (void)hipSetDevice(prev);
 }
 
 int yn_slice_create(yn_handle* h, int max_frames, int list_capacity, yn_slice** out)
@@ -2956,24 +3000,14 @@ int yn_slice_create(yn_handle* h, int max_frames, int list_capacity, yn_slice** 
     if (list_capacity < 1 || list_capacity > nms_max_segment())
         return fail(h, "yn_slice_create: list_capacity %d outside 1..%d (the largest list the merge's NMS takes)", list_capacity, nms_max_segment());
     yn_slice* s = new yn_slice();
-    s->device = h->cfg.device; s->max_frames = max_frames; s->cap = list_capacity;
-    s->A = h->cfg.num_anchors; s->C = h->cfg.num_classes;
-    s->state_host.resize(SLICE_STATE + max_frames);
-    const size_t lN = (size_t)max_frames * s->cap;
-    size_t failed = 0;                                  // bytes of the first allocation that failed
-    auto take = [&](auto& buf, size_t n) { if (!failed && buf.reserve(n)) failed = n * sizeof(buf[0]); };
-    take(s->lb, lN * 4); take(s->ls, lN); take(s->lc, lN);
-    take(s->state, (size_t)SLICE_STATE + max_frames);
-    take(s->mb, lN * 4); take(s->ms, lN); take(s->mc, lN); take(s->mcount, (size_t)max_frames);
-    take(s->rec, lN * 6); take(s->offsets, (size_t)max_frames + 1);
-    if (failed) {
+    Reserve take;
+    s->m.reserve(take, h->cfg, max_frames, list_capacity);
+    if (take.rc) {
         (void)hipGetLastError();
         yn_slice_destroy(s);
-        return fail(h, "yn_slice_create: out of device memory (%zu bytes for %d frames, %d rows per list)", failed, max_frames, list_capacity);
+        return fail(h, "yn_slice_create: out of device memory (%zu bytes for %d frames, %d rows per list)", take.failed, max_frames, list_capacity);
     }
-    // the lists' unused rows are never candidates (class -1, set per table), but the NMS kernels may load them: finite values once
-    if (hipMemsetAsync(s->lb, 0, lN * 4 * sizeof(float), h->stream) != hipSuccess || hipMemsetAsync(s->ls, 0, lN * sizeof(float), h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) {
+    if (!s->m.clear_once(h->stream)) {
         yn_slice_destroy(s);
         return fail(h, "yn_slice_create: clearing the merge lists failed");
     }
@@ -3007,14 +3041,15 @@ int yn_slice_append(yn_handle* h, yn_slice* s, int F, const int32_t* shapes, int
     if (n > 0 && N < 1) return fail(h, "yn_slice_append: capacity %d per tile", N);
     if (n > 0 && ((uintptr_t)out_boxes & 15)) return fail(h, "yn_slice_append: out_boxes_dev must be 16-byte aligned (a box is loaded as one float4)");
     if (edge_margin != edge_margin) return fail(h, "yn_slice_append: edge_margin is not a number");
-    if (t0 != 0 && (s->lists_F != F || s->lists_T != T || s->next_t != t0))
+    MergeLists& m = s->m;
+    if (t0 != 0 && (m.lists_n != F || s->lists_T != T || s->next_t != t0))
         return fail(h, "yn_slice_append: chunks go in table order - tile %d of %d over %d frames was expected next, got tile %d of %d over %d", s->next_t,
-                    s->lists_T, s->lists_F, t0, T, F);
+                    s->lists_T, m.lists_n, t0, T, F);
     if (slice_check(h, "yn_slice_append", F, nullptr, shapes, tiles, t0, n, h->grid.S)) return 1;
     if (t0 == 0 && slice_clear(h, s, F, T)) return 1;       // the first chunk opens the table
-    s->last_F = -1; s->total = -1; s->last_stream = h->stream;
+    m.drop_result(); m.last_stream = h->stream;
     if (n > 0 && F > 0) {
-        launch_slice_append(F, shapes, tiles, t0, n, h->grid.S, out_boxes, out_scores, out_cls, count, N, s->cap, edge_margin, s->lb, s->ls, s->lc, s->state,
+        launch_slice_append(F, shapes, tiles, t0, n, h->grid.S, out_boxes, out_scores, out_cls, count, N, m.cap, edge_margin, m.lb, m.ls, m.lc, m.state,
                             s->tstart, h->stream);
         HIPCHK(h, hipGetLastError());
     }
@@ -3026,17 +3061,12 @@ int yn_slice_merge(yn_handle* h, yn_slice* s, int F, float nms_thresh)
 {
     YN_ENTER(h);
     if (slice_object(h, s, "yn_slice_merge", F)) return 1;
-    s->last_F = -1; s->total = -1;
-    if (s->lists_F != F) return fail(h, "yn_slice_merge: the lists hold %d frames, not %d (yn_slice_append from tile 0 first)", s->lists_F, F);
-    s->last_stream = h->stream;
-    if (F == 0) {
-        HIPCHK(h, hipMemsetAsync(s->offsets, 0, sizeof(int32_t), h->stream));
-        s->last_F = 0; s->total = 0;
-        return 0;
-    }
-    if (int rc = merge_lists(h, s, "yn_slice_merge", "frame", F, nms_thresh, nullptr)) return rc;
-    s->last_F = F;
-    return 0;
+    MergeLists& m = s->m;
+    m.drop_result();
+    if (m.lists_n != F) return fail(h, "yn_slice_merge: the lists hold %d frames, not %d (yn_slice_append from tile 0 first)", m.lists_n, F);
+    m.last_stream = h->stream;
+    if (F == 0) return m.empty_result(h, 0);
+    return m.merge(h, "yn_slice_merge", "frame", F, nms_thresh);
 }
 
 int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frames, const int32_t* shapes, int T, const int32_t* tiles, const float* mean,
@@ -3045,13 +3075,11 @@ int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frame
     YN_ENTER(h);
     if (slice_object(h, s, "yn_slice_infer", F)) return 1;
     if (need_square_grid(h, "yn_slice_infer")) return 1;    // (before anything of the object's is touched)
-    s->last_F = -1; s->total = -1;
+    s->m.drop_result();
     if (T < 0) return fail(h, "yn_slice_infer: %d tiles", T);
     if (F == 0 || T == 0) {                                 // nothing to run: empty lists, F empty results
         if (slice_clear(h, s, F, 0)) return 1;
-        HIPCHK(h, hipMemsetAsync(s->offsets, 0, (size_t)(F + 1) * sizeof(int32_t), h->stream));
-        s->last_F = F; s->total = 0;
-        return 0;
+        return s->m.empty_result(h, F);
     }
     if (!frames || !shapes || !tiles || !mean || !stdv) return fail(h, "yn_slice_infer: null pointer");
     for (int c = 0; c < 3; ++c)
@@ -3063,54 +3091,38 @@ int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frame
     for (int f = 0; f < F; ++f)
         if (!frames[f]) return fail(h, "yn_slice_infer: frame %d is a null pointer", f);
     if (slice_check(h, "yn_slice_infer", F, frames, shapes, tiles, 0, T, side)) return 1;
-    const size_t fN = (size_t)mb * N;
-    if (s->x.cap() < (size_t)mb * 3 * side * side || s->fb.cap() < fN * 4) HIPCHK(h, hipStreamSynchronize(h->stream));      // a block in use goes
-    HIPCHK(h, s->x.reserve((size_t)mb * 3 * side * side));
-    HIPCHK(h, s->fb.reserve(fN * 4)); HIPCHK(h, s->fs.reserve(fN)); HIPCHK(h, s->fc.reserve(fN)); HIPCHK(h, s->fcount.reserve((size_t)mb));
+    InferOut& o = s->f;
+    if (s->x.cap() < (size_t)mb * 3 * side * side || o.fb.cap() < (size_t)mb * N * 4) HIPCHK(h, hipStreamSynchronize(h->stream));      // a block in use goes
+    Reserve take;
+    take(s->x, (size_t)mb * 3 * side * side);
+    o.reserve(take, (size_t)mb, (size_t)N);
+    if (take.rc) {
+        (void)hipGetLastError();
+        return fail(h, "yn_slice_infer: out of device memory (%zu bytes for %d tiles per forward at %d x %d): %s", take.failed, mb, side, side,
+                    hipGetErrorString((hipError_t)take.rc));
+    }
     for (int t0 = 0; t0 < T; t0 += mb) {
         const int n = T - t0 < mb ? T - t0 : mb;
         launch_slice_tiles(n, frames, shapes, tiles + (size_t)t0 * SLICE_ROW, side, mean, stdv, s->x, h->stream);
         HIPCHK(h, hipGetLastError());
-        if (int rc = yn_infer(h, s->x, n, s->fb, s->fs, s->fc, nullptr, s->fcount)) return rc;
-        if (int rc = yn_slice_append(h, s, F, shapes, T, tiles, t0, n, s->fb, s->fs, s->fc, s->fcount, N, edge_margin)) return rc;
+        if (int rc = yn_infer(h, s->x, n, o.fb, o.fs, o.fc, nullptr, o.fcount)) return rc;
+        if (int rc = yn_slice_append(h, s, F, shapes, T, tiles, t0, n, o.fb, o.fs, o.fc, o.fcount, N, edge_margin)) return rc;
     }
     return yn_slice_merge(h, s, F, nms_thresh);
 }
 
 int yn_slice_result(yn_slice* s, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
 {
-    if (!s || s->last_F < 0) return 1;
-    if (rec_dev) *rec_dev = s->rec;
-    if (offsets_dev) *offsets_dev = s->offsets;
-    if (total) {
-        if (s->total < 0) {
-            int prev = -1;
-            const bool moved = hipGetDevice(&prev) == hipSuccess && prev != s->device && hipSetDevice(s->device) == hipSuccess;
-            int32_t v = 0;
-            const bool ok = hipMemcpyAsync(&v, s->offsets + s->last_F, sizeof(int32_t), hipMemcpyDeviceToHost, s->last_stream) == hipSuccess &&
-                            hipStreamSynchronize(s->last_stream) == hipSuccess;
-            if (moved) (void)hipSetDevice(prev);
-            if (!ok) return 1;
-            s->total = v;
-        }
-        *total = s->total;
-    }
-    return 0;
+    return s ? s->m.result(rec_dev, offsets_dev, total) : 1;
 }
 
 int yn_slice_lists(yn_handle* h, yn_slice* s, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host, int32_t* tile_start_host)
 {
     YN_ENTER(h);
     if (!s) return fail(h, "yn_slice_lists: null object");
-    if (s->lists_F < 0) return fail(h, "yn_slice_lists: no yn_slice_append has filled the lists");
-    const int F = s->lists_F;
-    const size_t lN = (size_t)F * s->cap;
-    if (F > 0) {
-        if (boxes_host) HIPCHK(h, hipMemcpyAsync(boxes_host, s->lb, lN * 4 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (scores_host) HIPCHK(h, hipMemcpyAsync(scores_host, s->ls, lN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        if (cls_host) HIPCHK(h, hipMemcpyAsync(cls_host, s->lc, lN * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (count_host) HIPCHK(h, hipMemcpyAsync(count_host, s->state + SLICE_STATE, F * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    }
+    if (s->m.lists_n < 0) return fail(h, "yn_slice_lists: no yn_slice_append has filled the lists");
+    const int F = s->m.lists_n;
+    if (F > 0 && s->m.copy_lists(h, F, boxes_host, scores_host, cls_host, count_host)) return 1;
     if (tile_start_host && s->lists_T > 0)
         HIPCHK(h, hipMemcpyAsync(tile_start_host, s->tstart, (size_t)s->lists_T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

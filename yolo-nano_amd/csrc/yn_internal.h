@@ -291,16 +291,20 @@ void kmeans_stats(const KmeansState* e, int64_t* passes, int64_t* host_reads);
 void launch_nms_single(const float* dets, const float* scores, int n, float thresh, int diou,
                        int32_t* ids_scratch, float* sbox_scratch, void* matrix_scratch, int32_t* keep, int32_t* count, hipStream_t s);
 
+// ---- merge lists: what yn_tta and yn_slice append to (B lists [B][cap] of boxes / scores / classes) before their per-class NMS ---------------
+// state = int32 [MERGE_STATE + B]: [0] a list overflowed, [1] the largest size a list would have needed, [2] a count carried yn_infer's range
+// mark, [3] pad, [MERGE_STATE + b] = the cursor (size) of list b.  Written by tta_append_kernel / slice_append_kernel, read back once by
+// MergeLists::merge (yn_api.hip).
+constexpr int MERGE_STATE = 4;
+
 // ---- test-time augmentation (kernels_tta.hip): the kernels behind yn_tta / yn_resize_batch ------------------------------------------
-constexpr int TTA_STATE = 4;                    // int32 words in front of the per-image cursors: overflow flag, needed size, range mark, pad
 // x [B][3][S0][S0] -> out [flip ? 2B : B][3][s][s] (image 2b the resize, 2b + 1 its horizontal mirror)
 void launch_tta_resize(const float* x, int B, int S0, int s, int flip, float* out, hipStream_t st);
-// the kept rows of one yn_infer over (flip ? 2B : B) images, appended to the B merge lists [B][cap] at state[TTA_STATE + b]
+// the kept rows of one yn_infer over (flip ? 2B : B) images, appended to the B merge lists [B][cap] at state[MERGE_STATE + b]
 void launch_tta_append(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, int flip, int cap,
                        int bstride, int fwd, float* lboxes, float* lscores, int32_t* lcls, int32_t* state, int32_t* fstart, hipStream_t st);
 
 // ---- sliced inference (kernels_slice.hip): the kernels behind yn_slice ----------------------------------------------------------------
-constexpr int SLICE_STATE = 4;                  // as TTA_STATE: overflow flag, needed size, range mark, pad, then the per-frame cursors
 constexpr int SLICE_ROW = 9;                    // int32 per row of the tile table: frame, x, y, tw, th, rw, rh, left, top
 constexpr int SLICE_CHUNK = 64;                 // tiles per launch (their descriptors travel by value in the kernel arguments)
 // tiles [T][SLICE_ROW] of frames[f] (uint8 [h0][w0][3], shapes[f] = {h0, w0}), read in place -> out [T][3][side][side]; all host arrays, checked by the caller
@@ -483,6 +487,20 @@ struct HeadTailArgs {
 };
 bool head_tail_ok(const HeadTailArgs* q, int n, const GridInfo& g);
 void launch_head_tail_group(const HeadTailArgs* q, int n, const GridInfo& g, float conf_thresh, float* boxes, float* scores, int32_t* cls, hipStream_t s);
+
+// Makes `device` current for its lifetime and restores the caller's device afterwards; switches only when the two differ.  Every entry point and
+// every destroy runs under one: an object made on cuda:1 may be called or deleted while cuda:0 is current, and its allocations, launches,
+// hipFuncSetAttributes and hipFrees must not land there.
+struct DeviceScope {
+    int prev = -1;                                      // the device to go back to, -1: nothing was switched
+    explicit DeviceScope(int device)
+    {
+        if (hipGetDevice(&prev) != hipSuccess || prev == device || hipSetDevice(device) != hipSuccess) prev = -1;
+    }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+};
 
 // hipFuncSetAttribute acts on the CURRENT device: every call site keeps a bit mask of the devices it has configured
 inline bool attr_pending(unsigned long long& mask)

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import arch
-from .capi import Handle, YnError, YnRangeError
+from .capi import Handle, YnError, YnRangeError, records_to_host
 
 
 # ---- parameter containers with the reference's module tree (keys must match exactly) -----------
@@ -349,39 +349,40 @@ class YOLONano(nn.Module):
                 cls[b, :k].cpu().numpy().astype(np.int64))
 
     # ---- forward ------------------------------------------------------------------------------------------
-    def _range_guarded(self, h, run):
-        """Run `run(h)` on the default (split-f16) family and check the handle's range guard (yn_range_status): if an activation
-        reached 65504 — outside x = hi + lo * 2^-11, where the reference's fp32 is still finite — switch the handle to the f32-MFMA
-        family for good and run again.  Only forward_raw (device tensors out, nothing read back) goes through this form and pays its
-        synchronising 4-byte read-back; forward / forward_batch learn the same from yn_infer's counts (_infer_guarded)."""
-        out = run(h)
-        if not self._exact_f32:
-            _, overflow = h.range_status()
-            if overflow:
-                import warnings
-                warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
-                              "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
-                self._exact_f32 = True
-                h.exact_f32(True)
-                out = run(h)
-        return out
+    def _switch_to_exact(self, h, acknowledge=False):
+        """An activation left the split-f16 range (>= 65504: outside x = hi + lo * 2^-11, where the reference's fp32 is still finite): this model
+        runs on the f32-MFMA family from now on.  acknowledge: the mark came as a YnRangeError and is still set (yn_range_status clears it)."""
+        import warnings
+        warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
+                      "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
+        if acknowledge:
+            h.range_status()
+        self._exact_f32 = True
+        h.exact_f32(True)
 
-    def _infer_guarded(self, h, xf, finish):
-        """yn_infer + `finish(out)` (the read-back the caller makes anyway).  yn_infer itself reports an activation outside the split-f16 range
-        through NEGATIVE counts (compact_kernel), so the guard costs no extra synchronisation here: on that mark the handle is switched to the
-        f32-MFMA family for good and the call runs again."""
+    def _retry_exact(self, h, call):
+        """call(), and once more under exact f32 when it raises YnRangeError (yn_infer's negative counts, yn_tta_infer's / yn_slice_merge's status):
+        the guard costs no extra synchronisation on these routes.  A model that is exact already re-raises."""
         try:
-            return finish(h.infer(xf))
+            return call()
         except YnRangeError:
             if self._exact_f32:
                 raise
-            import warnings
-            warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
-                          "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
-            h.range_status()                                   # clears the device flag
-            self._exact_f32 = True
-            h.exact_f32(True)
-            return finish(h.infer(xf))
+            self._switch_to_exact(h, acknowledge=True)
+            return call()
+
+    def _range_guarded(self, h, run):
+        """Run `run(h)` and poll the handle's range guard (yn_range_status), switching and running again when it is set.  Only forward_raw
+        (device tensors out, nothing read back) goes through this form and pays its synchronising 4-byte read-back."""
+        out = run(h)
+        if not self._exact_f32 and h.range_status()[1]:
+            self._switch_to_exact(h)
+            out = run(h)
+        return out
+
+    def _infer_guarded(self, h, xf, finish):
+        """yn_infer + `finish(out)` (the read-back the caller makes anyway), under _retry_exact."""
+        return self._retry_exact(h, lambda: finish(h.infer(xf)))
 
     def forward_raw(self, x):
         """Raw head tensors as the reference's hooks see them: three NCHW views [B, A(5+C), H, W]."""
@@ -749,30 +750,12 @@ class TestTimeAugmentation(object):
         h = self.device_handle(model, x.shape[0])
         obj = self._tta
         xf = x.float()
-        try:
-            obj.infer(xf, self.nms_thresh, handle=h)
-        except YnRangeError:
-            if model._exact_f32:
-                raise
-            import warnings
-            warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
-                          "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
-            h.range_status()
-            model._exact_f32 = True
-            h.exact_f32(True)
-            obj.infer(xf, self.nms_thresh, handle=h)
+        model._retry_exact(h, lambda: obj.infer(xf, self.nms_thresh, handle=h))
         return obj.result()
 
     def batch(self, x, model):
         """One (bboxes [K,4] f32, scores [K] f32, cls_inds [K] i64) numpy triple per image of x [B,3,S,S]: two device-to-host copies."""
-        rec, offsets = self.records(x, model)
-        off = offsets.cpu().numpy()
-        host = rec[: int(off[-1])].cpu().numpy()
-        res = []
-        for b in range(len(off) - 1):
-            r = host[off[b]:off[b + 1]]
-            res.append((r[:, :4].copy(), r[:, 4].copy(), r[:, 5].astype(np.int64)))
-        return res
+        return records_to_host(*self.records(x, model))
 
 
 _resize_handles = {}

@@ -123,7 +123,6 @@ class SlicedInference(object):
         rec / offsets ON THE DEVICE in yn_pack_detections' layout, views of the yn_slice object's buffers, valid until the next records() /
         batch(); geoms the identity rows.  On the split-f16 range mark the model's own fallback runs: acknowledge, yn_exact_f32(1), once more."""
         import torch
-        from . import capi
         h = self.device_handle(model, len(frames))
         obj = self._obj
         dev = []
@@ -134,29 +133,12 @@ class SlicedInference(object):
             else:
                 dev.append(torch.as_tensor(np.ascontiguousarray(im, dtype=np.uint8)).to(h.device, non_blocking=True))
         tiles = self.table(dev)
-        args = (dev, tiles, self.mean, self.std, self.nms_thresh, self.edge_margin)
-        try:
-            obj.infer(*args, handle=h)
-        except capi.YnRangeError:
-            if model._exact_f32:
-                raise
-            import warnings
-            warnings.warn("yolo_nano_amd: an activation exceeded the split-f16 range (|x| >= 65504); re-running this and all later "
-                          "forwards of the model on the exact f32-MFMA kernels (yn_exact_f32)")
-            h.range_status()
-            model._exact_f32 = True
-            h.exact_f32(True)
-            obj.infer(*args, handle=h)
+        model._retry_exact(h, lambda: obj.infer(dev, tiles, self.mean, self.std, self.nms_thresh, self.edge_margin, handle=h))
         rec, off = obj.result()
         return rec, off, [identity_geometry(im.shape[0], im.shape[1]) for im in dev]
 
     def batch(self, frames, model):
         """One (bboxes [K,4] f32 normalised by max(h0, w0), scores [K] f32, cls_inds [K] i64) numpy triple per frame: two device-to-host copies."""
+        from .capi import records_to_host
         rec, offsets, _ = self.records(frames, model)
-        off = offsets.cpu().numpy()
-        host = rec[: int(off[-1])].cpu().numpy()
-        res = []
-        for b in range(len(off) - 1):
-            r = host[off[b]:off[b + 1]]
-            res.append((r[:, :4].copy(), r[:, 4].copy(), r[:, 5].astype(np.int64)))
-        return res
+        return records_to_host(rec, offsets)

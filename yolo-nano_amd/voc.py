@@ -175,6 +175,43 @@ def _rect_batch(model, tf, chunk):
     return x, geoms
 
 
+def _run_batches(who, model, images, batch, test_aug, rect, sliced, consume):
+    """The batch loop of evaluate / evaluate_coco (`who` names the caller in messages): per chunk of `batch` images one of the four routes - plain
+    (ValTransforms.batch -> yn_infer -> yn_pack_detections), rect (_rect_batch, the model's square grid back afterwards), test_aug (its records())
+    or sliced (its records()) - then consume(h, rec, offsets, geoms, lo, hi) with the chunk's records on the device and its slice lo:hi of the
+    per-image arguments.  The split-f16 range mark: on the plain and rect routes the pack AND consume run inside the model's retry (an evaluator's
+    add() refuses a marked batch with nothing added, so running again is safe); the other two routes retry inside their records()."""
+    from .model import ValTransforms
+    if rect and test_aug is not None:
+        raise ValueError("%s: test-time augmentation runs on square grids; rect=True and test_aug exclude each other" % who)
+    if sliced is not None and (rect or test_aug is not None):
+        raise ValueError("%s: sliced inference runs its own tiles on square grids; sliced and %s exclude each other" % (who, "rect=True" if rect else "test_aug"))
+    size = int(model.input_size)
+    try:
+        for lo in range(0, len(images), batch):
+            chunk, hi = images[lo:lo + batch], lo + batch
+            if sliced is not None:
+                h = sliced.device_handle(model, len(chunk))
+                rec, off, geoms = sliced.records(chunk, model)      # (boxes in the frame, identity geometry)
+                consume(h, rec, off, geoms, lo, hi)
+                continue
+            h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
+            tf = ValTransforms(size, handle=h)
+            if rect:
+                x, geoms = _rect_batch(model, tf, chunk)
+                h = model.handle(len(chunk))
+            else:
+                x = tf.batch(chunk)[0]
+                geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
+            if test_aug is not None:
+                consume(h, *test_aug.records(x, model), geoms, lo, hi)
+            else:
+                model._infer_guarded(h, x, lambda out: consume(h, *h.pack_detections(out), geoms, lo, hi))
+    finally:
+        if rect:
+            model.set_grid(size)
+
+
 def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=0.5, test_aug=None, rect=False, sliced=None):
     """VOCAPIEvaluator.evaluate + do_python_eval for `model` (an eval-mode yolo_nano_amd.YOLONano): `images` are decoded uint8 HxWx3
     BGR arrays, `annotations` one int array [G][6] per image (gt_array).  Per batch: ValTransforms.batch -> yn_infer ->
@@ -186,51 +223,15 @@ def evaluate(model, images, annotations, batch=32, use_07_metric=True, ovthresh=
     holds every frame's picture), the grid is set only when the window changes, and the model's square grid is back afterwards.
     sliced: a yolo_nano_amd.SlicedInference - every batch of frames goes through its records() (yn_slice_infer: overlapping tiles at native
     resolution plus the whole frame, merged per frame on the device); the model's grid must be the tile (model.set_grid(tile))."""
-    from .model import ValTransforms
-    if rect and test_aug is not None:
-        raise ValueError("evaluate: test-time augmentation runs on square grids; rect=True and test_aug exclude each other")
-    if sliced is not None and (rect or test_aug is not None):
-        raise ValueError("evaluate: sliced inference runs its own tiles on square grids; sliced and %s exclude each other" % ("rect=True" if rect else "test_aug"))
-    size = int(model.input_size)
-    try:
-        return _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms, sliced)
-    finally:
-        if rect:
-            model.set_grid(size)
+    ev = None                                                   # made on the first chunk, on the handle its route has settled on
 
-
-def _evaluate(model, images, annotations, batch, use_07_metric, ovthresh, test_aug, rect, size, ValTransforms, sliced=None):
-    ev = None
-    for s in range(0, len(images), batch):
-        chunk = images[s:s + batch]
-        if sliced is not None:
-            h = sliced.device_handle(model, len(chunk))
-            if ev is None:
-                ev = VOCEval(model.num_classes, ovthresh, handle=h)
-            rec, off, geoms = sliced.records(chunk, model)      # (its own range fallback; boxes in the frame, identity geometry)
-            ev.add(rec, off, geoms, annotations[s:s + batch], handle=h)
-            continue
-        h = model.handle(len(chunk)) if test_aug is None else test_aug.device_handle(model, len(chunk))
+    def consume(h, rec, off, geoms, lo, hi):
+        nonlocal ev
         if ev is None:
             ev = VOCEval(model.num_classes, ovthresh, handle=h)
-        tf = ValTransforms(size, handle=h)
-        if rect:
-            x, geoms = _rect_batch(model, tf, chunk)
-            h = model.handle(len(chunk))
-        else:
-            x = tf.batch(chunk)[0]
-            geoms = [voc_geometry(im.shape[0], im.shape[1], size) for im in chunk]
-        gts = annotations[s:s + batch]
-        if test_aug is not None:
-            rec, off = test_aug.records(x, model)               # (its own range fallback)
-            ev.add(rec, off, geoms, gts, handle=h)
-            continue
+        ev.add(rec, off, geoms, annotations[lo:hi], handle=h)
 
-        def finish(out, geoms=geoms, gts=gts, h=h):
-            rec, off = h.pack_detections(out)
-            ev.add(rec, off, geoms, gts, handle=h)
-
-        model._infer_guarded(h, x, finish)                      # the split-f16 range mark: re-run under exact f32, nothing added
+    _run_batches("evaluate", model, images, batch, test_aug, rect, sliced, consume)
     if ev is None:
         raise ValueError("evaluate: no images")
     aps, mAP = ev.compute(use_07_metric, handle=model.handle(1))
