@@ -9,6 +9,7 @@
 //   argmax_cand_kernel   :253-261 from caller-provided (all_local, all_conf)
 //   bucket / sort / matrix / resolve / compact : exact per-class greedy NMS (see the block comment below)
 #include "yn_device.h"
+#include "yn_head_tile_map.h"
 #include "yn_prep.h"
 
 namespace ynk {
@@ -433,7 +434,7 @@ void launch_head_decode_group(const GemmArgs* a, int n, const GridInfo& g, float
 // The tail of a detection head in ONE kernel (models/yolo_nano.py:60-82, 299-330, 362-367): depthwise 3x3 + pointwise conv (layers .2 and
 // .3), the last conv (.4) on the tile while it is still in LDS, and the candidate decode of head_decode_kernel.  Against
 // dwpw_pipe_group_kernel + head_decode_group_kernel the 96-channel activation of layer .3 (44 MB per 32-image step at 416 x 416) is
-// neither written nor read back, and a chip-filling launch disappears.  Workgroup = an 8 x 4 pixel tile of one image; in the depthwise
+// neither written nor read back, and a chip-filling launch disappears.  Workgroup = a tile of 32 pixels (eight runs of four, below); in the depthwise
 // phase thread = (4 channels, a run of 4 pixels along x) with its 3 x 6 window in one batch of clamped, masked loads (192 of the 256
 // threads), in the 96 -> 96 GEMM wavefront = one 32-column tile (three of the four).
 //   1. depthwise windows, taps, biases, the 96 x 96 split weight matrix and the first weight chunk of the last conv: one batch of loads
@@ -443,22 +444,30 @@ void launch_head_decode_group(const GemmArgs* a, int n, const GridInfo& g, float
 //   5. raw head tile [32][260] fp32 over the weight space, per-row candidate index / cell, then head_decode_kernel's three decode passes
 // Every sum runs in the order of the separate kernels and the operand split is the same function of the same fp32 values: bit-identical
 // outputs (test_head_tail_is_bit_identical).  LDS 50 KB: three workgroups per CU.
+// Which 32 pixels a workgroup takes is yn_head_tile_map.h's rule: eight consecutive runs of the level's run list - an 8 x 4 block where the eight
+// are aligned, other shapes at band, image and list ends, and never a row of pixels outside the image (8 x 4 blocks laid over every image were
+// 4 064 workgroups at 416 x 416, bs 32, 515 workgroups' worth of their rows outside the image and dropped only at the stores; the list gives 3 640).  Everything behind the
+// depthwise phase sees 32 independent tile rows, row = run * 4 + pixel of the run; a slot behind the list's end is an outside row.
 // -------------------------------------------------------------------------------------------------
+constexpr int HEAD_TAIL_HALVES = 2 * 32 * 104 + 2 * 12 * 96 * 8;        // planes + the larger of {W 96x96, a chunk of the last conv, the raw tile}
+static_assert(2 * 12 * 96 * 8 >= 2 * 4 * 256 * 8 && 2 * 12 * 96 * 8 >= 32 * 260 * 2 + 32 * 8 * 4 + 32 * 4 * 2, "weight space holds a chunk and the raw tile");
+constexpr size_t HEAD_TAIL_LDS = (size_t)HEAD_TAIL_HALVES * 2 + HEAD_TILE_RUNS * sizeof(HeadTileRun);      // ... and the tile's eight runs behind them
+static_assert(HEAD_TAIL_HALVES * 2 % 16 == 0 && sizeof(HeadTileRun) == 16, "the runs are 16-byte LDS words");
+
 template <int KMAX>
 __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const GridInfo& g, int scale, float conf_thresh,
                                                 float* __restrict__ boxes, float* __restrict__ scores, int32_t* __restrict__ cls,
                                                 h16* smem, unsigned bid, unsigned nblocks)
 {
-    constexpr int TW = 8, TH = 4, NO = TW * TH, C = 96, KQ = C / 8, BN1 = 96, AST = C + 8, R = 4, BN2 = 256, LD = BN2 + 4;
+    constexpr int NO = 32, C = 96, KQ = C / 8, BN1 = 96, AST = C + 8, R = 4, BN2 = 256, LD = BN2 + 4;
     h16* Ah = smem;                                       // [NO][AST]
     h16* Al = Ah + NO * AST;
     h16* Bs = Al + NO * AST;                              // [2][KQ][BN1][8], then chunks [2][4][BN2][8], then the raw tile
+    static_assert(NO == HEAD_TILE_RUNS * HEAD_RUN_PIXELS && R == HEAD_RUN_PIXELS, "a tile is eight runs of four pixels (yn_head_tile_map.h)");
+    HeadTileRun* ent = reinterpret_cast<HeadTileRun*>(smem + HEAD_TAIL_HALVES);     // [8]: this tile's runs, behind everything the phases carve up
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
-    const int tx_n = (a.W + TW - 1) / TW, ty_n = (a.H + TH - 1) / TH;
-    const int tile = (int)(((bid & 7u) * (nblocks >> 3)) + (bid >> 3));
-    if (tile >= a.B * ty_n * tx_n) return;
-    const int b = tile / (ty_n * tx_n), trem = tile - b * (ty_n * tx_n);
-    const int oy0 = (trem / tx_n) * TH, ox0 = (trem % tx_n) * TW;
+    const unsigned tile = (bid & 7u) * (nblocks >> 3) + (bid >> 3);
+    if (tile >= a.tm.tiles) return;
 
 #ifdef YN_EXP_TIMING
     long long TS[10]; int tsn = 0;
@@ -482,21 +491,26 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
             dma16(pl ? a.Wl : a.Wh, (unsigned)(g0 - pl * (KQ * BN1) + lane) * 16u, lds_bs + (unsigned)g0 * 16u);
         }
     }
+    // the tile's eight runs (image, row, first column, pixels inside the row), decoded ONCE into LDS: the multiplications of head_tile_run on eight
+    // lanes of one wavefront instead of on every thread of a kernel that is bound by what it issues.  (lds_barrier: no wait for the pieces above)
+    if (t < HEAD_TILE_RUNS) ent[t] = head_tile_run(a.tm, tile * HEAD_TILE_RUNS + (unsigned)t);
+    lds_barrier();
     const int cq = t % (C / 4), run = t / (C / 4);          // 24 channel quads x 8 runs of 4 pixels = 192 workers
-    const bool worker = run < 8;
-    const int c = cq * 4, ry = run >> 1, rx = (run & 1) * R;
+    const bool worker = run < HEAD_TILE_RUNS;
+    const int c = cq * 4;
     float4 win[3][R + 2], wd[9], bd = make_float4(0.f, 0.f, 0.f, 0.f);
     if (worker) {
-        const int oy = oy0 + ry;
+        const HeadTileRun en = ent[run];                    // a slot behind the list's end (valid == 0) is an outside row: every load masked
+        const int b = en.b, oy = en.y;
         unsigned wok = 0;                                   // which window values are inside the image: the masks are applied AFTER the whole batch
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
             const int iy = oy - 1 + ky;
-            const bool yok = oy < a.H && iy >= 0 && iy < a.H;
+            const bool yok = en.valid > 0 && iy >= 0 && iy < a.H;
             const float* rowp = a.in + ((size_t)(b * a.H + (yok ? iy : 0)) * a.W) * C + c;
 #pragma unroll
             for (int j = 0; j < R + 2; ++j) {
-                const int ix = ox0 + rx - 1 + j;
+                const int ix = en.x0 - 1 + j;
                 const bool ok = yok && ix >= 0 && ix < a.W;
                 win[ky][j] = *reinterpret_cast<const float4*>(rowp + (size_t)(ok ? ix : 0) * C);
                 wok |= (ok ? 1u : 0u) << (ky * (R + 2) + j);
@@ -544,7 +558,7 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) vfma(acc, win[ky][o + kx], wd[ky * 3 + kx]);
             acc = vact(acc, a.dw_act);
-            const int op = ry * TW + rx + o;
+            const int op = run * R + o;
             const float x4[4] = {acc.x, acc.y, acc.z, acc.w};
             h16x4 hi, lo;
 #pragma unroll
@@ -639,10 +653,11 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
     }
     int* rowinfo = reinterpret_cast<int*>(raw + NO * LD + NO * 16);     // [32][4]: first candidate, gx, gy, inside the image
     if (t < NO) {
-        const int py = oy0 + t / TW, px = ox0 + t % TW;
-        const bool ok = py < a.H && px < a.W;
+        const HeadTileRun en = ent[t / R];                  // tile row = run * 4 + pixel of the run
+        const int py = en.y, px = en.x0 + t % R;
+        const bool ok = t % R < en.valid;
         const int cell = ok ? py * a.W + px : 0;
-        *reinterpret_cast<int4*>(rowinfo + t * 4) = make_int4(b * g.N + g.off[scale] + cell * g.A, px, py, ok ? 1 : 0);
+        *reinterpret_cast<int4*>(rowinfo + t * 4) = make_int4(en.b * g.N + g.off[scale] + cell * g.A, px, py, ok ? 1 : 0);
     }
     const unsigned magicA = (65536u + (unsigned)g.A - 1u) / (unsigned)g.A;     // c / A == (c * magicA) >> 16 for c < 32 * A <= 256
     __syncthreads();
@@ -723,9 +738,6 @@ __device__ __forceinline__ void head_tail_block(const HeadTailArgs& a, const Gri
 #undef YN_TS
 }
 
-constexpr int HEAD_TAIL_HALVES = 2 * 32 * 104 + 2 * 12 * 96 * 8;        // planes + the larger of {W 96x96, a chunk of the last conv, the raw tile}
-static_assert(2 * 12 * 96 * 8 >= 2 * 4 * 256 * 8 && 2 * 12 * 96 * 8 >= 32 * 260 * 2 + 32 * 8 * 4 + 32 * 4 * 2, "weight space holds a chunk and the raw tile");
-
 template <int KMAX>
 __global__ __attribute__((amdgpu_flat_work_group_size(256, 256), amdgpu_waves_per_eu(3, 3)))     // exactly three wavefronts per SIMD: LDS holds three workgroups; aiming at four costs the load batch its registers
 void head_tail_group_kernel(Group<HeadTailArgs> q, GridInfo g, float conf_thresh,
@@ -741,7 +753,8 @@ bool head_tail_ok(const HeadTailArgs* q, int n, const GridInfo& g)
 {
     if (n < 1 || n > YN_GROUP_MAX || g.C > 80 || g.C <= 32 || g.A > 8 || g.A < 1) return false;
     for (int p = 0; p < n; ++p)
-        if (!q[p].Wh || !q[p].Wl || !q[p].Wfh || !q[p].Wfl || q[p].Npad <= 128 || q[p].Npad > 256 || g.A * (5 + g.C) > q[p].Npad || q[p].B <= 0) return false;
+        if (!q[p].Wh || !q[p].Wl || !q[p].Wfh || !q[p].Wfl || q[p].Npad <= 128 || q[p].Npad > 256 || g.A * (5 + g.C) > q[p].Npad || q[p].B <= 0 ||
+            !head_tile_map_ok(q[p].B, q[p].H, q[p].W)) return false;
     return true;
 }
 
@@ -751,10 +764,10 @@ void launch_head_tail_group(const HeadTailArgs* a, int n, const GridInfo& g, flo
     unsigned tot = 0;
     for (int p = 0; p < YN_GROUP_MAX; ++p) {
         q.first[p] = tot;
-        if (p < n) { q.a[p] = a[p]; tot += (unsigned)(((unsigned)a[p].B * ((a[p].H + 3) / 4) * ((a[p].W + 7) / 8) + 7u) & ~7u); }
+        if (p < n) { q.a[p] = a[p]; q.a[p].tm = head_tile_map(a[p].B, a[p].H, a[p].W); tot += xcd_grid(q.a[p].tm.tiles); }
     }
     q.first[YN_GROUP_MAX] = tot;
-    const size_t lds = (size_t)HEAD_TAIL_HALVES * 2;
+    const size_t lds = HEAD_TAIL_LDS;
     static unsigned long long attr = 0;
     if (attr_pending(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_tail_group_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     set_last_kernel_name("head_tail_group_kernel<5>");

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "yn_devbuf.h"
+#include "yn_head_tile_map.h"
 
 namespace ynk {
 
@@ -484,6 +485,7 @@ struct HeadTailArgs {
     const void *Wfh, *Wfl; const float* fbias; int Npad;   // last conv 96 -> A(5+C): split packs [12][Npad][8], bias [Npad]
     int B, H, W;
     unsigned* ovf;                                      // split-f16 range guard flag or null
+    HeadTileMap tm;                                     // tile -> pixels (yn_head_tile_map.h); filled by launch_head_tail_group from B, H, W
 };
 bool head_tail_ok(const HeadTailArgs* q, int n, const GridInfo& g);
 void launch_head_tail_group(const HeadTailArgs* q, int n, const GridInfo& g, float conf_thresh, float* boxes, float* scores, int32_t* cls, hipStream_t s);
