@@ -1495,9 +1495,22 @@ void launch_stem(const float* x, int B, int H, int W, const float* w, const floa
 // (backbone/shufflenetv2.py:109-116, 159).  A block owns 8x7 pooled pixels: it computes the 17x15 conv
 // pixels they need (255 of 256 threads busy, one conv pixel x COUT channels each) into LDS, then pools from
 // LDS.  The 24 x (S/2)^2 conv activation (133 MB per bs=32 step at 416) never goes to memory.
+//
+// Arithmetic of a conv pixel: bias, then the 27 products in (channel, ky, kx) order, one fma each - except channel 0, whose products
+// 15 ... 26 are a rounded multiply followed by a rounded add.  That is what the compiler made of the scalar form of this kernel (it peeled
+// channel 0 off its packed pairs and left those twelve products unfused), it is what every recorded output of the network was computed
+// with, and it is spelled out here so that the bits no longer depend on the vectoriser's choices.
 // -------------------------------------------------------------------------------------------------
+constexpr int STEM_POOL_C0_SPLIT = 15;
+constexpr int STEM_POOL_PIN = 9;     // products between two pins of the accumulators (below): one input channel
+__device__ __forceinline__ float mul_then_add(float a, float b, float c)
+{
+#pragma clang fp contract(off)
+    return c + a * b;
+}
+
 template <int COUT>
-__global__ __launch_bounds__(256) void stem_pool_kernel(const float* __restrict__ x, int B, int H, int W,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void stem_pool_kernel(const float* __restrict__ x, int B, int H, int W,
                                                          const float* __restrict__ w, const float* __restrict__ bias,
                                                          int act, float* __restrict__ y)
 {
@@ -1505,7 +1518,7 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const float* __restrict_
     // The weights are wave-uniform: they come through the scalar cache into SGPR operands of the packed FMAs (as broadcast
     // 16-byte LDS reads they took 8 LDS cycles per 4 VALU cycles — the kernel ran at the LDS rate, 58 us); LDS only holds
     // the conv tile the pooling reads.
-    __shared__ __attribute__((aligned(16))) float ct[CR * CC * COUT];
+    __shared__ __attribute__((aligned(16))) float ct[256 * COUT];       // one slot per thread (CR * CC = 255 conv pixels): the stores need no guard
     const int Hc = (H - 1) / 2 + 1, Wc = (W - 1) / 2 + 1;               // conv output extent
     const int Hp = (Hc - 1) / 2 + 1, Wp = (Wc - 1) / 2 + 1;             // pooled extent
     const int tiles_x = (Wp + PC - 1) / PC, tiles_y = (Hp + PR - 1) / PR;
@@ -1519,8 +1532,55 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const float* __restrict_
     const bool live = t < CR * CC && cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
     // all 27 input values of the thread's conv pixel in ONE batch of unconditional (clamped, masked) loads
     float in[27];
-    {
-        const int cyc = live ? cy : 0, cxc = live ? cx : 0;
+    const int cyc = live ? cy : 0, cxc = live ? cx : 0;
+    if ((W & 1) == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && (size_t)H * W <= (1u << 28)) {
+        // Even W: columns (2 cx, 2 cx + 1) are an aligned pair, and column 2 cx - 1 is the upper half of the pair that the lane to the
+        // left holds (conv column c - 1 of the same conv row: live whenever this lane is and cx > 0, so it read the same clamped row).
+        // One 8-byte load and one wave_shr:1 DPP move per (channel, ky); the first lane of a conv row and lane 0 of a wavefront have
+        // no such neighbour and load the column themselves.  Each lane applies its OWN masks after the shift.
+        // Addresses: a wave-uniform plane pointer plus a 32-bit byte offset per ky (an image's three planes stay below 4 GB, tested above),
+        // the scalar-base form of the load - three offsets instead of a 64-bit address per load.
+        asm volatile("; YN_STEM_PAIRED_BEGIN");
+        const bool edge = c == 0 || (t & 63) == 0;
+        const char* xb = reinterpret_cast<const char*>(x + (size_t)b * 3 * H * W);
+        const unsigned plane = (unsigned)H * (unsigned)W * 4u;
+        unsigned off[3];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = cyc * 2 - 1 + ky;
+            off[ky] = ((unsigned)(iy < 0 ? 0 : (iy >= H ? H - 1 : iy)) * (unsigned)W + (unsigned)cxc * 2u) * 4u;
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const int ci = q / 3, ky = q - ci * 3;
+            const float2 p = *reinterpret_cast<const float2*>(xb + ci * plane + off[ky]);   // 2 cxc + 1 <= W - 1: cxc < Wc = W / 2
+            in[q * 3 + 1] = p.x;
+            in[q * 3 + 2] = p.y;
+            in[q * 3] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p.y), 0x138, 0xf, 0xf, true));   // wave_shr:1, lane 0 reads 0
+        }
+        if (edge) {
+            const unsigned back = cxc > 0 ? 4u : 0u;                                        // column 2 cxc - 1, clamped
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                const int ci = q / 3, ky = q - ci * 3;
+                in[q * 3] = *reinterpret_cast<const float*>(xb + ci * plane + (off[ky] - back));
+            }
+        }
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = cyc * 2 - 1 + ky;
+            const bool rowok = live && iy >= 0 && iy < H;
+            const unsigned mk = opaque_mask(rowok), ml = opaque_mask(rowok && cxc > 0);
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci) {
+                const int q = ci * 3 + ky;
+                in[q * 3] = __uint_as_float(__float_as_uint(in[q * 3]) & ml);
+                in[q * 3 + 1] = __uint_as_float(__float_as_uint(in[q * 3 + 1]) & mk);
+                in[q * 3 + 2] = __uint_as_float(__float_as_uint(in[q * 3 + 2]) & mk);
+            }
+        }
+        asm volatile("; YN_STEM_PAIRED_END");
+    } else {
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
             const int ci = q / 3, ky = q - ci * 3;
@@ -1536,23 +1596,66 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const float* __restrict_
             }
         }
     }
-    float acc[COUT];
+    // Accumulators as native four-vectors, one per 16-byte LDS write: the packed FMAs pair channels (0,1), (2,3), ... and a quad sits in
+    // four consecutive registers.  (As 24 scalars the vectoriser paired (1,2) ... (21,22), and the tile went out in 4- and 8-byte writes,
+    // eight lanes to a bank.)
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    constexpr int C4 = COUT / 4;
+    f4 acc[C4];
+    // A dead lane (outside the image, or thread 255) starts from -inf, the max pool's padding, instead of the bias: its inputs are masked to
+    // zero, so it stays -inf through the products, and the select stands where a move of the bias stood.
 #pragma unroll
-    for (int co = 0; co < COUT; ++co) acc[co] = bias[co];
+    for (int g = 0; g < C4; ++g) {
+        f4 bv = f4{bias[g * 4], bias[g * 4 + 1], bias[g * 4 + 2], bias[g * 4 + 3]};
+        asm volatile("" : "+s"(bv));                         // loaded by every lane: `live ? bias[k] : -inf` alone branches around each load
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[g][k] = live ? bv[k] : -INFINITY;
+    }
 #pragma unroll
     for (int i = 0; i < 27; ++i) {
+        const float a0 = acc[0].x;
 #pragma unroll
-        for (int co = 0; co < COUT; ++co) acc[co] += in[i] * w[i * COUT + co];
+        for (int g = 0; g < C4; ++g) {
+            const float* wi = w + i * COUT + g * 4;
+            acc[g] = __builtin_elementwise_fma(f4{in[i], in[i], in[i], in[i]}, f4{wi[0], wi[1], wi[2], wi[3]}, acc[g]);
+        }
+        if (i >= STEM_POOL_C0_SPLIT) acc[0].x = mul_then_add(in[i], w[i * COUT], a0);
+        // All accumulators pass through an empty asm once per input channel, which keeps the channels' products in order.  Left alone the
+        // compiler loads weights far ahead of their use and spills them: 182 SGPRs written to VGPR lanes and read back.  Per product the
+        // pin costs a wait for the scalar loads each time (43.9 us), per three 41.2, per nine 40.7.
+        if (i % STEM_POOL_PIN == STEM_POOL_PIN - 1 && i != 26) asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]));
     }
+    // apply_act() (yn_device.h) written out per activation, a wave-uniform branch: ReLU is one max per channel (against -inf in a dead lane,
+    // which so keeps its padding), leaky ReLU a packed multiply, a compare and a select (0.1 * -inf = -inf), the identity nothing.  The
+    // general form took five instructions per channel with the dead lanes' select, 120 of the kernel's 650.  The six 16-byte writes and
+    // the barrier stand in each branch: behind the branches the accumulators would first be copied into common registers, 24 moves.
+    auto put_tile = [&]() {
 #pragma unroll
-    for (int co = 0; co < COUT; ++co) acc[co] = live ? apply_act(acc[co], act) : -INFINITY;   // -inf = max-pool padding
-    if (t < CR * CC) {
+        for (int g = 0; g < C4; ++g) *reinterpret_cast<f4*>(ct + t * COUT + g * 4) = acc[g];   // thread 255 too: its slot is never read
+        __syncthreads();
+    };
+    if (act == 1) {
+        const float floor = live ? 0.0f : -INFINITY;
 #pragma unroll
-        for (int co = 0; co < COUT; co += 4)
-            *reinterpret_cast<float4*>(ct + t * COUT + co) = make_float4(acc[co], acc[co + 1], acc[co + 2], acc[co + 3]);
+        for (int g = 0; g < C4; ++g)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                     // the instruction itself: fmaxf() puts a canonicalising max in front of each
+                float v = acc[g][k];
+                asm("v_max_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(floor));
+                acc[g][k] = v;
+            }
+        put_tile();
+    } else if (act == 2) {
+#pragma unroll
+        for (int g = 0; g < C4; ++g) {
+            const f4 neg = acc[g] * 0.1f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[g][k] = acc[g][k] > 0.0f ? acc[g][k] : neg[k];
+        }
+        put_tile();
+    } else {
+        put_tile();
     }
-    __syncthreads();
-    constexpr int C4 = COUT / 4;
     for (int i = t; i < PR * PC * C4; i += 256) {
         const int c4 = i % C4, pp = i / C4;
         const int pr = pp / PC, pc = pp - pr * PC;
