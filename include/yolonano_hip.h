@@ -602,6 +602,39 @@ int  yn_draw_status(yn_handle* h, yn_draw* d, int64_t* drawn, int64_t* skipped, 
  * class, x1, y1, x2, y2 (the unclipped integers), k; n = drawn, cap = rows of room.  Synchronises. */
 int  yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap);
 
+/* ---- detections tracked across video frames: B camera streams, one frame of each per step, identities kept on the device (DESIGN.md 29
+ * is the specification, tests/track_oracle.py its float32 restatement; the reference has no tracker, the rules are this library's own,
+ * of the ByteTrack / BoT-SORT family with a greedy instead of an optimal assignment).  The input is the rec_dev / offsets_dev pair of
+ * yn_pack_detections, yn_tta_result or yn_slice_result; boxes are used in whatever unit they carry.  Per stream max_tracks slots (free,
+ * tentative, confirmed, lost), each a constant-velocity Kalman filter in (cx, cy, w, h) with diagonal noise, and an id counter that
+ * starts at 1.  One step of one stream: the usable records (finite coordinates, x2 > x1, y2 > y1, score >= track_low; the first
+ * max_dets in record order, the rest counted as overflow, the unusable as ignored) -> predict -> IoU -> greedy matching, ties to the
+ * lowest slot, then the lowest detection, in three stages (confirmed + lost x high detections at iou_high, confirmed x low at iou_low,
+ * tentative x unmatched high at iou_new) -> update / age / free -> births from unmatched high detections with score >= new_thresh into
+ * the lowest free slots (none free: dropped_births) -> output.  All decisions in float32, bit-exact with the restatement. */
+typedef struct yn_track yn_track;
+typedef struct { float track_high, track_low, new_thresh, iou_high, iou_low, iou_new, w_pos, w_vel; int32_t max_lost, min_hits, class_aware; } yn_track_params;
+/* streams 1..4096, max_tracks and max_dets 1..128.  p NULL: track_high 0.5, track_low 0.1, new_thresh 0.6, iou_high 0.2, iou_low 0.5,
+ * iou_new 0.3, w_pos 1/20, w_vel 1/160, max_lost 30, min_hits 2, class_aware 1.  Refused with a reason: a value that is not finite,
+ * track_low > track_high, an IoU threshold outside (0, 1], max_lost < 0, min_hits < 1.  The object has its own lifetime (any handle of
+ * its device serves the later calls); its memory shows in yn_live_device_memory. */
+int  yn_track_create(yn_handle* h, int streams, int max_tracks, int max_dets, const yn_track_params* p /* NULL: defaults */, yn_track** out);
+void yn_track_destroy(yn_track* t);
+/* on the handle's stream, asynchronous */
+int  yn_track_reset(yn_handle* h, yn_track* t, int stream /* -1: all, and the counters; ids restart at 1 */);
+/* B frames; frame b belongs to stream stream_host[b] (NULL: b).  Refused before any launch: B > streams, an index out of range, an index twice, null
+ * pointers, a handle on another device.  B == 0 is no error (out_offsets_dev[0] = 0 when the pointer is given, nothing else).  out_rec_dev [B*max_tracks][6] = x1, y1, x2, y2 of the
+ * posterior, score, class of every confirmed track matched or born in this step, frame by frame in slot order; out_ids_dev [B*max_tracks]
+ * their ids; out_offsets_dev [B+1].  No record at or past rec_capacity is read, whatever the offsets hold (rec_dev may be NULL when it is 0).  offsets_dev[B] < 0 (the
+ * split-f16 range mark) is decided on the device: no state word changes, out_offsets_dev = 0, .., 0, -1, one range_mark is counted.  On the
+ * handle's stream: ceil(B / 256) + 1 launches, no copy, no synchronise. */
+int  yn_track_update(yn_handle* h, yn_track* t, int B, const int32_t* stream_host, const float* rec_dev, const int32_t* offsets_dev, int64_t rec_capacity,
+                     float* out_rec_dev, int32_t* out_ids_dev, int32_t* out_offsets_dev);
+/* testing aids; both synchronise.  A free slot reads 0, 0, 0, 0, -1 and zeros.  Any pointer of yn_track_state may be NULL. */
+int  yn_track_state(yn_handle* h, yn_track* t, int stream, int32_t* meta_host /* [max_tracks][5] state (0 free, 1 tentative, 2 confirmed, 3 lost), id, hits, lost_age, detection matched or born from in the last step or -1 */,
+                    float* filt_host /* [max_tracks][22] class, score, then p, v, P00, P01, P11 for cx, cy, w, h */, int32_t* next_id);
+int  yn_track_status(yn_handle* h, yn_track* t, int64_t counters_host[6] /* steps (frames stepped), births, dropped_births, overflow, ignored, range_marks; summed since create / reset(-1) */);
+
 /* ---- training loss (train.py:219-229, forward value + gradient w.r.t. the raw predictions) ---------- */
 /* models/yolo_nano.py:332-358 + tools.iou_score (tools.py:219-233) + tools.loss (tools.py:236-276).
  * Predictions in the reference's split layout: conf [B,N] (= [B,N,1]), cls [B,N,C], txtytwth [B,N,4];

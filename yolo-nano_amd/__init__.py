@@ -32,6 +32,9 @@ def __getattr__(name):
     if name in ("Visualizer", "class_colors", "default_font"):
         from . import draw                                    # numpy only until a Visualizer is made
         return getattr(draw, name)
+    if name == "Tracker":
+        from . import track                                   # numpy only until a Tracker is made
+        return track.Tracker
     if name in ("JPEGDecoder", "imread", "imread_batch", "JPEGEncoder", "imencode", "imwrite", "imwrite_batch"):
         from . import jpeg                                    # files -> device frames (yn_jpeg_*), and back (yn_jpeg_enc_*)
         return getattr(jpeg, name)

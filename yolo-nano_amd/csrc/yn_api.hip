@@ -68,6 +68,7 @@ struct GraphEntry {
 struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
+struct yn_track { ynk::TrackState* st; };    // likewise (kernels_track.hip)
 struct yn_jpeg { ynk::JpegState* st; };      // likewise (kernels_jpeg.hip)
 struct yn_jpeg_enc { ynk::JpegEncState* st; };      // likewise (kernels_jpeg_enc.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
@@ -2718,6 +2719,61 @@ int yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap)
     YN_ENTER(h);
     if (!d || (!host && cap > 0)) return fail(h, "yn_draw_prims: null argument");
     YN_EVAL_CALL(ynk::draw_prims(d->st, h->stream, host, cap, err));
+}
+
+// ---- detections tracked across frames (kernels_track.hip) ---------------------------------------------------------------------
+static_assert(sizeof(yn_track_params) == 11 * 4 && offsetof(yn_track_params, max_lost) == 8 * 4, "yn_track_params: eight floats, then three int32");
+
+int yn_track_create(yn_handle* h, int streams, int max_tracks, int max_dets, const yn_track_params* p, yn_track** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_track_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::TrackState* st = nullptr;
+    if (ynk::track_create(h->cfg.device, h->stream, streams, max_tracks, max_dets, p ? &p->track_high : nullptr, p ? &p->max_lost : nullptr, &st, err))
+        return fail(h, "%s", err.c_str());
+    *out = new yn_track{st};
+    return 0;
+}
+
+void yn_track_destroy(yn_track* t)
+{
+    if (!t) return;
+    ynk::track_destroy(t->st);
+    delete t;
+}
+
+#define YN_TRACK_ENTER(name)                                                                                         \
+    YN_ENTER(h);                                                                                                     \
+    if (!t) return fail(h, name ": null object");                                                                    \
+    if (ynk::track_device(t->st) != h->cfg.device)                                                                   \
+        return fail(h, name ": the object was made for device %d, the handle is on device %d", ynk::track_device(t->st), h->cfg.device)
+
+int yn_track_reset(yn_handle* h, yn_track* t, int stream)
+{
+    YN_TRACK_ENTER("yn_track_reset");
+    YN_EVAL_CALL(ynk::track_reset(t->st, h->stream, stream, err));
+}
+
+int yn_track_update(yn_handle* h, yn_track* t, int B, const int32_t* stream_host, const float* rec_dev, const int32_t* offsets_dev, int64_t rec_capacity,
+                    float* out_rec_dev, int32_t* out_ids_dev, int32_t* out_offsets_dev)
+{
+    YN_TRACK_ENTER("yn_track_update");
+    YN_EVAL_CALL(ynk::track_update(t->st, h->stream, B, stream_host, rec_dev, offsets_dev, rec_capacity, out_rec_dev, out_ids_dev, out_offsets_dev, err));
+}
+
+int yn_track_state(yn_handle* h, yn_track* t, int stream, int32_t* meta_host, float* filt_host, int32_t* next_id)
+{
+    YN_TRACK_ENTER("yn_track_state");
+    YN_EVAL_CALL(ynk::track_state(t->st, h->stream, stream, meta_host, filt_host, next_id, err));
+}
+
+int yn_track_status(yn_handle* h, yn_track* t, int64_t counters_host[6])
+{
+    YN_TRACK_ENTER("yn_track_status");
+    if (!counters_host) return fail(h, "yn_track_status: null argument");
+    YN_EVAL_CALL(ynk::track_status(t->st, h->stream, counters_host, err));
 }
 
 // ---- the merge lists of yn_tta and yn_slice (struct MergeLists above) ------------------------------------------------------------

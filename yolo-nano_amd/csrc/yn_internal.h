@@ -327,6 +327,19 @@ int  draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, cons
 int  draw_status(DrawState* d, hipStream_t s, int64_t* drawn, int64_t* skipped, int* range_mark, std::string& err);
 int  draw_prims(DrawState* d, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
 
+// ---- detections tracked across frames (kernels_track.hip): the state behind yn_track; 0 = ok, 1 = error (text in err) ----------------------
+struct TrackState;
+// params8 / params3: the float and the int32 members of yn_track_params in their order, or both null for the defaults
+int  track_create(int device, hipStream_t s, int streams, int max_tracks, int max_dets, const float* params8, const int32_t* params3, TrackState** out,
+                  std::string& err);
+void track_destroy(TrackState* t);
+int  track_device(const TrackState* t);
+int  track_reset(TrackState* t, hipStream_t s, int stream, std::string& err);
+int  track_update(TrackState* t, hipStream_t s, int B, const int32_t* stream_host, const float* rec_dev, const int32_t* offsets_dev, int64_t rec_capacity,
+                  float* out_rec, int32_t* out_ids, int32_t* out_offsets, std::string& err);
+int  track_state(TrackState* t, hipStream_t s, int stream, int32_t* meta_host, float* filt_host, int32_t* next_id, std::string& err);
+int  track_status(TrackState* t, hipStream_t s, int64_t* counters6, std::string& err);
+
 // ---- baseline JPEG decode (kernels_jpeg.hip, yn_jpeg_host.h): the state behind yn_jpeg; 0 = ok, 1 = error (text in err) -------------------
 struct JpegState;
 int  jpeg_create(int device, int max_batch, int64_t staging_bytes, int threads, JpegState** out, std::string& err);
