@@ -735,6 +735,12 @@ int  yn_op_dwconv3x3(yn_handle* h, const float* x, int B, int H, int W, int C, i
                      const float* w, const float* bias, int act, float* y);
 int  yn_op_pwconv(yn_handle* h, const float* x, int B, int H, int W, int Cin, int Cout,
                   const float* w, const float* bias, int act, float* y);
+/* Up to three pointwise convs as ONE grouped launch, as the network runs the three FPN laterals (models/yolo_nano.py:286-296): member p
+ * reads M[p] rows of Cin[p] floats at x[p] + m * in_ld[p] + in_off[p] and writes Cout floats at y[p] + m * out_ld[p] + out_off[p], on the
+ * caller's tensors.  Cin, in_ld and in_off even.  The kernel is the handle's choice (autotuner, or yn_set_pw_config: every index of the
+ * split-f16 family gives the same bits; the last one is pw_pipe_group_kernel where it has a form for the members). */
+int  yn_op_pwconv_group(yn_handle* h, int n, const float* const* x, const int* in_ld, const int* in_off, const int* M, const int* Cin, int Cout,
+                        const float* const* w, const float* const* bias, int act, float* const* y, const int* out_ld, const int* out_off);
 /* The tail of a ShuffleV2Block (backbone/shufflenetv2.py:72,74 + channel_shuffle :14-28) exactly as the network runs it:
  * y = channel_shuffle(cat(pass, act(pw(x))), 2), i.e. y[..., 2j] = pass[..., j], y[..., 2j+1] = act(pw(x))[..., j], written by
  * the GEMM epilogue (the shuffle is never materialised on its own).  pass [B,H,W,Cout], y [B,H,W,2*Cout]. */

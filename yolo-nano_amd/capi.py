@@ -106,6 +106,7 @@ SIGNATURES = {
     "yn_op_dwconv3x3": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_pwconv": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_pwconv_shuffle": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "yn_op_pwconv_group": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "yn_op_conv3x3": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_stem": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "yn_op_stem_pool": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
@@ -918,6 +919,34 @@ class Handle:
         self._ck(self.lib.yn_op_pwconv(self.h, _ptr(self._in(x)), B, H, W, Cin, Cout, _ptr(self._in(w)),
                                        _ptr(self._in(bias)) if bias is not None else None, act, y.data_ptr()), "yn_op_pwconv")
         return y
+
+    def op_pwconv_group(self, members, act=0, out=None):
+        """Up to three pointwise convs as one grouped launch (yn_op_pwconv_group).  members: [(x, w, bias)], x a contiguous [M, Cin] tensor or
+        (wide, off): columns [off, off + Cin) of a contiguous [M, ld] tensor; out: None (new [M, Cout] tensors) or [(wide, off)] per member.
+        Returns the output tensors ([M, Cout] views of `wide` where out is given)."""
+        n = len(members)
+        keep, xs, ws, bs, ys, ret = [], [], [], [], [], []
+        in_ld, in_off, Ms, Cin, out_ld, out_off = [], [], [], [], [], []
+        Cout = members[0][1].shape[0]
+        for p, (x, w, bias) in enumerate(members):
+            xt, off = x if isinstance(x, tuple) else (x, 0)
+            assert xt.dim() == 2 and xt.is_contiguous() and xt.dtype == torch.float32 and w.shape[0] == Cout
+            w, bias = self._in(w), (self._in(bias) if bias is not None else None)
+            keep += [w, bias]
+            xs.append(xt.data_ptr()); in_ld.append(xt.shape[1]); in_off.append(off); Ms.append(xt.shape[0]); Cin.append(w.shape[1])
+            ws.append(w.data_ptr()); bs.append(bias.data_ptr() if bias is not None else 0)
+            if out is None:
+                yt, yoff = torch.empty((xt.shape[0], Cout), dtype=torch.float32, device=xt.device), 0
+            else:
+                yt, yoff = out[p]
+                assert yt.dim() == 2 and yt.is_contiguous() and yt.dtype == torch.float32 and yt.shape[0] == xt.shape[0]
+            ys.append(yt.data_ptr()); out_ld.append(yt.shape[1]); out_off.append(yoff)
+            ret.append(yt[:, yoff:yoff + Cout])
+        pa = lambda v: (ctypes.c_void_p * n)(*v)
+        ia = lambda v: (ctypes.c_int32 * n)(*[int(q) for q in v])
+        self._ck(self.lib.yn_op_pwconv_group(self.h, n, pa(xs), ia(in_ld), ia(in_off), ia(Ms), ia(Cin), int(Cout), pa(ws), pa(bs), int(act),
+                                             pa(ys), ia(out_ld), ia(out_off)), "yn_op_pwconv_group")
+        return ret
 
     def op_pwconv_shuffle(self, x, passthrough, w, bias, act=0):
         B, H, W, Cin = x.shape

@@ -1089,6 +1089,9 @@ bool launch_pw_group(const GemmArgs* a, int n, int cfg, hipStream_t s)
     for (int p = 0; p < n; ++p)
         if (!a[p].Wsh || !a[p].Wsl || (a[p].K & 1) || (a[p].in_ld & 1) || (a[p].in_off & 1) || a[p].Npad != a[0].Npad) return false;
     int idx = cfg - N_PW_CFGS - N_PWD_CFGS;
+    // the persistent form (pw_pipe_group_kernel): only when asked for by index (the group autotuner times it beside the tiles); a group it has no
+    // form for takes the heuristic tile
+    if (idx == N_PWS_CFGS && launch_pw_pipe_group(a, n, s)) return true;
     if (idx < 0 || idx >= N_PWS_CFGS) {                     // untuned: the tile gemm_split would pick for the first (largest) problem
         const int nt32 = a[0].Npad / 32;
         idx = 0;

@@ -20,6 +20,7 @@
 // bit-identical to unit_chain2_kernel and to the three-kernel path (tests/test_gpu_parity.py::test_unit_chain_bit_identical_...).
 #include "yn_internal.h"
 #include "yn_unit_tile.h"
+#include "yn_lateral_grid.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -446,6 +447,46 @@ bool launch_unit_pipe(const ChainArgs& a, hipStream_t s, bool dry)
 // 120 registers / 33 KB of LDS leave room for FOUR workgroups per CU.  Same 16-deep k-steps in sequence, same epilogue function:
 // bit-identical to every gemm_split_kernel configuration; the autotuner times it next to them (the last pointwise configuration index).
 // -------------------------------------------------------------------------------------------------
+// ---- written once for pw_pipe_kernel and pw_pipe_group_kernel (below) ----
+// The split pass: BM fp32 rows of CG channel groups (VEC floats each; row stride RS floats) in LDS -> the hi / lo operand planes [BM][PS], every element
+// through the range guard.  Thread index from an OPAQUE copy: as loop invariants the addresses are hoisted out of the tile loop.
+template <int BM, int CG, int VEC, int RS, int PS, int NTHR>
+__device__ __forceinline__ void pw_split_rows(const float* raw, h16* Ph, h16* Pl, float& amax)
+{
+    typedef typename VecT<VEC>::type vec;
+    int tt = threadIdx.x;
+    asm volatile("" : "+v"(tt));
+#pragma unroll
+    for (int i0 = 0; i0 < BM * CG; i0 += NTHR) {
+        const int i = i0 + tt;
+        if (i < BM * CG) {
+            const int r = i / CG, cq = i - r * CG;
+            const vec v = *reinterpret_cast<const vec*>(raw + r * RS + VEC * cq);
+            float o[VEC];
+            if constexpr (VEC == 4) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; } else { o[0] = v.x; o[1] = v.y; }
+            typename H16Vec<VEC>::type hi, lo;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { amax = range_track(amax, o[j]); hi[j] = (h16)o[j]; lo[j] = split_lo(o[j], hi[j]); }
+            *reinterpret_cast<typename H16Vec<VEC>::type*>(Ph + r * PS + VEC * cq) = hi;
+            *reinterpret_cast<typename H16Vec<VEC>::type*>(Pl + r * PS + VEC * cq) = lo;
+        }
+    }
+}
+// The walk: tiles tile, tile + jstep, ... below tend - the first one ahead of the loop (unit_pipe_kernel's do_tile comment: hipcc flushes the
+// vector-memory counter in front of a loop) - and the range guard's report behind the last one.
+template <typename F>
+__device__ __forceinline__ void pw_walk_tiles(int tile, const int jstep, const int tend, unsigned* ovf, const float& amax, F&& do_tile)
+{
+    int next = tile + jstep < tend ? tile + jstep : -1;
+    do_tile(tile, next);
+    while (next >= 0) {
+        tile = next;
+        next = tile + jstep < tend ? tile + jstep : -1;
+        do_tile(tile, next);
+    }
+    range_report(ovf, amax);
+}
+
 template <int KK, int NPAD, int NW, int OCC>
 __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int tiles)
 {
@@ -511,25 +552,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
         const int m0 = tile * BM;
         lds_barrier();      // (1) this tile's rows have landed (every wavefront waited for its pieces), the previous tile's GEMM is done with the planes
         // ---- split pass: fp32 rows -> hi / lo planes ----
-        {
-            int tt = threadIdx.x;
-            asm volatile("" : "+v"(tt));
-#pragma unroll
-            for (int i0 = 0; i0 < BM * CG; i0 += NTHR) {
-                const int i = i0 + tt;
-                if (i < BM * CG) {
-                    const int r = i / CG, cq = i - r * CG;
-                    const vec v = *reinterpret_cast<const vec*>(raw + r * X1S + VEC * cq);
-                    float o[VEC];
-                    if constexpr (VEC == 4) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; } else { o[0] = v.x; o[1] = v.y; }
-                    typename H16Vec<VEC>::type hi, lo;
-#pragma unroll
-                    for (int j = 0; j < VEC; ++j) { amax = range_track(amax, o[j]); hi[j] = (h16)o[j]; lo[j] = split_lo(o[j], hi[j]); }
-                    *reinterpret_cast<typename H16Vec<VEC>::type*>(Ph + r * PS + VEC * cq) = hi;
-                    *reinterpret_cast<typename H16Vec<VEC>::type*>(Pl + r * PS + VEC * cq) = lo;
-                }
-            }
-        }
+        pw_split_rows<BM, CG, VEC, X1S, PS, NTHR>(raw, Ph, Pl, amax);
         lds_barrier();      // (2) planes complete; the row buffer is free
         if (next >= 0) issue_rows(next);
         f32x16 acc0[1], acc1[1];
@@ -549,17 +572,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void pw_pipe_kernel(GemmArgs a, int t
         vm_drain();         // the next tile's pieces - BEFORE this tile's stores, which need not be waited for
         gemm_epilogue_impl<1, false>(a, acc0, m0 + wm * 32, wn * 32, vecO, threadIdx.x & 63, bias1);     // (no pass-through form: its loads would make hipcc drain the memory counter - stores included - at the top of every tile)
     };
-    {
-        int next = tile + jstep < tend ? tile + jstep : -1;
-        vm_drain();         // the first tile's pieces (and the fragments): nothing else in the prologue waits for them
-        do_tile(tile, next);
-        while (next >= 0) {
-            tile = next;
-            next = tile + jstep < tend ? tile + jstep : -1;
-            do_tile(tile, next);
-        }
-    }
-    range_report(a.ovf, amax);
+    vm_drain();             // the first tile's pieces (and the fragments): nothing else in the prologue waits for them
+    pw_walk_tiles(tile, jstep, tend, a.ovf, amax, do_tile);
 }
 
 // false = this layer has no instantiated form (the caller takes a gemm_split_kernel configuration)
@@ -585,6 +599,207 @@ bool launch_pw_pipe(const GemmArgs& a, hipStream_t s)
     YN_PP(232, 256, 8, 1) YN_PP(232, 96, 4, 2)
 #undef YN_PP
     return false;
+}
+
+
+// -------------------------------------------------------------------------------------------------
+// pw_pipe_group_kernel: the three FPN laterals (models/yolo_nano.py:286-296; K = 464 / 232 / 116 -> 96 on the stride-32 / 16 / 8 maps) as
+// ONE launch of pw_pipe_kernel's walk.  Workgroup = three wavefronts, one per 32-column strip of N = 96, 32-row tiles, 168 registers and
+// 33 KB of LDS: four workgroups per CU, three wavefronts on every SIMD (dwpw_pipe_group_kernel's occupancy).  One symbol has one register
+// count and one LDS size, so the long-K members fit the K = 116 member's budget:
+//   * K walks in LDS chunks of LAT_CK = 128 channels (yn_lateral_grid.h; K = 232: 128 + 104, K = 464: 3 x 128 + 80).  The accumulators are
+//     carried across a tile's chunks, the next chunk's rows (of this tile, or the first chunk of the next one) arrive by LDS-DMA under the
+//     current chunk's MFMAs, the epilogue runs behind the last chunk.  Two barriers per chunk.
+//   * up to 12 k-steps of B fragments stay register-resident for the whole walk (K = 116: 64 registers; the 0.5x K = 192: 96);
+//   * K = 232 and 464 (15 / 29 k-steps) keep ONE chunk's panel (64 registers): behind the MFMAs of k-step s of a chunk, the panel's slot s is
+//     reloaded with the same step of the NEXT chunk (unit_pipe_kernel's STREAM technique) - a chunk's split pass and barriers of flight time.
+//     (K = 232 resident: 120 registers of fragments beside 32 of accumulators carried through the split pass - 66 spilled at 168.)
+// The pad columns that fill a short last chunk up to whole k-steps are zeroed WHENEVER that chunk is staged (a full chunk before it wrote
+// them).  Same 16-deep k-steps in ascending order into the same two accumulator sets, same epilogue function: bit-identical to every
+// gemm_split_kernel / gemm_split_group_kernel configuration and to pw_pipe_kernel.
+// -------------------------------------------------------------------------------------------------
+template <int KK>
+__device__ __forceinline__ void pw_pipe_group_block(const GemmArgs& a, unsigned char* smem, unsigned local, unsigned nb)
+{
+    constexpr int BM = LAT_BM, NTHR = 192, CK = LAT_CK, NCH = lateral_chunks(KK), SC = CK / 16;
+    constexpr int KQ = (KK + 7) >> 3, S = (KQ + 1) >> 1, PS = plane_stride(CK);
+    constexpr bool STREAM = S > 12;                                     // the whole matrix does not fit the registers beside the carried accumulators: one chunk's panel, streamed
+    constexpr int PANEL = STREAM ? SC : S;
+    static_assert(KK % 4 == 0 && NCH <= LAT_MAX_CHUNKS && PS == (int)LAT_PLANE_STRIDE, "16-byte pieces end with the row; yn_lateral_grid.h sizes the LDS");
+    static_assert((size_t)BM * CK * 4 + (size_t)2 * BM * PS * 2 == LAT_LDS, "the launcher's LDS size ends where the planes end");
+    float* raw = reinterpret_cast<float*>(smem);                        // fp32 rows of one chunk, [BM][chunk length]
+    h16* Ph = reinterpret_cast<h16*>(smem + (unsigned)BM * CK * 4u);    // operand planes of one chunk [BM][PS]
+    h16* Pl = Ph + BM * PS;
+    const unsigned lds_raw = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l31 = lane & 31, h = lane >> 5;
+    const int wn = wave;                                                // one 32-column strip per wavefront, all of them on the tile's 32 rows
+    const LateralWalk wk = lateral_walk(lateral_tiles(a.M), nb, local);
+    const int tend = wk.end, jstep = wk.step;
+    int tile = wk.first;
+    if (tile >= tend) return;
+
+    // rows [tl * BM, + BM) x channels [c * CK, + length of chunk c): rows past M come from row M - 1, no piece leaves its row (KK % 4 == 0)
+    auto issue_rows = [&](int tl, auto ci) {
+        constexpr int c = decltype(ci)::value, X1C = lateral_chunk_len(KK, c) / 4, nch = BM * X1C;
+        int tt = t;
+        asm volatile("" : "+v"(tt));
+        const int m0 = tl * BM;
+#pragma unroll
+        for (int c0 = 0; c0 < nch; c0 += NTHR) {
+            const int cc = c0 + tt;
+            const int row = cc / X1C;
+            const int j = cc - row * X1C;
+            const int m = m0 + row < a.M ? m0 + row : a.M - 1;
+            const unsigned src = ((unsigned)m * (unsigned)a.in_ld + (unsigned)a.in_off) * 4u + (unsigned)(c * CK * 4) + (unsigned)j * 16u;
+            if (cc < nch) dma16(a.in, src, lds_raw + (unsigned)(c0 + wave * 64) * 16u);
+        }
+    };
+    issue_rows(tile, std::integral_constant<int, 0>{});
+    h16x8 bw[PANEL][2];
+    const char* Wh = reinterpret_cast<const char*>(a.Wsh);
+    const char* Wl = reinterpret_cast<const char*>(a.Wsl);
+    {
+        const int n = wn * 32 + l31;
+#pragma unroll
+        for (int s = 0; s < PANEL; ++s) {
+            const unsigned off = frag_off<KQ>(s, h, n, a.Npad);          // (no masks)
+            bw[s][0] = *reinterpret_cast<const h16x8*>(Wh + off);
+            bw[s][1] = *reinterpret_cast<const h16x8*>(Wl + off);
+        }
+    }
+    // hipcc is TOLD where loaded fragments have landed (an empty asm that reads and writes them, behind a hand-placed drain): its own wait would sit
+    // in front of the MFMAs that read them, with the count of the loads IT knows of - and retire the DMA pieces issued in between
+    auto panel_landed = [&]() {
+#pragma unroll
+        for (int s = 0; s < PANEL; ++s) asm volatile("" : "+v"(bw[s][0]), "+v"(bw[s][1]));
+    };
+    float bias1[1];
+    { const int n = wn * 32 + l31; bias1[0] = n < a.N ? a.bias[n] : 0.0f; }
+    asm volatile("" : "+v"(bias1[0]));
+    // K tail of a single chunk: zero once (nothing below writes those columns; several chunks: in the last chunk's split pass)
+    if constexpr (NCH == 1 && KK % 16 != 0) {
+        constexpr int padn = ((KK + 15) & ~15) - KK;
+        for (int i = t; i < BM * padn; i += NTHR) { const int r = i / padn, c2 = KK + i - r * padn; Ph[r * PS + c2] = (h16)0.0f; Pl[r * PS + c2] = (h16)0.0f; }
+    }
+    float amax = 0.0f;
+    const bool vecO = ((a.N | a.out_ld | a.out_off) & 3) == 0;
+    f32x16 acc0[1], acc1[1];
+
+    auto do_chunk = [&](const int tile, const int next, auto ci) __attribute__((always_inline)) {
+        constexpr int c = decltype(ci)::value, LEN = lateral_chunk_len(KK, c), CG = LEN / 4, STEPS = (LEN + 15) / 16;
+        constexpr int cn = (c + 1) % NCH, STEPSN = (lateral_chunk_len(KK, cn) + 15) / 16;      // the chunk that follows (of the next tile: chunk 0)
+        lds_barrier();      // (1) this chunk's rows have landed (every wavefront waited for its pieces), the previous GEMM is done with the planes
+        // ---- split pass: fp32 rows -> hi / lo planes ----
+        pw_split_rows<BM, CG, 4, LEN, PS, NTHR>(raw, Ph, Pl, amax);
+        {
+            int tt = threadIdx.x;
+            asm volatile("" : "+v"(tt));
+            if constexpr (NCH > 1 && LEN % 16 != 0) {                   // a full chunk wrote the columns this one's last k-step needs to be zero
+                constexpr int PQ = (STEPS * 16 - LEN) / 4;
+                h16x4 z;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) z[j] = (h16)0.0f;
+                for (int i = tt; i < BM * PQ; i += NTHR) {
+                    const int r = i / PQ, c2 = LEN + 4 * (i - r * PQ);
+                    *reinterpret_cast<h16x4*>(Ph + r * PS + c2) = z;
+                    *reinterpret_cast<h16x4*>(Pl + r * PS + c2) = z;
+                }
+            }
+        }
+        lds_barrier();      // (2) planes complete; the row buffer is free
+        if constexpr (cn != 0) issue_rows(tile, std::integral_constant<int, cn>{});
+        else if (next >= 0) issue_rows(next, std::integral_constant<int, 0>{});
+        if constexpr (c == 0) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) { acc0[0][k] = 0.0f; acc1[0][k] = 0.0f; }
+        }
+        {
+            int ll = threadIdx.x & 63;
+            asm volatile("" : "+v"(ll));
+            const h16* ahp = Ph + (ll & 31) * PS + (ll >> 5) * 8;
+            const h16* alp = Pl + (ll & 31) * PS + (ll >> 5) * 8;
+            const unsigned lw = (unsigned)((ll >> 5) * a.Npad + wn * 32 + (ll & 31)) * 16u;     // this lane's fragment inside an octet pair of the pack
+#pragma unroll
+            for (int s = 0; s < (STREAM && STEPSN > STEPS ? STEPSN : STEPS); ++s) {
+                if (s < STEPS) panel_step(ahp, alp, s, bw[STREAM ? s : c * SC + s][0], bw[STREAM ? s : c * SC + s][1], acc0[0], acc1[0]);
+                if constexpr (STREAM) {
+                    if (s < STEPSN) {                                   // slot s: k-step cn * SC + s (the octet past the matrix reads the last one: frag_off)
+                        const int sg = cn * SC + s;
+                        const unsigned off = lw + (unsigned)(sg * 2) * (unsigned)a.Npad * 16u - (sg * 2 + 1 < KQ ? 0u : (unsigned)(ll >> 5) * (unsigned)a.Npad * 16u);
+                        bw[s][0] = *reinterpret_cast<const h16x8*>(Wh + off);
+                        bw[s][1] = *reinterpret_cast<const h16x8*>(Wl + off);
+                    }
+                }
+            }
+        }
+        vm_drain();         // the next chunk's pieces (and the streamed panel) - BEFORE this tile's stores, which need not be waited for
+        if constexpr (STREAM) panel_landed();
+        if constexpr (cn == 0) {
+            split_join(acc0[0], acc1[0]);
+            gemm_epilogue_impl<1, false>(a, acc0, tile * BM, wn * 32, vecO, threadIdx.x & 63, bias1);
+        }
+    };
+    auto do_tile = [&](const int tile, const int next) __attribute__((always_inline)) {
+        do_chunk(tile, next, std::integral_constant<int, 0>{});
+        if constexpr (NCH > 1) do_chunk(tile, next, std::integral_constant<int, 1>{});
+        if constexpr (NCH > 2) do_chunk(tile, next, std::integral_constant<int, 2>{});
+        if constexpr (NCH > 3) do_chunk(tile, next, std::integral_constant<int, 3>{});
+    };
+    vm_drain();             // the first chunk's pieces (and the fragments): nothing else in the prologue waits for them
+    panel_landed();
+    pw_walk_tiles(tile, jstep, tend, a.ovf, amax, do_tile);
+}
+
+// members in the order of the template arguments (longest K first, as run_network lists the laterals)
+template <int K0, int K1, int K2>
+__global__ __attribute__((amdgpu_flat_work_group_size(192, 192), amdgpu_waves_per_eu(3, 3))) void pw_pipe_group_kernel(Group<GemmArgs> g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ppg_smem[];
+    unsigned local, nb;
+    const int p = group_problem(g.first, blockIdx.x, local, nb);
+    if (p == 0) pw_pipe_group_block<K0>(g.a[0], ppg_smem, local, nb);
+    else if (p == 1) pw_pipe_group_block<K1>(g.a[1], ppg_smem, local, nb);
+    else pw_pipe_group_block<K2>(g.a[2], ppg_smem, local, nb);
+}
+
+// the group autotuner's question: a form exists AND its workgroups walk (yn_lateral_grid.h, lateral_walks)
+bool pw_pipe_group_candidate(const GemmArgs* a, int n)
+{
+    if (n != LAT_MEMBERS || lateral_triple(a[0].K, a[1].K, a[2].K) < 0) return false;
+    const int M[LAT_MEMBERS] = {a[0].M, a[1].M, a[2].M};
+    return lateral_walks(M, n);
+}
+
+// false = the group has a member this kernel has no form for (the caller takes a gemm_split_group_kernel tile): not three members, another K
+// triple, N != 96, a pass-through half, odd strides, fewer than 64 rows, byte offsets beyond 32 bits
+bool launch_pw_pipe_group(const GemmArgs* a, int n, hipStream_t s)
+{
+    if (n != LAT_MEMBERS) return false;
+    for (int p = 0; p < n; ++p) {
+        if (!a[p].Wsh || !a[p].Wsl || a[p].pass || (a[p].in_ld & 1) || (a[p].in_off & 1) || a[p].N != 96 || a[p].Npad != 96 || a[p].M < 64) return false;
+        if ((double)a[p].M * a[p].in_ld * 4.0 >= 4.0e9) return false;
+    }
+    const int triple = lateral_triple(a[0].K, a[1].K, a[2].K);
+    if (triple < 0) return false;
+    const int M[LAT_MEMBERS] = {a[0].M, a[1].M, a[2].M}, K[LAT_MEMBERS] = {a[0].K, a[1].K, a[2].K};
+    unsigned wgs[LAT_MEMBERS];
+    lateral_grid(M, K, n, wgs);
+    Group<GemmArgs> g{};
+    unsigned tot = 0;
+    for (int p = 0; p < YN_GROUP_MAX; ++p) {
+        g.first[p] = tot;
+        if (p < n) { g.a[p] = a[p]; tot += wgs[p]; }
+    }
+    g.first[YN_GROUP_MAX] = tot;
+    if (triple == 0) {
+        set_last_kernel_name("pw_pipe_group_kernel<464,232,116>");
+        hipLaunchKernelGGL((pw_pipe_group_kernel<464, 232, 116>), dim3(tot), dim3(192), (size_t)LAT_LDS, s, g);
+    } else {
+        set_last_kernel_name("pw_pipe_group_kernel<192,96,48>");
+        hipLaunchKernelGGL((pw_pipe_group_kernel<192, 96, 48>), dim3(tot), dim3(192), (size_t)LAT_LDS, s, g);
+    }
+    return true;
 }
 
 }  // namespace ynk

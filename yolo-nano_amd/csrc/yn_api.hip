@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -783,6 +784,7 @@ bool run_pw_group(yn_handle* h, const Layer* const l[], GemmArgs a[], int n, con
             float best_ms = 1e30f;
             for (int round = 0; round < 2; ++round)
                 for (int c = pw_f32_config_count(); c < pw_config_count(); ++c) {
+                    if (c == pw_config_count() - 1 && !pw_pipe_group_candidate(a, n)) continue;      // the persistent form: only where it has a form and its workgroups walk
                     if (!launch_pw_group(a, n, c, h->cur)) continue;                 // warm-up
                     (void)hipEventRecord(h->tune_e0, h->cur);
                     for (int r = 0; r < 5; ++r) (void)launch_pw_group(a, n, c, h->cur);
@@ -2239,6 +2241,28 @@ int yn_op_pwconv(yn_handle* h, const float* x, int B, int H, int W, int Cin, int
     TmpLayer t(h, K_PW, Cin, Cout, 1, act, w, bias);
     if (t.rc) return fail(h, "yn_op_pwconv: out of memory");
     run_pw(h, t.l, x, Cin, 0, (long)B * H * W, y, Cout, 0, nullptr, 0, 0);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int yn_op_pwconv_group(yn_handle* h, int n, const float* const* x, const int* in_ld, const int* in_off, const int* M, const int* Cin, int Cout,
+                       const float* const* w, const float* const* bias, int act, float* const* y, const int* out_ld, const int* out_off)
+{
+    YN_ENTER(h);
+    if (n < 1 || n > YN_GROUP_MAX) return fail(h, "yn_op_pwconv_group: 1 to %d members", YN_GROUP_MAX);
+    for (int p = 0; p < n; ++p)
+        if ((Cin[p] & 1) || (in_ld[p] & 1) || (in_off[p] & 1) || M[p] < 1 || in_ld[p] < in_off[p] + Cin[p] || out_ld[p] < out_off[p] + Cout)
+            return fail(h, "yn_op_pwconv_group: member %d: Cin, in_ld and in_off must be even, the rows inside their strides", p);
+    std::unique_ptr<TmpLayer> t[YN_GROUP_MAX];
+    const Layer* l[YN_GROUP_MAX];
+    GemmArgs a[YN_GROUP_MAX];
+    for (int p = 0; p < n; ++p) {
+        t[p].reset(new TmpLayer(h, K_PW, Cin[p], Cout, 1, act, w[p], bias ? bias[p] : nullptr));
+        if (t[p]->rc) return fail(h, "yn_op_pwconv_group: out of memory");
+        l[p] = &t[p]->l;
+        a[p] = pw_args(h, t[p]->l, x[p], in_ld[p], in_off[p], M[p], y[p], out_ld[p], out_off[p], nullptr, 0, 0);
+    }
+    if (!run_pw_group(h, l, a, n, "op_group")) return fail(h, "yn_op_pwconv_group: the members do not run as one grouped launch (split packs, equal padded widths)");
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -150,6 +150,8 @@ int  pw_config_count();                    // f32-MFMA family (tiled, then regis
 int  pw_f32_config_count();
 void launch_pw(const GemmArgs& a, hipStream_t s);
 bool launch_pw_pipe(const GemmArgs& a, hipStream_t s);      // kernels_pipe.hip: the persistent form (the last pointwise configuration index); false = not applicable
+bool pw_pipe_group_candidate(const GemmArgs* a, int n);                  // kernels_pipe.hip: whether the group autotuner times that index (a form exists and its workgroups walk)
+bool launch_pw_pipe_group(const GemmArgs* a, int n, hipStream_t s);     // kernels_pipe.hip: the same index for a group (the three laterals); false = no form for these members
 void launch_conv3x3(const GemmArgs& a, hipStream_t s);
 void launch_dw(const DwArgs& a, hipStream_t s);
 void launch_stem(const float* x_nchw, int B, int H, int W, const float* w /*[27][Cout]*/, const float* bias,
