@@ -262,6 +262,27 @@ int  yn_nms(yn_handle* h, const float* dets_dev, const float* scores_dev, int n,
 int  yn_nms_merge(yn_handle* h, const float* boxes_dev, const float* scores_dev, const int32_t* cls_dev, int n, int num_classes,
                   float nms_thresh, int diou, float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count_dev);
 
+/* Weighted box fusion over an arbitrary detection list - the twin of yn_nms_merge, and the second merge rule of yn_tta / yn_slice / yn_fuse
+ * (DESIGN.md 30 is the specification; tests/wbf_oracle.py restates it in float32 numpy and the kernel agrees bit for bit).  The rule is
+ * this package's own: parity with the ensemble_boxes family is UNPINNED.  Per class, rows are visited in yn_nms_merge's pick order (score
+ * descending, higher row first among equals).  A row joins the cluster whose FUSED box has the largest ovr with it among those with
+ * ovr > iou_thresh (strict; NaN never matches; equal ovr: the earliest cluster) - ovr in yn_nms_merge's arithmetic - and then
+ * n += 1, S += s, P[j] += s * b[j], fused[j] = P[j] / S; otherwise it founds a cluster whose fused box is its own box bit for bit.
+ * Every operation is one float32 operation.  Delivered per cluster, in ascending order of the founder's row: fused box, score
+ * (S / (float)n) * ((float)min(n, expected) / (float)expected), class, founder row (out_index), votes n (out_votes).  assign_dev [n] (may
+ * be NULL): per input row the founder row of the cluster it ended in (-1 for a row of class -1).  out_index / out_votes may be NULL.
+ * Output buffers have capacity n; count_dev[0] = clusters.  Refused, each by name: expected < 1, n < 0, num_classes other than the
+ * handle's.  n == 0 is an empty result.  No segment length is refused: clusters past yn_wbf_lds_clusters() live in device memory. */
+int  yn_wbf_merge(yn_handle* h, const float* boxes_dev, const float* scores_dev, const int32_t* cls_dev, int n, int num_classes,
+                  float iou_thresh, int expected, float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index,
+                  int32_t* out_votes, int32_t* assign_dev, int32_t* count_dev);
+/* clusters of one (list, class) segment whose state the kernel keeps in LDS (a testing aid: cases straddle it) */
+int  yn_wbf_lds_clusters(void);
+/* the documented cost model: the most 64-lane steps the walk of a segment of n_rows rows ending in n_clusters clusters takes */
+int64_t yn_wbf_cost(int64_t n_rows, int64_t n_clusters);
+/* the merge rules of yn_tta / yn_slice / yn_fuse */
+enum { YN_MERGE_NMS = 0, YN_MERGE_WBF = 1 };
+
 /* ValTransforms (data/transforms.py:445-458 = Resize :73-119 + Normalize :59-70 + ToTensor :394-398; call sites
  * benchmark.py:58, evaluator/vocapi_evaluator.py:64): img_dev = uint8 [h0][w0][3] BGR on the device -> x_dev float32
  * [3][side][side] RGB, normalised, letterboxed.  The caller supplies Resize's integer geometry (rw x rh resized extent placed
@@ -486,6 +507,9 @@ void yn_tta_destroy(yn_tta* t);
  * pass list_capacity fails, naming the first such image and the rows it needed; nothing is written past a list.  B == 0 is an empty
  * result, not an error. */
 int  yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, float nms_thresh);
+/* The rule yn_tta_infer's merge applies from now on: YN_MERGE_NMS (the default) or YN_MERGE_WBF (yn_wbf_merge's rule per list; the float
+ * argument of yn_tta_infer is then its iou_thresh).  expected: the expected votes, 0 = the object's default, its number of forwards. */
+int  yn_merge_rule_tta(yn_handle* h, yn_tta* t, int rule, int expected);
 /* the last successful yn_tta_infer's result, owned by the object and valid until its next call: rec_dev [total][6] + offsets_dev
  * [B+1], exactly yn_pack_detections' layout (what yn_eval_add / yn_coco_add take).  Any pointer may be NULL; asking for `total` costs
  * one 4-byte read-back (once per result).  Returns 1 when there is no result. */
@@ -548,6 +572,8 @@ int  yn_slice_append(yn_handle* h, yn_slice* s, int F, const int32_t* shapes_hos
  * stay in ascending list order) and yn_pack_detections into the object's record buffer.  A range mark returns YN_STATUS_RANGE; a list
  * that would have passed list_capacity fails, naming the first such frame and the rows it needed.  Nothing is delivered then. */
 int  yn_slice_merge(yn_handle* h, yn_slice* s, int F, float nms_thresh);
+/* The rule yn_slice_merge / yn_slice_infer apply from now on, as yn_merge_rule_tta; expected 0 = 1 (a tile's boxes need no confirmation). */
+int  yn_merge_rule_slice(yn_handle* h, yn_slice* s, int rule, int expected);
 /* The composition: per chunk of at most the handle's max_batch tiles, in table order, yn_slice_preprocess into the object's input buffer,
  * ONE yn_infer at the handle's current grid and thresholds, one yn_slice_append; then yn_slice_merge.  The grid must be square (its side
  * is the table's `side`); a window grid is refused and nothing is launched.  The result does not depend on where the chunk boundaries
@@ -565,6 +591,28 @@ int  yn_slice_result(yn_slice* s, const float** rec_dev, const int32_t** offsets
  * Synchronises the stream. */
 int  yn_slice_lists(yn_handle* h, yn_slice* s, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host,
                     int32_t* tile_start_host);
+
+/* ---- record lists fused per unit: the third client of the merge lists, for ensembles of models and for fusing any record lists (a TTA
+ * result with a sliced one).  max_units 1..4096 lists of list_capacity rows (1..131072); the handle gives the device and the class count. */
+typedef struct yn_fuse yn_fuse;
+int  yn_fuse_create(yn_handle* h, int max_units, int list_capacity, yn_fuse** out);
+void yn_fuse_destroy(yn_fuse* f);
+/* empties the B lists */
+int  yn_fuse_open(yn_handle* h, yn_fuse* f, int B);
+/* rec_dev / offsets_dev in yn_pack_detections' layout for B units: the rows of unit b go to the end of list b in order, the score
+ * multiplied by `weight` with one float32 multiply (1.0f copies the bits).  A negative offsets[B] sets the range mark.  A class that is
+ * not an integer in 0..C-1 is counted and the next yn_fuse_merge refuses, naming the unit; rows past list_capacity are counted, not
+ * written, and the merge refuses on them too.  rec_dev must be 8-byte aligned.  Asynchronous. */
+int  yn_fuse_append(yn_handle* h, yn_fuse* f, int B, const float* rec_dev, const int32_t* offsets_dev, float weight);
+/* ONE read-back, then the merge of the B lists by `rule` (YN_MERGE_NMS: yn_nms_merge's arithmetic, YN_MERGE_WBF: yn_wbf_merge's) at
+ * `thresh`, and yn_pack_detections into the object's record buffer.  expected 0 = the appends since yn_fuse_open.  A range mark returns
+ * YN_STATUS_RANGE. */
+int  yn_fuse_merge(yn_handle* h, yn_fuse* f, int B, int rule, float thresh, int expected);
+/* the last successful yn_fuse_merge's result, with the contract of yn_tta_result */
+int  yn_fuse_result(yn_fuse* f, const float** rec_dev, const int32_t** offsets_dev, int32_t* total);
+/* testing aid, like yn_slice_lists: boxes_host [B][list_capacity][4], scores_host / cls_host [B][list_capacity], count_host [B].  Any
+ * pointer may be NULL.  Synchronises the stream. */
+int  yn_fuse_lists(yn_handle* h, yn_fuse* f, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host);
 
 /* ---- detections painted onto frames in list order: test.py:50-92 / demo.py:48-71 (visualize, plot_bbox_labels) for B frames at once,
  * straight from the rec_dev / offsets_dev pair of yn_pack_detections or yn_tta_result: no read-back, no per-detection host work

@@ -32,6 +32,9 @@ def __getattr__(name):
     if name in ("Visualizer", "class_colors", "default_font"):
         from . import draw                                    # numpy only until a Visualizer is made
         return getattr(draw, name)
+    if name in ("weighted_boxes_fusion", "Ensemble"):
+        from . import fusion                                  # numpy only until a fusion runs
+        return getattr(fusion, name)
     if name == "Tracker":
         from . import track                                   # numpy only until a Tracker is made
         return track.Tracker

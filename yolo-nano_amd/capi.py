@@ -160,6 +160,18 @@ SIGNATURES = {
     "yn_kmeans_assign": (_i32, [_vp, _vp, _vp]),
     "yn_kmeans_stats": (_i32, [_vp, _i64p, _i64p]),
     "yn_resize_batch": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "yn_wbf_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "yn_wbf_lds_clusters": (_i32, []),
+    "yn_wbf_cost": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "yn_merge_rule_tta": (_i32, [_vp, _vp, _i32, _i32]),
+    "yn_merge_rule_slice": (_i32, [_vp, _vp, _i32, _i32]),
+    "yn_fuse_create": (_i32, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
+    "yn_fuse_destroy": (None, [_vp]),
+    "yn_fuse_open": (_i32, [_vp, _vp, _i32]),
+    "yn_fuse_append": (_i32, [_vp, _vp, _i32, _vp, _vp, _f32]),
+    "yn_fuse_merge": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32]),
+    "yn_fuse_result": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i32)]),
+    "yn_fuse_lists": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_tta_create": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "yn_tta_destroy": (None, [_vp]),
     "yn_tta_infer": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32]),
@@ -794,6 +806,22 @@ class Handle:
         k = int(cnt.item())
         return ob[:k], osc[:k], oc[:k], oi[:k]
 
+    def wbf_merge(self, boxes, scores, cls, num_classes, iou_thresh, expected=1, assign=False):
+        """Weighted box fusion over a detection list (yn_wbf_merge) -> (boxes [K,4], scores [K], cls [K], founder row [K],
+        votes [K]), with assign=True also the founder row of every input row's cluster [n]."""
+        n = int(boxes.shape[0])
+        boxes = self._in(boxes); scores = self._in(scores); cls = self._in(cls, torch.int32)
+        ob = torch.empty((max(n, 1), 4), dtype=torch.float32, device=self.device)
+        osc = torch.empty((max(n, 1),), dtype=torch.float32, device=self.device)
+        oc, oi, ov, asg = (torch.empty((max(n, 1),), dtype=torch.int32, device=self.device) for _ in range(4))
+        cnt = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._ck(self.lib.yn_wbf_merge(self.h, boxes.data_ptr(), scores.data_ptr(), cls.data_ptr(), n, int(num_classes), float(iou_thresh),
+                                       int(expected), ob.data_ptr(), osc.data_ptr(), oc.data_ptr(), oi.data_ptr(), ov.data_ptr(),
+                                       asg.data_ptr() if assign else None, cnt.data_ptr()), "yn_wbf_merge")
+        k = int(cnt.item())
+        out = (ob[:k], osc[:k], oc[:k], oi[:k], ov[:k])
+        return out + (asg[:n],) if assign else out
+
     def ema_update(self, ema, model, decay):
         """ema = ema * d + (1 - d) * model, in place (utils/misc.py:83-86); float32 tensors of equal size on this device."""
         assert ema.is_contiguous() and model.is_contiguous() and ema.numel() == model.numel() and ema.dtype == model.dtype == torch.float32
@@ -1291,6 +1319,17 @@ class Handle:
         return y
 
 
+MERGE_NMS, MERGE_WBF = 0, 1                 # YN_MERGE_NMS / YN_MERGE_WBF
+MERGE_RULES = {"nms": MERGE_NMS, "wbf": MERGE_WBF}
+
+
+def merge_rule_id(merge):
+    """"nms" / "wbf" -> YN_MERGE_*; anything else is refused by name."""
+    if merge not in MERGE_RULES:
+        raise ValueError("merge must be 'nms' or 'wbf', got %r" % (merge,))
+    return MERGE_RULES[merge]
+
+
 class _DeviceView:
     """A region of device memory the library owns, in the form torch.as_tensor adopts without a copy."""
 
@@ -1360,6 +1399,11 @@ class Tta(_MergeObject):
         self.n = None
         h._ck(self.lib.yn_tta_infer(h.h, self.obj, x.data_ptr(), int(x.shape[0]), int(x.shape[2]), float(nms_thresh)), "yn_tta_infer")
         self.n = int(x.shape[0])
+
+    def merge_rule(self, rule, expected=0, handle=None):
+        """The merge infer() ends in from now on: MERGE_NMS (default) or MERGE_WBF; expected 0 = the number of forwards (yn_merge_rule_tta)."""
+        h = self.handle if handle is None else handle
+        h._ck(self.lib.yn_merge_rule_tta(h.h, self.obj, int(rule), int(expected)), "yn_merge_rule_tta")
 
     def result(self, total=False):
         """(rec [max_batch * list_capacity, 6] float32, offsets [B+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
@@ -1460,6 +1504,11 @@ class Slice(_MergeObject):
                                       ctypes.cast(m, _vp), ctypes.cast(sd, _vp), float(nms_thresh), float(edge_margin)), "yn_slice_infer")
         self.n = len(frames)
 
+    def merge_rule(self, rule, expected=0, handle=None):
+        """The merge merge() / infer() apply from now on: MERGE_NMS (default) or MERGE_WBF; expected 0 = 1 (yn_merge_rule_slice)."""
+        h = self.handle if handle is None else handle
+        h._ck(self.lib.yn_merge_rule_slice(h.h, self.obj, int(rule), int(expected)), "yn_merge_rule_slice")
+
     def result(self, total=False):
         """(rec [max_frames * list_capacity, 6] float32, offsets [F+1] int32) on the device, in yn_pack_detections' layout: VIEWS of the
         object's buffers, valid until its next call (yn_slice_result).  total=True: also offsets[F] as an int (one read-back)."""
@@ -1477,3 +1526,56 @@ class Slice(_MergeObject):
         h._ck(self.lib.yn_slice_lists(h.h, self.obj, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data, start.ctypes.data),
               "yn_slice_lists")
         return boxes, scores, cls, count[:F], start[:T]
+
+
+class Fuse(_MergeObject):
+    """One yn_fuse: record lists fused per unit - ensembles of models, or a TTA result with a sliced one.  Thin, 1:1 with the C ABI."""
+    _destroy, _result = "yn_fuse_destroy", "yn_fuse_result"
+
+    def __init__(self, handle, max_units=1, list_capacity=8192):
+        self.lib = handle.lib
+        self.handle = handle
+        self.max_units, self.list_capacity = int(max_units), int(list_capacity)
+        self.units = self.max_units
+        f = _vp()
+        handle._ck(self.lib.yn_fuse_create(handle.h, self.max_units, self.list_capacity, ctypes.byref(f)), "yn_fuse_create")
+        self.obj = f
+        self.n = None                                           # units of the result
+        self.lists = None                                       # units of the open lists
+
+    def open(self, B, handle=None):
+        """Empties the B lists (yn_fuse_open)."""
+        h = self.handle if handle is None else handle
+        self.n = None
+        h._ck(self.lib.yn_fuse_open(h.h, self.obj, int(B)), "yn_fuse_open")
+        self.lists = int(B)
+
+    def append(self, rec, offsets, weight=1.0, handle=None):
+        """(rec, offsets [B+1]) in yn_pack_detections' layout, on the device: unit b's rows go to the end of list b, score * weight
+        (yn_fuse_append)."""
+        h = self.handle if handle is None else handle
+        assert rec.is_cuda and rec.is_contiguous() and rec.dtype == torch.float32 and offsets.is_cuda and offsets.dtype == torch.int32
+        self.n = None
+        h._ck(self.lib.yn_fuse_append(h.h, self.obj, int(offsets.numel()) - 1, rec.data_ptr(), offsets.data_ptr(), float(weight)), "yn_fuse_append")
+
+    def merge(self, B, rule=MERGE_WBF, thresh=0.55, expected=0, handle=None):
+        """One read-back, the merge of the B lists by `rule` and the pack (yn_fuse_merge); expected 0 = the appends since open()."""
+        h = self.handle if handle is None else handle
+        self.n = None
+        h._ck(self.lib.yn_fuse_merge(h.h, self.obj, int(B), int(rule), float(thresh), int(expected)), "yn_fuse_merge")
+        self.n = int(B)
+
+    def result(self, total=False):
+        """(rec [max_units * list_capacity, 6] float32, offsets [B+1] int32) on the device: VIEWS of the object's buffers, valid until its
+        next call (yn_fuse_result)."""
+        return self._result_views(total, "merge()")
+
+    def lists_to_host(self, handle=None):
+        """Testing aid (yn_fuse_lists): the merge lists -> (boxes [B,cap,4], scores [B,cap], cls [B,cap] int32, count [B] int32)."""
+        h = self.handle if handle is None else handle
+        if self.lists is None:
+            raise YnError("yn_fuse_lists: no lists (open() first)")
+        B = self.lists
+        boxes, scores, cls, count = self._list_arrays(B)
+        h._ck(self.lib.yn_fuse_lists(h.h, self.obj, boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data), "yn_fuse_lists")
+        return boxes, scores, cls, count[:B]

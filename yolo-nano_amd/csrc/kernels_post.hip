@@ -2492,14 +2492,13 @@ static void set_sort_attr()
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(single_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, YN_SORT_LARGE * 8);
 }
 
-void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C,
-                         float nms_thresh, int diou, const NmsWork& wk,
-                         float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
-                         hipStream_t s, const NmsHook* hook, NmsPlan* plan)
+// The bucket + sort part of the chain, shared by the NMS route (launch_nms_pipeline) and the WBF route (launch_wbf_pipeline, kernels_wbf.hip):
+// afterwards seg_count / seg_off, the ids in pick order (wk.bucket) and their boxes (wk.sbox) stand, and wk.keep is zero.  Returns the size
+// ranking the later per-segment kernels take (null on the fused route, which produces none); rec gets few / fused / chunks / merge.
+const int32_t* launch_nms_bucket_sort(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C, const NmsWork& wk,
+                                      hipStream_t s, const NmsHook* hook, NmsPlan& rec)
 {
     set_sort_attr();
-    NmsPlan rec{};                                          // the decisions below, as they are taken (host ints only; copied out at the end)
-    rec.B = B; rec.N = N; rec.C = C; rec.diou = diou != 0;
     const int large_cap = wk.large_cap;
     auto mark = [&](const char* k) { if (hook && hook->fn) hook->fn(hook->ctx, k); };
     float4* sbox = reinterpret_cast<float4*>(wk.sbox);
@@ -2553,6 +2552,29 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
             hipLaunchKernelGGL(sort_kernel, dim3(large_cap, B), dim3(1024), 0, s, boxes, scores, wk.seg_count, wk.seg_off, wk.bucket, sbox,
                                N, C, YN_SORT_LARGE, 1 << 30, M, wk.matrix_stride, (const int32_t*)wk.large_list, large_cap, (const int32_t*)nullptr);
     }
+    return seg_order;
+}
+
+// compact_kernel on its own: the rows whose keep flag is set, in ascending row order (the WBF route gathers its side arrays with it)
+void launch_nms_compact(const float* boxes, const float* scores, const int32_t* cls, int B, int N, const NmsWork& wk,
+                        float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count, hipStream_t s)
+{
+    hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(1024), 0, s, boxes, scores, cls, wk.keep, N, out_boxes, out_scores, out_cls, out_index, count, wk.ovf, wk.ovf_host);
+}
+
+void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C,
+                         float nms_thresh, int diou, const NmsWork& wk,
+                         float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
+                         hipStream_t s, const NmsHook* hook, NmsPlan* plan)
+{
+    NmsPlan rec{};                                          // the decisions below, as they are taken (host ints only; copied out at the end)
+    rec.B = B; rec.N = N; rec.C = C; rec.diou = diou != 0;
+    const int large_cap = wk.large_cap;
+    auto mark = [&](const char* k) { if (hook && hook->fn) hook->fn(hook->ctx, k); };
+    float4* sbox = reinterpret_cast<float4*>(wk.sbox);
+    u64* M = reinterpret_cast<u64*>(wk.matrix);
+    const int32_t* seg_order = launch_nms_bucket_sort(boxes, scores, cls, B, N, C, wk, s, hook, rec);
+    const bool few = rec.few != 0;
     const int32_t* m_count = wk.seg_count;
     const int32_t* m_toff = wk.tile_off;
     const int32_t* m_ids = wk.bucket;

@@ -107,7 +107,9 @@ struct MergeLists {
     int belongs(yn_handle* h, const char* who) const;
     void drop_result() { last_n = -1; total = -1; }
     int open(yn_handle* h, int n);
-    int merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh);
+    int rule = YN_MERGE_NMS, expected = 0;                           // the merge rule (yn_*_merge_rule); expected 0: the client's default
+    int set_rule(yn_handle* h, const char* who, int rule_, int expected_);
+    int merge(yn_handle* h, const char* who, const char* unit, int n, float thresh, int default_expected);
     int empty_result(yn_handle* h, int n);
     int result(const float** rec_dev, const int32_t** offsets_dev, int32_t* total_out);
     int copy_lists(yn_handle* h, int n, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host) const;
@@ -133,6 +135,12 @@ struct yn_slice {
     ynk::DevBuf<int32_t> tstart;                                     // [T] of the current table
     MergeLists m;                                                    // one list per frame; lists_n = the frames of the table being appended
     int lists_T = 0, next_t = 0;                                     // that table's tiles, the tile the next chunk starts at
+};
+
+// record lists fused per unit (kernels_wbf.hip): the third client of the merge lists
+struct yn_fuse {
+    MergeLists m;                                                    // one list per unit
+    int appends = 0;                                                 // yn_fuse_append calls since yn_fuse_open: the default `expected`
 };
 
 struct yn_handle {
@@ -162,6 +170,9 @@ struct yn_handle {
     DevBuf<int32_t> nms_seg[10];          // seg_count, seg_off, tile_off, large_list, seg_count2, tile_off2, seg_order, seg_sparse, work_off, ctr
     DevBuf<unsigned long long> nms_matrix, nms_pre_sync;
     NmsWork nms{};                        // the view of that scratch launch_nms_pipeline takes, filled by ensure_post
+    DevBuf<float> wbf_box, wbf_score, wbf_ofb, wbf_op, wbf_os;       // weighted box fusion's side and overflow arrays (ensure_wbf), [B*N] each ([4] per box)
+    DevBuf<int32_t> wbf_votes, wbf_index, wbf_on, wbf_ofounder;
+    WbfWork wbf{};                        // the view of them launch_wbf_pipeline takes
     NmsPlan nms_plan{};                   // launch_nms_pipeline's decisions in the last yn_postprocess / yn_infer / yn_nms_merge (yn_nms_stages; B = 0: none yet)
     DevBuf<float> heads_buf;              // the three raw head tensors, one block
     float* heads_int[3] = {nullptr, nullptr, nullptr};    // its split for the current grid (ensure_heads)
@@ -453,6 +464,25 @@ int ensure_post(yn_handle* h, int B, int N, int C)
     w.large_cap = (N / 1024 + 1) < C ? (N / 1024 + 1) : C;       // at most N/1024 segments can exceed 1024 items
     if (moved) drop_graphs(h);
     if (rc) return fail(h, "NMS scratch for %d x %d candidates: %s", B, N, hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+// the NMS scratch (the WBF route starts with its bucket + sort) plus weighted box fusion's own arrays, owned the same way
+int ensure_wbf(yn_handle* h, int B, int N, int C)
+{
+    if (ensure_post(h, B, N, C)) return 1;
+    const size_t need = (size_t)B * N;
+    int rc = 0;
+    bool drained = false;
+    auto take = [&](auto& buf, size_t n) {
+        if (rc || n <= buf.cap()) return;
+        if (!drained) { rc = (int)hipStreamSynchronize(h->stream); drained = true; }
+        if (!rc) rc = buf.reserve(n);
+    };
+    take(h->wbf_box, need * 4); take(h->wbf_score, need); take(h->wbf_ofb, need * 4); take(h->wbf_op, need * 4); take(h->wbf_os, need);
+    take(h->wbf_votes, need); take(h->wbf_index, need); take(h->wbf_on, need); take(h->wbf_ofounder, need);
+    h->wbf = WbfWork{h->wbf_box, h->wbf_score, h->wbf_votes, h->wbf_index, h->wbf_ofb, h->wbf_op, h->wbf_os, h->wbf_on, h->wbf_ofounder};
+    if (rc) return fail(h, "weighted box fusion scratch for %d x %d rows: %s", B, N, hipGetErrorString((hipError_t)rc));
     return 0;
 }
 
@@ -2011,6 +2041,28 @@ int yn_nms_merge(yn_handle* h, const float* boxes, const float* scores, const in
     return 0;
 }
 
+int yn_wbf_lds_clusters(void) { return ynk::YN_WBF_LDS_CLUSTERS; }
+int64_t yn_wbf_cost(int64_t n_rows, int64_t n_clusters) { return (int64_t)ynk::wbf_cost(n_rows, n_clusters); }
+
+int yn_wbf_merge(yn_handle* h, const float* boxes, const float* scores, const int32_t* cls, int n, int num_classes, float iou_thresh, int expected,
+                 float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* out_votes, int32_t* assign, int32_t* count)
+{
+    YN_ENTER(h);
+    if (!count) return fail(h, "yn_wbf_merge: count_dev is null");
+    if (n < 0) return fail(h, "yn_wbf_merge: n is %d (a list has 0 or more rows)", n);
+    if (expected < 1) return fail(h, "yn_wbf_merge: expected is %d (the expected votes are an integer of at least 1)", expected);
+    if (num_classes != h->cfg.num_classes) return fail(h, "yn_wbf_merge: num_classes is %d, the handle has %d", num_classes, h->cfg.num_classes);
+    if (n == 0) { HIPCHK(h, hipMemsetAsync(count, 0, sizeof(int32_t), h->stream)); return 0; }
+    if (!boxes || !scores || !cls || !out_boxes || !out_scores || !out_cls) return fail(h, "yn_wbf_merge: null argument");
+    if (ensure_wbf(h, 1, n, num_classes)) return 1;
+    NmsWork wk = h->nms;
+    wk.ovf = nullptr; wk.ovf_host = nullptr;
+    launch_wbf_pipeline(boxes, scores, cls, 1, n, num_classes, iou_thresh, expected, wk, h->wbf, out_boxes, out_scores, out_cls, out_index, out_votes, assign,
+                        count, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // the candidate decode of raw heads that a forward wrote out (no fused front end ran): heads with row stride g.head_ld -> h->cand_*
 static void decode_raw_heads(yn_handle* h, float* const heads[3], const GridInfo& g, int B)
 {
@@ -2838,7 +2890,15 @@ int MergeLists::open(yn_handle* h, int n)
 
 // n filled lists -> ONE read-back (sizes, overflow flag, range mark), per-class NMS in yn_nms_merge's arithmetic (never DIoU), yn_pack_detections into
 // rec / offsets.  `unit` names a list's owner in the overflow message; lists_n is n once the lists have been read, before any refusal.
-int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh)
+int MergeLists::set_rule(yn_handle* h, const char* who, int rule_, int expected_)
+{
+    if (rule_ != YN_MERGE_NMS && rule_ != YN_MERGE_WBF) return fail(h, "%s: rule %d is neither YN_MERGE_NMS (0) nor YN_MERGE_WBF (1)", who, rule_);
+    if (expected_ < 0) return fail(h, "%s: expected is %d (0 = the object's default, else the expected votes, at least 1)", who, expected_);
+    rule = rule_; expected = expected_;
+    return 0;
+}
+
+int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh, int default_expected)
 {
     int32_t* st = state_host.data();
     HIPCHK(h, hipMemcpyAsync(st, state, (MERGE_STATE + n) * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -2855,10 +2915,19 @@ int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, fl
         return fail(h, "%s: the merge list of %s %d needs %d rows, list_capacity is %d (the largest list of the batch needs %d)", who, unit, worst,
                     st[MERGE_STATE + worst], cap, st[1]);
     }
-    if (ensure_post(h, n, cap, C)) return 1;
+    if (st[3]) {
+        const int worst = 4095 - (st[3] >> 19);
+        return fail(h, "%s: %s %d was appended %d rows whose class is not an integer in 0..%d", who, unit, worst, st[3] & ((1 << 19) - 1), C - 1);
+    }
+    if (rule == YN_MERGE_WBF ? ensure_wbf(h, n, cap, C) : ensure_post(h, n, cap, C)) return 1;
     NmsWork wk = h->nms;
     wk.ovf = nullptr; wk.ovf_host = nullptr;
-    launch_nms_pipeline(lb, ls, lc, n, cap, C, nms_thresh, 0, wk, mb, ms, mc, nullptr, mcount, h->stream);
+    if (rule == YN_MERGE_WBF) {
+        const int e = expected > 0 ? expected : (default_expected > 0 ? default_expected : 1);
+        launch_wbf_pipeline(lb, ls, lc, n, cap, C, nms_thresh, e, wk, h->wbf, mb, ms, mc, nullptr, nullptr, nullptr, mcount, h->stream);
+    } else {
+        launch_nms_pipeline(lb, ls, lc, n, cap, C, nms_thresh, 0, wk, mb, ms, mc, nullptr, mcount, h->stream);
+    }
     launch_pack(mb, ms, mc, mcount, n, cap, rec, offsets, h->stream);
     HIPCHK(h, hipGetLastError());
     last_n = n;
@@ -2996,7 +3065,14 @@ int yn_tta_infer(yn_handle* h, yn_tta* t, const float* x_dev, int B, int S0, flo
                           t->fstart, h->stream);
         HIPCHK(h, hipGetLastError());
     }
-    return m.merge(h, "yn_tta_infer", "image", B, nms_thresh);
+    return m.merge(h, "yn_tta_infer", "image", B, nms_thresh, (int)t->scales.size() * (t->flip ? 2 : 1));
+}
+
+int yn_merge_rule_tta(yn_handle* h, yn_tta* t, int rule, int expected)
+{
+    YN_ENTER(h);
+    if (!t) return fail(h, "yn_merge_rule_tta: null object");
+    return t->m.set_rule(h, "yn_merge_rule_tta", rule, expected);
 }
 
 int yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
@@ -3146,7 +3222,14 @@ int yn_slice_merge(yn_handle* h, yn_slice* s, int F, float nms_thresh)
     if (m.lists_n != F) return fail(h, "yn_slice_merge: the lists hold %d frames, not %d (yn_slice_append from tile 0 first)", m.lists_n, F);
     m.last_stream = h->stream;
     if (F == 0) return m.empty_result(h, 0);
-    return m.merge(h, "yn_slice_merge", "frame", F, nms_thresh);
+    return m.merge(h, "yn_slice_merge", "frame", F, nms_thresh, 1);
+}
+
+int yn_merge_rule_slice(yn_handle* h, yn_slice* s, int rule, int expected)
+{
+    YN_ENTER(h);
+    if (!s) return fail(h, "yn_merge_rule_slice: null object");
+    return s->m.set_rule(h, "yn_merge_rule_slice", rule, expected);
 }
 
 int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frames, const int32_t* shapes, int T, const int32_t* tiles, const float* mean,
@@ -3205,6 +3288,105 @@ int yn_slice_lists(yn_handle* h, yn_slice* s, float* boxes_host, float* scores_h
     if (F > 0 && s->m.copy_lists(h, F, boxes_host, scores_host, cls_host, count_host)) return 1;
     if (tile_start_host && s->lists_T > 0)
         HIPCHK(h, hipMemcpyAsync(tile_start_host, s->tstart, (size_t)s->lists_T * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- record lists fused per unit: ensembles, or a TTA result with a sliced one (kernels_wbf.hip) ----------------------------------
+void yn_fuse_destroy(yn_fuse* f)
+{
+    if (!f) return;
+    DeviceScope on(f->m.device);
+    (void)hipDeviceSynchronize();
+    delete f;
+}
+
+int yn_fuse_create(yn_handle* h, int max_units, int list_capacity, yn_fuse** out)
+{
+    YN_ENTER(h);
+    if (!out) return fail(h, "yn_fuse_create: null argument");
+    *out = nullptr;
+    if (max_units < 1 || max_units > 4096) return fail(h, "yn_fuse_create: max_units %d outside 1..4096", max_units);
+    if (list_capacity < 1 || list_capacity > nms_max_segment())
+        return fail(h, "yn_fuse_create: list_capacity %d outside 1..%d (the largest list the merge takes)", list_capacity, nms_max_segment());
+    yn_fuse* f = new yn_fuse();
+    Reserve take;
+    f->m.reserve(take, h->cfg, max_units, list_capacity);
+    if (take.rc) {
+        (void)hipGetLastError();
+        yn_fuse_destroy(f);
+        return fail(h, "yn_fuse_create: out of device memory (%zu bytes for %d units, %d rows per list)", take.failed, max_units, list_capacity);
+    }
+    if (!f->m.clear_once(h->stream)) {
+        yn_fuse_destroy(f);
+        return fail(h, "yn_fuse_create: clearing the merge lists failed");
+    }
+    *out = f;
+    return 0;
+}
+
+static int fuse_object(yn_handle* h, const yn_fuse* f, const char* who, int B)
+{
+    if (!f) return fail(h, "%s: null object", who);
+    if (f->m.belongs(h, who)) return 1;
+    if (B < 0 || B > f->m.units) return fail(h, "%s: %d units, the object's max_units is %d", who, B, f->m.units);
+    return 0;
+}
+
+int yn_fuse_open(yn_handle* h, yn_fuse* f, int B)
+{
+    YN_ENTER(h);
+    if (fuse_object(h, f, "yn_fuse_open", B)) return 1;
+    MergeLists& m = f->m;
+    m.drop_result(); m.lists_n = -1; m.last_stream = h->stream;
+    if (m.open(h, B)) return 1;
+    m.lists_n = B; f->appends = 0;
+    return 0;
+}
+
+int yn_fuse_append(yn_handle* h, yn_fuse* f, int B, const float* rec_dev, const int32_t* offsets_dev, float weight)
+{
+    YN_ENTER(h);
+    if (fuse_object(h, f, "yn_fuse_append", B)) return 1;
+    MergeLists& m = f->m;
+    if (m.lists_n != B) return fail(h, "yn_fuse_append: the lists hold %d units, not %d (yn_fuse_open first)", m.lists_n, B);
+    if (B > 0 && (!rec_dev || !offsets_dev)) return fail(h, "yn_fuse_append: null pointer");
+    if (B > 0 && ((uintptr_t)rec_dev & 7)) return fail(h, "yn_fuse_append: rec_dev must be 8-byte aligned (a record is loaded as three float2)");
+    if (weight != weight) return fail(h, "yn_fuse_append: weight is not a number");
+    m.drop_result(); m.last_stream = h->stream;
+    if (B > 0) {
+        launch_fuse_append(rec_dev, offsets_dev, B, m.C, m.cap, weight, m.lb, m.ls, m.lc, m.state, h->stream);
+        HIPCHK(h, hipGetLastError());
+    }
+    ++f->appends;
+    return 0;
+}
+
+int yn_fuse_merge(yn_handle* h, yn_fuse* f, int B, int rule, float thresh, int expected)
+{
+    YN_ENTER(h);
+    if (fuse_object(h, f, "yn_fuse_merge", B)) return 1;
+    MergeLists& m = f->m;
+    m.drop_result();
+    if (m.lists_n != B) return fail(h, "yn_fuse_merge: the lists hold %d units, not %d (yn_fuse_open first)", m.lists_n, B);
+    if (m.set_rule(h, "yn_fuse_merge", rule, expected)) return 1;
+    m.last_stream = h->stream;
+    if (B == 0) return m.empty_result(h, 0);
+    return m.merge(h, "yn_fuse_merge", "unit", B, thresh, f->appends);
+}
+
+int yn_fuse_result(yn_fuse* f, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
+{
+    return f ? f->m.result(rec_dev, offsets_dev, total) : 1;
+}
+
+int yn_fuse_lists(yn_handle* h, yn_fuse* f, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host)
+{
+    YN_ENTER(h);
+    if (!f) return fail(h, "yn_fuse_lists: null object");
+    if (f->m.lists_n < 0) return fail(h, "yn_fuse_lists: no yn_fuse_open has prepared the lists");
+    const int B = f->m.lists_n;
+    if (B > 0 && f->m.copy_lists(h, B, boxes_host, scores_host, cls_host, count_host)) return 1;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -254,6 +254,33 @@ void launch_nms_pipeline(const float* boxes, const float* scores, const int32_t*
                          float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count,
                          hipStream_t s, const NmsHook* hook = nullptr, NmsPlan* plan = nullptr);
 void launch_pack(const float* boxes, const float* scores, const int32_t* cls, const int32_t* count, int B, int N, float* rec, int32_t* offsets, hipStream_t s);
+// the chain's bucket + sort launches alone (what launch_nms_pipeline starts with) and its compaction alone: the two ends the WBF route shares
+const int32_t* launch_nms_bucket_sort(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C, const NmsWork& wk,
+                                      hipStream_t s, const NmsHook* hook, NmsPlan& rec);
+void launch_nms_compact(const float* boxes, const float* scores, const int32_t* cls, int B, int N, const NmsWork& wk,
+                        float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count, hipStream_t s);
+
+// ---- weighted box fusion (kernels_wbf.hip): the second merge rule of the merge lists -------------------------------------------------
+constexpr int YN_WBF_LDS_CLUSTERS = 512;        // clusters of a segment whose state lives in LDS; later ones live in WbfWork's overflow arrays
+struct WbfWork {                                // per-handle scratch beside NmsWork (ensure_wbf), all [B][N]
+    float* wbox;                                // [B][N][4] fused box, at the founder's row
+    float* wscore;                              // [B][N]    fused score, at the founder's row
+    int32_t* wvotes;                            // [B][N]    votes, at the founder's row
+    int32_t* windex;                            // [B][N]    founder rows of the compacted result (when the caller asks for none)
+    float* ofb; float* op;                      // [B][N][4] overflow clusters: fused box, sums of s * coord (cluster k of a segment at seg_off + k)
+    float* os; int32_t* on; int32_t* ofounder;  // [B][N]    their score sums, votes, founder rows
+};
+// B lists of N rows (class -1: not a row) -> per list the clusters in ascending founder row: fused box, fused score, class, founder row, votes;
+// assign [B][N] (or null): per input row the founder row of its cluster (-1 for a row that is none).  expected >= 1.
+void launch_wbf_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C, float iou_thresh, int expected,
+                         const NmsWork& wk, const WbfWork& ww, float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index,
+                         int32_t* out_votes, int32_t* assign, int32_t* count, hipStream_t s);
+// the documented cost model: lane steps of wbf_cluster_kernel for a segment of n_rows rows that ends in n_clusters clusters (upper bound)
+long long wbf_cost(long long n_rows, long long n_clusters);
+// rows [offsets[b], offsets[b + 1]) of rec (yn_pack_detections layout) -> the end of merge list b, score * weight (kernels_wbf.hip); state: MERGE_STATE words,
+// [3] = the bad-class mark ((4095 - unit) << 19 | rows, the lowest unit wins)
+void launch_fuse_append(const float* rec, const int32_t* offsets, int B, int C, int cap, float weight, float* lboxes, float* lscores, int32_t* lcls,
+                        int32_t* state, hipStream_t st);
 
 // ---- VOC mAP (kernels_eval.hip): the state behind yn_eval; 0 = ok, 1 = error (text in err), 2 = range mark (eval_add only) --------
 struct EvalState;

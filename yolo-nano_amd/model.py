@@ -680,10 +680,15 @@ class TestTimeAugmentation(object):
     Same constructor and call signature; the forwards run through the model's handle, the merge through yn_nms_merge."""
     __test__ = False                                           # not a pytest class
 
-    def __init__(self, num_classes=80, nms_thresh=0.4, scale_range=[320, 640, 32]):
+    def __init__(self, num_classes=80, nms_thresh=0.4, scale_range=[320, 640, 32], merge="nms", expected=None):
+        """merge: "nms" (the reference's per-class NMS) or "wbf" (weighted box fusion, yn_wbf_merge: nms_thresh is then its IoU
+        threshold); expected: WBF's expected votes, None = the number of forwards."""
+        from .capi import merge_rule_id
         self.num_classes = num_classes
         self.nms_thresh = nms_thresh
         self.scales = np.arange(scale_range[0], scale_range[1] + 1, scale_range[2])
+        self.merge, self._rule = merge, merge_rule_id(merge)
+        self.expected = None if expected is None else int(expected)
 
     def __call__(self, x, model):
         bboxes_list, scores_list, labels_list = [], [], []
@@ -710,6 +715,11 @@ class TestTimeAugmentation(object):
             return bboxes, scores, labels
         h = model.handle()
         dev = h.device
+        if self.merge == "wbf":
+            ob, osc, oc, _, _ = h.wbf_merge(torch.as_tensor(bboxes).to(dev), torch.as_tensor(scores).to(dev),
+                                            torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.nms_thresh,
+                                            2 * len(self.scales) if self.expected is None else self.expected)
+            return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
         ob, osc, oc, _ = h.nms_merge(torch.as_tensor(bboxes).to(dev), torch.as_tensor(scores).to(dev),
                                      torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.nms_thresh)
         return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
@@ -741,6 +751,7 @@ class TestTimeAugmentation(object):
                 obj.close()
             self._tta = None
             obj = self._tta = capi.Tta(h, [int(s) for s in self.scales], True, max_batch=max(int(B), 1), list_capacity=cap)
+        obj.merge_rule(self._rule, 0 if self.expected is None else self.expected, handle=h)
         return h
 
     def records(self, x, model):

@@ -76,7 +76,8 @@ def to_pixels(bboxes, h0, w0):
 class SlicedInference(object):
     """tile / overlap / full_frame: slice_grid's; nms_thresh: of the per-frame merge; edge_margin (pixels, < 0 off): a tile's box that comes
     within the margin of a side where the tile was cut out of the frame is dropped - the neighbouring tile sees that object whole;
-    list_capacity: rows of one frame's merge list; mean / std: ValTransforms' (BGR order).
+    list_capacity: rows of one frame's merge list; mean / std: ValTransforms' (BGR order); merge: "nms" (per-class NMS) or "wbf" (weighted box
+    fusion, yn_wbf_merge's rule: nms_thresh is then its IoU threshold) with `expected` votes (None: 1).
 
     Tiles run through the MODEL'S handle, `max_batch` of them per forward.  A handle is made for `chunk` (32) tiles only when the model has
     none yet: a model that already ran at batch 1 keeps that handle and slices one tile per forward - the same result (it does not depend on
@@ -84,7 +85,10 @@ class SlicedInference(object):
     slice first, to choose."""
 
     def __init__(self, tile=416, overlap=0.2, full_frame=True, nms_thresh=0.5, edge_margin=-1.0, list_capacity=8192,
-                 mean=(0.406, 0.456, 0.485), std=(0.225, 0.224, 0.229)):
+                 mean=(0.406, 0.456, 0.485), std=(0.225, 0.224, 0.229), merge="nms", expected=None):
+        from .capi import merge_rule_id
+        self.merge, self._rule = merge, merge_rule_id(merge)
+        self.expected = None if expected is None else int(expected)
         self.tile, self.overlap, self.full_frame = int(tile), overlap, bool(full_frame)
         self.nms_thresh, self.edge_margin, self.list_capacity = float(nms_thresh), float(edge_margin), int(list_capacity)
         self.mean = np.array(mean, dtype=np.float32)
@@ -116,6 +120,7 @@ class SlicedInference(object):
                 obj.close()
             self._obj = None
             obj = self._obj = capi.Slice(h, max_frames=max(int(F), 1), list_capacity=self.list_capacity)
+        obj.merge_rule(self._rule, 0 if self.expected is None else self.expected, handle=h)
         return h
 
     def records(self, frames, model):
