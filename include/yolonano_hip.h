@@ -283,6 +283,38 @@ int64_t yn_wbf_cost(int64_t n_rows, int64_t n_clusters);
 /* the merge rules of yn_tta / yn_slice / yn_fuse */
 enum { YN_MERGE_NMS = 0, YN_MERGE_WBF = 1 };
 
+/* ---- Soft-NMS (after Bodla et al., 2017): the per-class NMS with another suppression function.  A neighbour of a kept box is not dropped
+ * but has its score marked down by a function of the overlap (DESIGN.md 31 is the specification; tests/soft_nms_oracle.py restates it in
+ * float32 numpy and the kernel agrees bit for bit).  The rule is this package's own: parity with any third-party Soft-NMS is UNPINNED.
+ * It is NOT a third merge rule: it is how the YN_MERGE_NMS rule (and the NMS inside yn_infer / yn_postprocess) suppresses.
+ * Per (list, class) segment: the live rows are those with score > score_floor (strict: a NaN score is never live).  While a row is live,
+ * the live row with the largest CURRENT score is picked (equal scores: the higher row), kept with that score and taken out; every other
+ * live row's score is multiplied (one float32 multiply) by w(ovr), ovr in yn_nms_merge's arithmetic against the picked box (never DIoU),
+ * hit = !(ovr <= iou_thresh) (a NaN hits):
+ *     YN_SOFT_HARD      w = hit ? 0 : 1
+ *     YN_SOFT_LINEAR    w = hit ? 1 - ovr : 1
+ *     YN_SOFT_GAUSSIAN  w = E(-((ovr * ovr) / sigma)) for every row (iou_thresh is not used); E is the package's own float32 exp
+ * and the row leaves the live set unless its new score is > score_floor.  Kept rows are delivered in ascending row order: the box bit for
+ * bit, the decayed score, the class, the row.  With YN_SOFT_HARD, score_floor 0 and positive scores the result is yn_nms_merge's. */
+enum { YN_SOFT_OFF = 0, YN_SOFT_HARD = 1, YN_SOFT_LINEAR = 2, YN_SOFT_GAUSSIAN = 3 };
+/* The twin of yn_nms_merge / yn_wbf_merge, with their conventions: output buffers have capacity n, out_index may be NULL, n == 0 is an
+ * empty result, count_dev[0] = kept rows.  Refused, each by name: a method outside 1..3, a sigma that is not positive and finite, a
+ * score_floor that is negative or not finite, n < 0, num_classes other than the handle's.  No segment length is refused: the scores of
+ * rows past yn_soft_lds_rows() live in device memory. */
+int  yn_soft_nms_merge(yn_handle* h, const float* boxes_dev, const float* scores_dev, const int32_t* cls_dev, int n, int num_classes,
+                       int method, float iou_thresh, float sigma, float score_floor, float* out_boxes, float* out_scores, int32_t* out_cls,
+                       int32_t* out_index, int32_t* count_dev);
+/* How the per-class NMS inside yn_infer and yn_postprocess suppresses from now on.  YN_SOFT_OFF (the default) is the NMS chain, launch for
+ * launch; any other method runs the Soft-NMS route at the handle's nms_thresh with the same output layout and capacity (scores are the
+ * decayed ones).  Use the handle's conf_thresh as score_floor to keep the delivered scores at or above it.  A change drops the captured
+ * graphs.  With diou_nms set on the handle and a method other than OFF, yn_infer / yn_postprocess refuse by name: Soft-NMS has no DIoU
+ * form here.  yn_nms, yn_nms_merge and yn_nms_stages are not affected. */
+int  yn_soft_nms(yn_handle* h, int method, float sigma, float score_floor);
+/* rows of one (list, class) segment whose state the kernel keeps in LDS (a testing aid: cases straddle it) */
+int  yn_soft_lds_rows(void);
+/* testing aid: y_dev[i] = E(x_dev[i]) for n floats - the exp of YN_SOFT_GAUSSIAN on its own (E(NaN) = NaN, E(x < -87) = 0) */
+int  yn_op_soft_exp(yn_handle* h, const float* x_dev, float* y_dev, int64_t n);
+
 /* ValTransforms (data/transforms.py:445-458 = Resize :73-119 + Normalize :59-70 + ToTensor :394-398; call sites
  * benchmark.py:58, evaluator/vocapi_evaluator.py:64): img_dev = uint8 [h0][w0][3] BGR on the device -> x_dev float32
  * [3][side][side] RGB, normalised, letterboxed.  The caller supplies Resize's integer geometry (rw x rh resized extent placed
@@ -613,6 +645,14 @@ int  yn_fuse_result(yn_fuse* f, const float** rec_dev, const int32_t** offsets_d
 /* testing aid, like yn_slice_lists: boxes_host [B][list_capacity][4], scores_host / cls_host [B][list_capacity], count_host [B].  Any
  * pointer may be NULL.  Synchronises the stream. */
 int  yn_fuse_lists(yn_handle* h, yn_fuse* f, float* boxes_host, float* scores_host, int32_t* cls_host, int32_t* count_host);
+
+/* How the YN_MERGE_NMS rule of the object suppresses from now on: YN_SOFT_OFF (the default: per-class NMS as before) or a Soft-NMS method
+ * with its sigma and score_floor (yn_soft_nms_merge's rule per list; the float argument of yn_tta_infer / yn_slice_merge / yn_slice_infer
+ * / yn_fuse_merge stays the IoU threshold).  The setting is kept but unused while the object's rule is YN_MERGE_WBF.  Refused by name: a
+ * method outside 0..3, a sigma that is not positive and finite, a score_floor that is negative or not finite. */
+int  yn_merge_soft_tta(yn_handle* h, yn_tta* t, int method, float sigma, float score_floor);
+int  yn_merge_soft_slice(yn_handle* h, yn_slice* s, int method, float sigma, float score_floor);
+int  yn_merge_soft_fuse(yn_handle* h, yn_fuse* f, int method, float sigma, float score_floor);
 
 /* ---- detections painted onto frames in list order: test.py:50-92 / demo.py:48-71 (visualize, plot_bbox_labels) for B frames at once,
  * straight from the rec_dev / offsets_dev pair of yn_pack_detections or yn_tta_result: no read-back, no per-detection host work

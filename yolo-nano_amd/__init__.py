@@ -32,7 +32,7 @@ def __getattr__(name):
     if name in ("Visualizer", "class_colors", "default_font"):
         from . import draw                                    # numpy only until a Visualizer is made
         return getattr(draw, name)
-    if name in ("weighted_boxes_fusion", "Ensemble"):
+    if name in ("weighted_boxes_fusion", "soft_nms", "Ensemble"):
         from . import fusion                                  # numpy only until a fusion runs
         return getattr(fusion, name)
     if name == "Tracker":

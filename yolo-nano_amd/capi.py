@@ -163,6 +163,13 @@ SIGNATURES = {
     "yn_wbf_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yn_wbf_lds_clusters": (_i32, []),
     "yn_wbf_cost": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "yn_soft_nms_merge": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "yn_soft_nms": (_i32, [_vp, _i32, _f32, _f32]),
+    "yn_soft_lds_rows": (_i32, []),
+    "yn_op_soft_exp": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
+    "yn_merge_soft_tta": (_i32, [_vp, _vp, _i32, _f32, _f32]),
+    "yn_merge_soft_slice": (_i32, [_vp, _vp, _i32, _f32, _f32]),
+    "yn_merge_soft_fuse": (_i32, [_vp, _vp, _i32, _f32, _f32]),
     "yn_merge_rule_tta": (_i32, [_vp, _vp, _i32, _i32]),
     "yn_merge_rule_slice": (_i32, [_vp, _vp, _i32, _i32]),
     "yn_fuse_create": (_i32, [_vp, _i32, _i32, ctypes.POINTER(_vp)]),
@@ -822,6 +829,35 @@ class Handle:
         out = (ob[:k], osc[:k], oc[:k], oi[:k], ov[:k])
         return out + (asg[:n],) if assign else out
 
+    def soft_nms_merge(self, boxes, scores, cls, num_classes, method, iou_thresh=0.5, sigma=0.5, score_floor=0.001):
+        """Soft-NMS over a detection list (yn_soft_nms_merge) -> (boxes [K,4], scores [K] decayed, cls [K], row [K]), the kept
+        rows in ascending row order.  method: SOFT_HARD / SOFT_LINEAR / SOFT_GAUSSIAN or its name."""
+        n = int(boxes.shape[0])
+        method = soft_method_id(method) if isinstance(method, str) else int(method)
+        boxes = self._in(boxes); scores = self._in(scores); cls = self._in(cls, torch.int32)
+        ob = torch.empty((max(n, 1), 4), dtype=torch.float32, device=self.device)
+        osc = torch.empty((max(n, 1),), dtype=torch.float32, device=self.device)
+        oc, oi = (torch.empty((max(n, 1),), dtype=torch.int32, device=self.device) for _ in range(2))
+        cnt = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._ck(self.lib.yn_soft_nms_merge(self.h, boxes.data_ptr(), scores.data_ptr(), cls.data_ptr(), n, int(num_classes), method,
+                                            float(iou_thresh), float(sigma), float(score_floor), ob.data_ptr(), osc.data_ptr(), oc.data_ptr(),
+                                            oi.data_ptr(), cnt.data_ptr()), "yn_soft_nms_merge")
+        k = int(cnt.item())
+        return ob[:k], osc[:k], oc[:k], oi[:k]
+
+    def soft_nms(self, method, sigma=0.5, score_floor=0.0):
+        """How the NMS inside infer() / postprocess() suppresses from now on (yn_soft_nms): None / SOFT_OFF = the NMS chain as before, else
+        "hard" / "linear" / "gaussian" (or SOFT_*) at the handle's nms_thresh.  score_floor: rows at or below it are dropped."""
+        method = soft_method_id(method) if method is None or isinstance(method, str) else int(method)
+        self._ck(self.lib.yn_soft_nms(self.h, method, float(sigma), float(score_floor)), "yn_soft_nms")
+
+    def soft_exp(self, x):
+        """Testing aid (yn_op_soft_exp): E(x), the exp of the gaussian method, elementwise over a float32 tensor."""
+        x = self._in(x)
+        y = torch.empty_like(x)
+        self._ck(self.lib.yn_op_soft_exp(self.h, _ptr(x), _ptr(y), x.numel()), "yn_op_soft_exp")
+        return y
+
     def ema_update(self, ema, model, decay):
         """ema = ema * d + (1 - d) * model, in place (utils/misc.py:83-86); float32 tensors of equal size on this device."""
         assert ema.is_contiguous() and model.is_contiguous() and ema.numel() == model.numel() and ema.dtype == model.dtype == torch.float32
@@ -1330,6 +1366,24 @@ def merge_rule_id(merge):
     return MERGE_RULES[merge]
 
 
+SOFT_OFF, SOFT_HARD, SOFT_LINEAR, SOFT_GAUSSIAN = 0, 1, 2, 3      # YN_SOFT_*
+SOFT_METHODS = {None: SOFT_OFF, "hard": SOFT_HARD, "linear": SOFT_LINEAR, "gaussian": SOFT_GAUSSIAN}
+
+
+def soft_method_id(soft):
+    """None / "hard" / "linear" / "gaussian" -> YN_SOFT_*; anything else is refused by name."""
+    if not (soft is None or isinstance(soft, str)) or soft not in SOFT_METHODS:
+        raise ValueError("soft must be None, 'hard', 'linear' or 'gaussian', got %r" % (soft,))
+    return SOFT_METHODS[soft]
+
+
+def check_soft_with_merge(who, merge, soft):
+    """Soft-NMS is how the "nms" rule suppresses: it does not combine with merge="wbf"."""
+    if soft is not None and merge == "wbf":
+        raise ValueError("%s: soft=%r cannot be combined with merge='wbf' (Soft-NMS is a suppression of the 'nms' rule)" % (who, soft))
+    return soft_method_id(soft)
+
+
 class _DeviceView:
     """A region of device memory the library owns, in the form torch.as_tensor adopts without a copy."""
 
@@ -1340,7 +1394,7 @@ class _DeviceView:
 
 class _MergeObject:
     """What Tta and Slice share: the object's lifetime, the (rec, offsets) views of its result and the host arrays of its merge lists.  A subclass
-    names its C functions (_destroy, _result) and sets .obj, .units (its max_batch / max_frames) and .n (the units of the result, None: no
+    names its C functions (_destroy, _result, _soft) and sets .obj, .units (its max_batch / max_frames) and .n (the units of the result, None: no
     result)."""
 
     def close(self):
@@ -1353,6 +1407,13 @@ class _MergeObject:
             self.close()
         except Exception:
             pass
+
+    def merge_soft(self, method, sigma=0.5, score_floor=0.001, handle=None):
+        """How the object's MERGE_NMS rule suppresses from now on (yn_merge_soft_tta / _slice / _fuse): None / SOFT_OFF = per-class NMS as
+        before, else "hard" / "linear" / "gaussian" (or SOFT_*).  Kept but unused while the rule is MERGE_WBF."""
+        h = self.handle if handle is None else handle
+        method = soft_method_id(method) if method is None or isinstance(method, str) else int(method)
+        h._ck(getattr(self.lib, self._soft)(h.h, self.obj, method, float(sigma), float(score_floor)), self._soft)
 
     def _result_views(self, total, hint):
         if self.n is None:
@@ -1374,7 +1435,7 @@ class _MergeObject:
 class Tta(_MergeObject):
     """One yn_tta: test-time augmentation for whole batches.  Thin, 1:1 with the C ABI; `handle` gives the device, the anchors per cell
     and the class count, and is the default handle of infer()."""
-    _destroy, _result = "yn_tta_destroy", "yn_tta_result"
+    _destroy, _result, _soft = "yn_tta_destroy", "yn_tta_result", "yn_merge_soft_tta"
 
     def __init__(self, handle, scales, flip=True, max_batch=1, list_capacity=8192):
         self.lib = handle.lib
@@ -1425,7 +1486,7 @@ class Slice(_MergeObject):
     """One yn_slice: sliced inference - tiles of large frames, merged per frame.  Thin, 1:1 with the C ABI; `handle` gives the device, the
     anchors per cell and the class count, and is the default handle of every call.  Frames are uint8 [h0,w0,3] CUDA tensors, `tiles` an
     int32 [T,9] table (slicing.tile_table)."""
-    _destroy, _result = "yn_slice_destroy", "yn_slice_result"
+    _destroy, _result, _soft = "yn_slice_destroy", "yn_slice_result", "yn_merge_soft_slice"
 
     def __init__(self, handle, max_frames=1, list_capacity=8192):
         self.lib = handle.lib
@@ -1530,7 +1591,7 @@ class Slice(_MergeObject):
 
 class Fuse(_MergeObject):
     """One yn_fuse: record lists fused per unit - ensembles of models, or a TTA result with a sliced one.  Thin, 1:1 with the C ABI."""
-    _destroy, _result = "yn_fuse_destroy", "yn_fuse_result"
+    _destroy, _result, _soft = "yn_fuse_destroy", "yn_fuse_result", "yn_merge_soft_fuse"
 
     def __init__(self, handle, max_units=1, list_capacity=8192):
         self.lib = handle.lib

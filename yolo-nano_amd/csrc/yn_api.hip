@@ -109,6 +109,8 @@ struct MergeLists {
     int open(yn_handle* h, int n);
     int rule = YN_MERGE_NMS, expected = 0;                           // the merge rule (yn_*_merge_rule); expected 0: the client's default
     int set_rule(yn_handle* h, const char* who, int rule_, int expected_);
+    int soft = YN_SOFT_OFF; float soft_sigma = 0.5f, soft_floor = 0.0f;      // how the YN_MERGE_NMS rule suppresses (yn_merge_soft_*)
+    int set_soft(yn_handle* h, const char* who, int method, float sigma, float score_floor);
     int merge(yn_handle* h, const char* who, const char* unit, int n, float thresh, int default_expected);
     int empty_result(yn_handle* h, int n);
     int result(const float** rec_dev, const int32_t** offsets_dev, int32_t* total_out);
@@ -173,6 +175,10 @@ struct yn_handle {
     DevBuf<float> wbf_box, wbf_score, wbf_ofb, wbf_op, wbf_os;       // weighted box fusion's side and overflow arrays (ensure_wbf), [B*N] each ([4] per box)
     DevBuf<int32_t> wbf_votes, wbf_index, wbf_on, wbf_ofounder;
     WbfWork wbf{};                        // the view of them launch_wbf_pipeline takes
+    DevBuf<float> soft_score, soft_spill; // Soft-NMS's side scores and spilled scores (ensure_soft, allocated on the first soft call), [B*N] each
+    SoftWork soft{};                      // the view of them launch_soft_pipeline takes
+    int soft_method = YN_SOFT_OFF;        // how yn_infer's / yn_postprocess's NMS suppresses (yn_soft_nms)
+    float soft_sigma = 0.5f, soft_floor = 0.0f;
     NmsPlan nms_plan{};                   // launch_nms_pipeline's decisions in the last yn_postprocess / yn_infer / yn_nms_merge (yn_nms_stages; B = 0: none yet)
     DevBuf<float> heads_buf;              // the three raw head tensors, one block
     float* heads_int[3] = {nullptr, nullptr, nullptr};    // its split for the current grid (ensure_heads)
@@ -485,6 +491,36 @@ int ensure_wbf(yn_handle* h, int B, int N, int C)
     if (rc) return fail(h, "weighted box fusion scratch for %d x %d rows: %s", B, N, hipGetErrorString((hipError_t)rc));
     return 0;
 }
+
+// the NMS scratch (the Soft-NMS route starts with its bucket + sort) plus Soft-NMS's two score arrays; yn_infer captures them in its graphs
+int ensure_soft(yn_handle* h, int B, int N, int C)
+{
+    if (ensure_post(h, B, N, C)) return 1;
+    const size_t need = (size_t)B * N;
+    int rc = 0;
+    bool moved = false, drained = false;
+    auto take = [&](auto& buf, size_t n) {
+        if (rc || n <= buf.cap()) return;
+        if (!drained) { rc = (int)hipStreamSynchronize(h->stream); drained = true; }
+        if (!rc) rc = buf.reserve(n, 0, &moved);
+    };
+    take(h->soft_score, need); take(h->soft_spill, need);
+    h->soft = SoftWork{h->soft_score, h->soft_spill};
+    if (moved) drop_graphs(h);
+    if (rc) return fail(h, "Soft-NMS scratch for %d x %d rows: %s", B, N, hipGetErrorString((hipError_t)rc));
+    return 0;
+}
+
+// the parameter checks every Soft-NMS entry shares; lo = the smallest method the entry takes (YN_SOFT_OFF for the setters, YN_SOFT_HARD for a merge)
+int soft_params(yn_handle* h, const char* who, int lo, int method, float sigma, float score_floor)
+{
+    if (method < lo || method > YN_SOFT_GAUSSIAN)
+        return fail(h, "%s: method %d is not %sYN_SOFT_HARD (1), YN_SOFT_LINEAR (2) or YN_SOFT_GAUSSIAN (3)", who, method, lo == YN_SOFT_OFF ? "YN_SOFT_OFF (0), " : "");
+    if (!(sigma > 0.0f) || sigma > 3.4028234e38f) return fail(h, "%s: sigma is %g (it must be positive and finite)", who, (double)sigma);
+    if (!(score_floor >= 0.0f) || score_floor > 3.4028234e38f) return fail(h, "%s: score_floor is %g (it must be 0 or more and finite)", who, (double)score_floor);
+    return 0;
+}
+static_assert(YN_SOFT_HARD == ynk::SOFT_HARD && YN_SOFT_LINEAR == ynk::SOFT_LINEAR && YN_SOFT_GAUSSIAN == ynk::SOFT_GAUSSIAN, "Soft-NMS methods (yn_internal.h)");
 
 int ensure_heads(yn_handle* h, int B)
 {
@@ -1903,10 +1939,16 @@ int yn_postprocess(yn_handle* h, const float* all_local, const float* all_conf, 
     YN_ENTER(h);
     if (B <= 0 || N < 0 || C <= 0) return fail(h, "yn_postprocess: bad sizes B=%d N=%d C=%d", B, N, C);
     if (N == 0) { HIPCHK(h, hipMemsetAsync(count, 0, sizeof(int32_t) * B, h->stream)); return 0; }
-    if (ensure_post(h, B, N, C)) return 1;
+    const bool soft = h->soft_method != YN_SOFT_OFF;
+    if (soft && h->cfg.diou_nms) return fail(h, "yn_postprocess: Soft-NMS (yn_soft_nms method %d) has no DIoU form; clear diou_nms or set YN_SOFT_OFF", h->soft_method);
+    if (soft ? ensure_soft(h, B, N, C) : ensure_post(h, B, N, C)) return 1;
     launch_argmax_cand(all_local, all_conf, B, N, C, h->cfg.conf_thresh, h->cand_boxes, h->cand_scores, h->cand_cls, h->stream);
-    launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, N, C, h->cfg.nms_thresh, h->cfg.diou_nms, h->nms,
-                        out_boxes, out_scores, out_cls, out_index, count, h->stream, nullptr, &h->nms_plan);
+    if (soft)
+        launch_soft_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, N, C, h->soft_method, h->cfg.nms_thresh, h->soft_sigma, h->soft_floor, h->nms,
+                             h->soft, out_boxes, out_scores, out_cls, out_index, count, h->stream);
+    else
+        launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, N, C, h->cfg.nms_thresh, h->cfg.diou_nms, h->nms,
+                            out_boxes, out_scores, out_cls, out_index, count, h->stream, nullptr, &h->nms_plan);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -2063,6 +2105,46 @@ int yn_wbf_merge(yn_handle* h, const float* boxes, const float* scores, const in
     return 0;
 }
 
+int yn_soft_lds_rows(void) { return ynk::YN_SOFT_LDS_ROWS; }
+
+int yn_soft_nms_merge(yn_handle* h, const float* boxes, const float* scores, const int32_t* cls, int n, int num_classes, int method, float iou_thresh,
+                      float sigma, float score_floor, float* out_boxes, float* out_scores, int32_t* out_cls, int32_t* out_index, int32_t* count)
+{
+    YN_ENTER(h);
+    if (!count) return fail(h, "yn_soft_nms_merge: count_dev is null");
+    if (n < 0) return fail(h, "yn_soft_nms_merge: n is %d (a list has 0 or more rows)", n);
+    if (soft_params(h, "yn_soft_nms_merge", YN_SOFT_HARD, method, sigma, score_floor)) return 1;
+    if (num_classes != h->cfg.num_classes) return fail(h, "yn_soft_nms_merge: num_classes is %d, the handle has %d", num_classes, h->cfg.num_classes);
+    if (n == 0) { HIPCHK(h, hipMemsetAsync(count, 0, sizeof(int32_t), h->stream)); return 0; }
+    if (!boxes || !scores || !cls || !out_boxes || !out_scores || !out_cls) return fail(h, "yn_soft_nms_merge: null argument");
+    if (ensure_soft(h, 1, n, num_classes)) return 1;
+    NmsWork wk = h->nms;
+    wk.ovf = nullptr; wk.ovf_host = nullptr;
+    launch_soft_pipeline(boxes, scores, cls, 1, n, num_classes, method, iou_thresh, sigma, score_floor, wk, h->soft, out_boxes, out_scores, out_cls, out_index,
+                         count, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int yn_soft_nms(yn_handle* h, int method, float sigma, float score_floor)
+{
+    YN_ENTER(h);
+    if (soft_params(h, "yn_soft_nms", YN_SOFT_OFF, method, sigma, score_floor)) return 1;
+    if (method != h->soft_method || sigma != h->soft_sigma || score_floor != h->soft_floor) drop_graphs(h);
+    h->soft_method = method; h->soft_sigma = sigma; h->soft_floor = score_floor;
+    return 0;
+}
+
+int yn_op_soft_exp(yn_handle* h, const float* x, float* y, int64_t n)
+{
+    YN_ENTER(h);
+    if (n < 0) return fail(h, "yn_op_soft_exp: n is %lld", (long long)n);
+    if (n > 0 && (!x || !y)) return fail(h, "yn_op_soft_exp: null argument");
+    launch_soft_exp(x, y, (long)n, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // the candidate decode of raw heads that a forward wrote out (no fused front end ran): heads with row stride g.head_ld -> h->cand_*
 static void decode_raw_heads(yn_handle* h, float* const heads[3], const GridInfo& g, int B)
 {
@@ -2079,7 +2161,9 @@ int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* o
     if (int rp = range_pending(h, "yn_infer")) return rp;
     GridInfo g = h->grid;
     g.head_ld = (h->head_ch + 3) & ~3;
-    if (ensure_arena(h, B, g.H, g.W) || ensure_post(h, B, g.N, g.C) || ensure_heads(h, B)) return 1;
+    const bool soft = h->soft_method != YN_SOFT_OFF;
+    if (soft && h->cfg.diou_nms) return fail(h, "yn_infer: Soft-NMS (yn_soft_nms method %d) has no DIoU form; clear diou_nms or set YN_SOFT_OFF", h->soft_method);
+    if (ensure_arena(h, B, g.H, g.W) || (soft ? ensure_soft(h, B, g.N, g.C) : ensure_post(h, B, g.N, g.C)) || ensure_heads(h, B)) return 1;
     std::vector<uintptr_t> key = {2, (uintptr_t)B, (uintptr_t)g.H, (uintptr_t)g.W, (uintptr_t)g.side, (uintptr_t)g.left, (uintptr_t)g.top, (uintptr_t)x_dev, (uintptr_t)out_boxes, (uintptr_t)out_scores,
                                   (uintptr_t)out_cls, (uintptr_t)out_index, (uintptr_t)count};
     return run_maybe_graph(h, key, [&]() {
@@ -2099,8 +2183,12 @@ int yn_infer(yn_handle* h, const float* x_dev, int B, float* out_boxes, float* o
             NmsWork wk = h->nms;
             wk.ovf = exact(h) ? nullptr : h->range_flags + 1;         // the network's range flag rides out with the counts (compact_kernel)
             wk.ovf_host = exact(h) ? nullptr : h->range_host_dev;     // ... and into the handle's pinned word (range_pending)
-            launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, g.N, g.C, h->cfg.nms_thresh, h->cfg.diou_nms, wk,
-                                out_boxes, out_scores, out_cls, out_index, count, h->stream, h->profiling ? &hook : nullptr, &h->nms_plan);
+            if (soft)
+                launch_soft_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, g.N, g.C, h->soft_method, h->cfg.nms_thresh, h->soft_sigma, h->soft_floor,
+                                     wk, h->soft, out_boxes, out_scores, out_cls, out_index, count, h->stream, h->profiling ? &hook : nullptr);
+            else
+                launch_nms_pipeline(h->cand_boxes, h->cand_scores, h->cand_cls, B, g.N, g.C, h->cfg.nms_thresh, h->cfg.diou_nms, wk,
+                                    out_boxes, out_scores, out_cls, out_index, count, h->stream, h->profiling ? &hook : nullptr, &h->nms_plan);
             delete ctx.cur;
         }
         HIPCHK(h, hipGetLastError());
@@ -2898,6 +2986,13 @@ int MergeLists::set_rule(yn_handle* h, const char* who, int rule_, int expected_
     return 0;
 }
 
+int MergeLists::set_soft(yn_handle* h, const char* who, int method, float sigma, float score_floor)
+{
+    if (soft_params(h, who, YN_SOFT_OFF, method, sigma, score_floor)) return 1;
+    soft = method; soft_sigma = sigma; soft_floor = score_floor;
+    return 0;
+}
+
 int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, float nms_thresh, int default_expected)
 {
     int32_t* st = state_host.data();
@@ -2919,12 +3014,15 @@ int MergeLists::merge(yn_handle* h, const char* who, const char* unit, int n, fl
         const int worst = 4095 - (st[3] >> 19);
         return fail(h, "%s: %s %d was appended %d rows whose class is not an integer in 0..%d", who, unit, worst, st[3] & ((1 << 19) - 1), C - 1);
     }
-    if (rule == YN_MERGE_WBF ? ensure_wbf(h, n, cap, C) : ensure_post(h, n, cap, C)) return 1;
+    const bool soft_on = rule == YN_MERGE_NMS && soft != YN_SOFT_OFF;      // (the setting is kept but unused under the WBF rule)
+    if (rule == YN_MERGE_WBF ? ensure_wbf(h, n, cap, C) : (soft_on ? ensure_soft(h, n, cap, C) : ensure_post(h, n, cap, C))) return 1;
     NmsWork wk = h->nms;
     wk.ovf = nullptr; wk.ovf_host = nullptr;
     if (rule == YN_MERGE_WBF) {
         const int e = expected > 0 ? expected : (default_expected > 0 ? default_expected : 1);
         launch_wbf_pipeline(lb, ls, lc, n, cap, C, nms_thresh, e, wk, h->wbf, mb, ms, mc, nullptr, nullptr, nullptr, mcount, h->stream);
+    } else if (soft_on) {
+        launch_soft_pipeline(lb, ls, lc, n, cap, C, soft, nms_thresh, soft_sigma, soft_floor, wk, h->soft, mb, ms, mc, nullptr, mcount, h->stream);
     } else {
         launch_nms_pipeline(lb, ls, lc, n, cap, C, nms_thresh, 0, wk, mb, ms, mc, nullptr, mcount, h->stream);
     }
@@ -3073,6 +3171,13 @@ int yn_merge_rule_tta(yn_handle* h, yn_tta* t, int rule, int expected)
     YN_ENTER(h);
     if (!t) return fail(h, "yn_merge_rule_tta: null object");
     return t->m.set_rule(h, "yn_merge_rule_tta", rule, expected);
+}
+
+int yn_merge_soft_tta(yn_handle* h, yn_tta* t, int method, float sigma, float score_floor)
+{
+    YN_ENTER(h);
+    if (!t) return fail(h, "yn_merge_soft_tta: null object");
+    return t->m.set_soft(h, "yn_merge_soft_tta", method, sigma, score_floor);
 }
 
 int yn_tta_result(yn_tta* t, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)
@@ -3232,6 +3337,13 @@ int yn_merge_rule_slice(yn_handle* h, yn_slice* s, int rule, int expected)
     return s->m.set_rule(h, "yn_merge_rule_slice", rule, expected);
 }
 
+int yn_merge_soft_slice(yn_handle* h, yn_slice* s, int method, float sigma, float score_floor)
+{
+    YN_ENTER(h);
+    if (!s) return fail(h, "yn_merge_soft_slice: null object");
+    return s->m.set_soft(h, "yn_merge_soft_slice", method, sigma, score_floor);
+}
+
 int yn_slice_infer(yn_handle* h, yn_slice* s, int F, const uint8_t* const* frames, const int32_t* shapes, int T, const int32_t* tiles, const float* mean,
                    const float* stdv, float nms_thresh, float edge_margin)
 {
@@ -3373,6 +3485,13 @@ int yn_fuse_merge(yn_handle* h, yn_fuse* f, int B, int rule, float thresh, int e
     m.last_stream = h->stream;
     if (B == 0) return m.empty_result(h, 0);
     return m.merge(h, "yn_fuse_merge", "unit", B, thresh, f->appends);
+}
+
+int yn_merge_soft_fuse(yn_handle* h, yn_fuse* f, int method, float sigma, float score_floor)
+{
+    YN_ENTER(h);
+    if (!f) return fail(h, "yn_merge_soft_fuse: null object");
+    return f->m.set_soft(h, "yn_merge_soft_fuse", method, sigma, score_floor);
 }
 
 int yn_fuse_result(yn_fuse* f, const float** rec_dev, const int32_t** offsets_dev, int32_t* total)

@@ -282,6 +282,21 @@ long long wbf_cost(long long n_rows, long long n_clusters);
 void launch_fuse_append(const float* rec, const int32_t* offsets, int B, int C, int cap, float weight, float* lboxes, float* lscores, int32_t* lcls,
                         int32_t* state, hipStream_t st);
 
+// ---- Soft-NMS (kernels_soft.hip): the NMS rule with another suppression function -----------------------------------------------------
+constexpr int YN_SOFT_LDS_ROWS = 2048;          // rows of a segment whose state (box, score, row id: 24 bytes) lives in LDS - 48 KB, three workgroups per CU;
+                                                // the scores of later rows live in SoftWork's spill array, their boxes stay in NmsWork's sbox
+constexpr int SOFT_HARD = 1, SOFT_LINEAR = 2, SOFT_GAUSSIAN = 3;      // YN_SOFT_* of the C header (yn_api.hip asserts the match)
+struct SoftWork {                               // per-handle scratch beside NmsWork (ensure_soft), both [B][N]
+    float* wscore;                              // the kept rows' decayed scores, at their rows
+    float* spill;                               // current scores of the rows past YN_SOFT_LDS_ROWS, at their sorted slots
+};
+// B lists of N rows (class -1: not a row) -> per list the kept rows in ascending row order: box bit for bit, decayed score, class, row.
+// method: SOFT_HARD / SOFT_LINEAR / SOFT_GAUSSIAN; sigma > 0 and score_floor >= 0, both finite (checked by the callers).
+void launch_soft_pipeline(const float* boxes, const float* scores, const int32_t* cls, int B, int N, int C, int method, float iou_thresh,
+                          float sigma, float score_floor, const NmsWork& wk, const SoftWork& sw, float* out_boxes, float* out_scores,
+                          int32_t* out_cls, int32_t* out_index, int32_t* count, hipStream_t s, const NmsHook* hook = nullptr);
+void launch_soft_exp(const float* x, float* y, long n, hipStream_t s);      // y = E(x), the package's exp for x <= 0 (testing aid)
+
 // ---- VOC mAP (kernels_eval.hip): the state behind yn_eval; 0 = ok, 1 = error (text in err), 2 = range mark (eval_add only) --------
 struct EvalState;
 int  eval_create(int device, int C, double ovthresh, EvalState** out, std::string& err);

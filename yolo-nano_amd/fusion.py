@@ -5,10 +5,16 @@ with the ensemble_boxes package is UNPINNED: the call shapes below follow it, th
 
     boxes, scores, labels = weighted_boxes_fusion(boxes_list, scores_list, labels_list, iou_thr=0.55)
     ens = Ensemble([model_a, model_b]); rec, offsets = ens.records(x); per_image = ens.batch(x)
+
+Soft-NMS (yn_soft_nms_merge; csrc/kernels_soft.hip) keeps the neighbours of a kept box and marks their scores down; the rule
+is the package's own as well (tests/soft_nms_oracle.py), parity with third-party implementations UNPINNED.
+
+    boxes, scores, labels = soft_nms(boxes, scores, labels, method="gaussian", sigma=0.5)
+    ens = Ensemble([model_a, model_b], merge="nms", soft="linear")
 """
 import numpy as np
 
-from .capi import MERGE_WBF, YnError, merge_rule_id, records_to_host
+from .capi import MERGE_WBF, YnError, check_soft_with_merge, merge_rule_id, records_to_host, soft_method_id
 
 _handles = {}
 
@@ -68,13 +74,44 @@ def weighted_boxes_fusion(boxes_list, scores_list, labels_list, iou_thr=0.55, ex
     return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
 
 
+def soft_nms(boxes, scores, labels, method="gaussian", iou_thr=0.5, sigma=0.5, score_floor=0.001, num_classes=None, device=None):
+    """One image: boxes [n, 4], scores [n], labels [n] (integers) -> (boxes [K, 4] f32, scores [K] f32 decayed, labels [K] i64), the kept rows
+    in ascending row order.  method "hard" / "linear" / "gaussian" (DESIGN.md 31); rows whose score is or falls to score_floor or below are
+    dropped.  Runs yn_soft_nms_merge on the GPU (there is no CPU fallback)."""
+    import torch
+    if method is None:
+        raise ValueError("soft_nms: method must be 'hard', 'linear' or 'gaussian', got None")
+    m = soft_method_id(method)
+    b = np.asarray(boxes, np.float32).reshape(-1, 4)
+    s = np.asarray(scores, np.float32).reshape(-1)
+    lab = np.asarray(labels).reshape(-1)
+    if not (len(b) == len(s) == len(lab)):
+        raise ValueError("soft_nms: %d boxes, %d scores, %d labels" % (len(b), len(s), len(lab)))
+    if len(lab) and not np.array_equal(lab, np.floor(lab)):
+        raise ValueError("soft_nms: a label is not an integer")
+    lab = lab.astype(np.int64)
+    if len(lab) and lab.min() < 0:
+        raise ValueError("soft_nms: negative label")
+    C = int(num_classes) if num_classes is not None else (int(lab.max()) + 1 if len(lab) else 1)
+    if len(lab) and lab.max() >= C:
+        raise ValueError("soft_nms: label %d with num_classes %d" % (int(lab.max()), C))
+    if len(b) == 0:
+        return b, s, lab
+    h = _bare_handle(C, device)
+    ob, osc, oc, _ = h.soft_nms_merge(torch.from_numpy(b).to(h.device), torch.from_numpy(s).to(h.device),
+                                      torch.from_numpy(lab.astype(np.int32)).to(h.device), C, m, iou_thr, sigma, score_floor)
+    return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
+
+
 class Ensemble(object):
     """Several YOLONano models of one class count on one batch: each model's yn_infer + yn_pack_detections is appended to the B merge
     lists of a yn_fuse and the lists are merged once (merge "wbf": weighted box fusion, "nms": per-class NMS) at iou_thr.  weights: one
-    score factor per model.  records() gives the device record lists VOCEval.add / COCOEval.add / Visualizer / Tracker take."""
+    score factor per model.  soft ("hard" / "linear" / "gaussian", with merge="nms" only): the NMS merge suppresses by Soft-NMS.  records() gives the device record lists VOCEval.add / COCOEval.add / Visualizer / Tracker take."""
     list_capacity = 8192                                       # rows of one image's merge list (all models together)
 
-    def __init__(self, models, iou_thr=0.55, merge="wbf", weights=None, expected=None):
+    def __init__(self, models, iou_thr=0.55, merge="wbf", weights=None, expected=None, soft=None, sigma=0.5, score_floor=0.001):
+        check_soft_with_merge("Ensemble", merge, soft)
+        self.soft, self.sigma, self.score_floor = soft, float(sigma), float(score_floor)
         self.models = list(models)
         if not self.models:
             raise ValueError("Ensemble: no models")
@@ -115,6 +152,7 @@ class Ensemble(object):
         for m, h, w in zip(self.models, handles, self.weights):
             rec, off = m._retry_exact(h, lambda: self._packed(h, xf))
             obj.append(rec, off, w, handle=h0)
+        obj.merge_soft(self.soft, self.sigma, self.score_floor, handle=h0)
         obj.merge(B, self._rule, self.iou_thr, 0 if self.expected is None else self.expected)
         return obj.result()
 
@@ -132,4 +170,4 @@ class Ensemble(object):
         return records_to_host(*self.records(x))
 
 
-__all__ = ["weighted_boxes_fusion", "Ensemble", "MERGE_WBF"]
+__all__ = ["weighted_boxes_fusion", "soft_nms", "Ensemble", "MERGE_WBF"]

@@ -180,6 +180,7 @@ class YOLONano(nn.Module):
         self.dp_average = True               # data-parallel: average gradients over ranks inside backward()
         self._train_dtype = "f32"            # arithmetic of the training step (train_precision)
         self._exact_f32 = False              # set once an activation left the split-f16 range (_range_guarded): f32-MFMA kernels from then on
+        self._soft = (None, 0.5, None)       # Soft-NMS in place of the per-class NMS (set_soft_nms): method, sigma, score_floor
 
     def __deepcopy__(self, memo):
         """deepcopy (utils/misc.py:70 ModelEMA) must not clone the native handle; the copy builds its own."""
@@ -294,6 +295,11 @@ class YOLONano(nn.Module):
         h.follow_current_stream()
         self._sync_grid(h)
         h.set_thresholds(self.conf_thresh, self.nms_thresh, self.use_diou_nms)
+        method, sigma, floor = getattr(self, "_soft", (None, 0.5, None))
+        soft = None if method is None else (method, float(sigma), float(self.conf_thresh if floor is None else floor))
+        if soft != getattr(h, "_soft_state", None):            # (a handle starts with the suppression off)
+            h.soft_nms(*(soft or (None,)))
+            h._soft_state = soft
         if sig != self._sig:
             for k, v in sd.items():
                 if not k.endswith("num_batches_tracked"):
@@ -301,6 +307,14 @@ class YOLONano(nn.Module):
             h.fold_bn()
             self._sig = sig
         return h
+
+    def set_soft_nms(self, method=None, sigma=0.5, score_floor=None):
+        """Soft-NMS in place of the per-class NMS of the forward (yn_soft_nms): method None (off, the default), "hard",
+        "linear" or "gaussian"; score_floor None = the model's conf_thresh.  Neighbours of a kept box stay, with their scores marked
+        down.  Not with diou_nms: the forward then refuses by name."""
+        from .capi import soft_method_id
+        soft_method_id(method)
+        self._soft = (method, float(sigma), None if score_floor is None else float(score_floor))
 
     # ---- decode / NMS helpers with the reference's signatures -----------------------------------------
     def decode_xywh(self, txtytwth_pred):
@@ -680,10 +694,14 @@ class TestTimeAugmentation(object):
     Same constructor and call signature; the forwards run through the model's handle, the merge through yn_nms_merge."""
     __test__ = False                                           # not a pytest class
 
-    def __init__(self, num_classes=80, nms_thresh=0.4, scale_range=[320, 640, 32], merge="nms", expected=None):
+    def __init__(self, num_classes=80, nms_thresh=0.4, scale_range=[320, 640, 32], merge="nms", expected=None, soft=None, sigma=0.5,
+                 score_floor=None):
         """merge: "nms" (the reference's per-class NMS) or "wbf" (weighted box fusion, yn_wbf_merge: nms_thresh is then its IoU
-        threshold); expected: WBF's expected votes, None = the number of forwards."""
-        from .capi import merge_rule_id
+        threshold); expected: WBF's expected votes, None = the number of forwards.  soft: None, or "hard" / "linear" / "gaussian" -
+        the "nms" merge then suppresses by Soft-NMS (yn_soft_nms_merge) with sigma and score_floor (None: the model's conf_thresh)."""
+        from .capi import check_soft_with_merge, merge_rule_id
+        check_soft_with_merge("TestTimeAugmentation", merge, soft)
+        self.soft, self.sigma, self.score_floor = soft, float(sigma), None if score_floor is None else float(score_floor)
         self.num_classes = num_classes
         self.nms_thresh = nms_thresh
         self.scales = np.arange(scale_range[0], scale_range[1] + 1, scale_range[2])
@@ -720,9 +738,17 @@ class TestTimeAugmentation(object):
                                             torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.nms_thresh,
                                             2 * len(self.scales) if self.expected is None else self.expected)
             return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
+        if self.soft is not None:
+            ob, osc, oc, _ = h.soft_nms_merge(torch.as_tensor(bboxes).to(dev), torch.as_tensor(scores).to(dev),
+                                              torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.soft, self.nms_thresh,
+                                              self.sigma, self._floor(model))
+            return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
         ob, osc, oc, _ = h.nms_merge(torch.as_tensor(bboxes).to(dev), torch.as_tensor(scores).to(dev),
                                      torch.as_tensor(labels.astype(np.int32)).to(dev), self.num_classes, self.nms_thresh)
         return ob.cpu().numpy().copy(), osc.cpu().numpy().copy(), oc.cpu().numpy().astype(np.int64)
+
+    def _floor(self, model):
+        return float(model.conf_thresh) if self.score_floor is None else self.score_floor
 
     # ---- whole batches on the device (yn_tta_*, kernels_tta.hip).  Everything below stands BESIDE __call__, which stays the reference's
     # loop statement for statement: per scale one resize + mirror launch and ONE yn_infer over the 2B images, one append per scale, one
@@ -752,6 +778,7 @@ class TestTimeAugmentation(object):
             self._tta = None
             obj = self._tta = capi.Tta(h, [int(s) for s in self.scales], True, max_batch=max(int(B), 1), list_capacity=cap)
         obj.merge_rule(self._rule, 0 if self.expected is None else self.expected, handle=h)
+        obj.merge_soft(self.soft, self.sigma, self._floor(model), handle=h)
         return h
 
     def records(self, x, model):

@@ -77,7 +77,8 @@ class SlicedInference(object):
     """tile / overlap / full_frame: slice_grid's; nms_thresh: of the per-frame merge; edge_margin (pixels, < 0 off): a tile's box that comes
     within the margin of a side where the tile was cut out of the frame is dropped - the neighbouring tile sees that object whole;
     list_capacity: rows of one frame's merge list; mean / std: ValTransforms' (BGR order); merge: "nms" (per-class NMS) or "wbf" (weighted box
-    fusion, yn_wbf_merge's rule: nms_thresh is then its IoU threshold) with `expected` votes (None: 1).
+    fusion, yn_wbf_merge's rule: nms_thresh is then its IoU threshold) with `expected` votes (None: 1); soft: None, or "hard" / "linear" /
+    "gaussian" - the "nms" merge then suppresses by Soft-NMS with sigma and score_floor (None: the model's conf_thresh).
 
     Tiles run through the MODEL'S handle, `max_batch` of them per forward.  A handle is made for `chunk` (32) tiles only when the model has
     none yet: a model that already ran at batch 1 keeps that handle and slices one tile per forward - the same result (it does not depend on
@@ -85,8 +86,10 @@ class SlicedInference(object):
     slice first, to choose."""
 
     def __init__(self, tile=416, overlap=0.2, full_frame=True, nms_thresh=0.5, edge_margin=-1.0, list_capacity=8192,
-                 mean=(0.406, 0.456, 0.485), std=(0.225, 0.224, 0.229), merge="nms", expected=None):
-        from .capi import merge_rule_id
+                 mean=(0.406, 0.456, 0.485), std=(0.225, 0.224, 0.229), merge="nms", expected=None, soft=None, sigma=0.5, score_floor=None):
+        from .capi import check_soft_with_merge, merge_rule_id
+        check_soft_with_merge("SlicedInference", merge, soft)
+        self.soft, self.sigma, self.score_floor = soft, float(sigma), None if score_floor is None else float(score_floor)
         self.merge, self._rule = merge, merge_rule_id(merge)
         self.expected = None if expected is None else int(expected)
         self.tile, self.overlap, self.full_frame = int(tile), overlap, bool(full_frame)
@@ -121,6 +124,7 @@ class SlicedInference(object):
             self._obj = None
             obj = self._obj = capi.Slice(h, max_frames=max(int(F), 1), list_capacity=self.list_capacity)
         obj.merge_rule(self._rule, 0 if self.expected is None else self.expected, handle=h)
+        obj.merge_soft(self.soft, self.sigma, float(model.conf_thresh) if self.score_floor is None else self.score_floor, handle=h)
         return h
 
     def records(self, frames, model):
