@@ -690,6 +690,46 @@ int  yn_draw_status(yn_handle* h, yn_draw* d, int64_t* drawn, int64_t* skipped, 
  * class, x1, y1, x2, y2 (the unclipped integers), k; n = drawn, cap = rows of room.  Synchronises. */
 int  yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap);
 
+/* ---- detections cut out of frames as fixed-size chips (DESIGN.md 32 is the specification, tests/chip_oracle.py its restatement): the
+ * pixels of the detections for a second stage (a classifier, a re-ID embedding, OCR, a zoomed second pass, thumbnails), straight from
+ * the rec_dev / offsets_dev pair of yn_pack_detections, yn_tta_result, yn_slice_result, yn_fuse_result or yn_track_update.  Frames,
+ * geom_host and space are yn_draw_batch's.  Per record, in record order: selected iff score > min_score (strict, float32) and, after a
+ * class that is no integer in 0..C-1 has been skipped and counted, class_keep[class] is set; the box goes to pixels and through int()
+ * as for yn_draw_batch (a coordinate that is not finite with |v| < 2^30, or X2 < X1 or Y2 < Y1: skipped); the margin mx = margin_px +
+ * (bw0 * margin_permille + 500) / 1000 (my likewise) widens it, the frame clips it (empty, or a side below min_side: skipped); the
+ * source rectangle sw x sh is fitted into the cw x ch chip (YN_CHIP_STRETCH: all of it; YN_CHIP_LETTERBOX: Resize.__call__'s arithmetic,
+ * sh*cw > sw*ch: rh = ch, rw = (int)((double)sw / sh * ch), left = (cw - rw) / 2; the mirror image; equal: all of it; rw or rh 0:
+ * skipped) and resampled like cv2.resize's 8-bit INTER_LINEAR (copy, the exact 2:1 box, or linear: the per-pixel rule of
+ * yn_preprocess_batch, the same bits); outside the fitted extent the pixel is fill (BGR).  YN_CHIP_U8: uint8 [slot][ch][cw][3] BGR.
+ * YN_CHIP_F32: float32 [slot][3][ch][cw] RGB, every value through Normalize with mean / std (BGR order); with fill[c] = float32(mean[c])
+ * * 255 a square letterbox chip is what yn_preprocess_batch writes for the cropped image.  Usable records get the slots 0, 1, 2, ... in
+ * record order; those past max_chips are counted as overflow. */
+#define YN_CHIP_LETTERBOX 0
+#define YN_CHIP_STRETCH   1
+#define YN_CHIP_U8  0
+#define YN_CHIP_F32 1
+typedef struct yn_chip yn_chip;
+typedef struct { int32_t cw, ch, fit, format, margin_px, margin_permille, min_side; float min_score, fill[3], mean[3], std[3]; } yn_chip_params;
+/* num_classes 1..2000, max_chips 1..65536, cw and ch 8..1024, cw a multiple of 4, margin_px 0..4096, margin_permille 0..4000, min_side
+ * 1..16384.  Refused with a reason, in this order: a value outside these limits, a float that is not finite, a std that is not positive,
+ * a u8 fill that is no integer in 0..255.  The object has its own lifetime (any handle of its device serves the later calls); its
+ * memory shows in yn_live_device_memory. */
+int  yn_chip_create(yn_handle* h, int num_classes, const uint8_t* class_keep_host /* [C] or NULL: all */, int max_chips, const yn_chip_params* p, yn_chip** out);
+void yn_chip_destroy(yn_chip* c);
+/* On the handle's stream, ceil(B / 32) + 2 launches whatever the records hold, no copy back, no synchronise.  B 0..1024; chips_dev
+ * [max_chips] chips, 16-byte aligned; index_dev [max_chips] the record index of every slot; rect_dev [max_chips][8] = source x, y, sw,
+ * sh, rw, rh, left, top; chip_offsets_dev [B+1]: the slots used by the frames before b, [B] the count.  Slots at or past the count are
+ * not written in any output.  No record at or past rec_capacity is read, whatever the offsets hold.  offsets_dev[B] < 0 (the split-f16
+ * range mark) is decided on the device: nothing is written but chip_offsets_dev = 0, .., 0, -1, and the status' range word is set.
+ * Refused before any launch, in this order: B, rec_capacity or the alignment outside their limits, null pointers, a frame side outside
+ * 1..16384 or a bad letterbox geometry (naming the frame), a space that is neither mode, a handle on another device than the object's.
+ * B == 0 is no error: chip_offsets_dev[0] = 0 and nothing else.  Work buffers grow with rec_capacity and B (a growth frees the old
+ * buffer, which waits for the device). */
+int  yn_chip_batch(yn_handle* h, yn_chip* c, int B, const uint8_t* const* frames_host, const int32_t* geom_host, int space,
+                   const float* rec_dev, const int32_t* offsets_dev, int64_t rec_capacity,
+                   void* chips_dev, int32_t* index_dev, int32_t* rect_dev, int32_t* chip_offsets_dev);
+int  yn_chip_status(yn_handle* h, yn_chip* c, int64_t counters_host[4] /* chips, skipped, overflow, range_mark of the last call; synchronises */);
+
 /* ---- detections tracked across video frames: B camera streams, one frame of each per step, identities kept on the device (DESIGN.md 29
  * is the specification, tests/track_oracle.py its float32 restatement; the reference has no tracker, the rules are this library's own,
  * of the ByteTrack / BoT-SORT family with a greedy instead of an optimal assignment).  The input is the rec_dev / offsets_dev pair of

@@ -35,6 +35,9 @@ def __getattr__(name):
     if name in ("weighted_boxes_fusion", "soft_nms", "Ensemble"):
         from . import fusion                                  # numpy only until a fusion runs
         return getattr(fusion, name)
+    if name in ("ChipExtractor", "unchip_boxes"):
+        from . import chips                                   # numpy only until a ChipExtractor is made
+        return getattr(chips, name)
     if name == "Tracker":
         from . import track                                   # numpy only until a Tracker is made
         return track.Tracker

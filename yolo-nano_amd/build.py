@@ -9,7 +9,7 @@ sequence bit for bit (models/yolo_nano.py:159-188); so is kernels_eval.hip, whos
 TrainTransforms chain and resize restate the reference's float32 numpy steps and cv2's scalar float code, and kernels_kmeans.hip, whose
 float64 IoU distance restates kmeans_anchor.py's, and kernels_tta.hip, whose bilinear resize is pinned operation by operation
 (tests/tta_oracle.py), and kernels_slice.hip, whose tile kernel shares kernels_post.hip's per-pixel body (csrc/yn_prep.h) and whose box remap is pinned operation by
-operation (tests/slice_oracle.py), and kernels_draw.hip, which maps boxes to pixels with the evaluators' unletterbox() (integer arithmetic after that), and kernels_track.hip, whose float32 Kalman filter and IoU restate tests/track_oracle.py operation by operation, and kernels_wbf.hip, whose float32 weighted box fusion restates tests/wbf_oracle.py operation by operation, and kernels_soft.hip, whose float32 Soft-NMS (its exp included) restates tests/soft_nms_oracle.py operation by operation.  kernels_jpeg.hip, kernels_jpeg_huff.hip and kernels_jpeg_enc.hip are integer arithmetic throughout.
+operation (tests/slice_oracle.py), and kernels_draw.hip, which maps boxes to pixels with the evaluators' unletterbox() (integer arithmetic after that), and kernels_chip.hip, whose chip resampling must give the bits of kernels_post.hip's per-pixel body (csrc/yn_prep.h) from set-up values computed once per tile, and kernels_track.hip, whose float32 Kalman filter and IoU restate tests/track_oracle.py operation by operation, and kernels_wbf.hip, whose float32 weighted box fusion restates tests/wbf_oracle.py operation by operation, and kernels_soft.hip, whose float32 Soft-NMS (its exp included) restates tests/soft_nms_oracle.py operation by operation.  kernels_jpeg.hip, kernels_jpeg_huff.hip and kernels_jpeg_enc.hip are integer arithmetic throughout.
 """
 import os
 import subprocess
@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libyolonano_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = [("kernels_conv.hip", []), ("kernels_post.hip", ["-ffp-contract=off"]), ("kernels_train.hip", []), ("kernels_bwd.hip", []), ("kernels_h16.hip", []), ("kernels_chain.hip", []), ("kernels_pipe.hip", []), ("kernels_stage.hip", []), ("kernels_eval.hip", ["-ffp-contract=off"]), ("kernels_coco.hip", ["-ffp-contract=off"]), ("kernels_aug.hip", ["-ffp-contract=off"]), ("kernels_kmeans.hip", ["-ffp-contract=off"]), ("kernels_tta.hip", ["-ffp-contract=off"]), ("kernels_slice.hip", ["-ffp-contract=off"]), ("kernels_draw.hip", ["-ffp-contract=off"]), ("kernels_track.hip", ["-ffp-contract=off"]), ("kernels_wbf.hip", ["-ffp-contract=off"]), ("kernels_soft.hip", ["-ffp-contract=off"]), ("kernels_jpeg.hip", []), ("kernels_jpeg_huff.hip", []), ("kernels_jpeg_enc.hip", []), ("yn_api.hip", [])]
+SOURCES = [("kernels_conv.hip", []), ("kernels_post.hip", ["-ffp-contract=off"]), ("kernels_train.hip", []), ("kernels_bwd.hip", []), ("kernels_h16.hip", []), ("kernels_chain.hip", []), ("kernels_pipe.hip", []), ("kernels_stage.hip", []), ("kernels_eval.hip", ["-ffp-contract=off"]), ("kernels_coco.hip", ["-ffp-contract=off"]), ("kernels_aug.hip", ["-ffp-contract=off"]), ("kernels_kmeans.hip", ["-ffp-contract=off"]), ("kernels_tta.hip", ["-ffp-contract=off"]), ("kernels_slice.hip", ["-ffp-contract=off"]), ("kernels_draw.hip", ["-ffp-contract=off"]), ("kernels_chip.hip", ["-ffp-contract=off"]), ("kernels_track.hip", ["-ffp-contract=off"]), ("kernels_wbf.hip", ["-ffp-contract=off"]), ("kernels_soft.hip", ["-ffp-contract=off"]), ("kernels_jpeg.hip", []), ("kernels_jpeg_huff.hip", []), ("kernels_jpeg_enc.hip", []), ("yn_api.hip", [])]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result",
           "-Wno-pass-failed"]
 

@@ -197,6 +197,10 @@ SIGNATURES = {
     "yn_draw_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, ctypes.c_int64, _f32]),
     "yn_draw_status": (_i32, [_vp, _vp, _i64p, _i64p, ctypes.POINTER(_i32)]),
     "yn_draw_prims": (_i32, [_vp, _vp, _vp, ctypes.c_int64]),
+    "yn_chip_create": (_i32, [_vp, _i32, _vp, _i32, _vp, ctypes.POINTER(_vp)]),
+    "yn_chip_destroy": (None, [_vp]),
+    "yn_chip_batch": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "yn_chip_status": (_i32, [_vp, _vp, _vp]),
     "yn_track_create": (_i32, [_vp, _i32, _i32, _i32, _vp, ctypes.POINTER(_vp)]),
     "yn_track_destroy": (None, [_vp]),
     "yn_track_reset": (_i32, [_vp, _vp, _i32]),

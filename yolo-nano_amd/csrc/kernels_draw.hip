@@ -27,7 +27,7 @@ namespace ynk {
 
 namespace {
 
-constexpr int DRAW_THREADS = 256;
+constexpr int DRAW_THREADS = 256;                // evs::ordered_rank's workgroup
 constexpr int DRAW_TW = 64, DRAW_TH = 16;       // tile: one lane per column, each wave four rows
 constexpr int DRAW_ROWS = DRAW_TH / (DRAW_THREADS / 64);
 constexpr int DRAW_FRAMES = 32;                 // frames per launch (descriptors travel in the kernel arguments)
@@ -48,26 +48,6 @@ struct DrawStyle {
     const unsigned char* atlas;                 // [95][gh][gw]
     int32_t gw, gh, thickness, C;
 };
-
-// position of this thread's flagged element among the workgroup's flagged elements in thread order, and their number
-__device__ __forceinline__ int ordered_rank(bool flag, int* wsum, int& total)
-{
-    const unsigned long long m = __ballot(flag);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wv] = __popcll(m);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < DRAW_THREADS / 64; ++w) {
-        const int c = wsum[w];
-        if (w < wv) base += c;
-        total += c;
-    }
-    __syncthreads();                            // wsum may be written again
-    return base + r;
-}
 
 // stat: [0] drawn, [1] skipped, [2] range mark.  book [2][bcap]: start and count of every frame's primitive list.
 __global__ __launch_bounds__(DRAW_THREADS) void draw_prims_kernel(DrawFrames fr, int frame0, int B, int bcap, const float* __restrict__ rec,
@@ -119,7 +99,7 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_prims_kernel(DrawFrames fr,
             }
         }
         int n;
-        const int rank = ordered_rank(draw, wsum, n);
+        const int rank = evs::ordered_rank(draw, wsum, n);
         if (draw) {
             int32_t* p = prims + (lo + running + rank) * DRAW_PRIM;                      // running + rank <= i - lo: inside the frame's slots
             *reinterpret_cast<int4*>(p) = make_int4(v[0], v[1], v[2], v[3]);
@@ -197,7 +177,7 @@ __global__ __launch_bounds__(DRAW_THREADS) void draw_tile_kernel(DrawFrames fr, 
             if (s.bar) meets = meets || rects_meet(s.bx0, s.by0, s.bx1, s.by1, tx0, ty0, tx1, ty1);
         }
         int n;
-        const int rank = ordered_rank(meets, wsum, n);
+        const int rank = evs::ordered_rank(meets, wsum, n);
         if (meets) { list[rank][0] = q; list[rank][1] = e; }
         __syncthreads();
         for (int j = 0; j < n; ++j) {

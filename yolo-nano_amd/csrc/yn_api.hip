@@ -70,6 +70,7 @@ struct yn_coco { ynk::CocoState* st; };      // likewise (kernels_coco.hip)
 struct yn_kmeans { ynk::KmeansState* st; };  // likewise (kernels_kmeans.hip)
 struct yn_draw { ynk::DrawState* st; };      // likewise (kernels_draw.hip)
 struct yn_track { ynk::TrackState* st; };    // likewise (kernels_track.hip)
+struct yn_chip { ynk::ChipState* st; };      // likewise (kernels_chip.hip)
 struct yn_jpeg { ynk::JpegState* st; };      // likewise (kernels_jpeg.hip)
 struct yn_jpeg_enc { ynk::JpegEncState* st; };      // likewise (kernels_jpeg_enc.hip)
 struct yn_eval { ynk::EvalState* st; };      // opaque to callers: its own lifetime, launches on the stream of the handle passed per call
@@ -2883,6 +2884,45 @@ int yn_draw_prims(yn_handle* h, yn_draw* d, int32_t* host, int64_t cap)
     YN_ENTER(h);
     if (!d || (!host && cap > 0)) return fail(h, "yn_draw_prims: null argument");
     YN_EVAL_CALL(ynk::draw_prims(d->st, h->stream, host, cap, err));
+}
+
+// ---- detections cut out of frames as chips (kernels_chip.hip) --------------------------------------------------------------------
+static_assert(sizeof(yn_chip_params) == 17 * 4 && offsetof(yn_chip_params, min_score) == 7 * 4, "yn_chip_params: seven int32, then ten floats");
+static_assert(YN_CHIP_LETTERBOX == 0 && YN_CHIP_STRETCH == 1 && YN_CHIP_U8 == 0 && YN_CHIP_F32 == 1, "yn_chip_params fits and formats");
+
+int yn_chip_create(yn_handle* h, int num_classes, const uint8_t* class_keep_host, int max_chips, const yn_chip_params* p, yn_chip** out)
+{
+    YN_ENTER(h);
+    if (!out || !p) return fail(h, "yn_chip_create: null argument");
+    *out = nullptr;
+    std::string err;
+    ynk::ChipState* st = nullptr;
+    if (ynk::chip_create(h->cfg.device, num_classes, class_keep_host, max_chips, &p->cw, &p->min_score, &st, err)) return fail(h, "%s", err.c_str());
+    *out = new yn_chip{st};
+    return 0;
+}
+
+void yn_chip_destroy(yn_chip* c)
+{
+    if (!c) return;
+    ynk::chip_destroy(c->st);
+    delete c;
+}
+
+int yn_chip_batch(yn_handle* h, yn_chip* c, int B, const uint8_t* const* frames_host, const int32_t* geom_host, int space, const float* rec_dev,
+                  const int32_t* offsets_dev, int64_t rec_capacity, void* chips_dev, int32_t* index_dev, int32_t* rect_dev, int32_t* chip_offsets_dev)
+{
+    YN_ENTER(h);
+    if (!c) return fail(h, "yn_chip_batch: null object");
+    YN_EVAL_CALL(ynk::chip_batch(c->st, h->cfg.device, h->stream, B, frames_host, geom_host, space, rec_dev, offsets_dev, rec_capacity, chips_dev, index_dev,
+                                 rect_dev, chip_offsets_dev, err));
+}
+
+int yn_chip_status(yn_handle* h, yn_chip* c, int64_t counters_host[4])
+{
+    YN_ENTER(h);
+    if (!c || !counters_host) return fail(h, "yn_chip_status: null argument");
+    YN_EVAL_CALL(ynk::chip_status(c->st, h->stream, counters_host, err));
 }
 
 // ---- detections tracked across frames (kernels_track.hip) ---------------------------------------------------------------------

@@ -103,6 +103,27 @@ __device__ __forceinline__ int64_t lower_bound(const K* a, int64_t n, K key)   /
     return lo;
 }
 
+// position of this thread's flagged element among the flagged elements of a 256-thread workgroup in thread order, and their
+// number; wsum holds 4 ints
+__device__ __forceinline__ int ordered_rank(bool flag, int* wsum, int& total)
+{
+    const unsigned long long m = __ballot(flag);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wv] = __popcll(m);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = wsum[w];
+        if (w < wv) base += c;
+        total += c;
+    }
+    __syncthreads();                            // wsum may be written again
+    return base + r;
+}
+
 // inclusive scan over the 256 threads of a workgroup in thread order; lds holds 4 elements
 template <typename T, typename Op>
 __device__ __forceinline__ T block_scan_incl(T v, Op op, T* lds)

@@ -371,6 +371,18 @@ int  draw_batch(DrawState* d, hipStream_t s, int B, uint8_t* const* frames, cons
 int  draw_status(DrawState* d, hipStream_t s, int64_t* drawn, int64_t* skipped, int* range_mark, std::string& err);
 int  draw_prims(DrawState* d, hipStream_t s, int32_t* host, int64_t cap, std::string& err);
 
+// ---- detections cut out of frames as chips (kernels_chip.hip): the state behind yn_chip; 0 = ok, 1 = error (text in err) ---------------------
+struct ChipState;
+// params7 / params10: the int32 and the float members of yn_chip_params in their order
+int  chip_create(int device, int C, const uint8_t* class_keep, int max_chips, const int32_t* params7, const float* params10, ChipState** out,
+                 std::string& err);
+void chip_destroy(ChipState* c);
+int  chip_device(const ChipState* c);
+int  chip_batch(ChipState* c, int handle_device, hipStream_t s, int B, const uint8_t* const* frames, const int32_t* geom, int space, const float* rec_dev,
+                const int32_t* offsets_dev, int64_t rec_capacity, void* chips_dev, int32_t* index_dev, int32_t* rect_dev, int32_t* chip_offsets_dev,
+                std::string& err);
+int  chip_status(ChipState* c, hipStream_t s, int64_t* counters4, std::string& err);
+
 // ---- detections tracked across frames (kernels_track.hip): the state behind yn_track; 0 = ok, 1 = error (text in err) ----------------------
 struct TrackState;
 // params8 / params3: the float and the int32 members of yn_track_params in their order, or both null for the defaults
